@@ -23,11 +23,19 @@ the end, INSIDE the timed region.  The loop and the cross-rank aggregation live 
 two gloo ranks and a stub engine).
 
 Timing: K steps between barrier + synchronize on both sides with the HIP-event instrumentation OFF -> `value`.
+A plain run does only that: set-up, warm-up, the K timed steps, the outputs (--dump-outputs) and the result line.
+Everything else runs only with --full:
 Rooflines: the same K steps are then run once more with the events of csrc/prof.cpp ON (events recorded on the launch
 stream around each instrumented kernel) -> `roofline` (dominant kernel family) and `rooflines` (+ the two north-star
 entries: kNN+PPF against HBM on algorithmic bytes, the global transformer phase against HBM -- it is the stream of the
-geometric embedding E -- with its executed matrix work against the MFMA peak beside it; + `whole_forward`).
-Prints ONE JSON line (rank 0); `cpu_baseline` = the CPU oracle timed on this host (rank 0, N=1 only).
+geometric embedding E -- with its executed matrix work against the MFMA peak beside it; + `whole_forward`);
+`single_pair_mode` (one pair per call); `cpu_baseline` = the CPU oracle timed on this host (rank 0, N=1 only).
+Without --full `roofline` is null and `rooflines` empty.  Prints ONE JSON line (rank 0).
+
+--dump-outputs DIR writes what the last timed step returned, as DIR/<name>.npy (float32; integer and boolean arrays as
+float64): configs 2 - 4 every array of the result dicts of a fixed, seeded sample of the step's pairs
+(pair<slot>.<key>.npy), config 5 a fixed, seeded sample of query rows (rows.npy, group_idx.npy, ppf.npy); at most 64 MB.
+The inputs depend on the arguments alone, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -89,7 +97,17 @@ def parse():
     ap.add_argument("--record-scores-per-pair", type=int, default=None,
                     help="average score capacity per pair of the gathered result block (shard.py); the block carries every timed step "
                          "(default 4092; config 4: 12288 -- the adaptive matching emits ~10 k correspondences per pair)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the instrumented repeat of the timed steps (rooflines), the "
+                         "one-pair-per-call measurement and the CPU baseline (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_profile_pass = args.no_single_pair = args.no_cpu_baseline = True
+    return args
 
 
 def test_engine_hook():
@@ -249,12 +267,15 @@ def forward_bench(args, rank, world, distributed):
         gc.disable()   # a generation-2 collection of the result dicts costs ~40 ms every dozen steps
         if not stub:
             model.host_ms.update(launch=0.0, unpack=0.0, calls=0)
+        timed = KeepLastResults(model) if args.dump_outputs else model
         t0 = time.perf_counter()
-        n_corr_total, records = benchloop.run_steps(model, batch, B, args.warmup, args.steps, rank, world, True, spp, trace)
+        n_corr_total, records = benchloop.run_steps(timed, batch, B, args.warmup, args.steps, rank, world, True, spp, trace)
         barrier()
         dt = time.perf_counter() - t0
         gc.enable()
         host_ms = None if stub else {k: round(v / max(args.steps, 1), 3) for k, v in model.host_ms.items() if k != "calls"}
+        dumped = dump_pair_results(args.dump_outputs, timed.last) if args.dump_outputs and rank == 0 else None
+        timed = None
 
         # ---- the same steps once more with the HIP-event instrumentation on (not part of `value`)
         prof, prof_steps, ot_counts = {}, 0, [0, 0, 0]
@@ -334,6 +355,8 @@ def forward_bench(args, rank, world, distributed):
         if gt else "fp32 MFMA GEMM form (geo_embed_kernel)")
     if gt:
         out["config"]["geometric_embedding_table"] = {"interval": gt["interval"], "lds_bytes": gt["lds_bytes"], "rel_fit_d": gt["rel_d"], "rel_fit_a": gt["rel_a"]}
+    if dumped:
+        out["dump_outputs"] = dumped
     if host_ms:
         # host-side Python per step on THIS rank inside the timed region: launch = packing + allocation + the engine call (its ~350 kernel
         # launches), unpack = finish_batch after the device answered; both run while the device works on the other batch in flight
@@ -342,7 +365,7 @@ def forward_bench(args, rank, world, distributed):
         if records is not None:
             out["result_gather"] = benchloop.gather_summary(records, B, args.steps, spp)
         roofs = rooflines(prof, prof_steps, dtype)
-        pmc = attach_traffic(roofs, B, args.config)
+        pmc = attach_traffic(roofs, B, args.config) if roofs else None
         out["roofline"] = roofs[0] if roofs else None
         out["rooflines"] = roofs
         if prof_steps:
@@ -392,43 +415,124 @@ def knn_stress(args, rank, world, distributed):
         step()
     barrier()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = None             # the previous call's outputs go back to the allocator before the next call, as when they are discarded
+        last = step()
     barrier()
     dt = time.perf_counter() - t0
-    # per-launch duration of the call on its stream (HIP events on torch's current stream = the stream pointops launches on)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(args.steps):
-        step()
-    e1.record()
-    torch.cuda.synchronize()
-    call_ms = e0.elapsed_time(e1) / args.steps
+    dumped = dump_knn_results(args.dump_outputs, last) if args.dump_outputs and rank == 0 else None
+    last = None
+    roof = None
+    if args.full:
+        # per-launch duration of the call on its stream (HIP events on torch's current stream = the stream pointops launches on)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.steps):
+            step()
+        e1.record()
+        torch.cuda.synchronize()
+        call_ms = e0.elapsed_time(e1) / args.steps
     if distributed:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t[0].item())
     queries = N * B * args.steps * world
-    algo = (24.0 * N + 20.0 * N * K) * B          # 24 R + 4 M K (idx) + 16 M K (ppf), queries == refs
-    achieved = algo / (call_ms * 1e-3) / 1e9
-    roof = {"bound": "hbm", "kernel": "knn+ppf call (grid_build_kernel + knn_cell_kernel / knn_gridsel_kernel / knn_replay_kernel, PPF fused)",
-            "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": None,
-            "avg_launch_ms": round(call_ms, 5), "algorithmic_bytes_per_launch": int(algo), "launches_timed": args.steps,
-            "pair_evaluations_brute_force": int(float(N) * N * B),
-            "note": "an exact kNN is bound by VALU issue (selecting 64 of ~700 staged candidates per query), not by the 39 MB per cloud "
-                    "it has to move (SURVEY.md finding 3): see valu_issue"}
-    sq = load_profile_json("sq_knn_config5.json")
-    from roitr_amd.build import source_hash
-    if sq and sq.get("clouds") == B and sq.get("n_points") == N and sq.get("kernel_source_sha16") == source_hash():
-        roof["valu_issue"] = sq
+    if args.full:
+        algo = (24.0 * N + 20.0 * N * K) * B          # 24 R + 4 M K (idx) + 16 M K (ppf), queries == refs
+        achieved = algo / (call_ms * 1e-3) / 1e9
+        roof = {"bound": "hbm", "kernel": "knn+ppf call (grid_build_kernel + knn_cell_kernel / knn_gridsel_kernel / knn_replay_kernel, PPF fused)",
+                "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": None,
+                "avg_launch_ms": round(call_ms, 5), "algorithmic_bytes_per_launch": int(algo), "launches_timed": args.steps,
+                "pair_evaluations_brute_force": int(float(N) * N * B),
+                "note": "an exact kNN is bound by VALU issue (selecting 64 of ~700 staged candidates per query), not by the 39 MB per cloud "
+                        "it has to move (SURVEY.md finding 3): see valu_issue"}
+        sq = load_profile_json("sq_knn_config5.json")
+        from roitr_amd.build import source_hash
+        if sq and sq.get("clouds") == B and sq.get("n_points") == N and sq.get("kernel_source_sha16") == source_hash():
+            roof["valu_issue"] = sq
     out = {"metric": "kNN+PPF queries/s (k = 64, N = 30000 per cloud)", "value": round(queries / dt, 1), "unit": "queries/s", "n_gpus": world,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
            "config": {"workload": wl["text"].format(N=N, B=B), "baseline_config": 5, "clouds_per_step": B, "n_points": N, "k": K},
-           "roofline": roof, "rooflines": [roof]}
+           "roofline": roof, "rooflines": [roof] if roof else []}
+    if dumped:
+        out["dump_outputs"] = dumped
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_knn(N, K, args.cpu_baseline_seconds)
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 20240611
+DUMP_PAIRS = 3           # result dicts written per dump (a fixed, seeded sample of the last step's slots)
+DUMP_QUERY_ROWS = 16384  # config 5: query rows written per dump
+
+
+class KeepLastResults:
+    """The model as benchloop.run_steps sees it, keeping a reference to what the last finish_batch returned (--dump-outputs).
+    run_steps holds each step's results exactly as long itself, so the timed loop's memory use does not change."""
+
+    def __init__(self, model):
+        self.model, self.last = model, None
+
+    def finish_batch(self, h):
+        self.last = self.model.finish_batch(h)
+        return self.last
+
+    def __getattr__(self, name):
+        return getattr(self.model, name)
+
+
+def dump_array(x):
+    """A result array as numpy: floating point as float32, integers and booleans as float64 (exact)."""
+    import numpy as np
+    import torch
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy() if x.dtype != torch.bfloat16 else x.detach().float().cpu().numpy()
+    x = np.asarray(x)
+    return x.astype(np.float32 if x.dtype.kind == "f" else np.float64)
+
+
+def write_dump(dirname, arrays):
+    """[(name, array)] -> DIR/<name>.npy, whole groups of arrays in order until the byte limit; returns the summary for the line."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total, files = 0, 0
+    for group in arrays:
+        size = sum(a.nbytes for _, a in group)
+        if total + size > DUMP_LIMIT_BYTES:
+            break
+        for name, a in group:
+            np.save(os.path.join(dirname, name + ".npy"), a)
+        total, files = total + size, files + len(group)
+    return {"dir": dirname, "files": files, "bytes": total}
+
+
+def dump_pair_results(dirname, results):
+    """Configs 2 - 4: every array of the result dicts of DUMP_PAIRS slots of the last timed step (slots drawn with a fixed seed;
+    a pair whose arrays would pass the byte limit ends the dump)."""
+    import numpy as np
+    B = len(results)
+    slots = sorted(np.random.default_rng(DUMP_SEED).choice(B, min(B, DUMP_PAIRS), replace=False).tolist())
+    groups = []
+    for s in slots:
+        r = results[s]
+        groups.append([(f"pair{s:03d}.{k}", dump_array(r[k])) for k in sorted(r.keys()) if r[k] is not None])
+    return dict(write_dump(dirname, groups), pair_slots=slots)
+
+
+def dump_knn_results(dirname, result):
+    """Config 5: group_idx (rows, 64) and ppf (rows, 64, 4) of DUMP_QUERY_ROWS query rows of the last timed call, drawn with a
+    fixed seed; rows.npy says which."""
+    import numpy as np
+    import torch
+    grp, ppf = result
+    M = grp.shape[0]
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(M, min(M, DUMP_QUERY_ROWS), replace=False))
+    sel = torch.from_numpy(rows).to(grp.device)
+    return write_dump(dirname, [[("rows", dump_array(rows)), ("group_idx", dump_array(grp.index_select(0, sel))),
+                                 ("ppf", dump_array(ppf.index_select(0, sel)))]])
 
 
 def ot_stats(enable):

@@ -28,26 +28,26 @@ python scripts/sq_forward_json.py $out/sq/a $out/sq_forward.json > /dev/null 2>&
 # the bench lines below attach these counters only when their kernel-source stamp matches the build they time (bench.py attach_traffic)
 cp $out/sq_forward.json profiles/sq_forward.json
 cp $out/sq_knn_config5.json profiles/sq_knn_config5.json
-python bench.py > $out/bench.log 2>&1
+python bench.py --full > $out/bench.log 2>&1
 tail -1 $out/bench.log > $out/${tag}_bench.json
-python bench.py --pairs-per-step 1 --steps 200 --warmup 20 --no-cpu-baseline > $out/bench_b1.log 2>&1
+python bench.py --full --pairs-per-step 1 --steps 200 --warmup 20 --no-cpu-baseline > $out/bench_b1.log 2>&1
 tail -1 $out/bench_b1.log > $out/${tag}_bench_pairs1.json
-python bench.py --cloud surface --no-cpu-baseline --no-single-pair > $out/bench_surface.log 2>&1
+python bench.py --full --cloud surface --no-cpu-baseline --no-single-pair > $out/bench_surface.log 2>&1
 tail -1 $out/bench_surface.log > $out/${tag}_bench_surface.json
-python bench.py --weights plain --no-cpu-baseline --no-single-pair > $out/bench_plain.log 2>&1
+python bench.py --full --weights plain --no-cpu-baseline --no-single-pair > $out/bench_plain.log 2>&1
 tail -1 $out/bench_plain.log > $out/${tag}_bench_plain_weights.json
-python bench.py --config 3 --no-cpu-baseline --no-single-pair > $out/bench_c3.log 2>&1
+python bench.py --full --config 3 --no-cpu-baseline --no-single-pair > $out/bench_c3.log 2>&1
 tail -1 $out/bench_c3.log > $out/${tag}_bench_config3.json
-python bench.py --config 4 --no-single-pair > $out/bench_c4.log 2>&1
+python bench.py --full --config 4 --no-single-pair > $out/bench_c4.log 2>&1
 tail -1 $out/bench_c4.log > $out/${tag}_bench_config4_bf16.json
-python bench.py --config 4 --dtype f32 --no-cpu-baseline --no-single-pair > $out/bench_c4f.log 2>&1
+python bench.py --full --config 4 --dtype f32 --no-cpu-baseline --no-single-pair > $out/bench_c4f.log 2>&1
 tail -1 $out/bench_c4f.log > $out/${tag}_bench_config4_f32.json
-python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver.log 2>&1
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_driver.log 2>&1
 tail -1 $out/bench_driver.log > $out/${tag}_bench_driver_cmd.json
-python bench.py --config 5 > $out/bench_c5.log 2>&1
+python bench.py --full --config 5 > $out/bench_c5.log 2>&1
 tail -1 $out/bench_c5.log > $out/${tag}_bench_config5.json
 # round 6: the three-way-split engine mode beside the fp32 headline, the split GEMM alone, the host share with eight rank processes
-python bench.py --dtype f32x3 --no-cpu-baseline > $out/bench_x3.log 2>&1
+python bench.py --full --dtype f32x3 --no-cpu-baseline > $out/bench_x3.log 2>&1
 tail -1 $out/bench_x3.log > $out/${tag}_bench_f32x3.json
 timeout 300 python scripts/bench_gemm_x3.py > $out/${tag}_gemm_x3.txt 2>&1
 PAIRS=128 timeout 600 bash scripts/host_share_8ranks.sh $out/host8 > $out/host8.log 2>&1

@@ -73,3 +73,48 @@ def test_bench_default_is_one_rank():
     assert r.returncode == 0, r.stderr[-2000:]
     o = _json_lines(r.stdout)[0]
     assert o["n_gpus"] == 1 and o["result_gather"]["records"] == 4
+
+
+def test_bench_dump_outputs_repeat(tmp_path):
+    """--dump-outputs DIR: what the last timed step returned, as float32 / float64 .npy files, the same from run to run with the
+    same arguments; --steps sets the number of timed steps."""
+    import numpy as np
+    argv = ["--steps", "5", "--warmup", "2", "--pairs-per-step", "16", "--record-scores-per-pair", "8"]
+    lines = []
+    for d in ("a", "b"):
+        r = _run(argv + ["--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(_json_lines(r.stdout)[0])
+    o = lines[0]
+    assert o["steps"] == 5 and o["warmup"] == 2 and o["ms_per_step"] > 0 and o["result_gather"]["records"] == 5 * 16
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert len(files) == o["dump_outputs"]["files"] == len(o["dump_outputs"]["pair_slots"]) == 3
+    assert o["dump_outputs"]["bytes"] <= 64 << 20
+    # the stub's pair in slot s of the last timed step (step 2 + 5 - 1 = 6) is pool entry (6 * 16 + s) % 24: (seed mod 5) scores = seed
+    for s in o["dump_outputs"]["pair_slots"]:
+        a = np.load(tmp_path / "a" / f"pair{s:03d}.corr_scores.npy")
+        assert a.dtype in (np.float32, np.float64)
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"pair{s:03d}.corr_scores.npy"))
+        seed = (6 * 16 + s) % 24
+        assert np.array_equal(a, np.full(seed % 5, float(seed), np.float32))
+
+
+def test_bench_plain_run_is_lean(monkeypatch):
+    """Without --full the line carries the headline alone: no instrumented pass, no one-pair mode, no CPU baseline."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = b.parse()
+    assert a.steps == 7 and a.warmup == 3 and not a.full and a.dump_outputs is None
+    assert a.no_profile_pass and a.no_single_pair and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = b.parse()
+    assert a.full and not (a.no_profile_pass or a.no_single_pair or a.no_cpu_baseline)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    assert b.parse().no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        b.parse()
