@@ -833,7 +833,9 @@ extern "C" int roitr_geo_indices(int rows, const float* pts, const int* offset, 
                                  float sigma_d, float sigma_a, int angle_k, int n_max, float* d_idx, float* a_idx, hipStream_t stream)
 {
     if (rows <= 0) return ROITR_OK;
-    if (n_max > 1024 || angle_k > 6) return ROITR_ERR_UNSUPPORTED;
+    // sd[1024] holds a row's distances, nb[8] the angle_k + 1 nearest
+    if (n_max > 1024) { roitr_set_error("roitr_geo_indices: clouds of at most 1024 nodes (n_max > 1024)", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
+    if (angle_k > 6) { roitr_set_error("roitr_geo_indices: at most 6 angle neighbours (angle_k > 6)", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
     const float factor_a = (float)(180.0 / ((double)sigma_a * 3.14159265358979323846));
     geo_indices_kernel<<<rows, 256, 0, stream>>>(pts, offset, cloud_of_row, eoff, 0.f, sigma_d, factor_a, angle_k, d_idx, a_idx);
     ROITR_LAUNCH_CHECK();
@@ -843,10 +845,16 @@ extern "C" int roitr_geo_indices(int rows, const float* pts, const int* offset, 
 extern "C" int roitr_mha(const RoitrMha* a, hipStream_t stream)
 {
     if (a->q_rows <= 0) return ROITR_OK;
+    if (a->heads < 1 || a->heads > 8) { roitr_set_error("roitr_mha: 1 to 8 heads", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
+    if (a->C % a->heads) { roitr_set_error("roitr_mha: C must be a multiple of heads", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
     const int c = a->C / a->heads;
-    if (a->heads > 8 || a->C % a->heads || c % 4 || a->ldk % 4 || a->C % 4) return ROITR_ERR_UNSUPPORTED;
+    if (c % 4) { roitr_set_error("roitr_mha: C / heads must be a multiple of 4", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
+    if (a->ldk % 4) { roitr_set_error("roitr_mha: ldk must be a multiple of 4", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
     size_t floats = (size_t)a->C + (a->E ? (size_t)a->heads * a->C : 0) + (size_t)a->heads * a->nk_max * (a->E ? 2 : 1) + 8;
-    if (floats * 4 > 150 * 1024) return ROITR_ERR_UNSUPPORTED;
+    if (floats * 4 > 150 * 1024) {
+        roitr_set_error("roitr_mha: heads x nk_max score table over the 150 KB LDS bound of the generic kernel", __FILE__, __LINE__);
+        return ROITR_ERR_UNSUPPORTED;
+    }
     ROITR_GRANT_LDS(mha_kernel, 150 * 1024);
     roitr_prof_begin(ROITR_PROF_MHA, -1.0, stream);   // bytes: roitr_prof_next_bytes of the caller (0 otherwise)
     {   // factor-2 width (C = 512) and / or E stored in bf16: the wide kernels

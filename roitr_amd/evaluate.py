@@ -72,13 +72,17 @@ class Evaluator(torch.nn.Module):
     @torch.no_grad()
     def evaluate_batch(self, handle):
         """IR / PIR of every pair of a RIGA_v2.launch_batch() handle (needs rot/trans): two launches for the whole batch.
+        Call it after finish_batch(handle): a call whose patch buffers were overfull is repeated there, and the handle then holds
+        the repeated call's outputs.
         Returns (ir (B,), pir (B,), n_corr_fine (B,), n_corr_coarse (B,)) as device tensors; empty sets give IR 0 / PIR nan."""
         out, B, P = handle["out"], handle["B"], handle["P"]
         dev = out["n_out"].device
         if not handle["have_gt"]:
             raise L.RoitrError("evaluate_batch needs ground-truth transforms (rot / trans) in the pairs")
         rot, trans = handle["keep"][4], handle["keep"][5]
-        starts = torch.cat([out["fine_offsets"].view(B, P)[:, 0], out["n_out"]]).contiguous()
+        # first output row of every pair, then the total: written by the engine in the strided (3DMatch) and the compacted
+        # (4DMatch) patch layout alike -- fine_offsets is per patch SLOT, and pair b's first slot is b * P in the first only
+        starts = out["pair_starts"]
         inl = _inlier_counts(starts, out["out_src_pts"], out["out_tgt_pts"], rot, trans, self.acceptance_radius)
         n_fine = (starts[1:] - starts[:-1])
         hits = torch.empty((B,), dtype=torch.int32, device=dev)

@@ -470,3 +470,81 @@ def local_block(x, kv, group_idx, ppf, w, node_order=None, variant=None, bf16_we
     else:
         L.check(L.lib().roitr_local_block_dbg(ctypes.byref(a), int(variant), L.stream_ptr()), "local_block_dbg")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Global geometric transformer (csrc/geo_attn.hip)
+# ------------------------------------------------------------------------------------------------
+class _Mha(ctypes.Structure):
+    _fields_ = [("q_row0", ctypes.c_int), ("q_rows", ctypes.c_int), ("C", ctypes.c_int), ("heads", ctypes.c_int),
+                ("q", _P), ("ldq", ctypes.c_int), ("k", _P), ("ldk", ctypes.c_int), ("v", _P), ("ldv", ctypes.c_int),
+                ("offset", _P), ("cloud_of_row", _P), ("partner", _P),
+                ("E", _P), ("eoff", _P), ("qt", _P), ("bp", _P),
+                ("scale", ctypes.c_float), ("nk_max", ctypes.c_int), ("out", _P), ("ldo", ctypes.c_int), ("ebar", _P),
+                ("e_bf16", ctypes.c_int)]
+
+
+def _rows(t, what):
+    """Row stride of a 2-D float32 device operand whose rows are contiguous (a column slice of a wider buffer is fine)."""
+    if t.dim() != 2 or t.stride(1) != 1 or t.dtype != torch.float32:
+        raise L.RoitrError(f"multi_head_attention: {what} must be a 2-D float32 tensor with contiguous rows")
+    return t.stride(0)
+
+
+def multi_head_attention(q, k, v, offset, cloud_of_row, nk_max, heads=4, partner=None, E=None, eoff=None, qt=None, bp=None,
+                         scale=None, q_row0=0, q_rows=None, out=None, ebar=None):
+    """roitr_mha (include/roitr_engine.h RoitrMha): geoattention.py:26-66 without E, geoattention.py:87-136 with the RPE branch
+    folded with E.  q / k / v (T, C) rows of all clouds, each with its own leading dimension (their row strides: q | k | v may be
+    the column blocks of one (T, 3C) buffer); offset (b,) int32 cumulative cloud ends, cloud_of_row (T,) int32, partner (b,) int32
+    key cloud of every cloud (None: self attention); nk_max bounds the key count of every cloud.  With E: E the concatenated
+    (n_c, n_c, C) blocks (float32 or bfloat16) at element offsets eoff (b,) int64 / C, qt (T, heads, C) = Wp_h^T q_h,
+    bp (C,) = proj_p.bias.  Query rows [q_row0, q_row0 + q_rows) are computed into out (T, C) and ebar (T, heads, C) =
+    sum_j a'_hj E_ij (preallocated ones are written in those rows only).  Returns (out, ebar); ebar is None without E."""
+    T, C = int(q.shape[0]), int(q.shape[1])
+    q_rows = T - q_row0 if q_rows is None else int(q_rows)
+    if q_row0 < 0 or q_row0 + q_rows > min(T, int(cloud_of_row.numel())):
+        raise L.RoitrError("multi_head_attention: query rows outside q / cloud_of_row")
+    ldq, ldk, ldv = _rows(q, "q"), _rows(k, "k"), _rows(v, "v")
+    if out is None:
+        out = torch.empty((T, C), dtype=torch.float32, device=q.device)
+    ldo = _rows(out, "out")
+    a = _Mha()
+    a.q_row0, a.q_rows, a.C, a.heads = int(q_row0), q_rows, C, int(heads)
+    a.q, a.ldq, a.k, a.ldk, a.v, a.ldv = L.ptr(q), ldq, L.ptr(k), ldk, L.ptr(v), ldv
+    a.offset, a.cloud_of_row, a.partner = L.ptr(offset), L.ptr(cloud_of_row), L.ptr(partner)
+    a.scale = 1.0 / float(C // heads) ** 0.5 if scale is None else float(scale)
+    a.nk_max, a.out, a.ldo = int(nk_max), L.ptr(out), ldo
+    if E is not None:
+        if E.dtype not in (torch.float32, torch.bfloat16) or not E.is_contiguous() or eoff.dtype != torch.int64:
+            raise L.RoitrError("multi_head_attention: E float32 / bfloat16 contiguous, eoff int64")
+        if qt.shape != (T, heads, C) or not qt.is_contiguous() or bp.numel() != C:
+            raise L.RoitrError("multi_head_attention: qt (T, heads, C) contiguous, bp (C,)")
+        if ebar is None:
+            ebar = torch.empty((T, heads, C), dtype=torch.float32, device=q.device)
+        if ebar.shape != (T, heads, C) or not ebar.is_contiguous():
+            raise L.RoitrError("multi_head_attention: ebar (T, heads, C) contiguous")
+        a.E, a.eoff, a.qt, a.bp, a.ebar = L.ptr(E), L.ptr(eoff), L.ptr(qt), L.ptr(bp), L.ptr(ebar)
+        a.e_bf16 = int(E.dtype == torch.bfloat16)
+    L.check(L.lib().roitr_mha(ctypes.byref(a), L.stream_ptr()), "mha")
+    return out, ebar
+
+
+def geo_indices(points, sizes, sigma_d=0.2, sigma_a=15.0, angle_k=3):
+    """roitr_geo_indices: positional_encoding.py:110-137 get_embedding_indices for the clouds of `sizes` (host ints) laid out back
+    to back in points (rows, 3).  Returns (d_idx, a_idx): the concatenated (n_c, n_c) and (n_c, n_c, angle_k) blocks, flat,
+    as (sum n_c^2,) and (sum n_c^2, angle_k)."""
+    dev = points.device
+    sizes = [int(n) for n in sizes]
+    ends = torch.tensor(sizes, dtype=torch.int64).cumsum(0)
+    blocks = torch.tensor([n * n for n in sizes], dtype=torch.int64)
+    eoff = (blocks.cumsum(0) - blocks).to(dev)
+    offset = ends.to(torch.int32).to(dev)
+    cloud_of_row = torch.repeat_interleave(torch.arange(len(sizes), dtype=torch.int32), torch.tensor(sizes)).to(dev)
+    etot = int(blocks.sum())
+    pts = points.contiguous().float()
+    d_idx = torch.empty((etot,), dtype=torch.float32, device=dev)
+    a_idx = torch.empty((etot, angle_k), dtype=torch.float32, device=dev)
+    L.check(L.lib().roitr_geo_indices(int(ends[-1]), L.ptr(pts), L.ptr(offset), L.ptr(cloud_of_row), L.ptr(eoff), L.c_float(sigma_d),
+                                      L.c_float(sigma_a), int(angle_k), max(sizes), L.ptr(d_idx), L.ptr(a_idx), L.stream_ptr()),
+            "geo_indices")
+    return d_idx, a_idx

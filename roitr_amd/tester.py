@@ -84,11 +84,11 @@ class Tester:
                 ids, items, pairs, handle = nxt
                 # the next batch is loaded and enqueued before this one is unpacked and written to disk
                 nxt = load(starts[k + 1]) if k + 1 < len(starts) else None
+                outs = self.model.finish_batch(handle)
                 aux = None
-                if evaluator is not None:
+                if evaluator is not None:   # after finish_batch: an overfull 4DMatch call has been repeated into the handle
                     ir, pir, _, _ = evaluator.evaluate_batch(handle)
                     aux = torch.stack([ir.float(), pir.float()], 1)
-                outs = self.model.finish_batch(handle)
                 blocks.append(self.model.batch_records(handle, ids, aux))
                 for idx, it, p, o in zip(ids, items, pairs, outs):
                     data = dict()  # lib/tester.py:56-69

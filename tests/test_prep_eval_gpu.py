@@ -123,3 +123,82 @@ def test_tester_evaluates_and_estimates_normals(tmp_path):
         irs.append(eval_ref.inlier_ratio(d["src_corr_pts"].numpy(), d["tgt_corr_pts"].numpy(), d["rot"].numpy().reshape(3, 3),
                                          d["trans"].numpy().reshape(3), 0.1))
     assert abs(np.mean(irs) - t.metrics["IR"]) < 1e-6
+
+
+def _check_batch_against_oracle(ev, res, pairs, ir, pir, n_fine, n_coarse):
+    from oracle import eval_ref
+    c = lambda t: t.detach().cpu().numpy()
+    for b, (r, p) in enumerate(zip(res, pairs)):
+        ir_ref = eval_ref.inlier_ratio(c(r["src_corr_points"]), c(r["tgt_corr_points"]), c(p["rot"]).reshape(3, 3), c(p["trans"]).reshape(3),
+                                       ev.acceptance_radius)
+        assert abs(float(ir[b]) - ir_ref) < 1e-6 and int(n_fine[b]) == r["corr_scores"].shape[0], (b, float(ir[b]), ir_ref)
+        assert int(n_coarse[b]) == r["src_node_corr_indices"].shape[0]
+        pir_ref = eval_ref.coarse_precision(r["tgt_nodes"].shape[0], r["src_nodes"].shape[0], c(r["gt_node_corr_indices"]),
+                                            c(r["gt_node_corr_overlaps"]), c(r["tgt_node_corr_indices"]), c(r["src_node_corr_indices"]),
+                                            ev.acceptance_overlap)
+        assert abs(float(pir[b]) - pir_ref) < 1e-6, (b, float(pir[b]), pir_ref)
+
+
+@pytest.mark.parametrize("sizes,slots_per_pair", [((1500, 1024, 2048), None), ((3100, 1500), None), ((1500, 3100, 1024), 4)],
+                         ids=["P<=2048", "P>2048", "overfull-repeated"])
+def test_evaluate_batch_on_the_4dmatch_layout_equals_per_pair_oracle(sizes, slots_per_pair):
+    """4DMatch keeps the patches of a call back to back (S = B * min(P, patch_slots_per_pair) slots, P = n4max^2), so the first
+    output row of pair b is not at patch slot b * P: evaluate_batch takes it from pair_starts.  Cases: P <= 2048 (the strided read
+    would succeed and read the wrong slots), P > 2048 (a 3100-point pair: the strided view does not even exist), and buffers far too
+    small, so finish_batch repeats the call and evaluate_batch (called after it) sees the repeated call's outputs."""
+    import warnings
+
+    from roitr_amd.evaluate import Evaluator
+    from roitr_amd.synthetic import make_pair
+    from tests.gpu_util import build_model, pair_to_device
+    model = build_model("4DMatch", weights="selective")
+    if slots_per_pair is not None:
+        model.patch_slots_per_pair = slots_per_pair
+    pairs = [pair_to_device(make_pair(n, config=4, pair_index=70 + i, normals="field")) for i, n in enumerate(sizes)]
+    ev = Evaluator(dict(eval_acceptance_overlap=0.0, eval_acceptance_radius=0.1))
+    with torch.no_grad(), warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        h = model.launch_batch(pairs, want_gt=True)
+        res = model.finish_batch(h)
+        ir, pir, n_fine, n_coarse = ev.evaluate_batch(h)
+    assert (slots_per_pair is not None) == any("repeating the call" in str(x.message) for x in w)
+    assert min(r["corr_scores"].shape[0] for r in res) > 0        # fine correspondences in every pair: the IRs mean something
+    _check_batch_against_oracle(ev, res, pairs, ir, pir, n_fine, n_coarse)
+
+
+def test_tester_evaluates_4dmatch_after_a_repeated_call(tmp_path):
+    """Tester(evaluate=True) on 4DMatch with patch buffers too small for the call: the per-pair IR / PIR records equal the per-pair
+    oracle on the saved result files (IR) and on the same pairs' outputs (PIR)."""
+    import warnings
+
+    from oracle import eval_ref
+    from roitr_amd.config import test_config
+    from roitr_amd.evaluate import Evaluator
+    from roitr_amd.synthetic import make_pair
+    from roitr_amd.tester import Tester
+    from tests.gpu_util import build_model, pair_to_device
+    cfg = test_config("4DMatch")
+    model = build_model("4DMatch", weights="selective")
+    model.patch_slots_per_pair = 4
+    raw = [make_pair(n, config=4, pair_index=80 + i, normals="field") for i, n in enumerate((1500, 1024, 2048))]
+    data = [{k: torch.from_numpy(v) for k, v in p.items()} for p in raw]
+    t = Tester(cfg, model, data, str(tmp_path), pairs_per_forward=3, evaluate=True)
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        t.test()
+    assert any("repeating the call" in str(x.message) for x in w)
+    ev = Evaluator(cfg)
+    with torch.no_grad():
+        res = build_model("4DMatch", weights="selective").forward_batch([pair_to_device(p) for p in raw])
+    assert t.metrics["pairs"] == 3
+    for i, r in enumerate(res):
+        d = torch.load(tmp_path / "4DMatch" / f"{i}.pth")
+        assert d["src_corr_pts"].shape[0] > 0
+        ir_ref = eval_ref.inlier_ratio(d["src_corr_pts"].numpy(), d["tgt_corr_pts"].numpy(), d["rot"].numpy().reshape(3, 3),
+                                       d["trans"].numpy().reshape(3), ev.acceptance_radius)
+        c = lambda x: x.detach().cpu().numpy()
+        pir_ref = eval_ref.coarse_precision(r["tgt_nodes"].shape[0], r["src_nodes"].shape[0], c(r["gt_node_corr_indices"]),
+                                            c(r["gt_node_corr_overlaps"]), c(r["tgt_node_corr_indices"]), c(r["src_node_corr_indices"]),
+                                            ev.acceptance_overlap)
+        ir, pir = t.records.aux[i]
+        assert abs(ir - ir_ref) < 1e-6 and abs(pir - pir_ref) < 1e-6, (i, ir, ir_ref, pir, pir_ref)
