@@ -453,18 +453,27 @@ __global__ void patch_gather_kernel(RoitrPatch a, long total)
 constexpr int OTN = 65;
 constexpr float OT_FAST_SPREAD = 30.f;   // widest score range of a row (dustbin included) the exponential form takes
 // ACC += KV * (B of lane (row, (col - N) & 15)): the DPP row rotate rides as a source modifier of the FMA (hipcc emits a
-// separate v_mov_b32_dpp per term from the builtin, which doubles the VALU work of the loop).  B is always written
-// several instructions before its first use here (the three ds_bpermute sit in between), which covers the
-// VALU-write -> DPP-read hazard the assembler cannot see inside inline asm.
+// separate v_mov_b32_dpp per term from the builtin, which doubles the VALU work of the loop).  A DPP instruction needs 2 wait
+// states after a VALU write of any VGPR it reads, and nobody inserts them inside an asm statement: x gets them from the s_nop
+// in ot_dot64; the accumulators s1..s3 START with a v_mul_f32_dpp (ACC = KV * B, the accumulator is not read), so no
+// accumulator is ever read right after the compiler materialised its zero (tests/test_dpp_hazards_cpu.py checks the assembly).
+// Every product is >= 0, so the product alone has the bits of 0 + product.
 #define OT_FMAC_DPP(ACC, B, KV, N_) asm volatile("v_fmac_f32_dpp %0, %1, %2 row_ror:" #N_ " row_mask:0xf bank_mask:0xf" : "+v"(ACC) : "v"(B), "v"(KV))
+#define OT_MUL_DPP(ACC, B, KV, N_) asm volatile("v_mul_f32_dpp %0, %1, %2 row_ror:" #N_ " row_mask:0xf bank_mask:0xf" : "=v"(ACC) : "v"(B), "v"(KV))
 // s0..s3 += sum_n ror16<n>(B) * KARR[16 T + n]: one 16-lane row block of a 64-term dot product whose vector operand is
 // distributed over the lanes (lane j holds element j)
 #define OT_TERM(ACC, B, KARR, T_, N_) OT_FMAC_DPP(ACC, B, KARR[(T_) * 16 + (N_)], N_)
-#define OT_BLOCK(B, KARR, T_)                                                                                              \
-    s0 = fmaf(B, KARR[(T_) * 16], s0); OT_TERM(s1, B, KARR, T_, 1); OT_TERM(s2, B, KARR, T_, 2); OT_TERM(s3, B, KARR, T_, 3);     \
+#define OT_BLOCK_REST(B, KARR, T_)                                                                                         \
     OT_TERM(s0, B, KARR, T_, 4); OT_TERM(s1, B, KARR, T_, 5); OT_TERM(s2, B, KARR, T_, 6); OT_TERM(s3, B, KARR, T_, 7);     \
     OT_TERM(s0, B, KARR, T_, 8); OT_TERM(s1, B, KARR, T_, 9); OT_TERM(s2, B, KARR, T_, 10); OT_TERM(s3, B, KARR, T_, 11);   \
     OT_TERM(s0, B, KARR, T_, 12); OT_TERM(s1, B, KARR, T_, 13); OT_TERM(s2, B, KARR, T_, 14); OT_TERM(s3, B, KARR, T_, 15)
+#define OT_BLOCK(B, KARR, T_)                                                                                              \
+    s0 = fmaf(B, KARR[(T_) * 16], s0); OT_TERM(s1, B, KARR, T_, 1); OT_TERM(s2, B, KARR, T_, 2); OT_TERM(s3, B, KARR, T_, 3);     \
+    OT_BLOCK_REST(B, KARR, T_)
+// the first block: s1..s3 start with their first product
+#define OT_BLOCK_FIRST(B, KARR)                                                                                               \
+    s0 = fmaf(B, KARR[0], s0); OT_MUL_DPP(s1, B, KARR[1], 1); OT_MUL_DPP(s2, B, KARR[2], 2); OT_MUL_DPP(s3, B, KARR[3], 3);          \
+    OT_BLOCK_REST(B, KARR, 0)
 // K . x for the lane-distributed 64-vector x: the three other row blocks of x arrive by ds_bpermute (LDS crossbar, no
 // LDS storage), every product is then one DPP-modified FMA -- no LDS reads in the Sinkhorn loop at all
 __device__ __forceinline__ float ot_dot64(const float (&KARR)[64], float x, float init, int lane)
@@ -472,9 +481,9 @@ __device__ __forceinline__ float ot_dot64(const float (&KARR)[64], float x, floa
     const float x1 = __int_as_float(__builtin_amdgcn_ds_bpermute(((lane + 16) & 63) << 2, __float_as_int(x)));
     const float x2 = __int_as_float(__builtin_amdgcn_ds_bpermute(((lane + 32) & 63) << 2, __float_as_int(x)));
     const float x3 = __int_as_float(__builtin_amdgcn_ds_bpermute(((lane + 48) & 63) << 2, __float_as_int(x)));
-    float s0 = init, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    asm volatile("s_nop 1" : : "v"(x), "v"(s1), "v"(s2), "v"(s3));   // 2 wait states between the VALU write of x and its first DPP read
-    OT_BLOCK(x, KARR, 0);
+    float s0 = init, s1, s2, s3;
+    asm volatile("s_nop 1" : : "v"(x));   // 2 wait states between the VALU write of x and its first DPP read
+    OT_BLOCK_FIRST(x, KARR);
     OT_BLOCK(x1, KARR, 1);
     OT_BLOCK(x2, KARR, 2);
     OT_BLOCK(x3, KARR, 3);
@@ -722,9 +731,11 @@ __global__ __launch_bounds__(256) void fine_flag_kernel(RoitrFine a)
     for (int e = tid; e < L * L; e += 256) { const int i = e >> 6, j = e & 63; E[i][j] = expf(sc[i * (L + 1) + j]); }
     __syncthreads();
     if (a.k <= 4) {
-        // wave 0: lane = row, wave 1: lane = column.  One pass over the 64 entries keeps the k best in registers (strict >
-        // against entries met earlier: the lower index stays ahead among equals, the order topk_mask peels them off in);
-        // E[lane][j] / E[j][lane] are conflict-free (row pitch 65).  ~64 x 12 VALU per wave instead of 96 wave-wide maxima.
+        // wave 0: lane = row, wave 1: lane = column.  One pass over the 64 entries keeps the k best in registers, ordered by
+        // (value descending, index ascending): the lower index stays ahead among equals, the order topk_mask peels them off in.
+        // The index decides ties explicitly: an entry pushed down the list by a larger newcomer has a LOWER index than an
+        // equal entry met after it, so a plain strict > would leave it behind that entry (and outside the k at the boundary).
+        // E[lane][j] / E[j][lane] are conflict-free (row pitch 65).  ~64 x 16 VALU per wave instead of 96 wave-wide maxima.
         if (wave < 2) {
             float bv[4] = {-1.f, -1.f, -1.f, -1.f};
             int bi[4] = {0, 0, 0, 0};
@@ -734,7 +745,7 @@ __global__ __launch_bounds__(256) void fine_flag_kernel(RoitrFine a)
                 int xi = j;
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    const bool up = x > bv[t];
+                    const bool up = x > bv[t] || (x == bv[t] && xi < bi[t]);
                     const float tv = bv[t]; const int ti = bi[t];
                     bv[t] = up ? x : tv; bi[t] = up ? xi : ti;
                     x = up ? tv : x; xi = up ? ti : xi;
