@@ -505,6 +505,50 @@ int roitr_coarse_hits(int pairs, int num_corr, const int* n_corr, const int* tgt
                       const int* gt_idx, const float* gt_overlaps, const int* gt_count, float acceptance_overlap, int* hits,
                       roitr_stream_t stream);
 
+
+/* ------------------------------------------------------------------ registration, batched over pairs
+ * registration/evaluate_registration_c2f.py:78-85 + registration/benchmark_utils.py:169-215 (Open3D correspondence RANSAC) and
+ * lib/utils.py:159-212 (weighted_procrustes).  Pair b owns rows [starts[b], starts[b+1]) of src_pts / tgt_pts / scores
+ * (fp32 (N,3), (N,3), (N); scores may be NULL = all 1), the layout RoitrForwardIO::pair_starts / out_*_pts / out_scores has.
+ * total_rows >= starts[pairs] (rows past it are never read).
+ *
+ * Random stream (registration_math.h): splitmix64 s(x); hypothesis draw d of iteration i of the pair with key k:
+ *   u = hi32(s(seed ^ s(k << 32 | i << 4 | d))), index = (u * n) >> 32; draws 0..15 in order, an index already taken is skipped,
+ *   the first three distinct ones are the triple (none after draw 15: the iteration is invalid).
+ * Selection (sample_mode): 0 all rows; 1 the n_points largest scores (ties: lower index); 2 n_points rows without replacement with
+ *   probability proportional to the score (Efraimidis-Spirakis: the n_points largest log(v_j) / w_j, ties: lower index,
+ *   v_j = (hi32(s(seed ^ 0xA0761D6478BD642F ^ s(k << 32 | j))) + 0.5) / 2^32, j the row's index in the pair).  Rows with a score
+ *   <= 0 (or not finite) are never drawn in mode 2; with fewer than n_points of them all are taken (numpy's choice would raise).
+ * Hypothesis of iteration i: the triple; edge checker: reject if |s_i - s_j| < sim |t_i - t_j| or |t_i - t_j| < sim |s_i - s_j|;
+ *   degenerate triangles rejected (|a x b|^2 <= 1e-12 |a|^2 |b|^2 in source or target); float64 Kabsch (proper rotation);
+ *   distance checker: every sample with ||R s + t - g||^2 <= thr^2 (fp32).  Valid hypotheses are scored over all selected rows:
+ *   inliers = #{ ||R s + t - g||^2 < thr^2 } (fp32), ties broken by the smaller sum of inlier d^2, then the lower iteration.
+ * refine_iters rounds of Procrustes on the current inlier set (unweighted, or weighted by the score with refine_weighted).
+ * Outputs per pair: transforms (B,4,4) row-major, inliers (count under the final transform), best_iteration (-1: none),
+ * valid_hypotheses (passed both checkers), n_used (selected rows), selected (optional, int32 (total_rows)): the selected rows'
+ * local indices at [starts[b], starts[b] + n_used[b]) in increasing order.  No valid hypothesis (or fewer than 3 rows): identity,
+ * inliers 0, valid_hypotheses 0.
+ * chunks: hypothesis workgroups per pair (0: automatic); results do not depend on it.  The workspace (device, caller-owned) holds at
+ * least roitr_registration_workspace_bytes(pairs, total_rows, iterations, chunks) bytes.
+ * Refusals: ransac_n != 3 -> ROITR_ERR_UNSUPPORTED; iterations outside [1, 2^28], thresholds not finite and positive,
+ * edge_similarity outside (0, 1], null pointers, a short workspace -> ROITR_ERR_ARG. */
+size_t roitr_registration_workspace_bytes(int pairs, int total_rows, int iterations, int chunks);
+int roitr_ransac_correspondences(int pairs, const int* starts, int total_rows, const float* src_pts, const float* tgt_pts,
+                                 const float* scores, const unsigned int* pair_keys, int sample_mode, int n_points, int ransac_n,
+                                 float distance_threshold, float edge_similarity, int iterations, int refine_iters, int refine_weighted,
+                                 unsigned long long seed, int chunks, void* workspace, size_t workspace_bytes, float* transforms,
+                                 int* inliers, int* best_iteration, int* valid_hypotheses, int* n_used, int* selected,
+                                 roitr_stream_t stream);
+/* The triples of iterations [it0, it0 + count) for each pair (n[b] rows, key pair_keys[b]): out (pairs, count, 3) int32, -1 for an
+ * invalid iteration or n[b] < 3.  Device pointers; the stream above bit for bit. */
+int roitr_ransac_samples(int pairs, const int* n, const unsigned int* pair_keys, unsigned long long seed, int it0, int count, int* out,
+                         roitr_stream_t stream);
+/* lib/utils.py:159-212 weighted_procrustes on dense (batch, n, 3) src / tgt and (batch, n) weights (NULL = all 1): weights below
+ * weight_thresh count 0, centroids sum(w p) / (sum w + eps), H = sum w (s - cs)(t - ct)^T, the rotation with the sign(det) fix,
+ * t = ct - R cs; transforms (batch, 4, 4). */
+int roitr_weighted_procrustes(int batch, int n, const float* src_pts, const float* tgt_pts, const float* weights, float weight_thresh,
+                              float eps, float* transforms, roitr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

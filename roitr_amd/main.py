@@ -26,6 +26,10 @@ def main():
     ap.add_argument("--pairs-per-forward", type=int, default=8)
     ap.add_argument("--evaluate", action="store_true", help="report mean PIR / IR (lib/loss.py Evaluator) computed on the device")
     ap.add_argument("--estimate-normals", action="store_true", help="recompute the normals on the GPU (open3d knn=33 + normal_redirect)")
+    ap.add_argument("--register", action="store_true",
+                    help="estimate every pair's pose on the GPU (correspondence RANSAC, registration.py) and save it as est_transform")
+    ap.add_argument("--ransac-iterations", type=int, default=50000)
+    ap.add_argument("--ransac-points", type=int, default=1000, help="correspondences drawn per pair (probability ~ confidence)")
     args = ap.parse_args()
     config = Config(load_config(args.config))
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
@@ -49,15 +53,37 @@ def main():
         print("[roitr_amd] no checkpoint given: using closed-form weights (roitr_amd/weights.py)")
     data = SyntheticPairs(args.synthetic, args.n_points)
     tester = Tester(config, model, data, args.snapshot_dir, args.pairs_per_forward, rank, world, evaluate=args.evaluate,
-                    estimate_normals=args.estimate_normals)
+                    estimate_normals=args.estimate_normals, register=args.register,
+                    ransac=dict(iterations=args.ransac_iterations, n_points=args.ransac_points))
     counts = tester.test()
     if rank == 0 and tester.metrics:
         print(f"[roitr_amd] PIR {tester.metrics['PIR']:.4f}  IR {tester.metrics['IR']:.4f}  over {tester.metrics['pairs']} pairs")
+    if args.register and args.evaluate:
+        _print_registration(tester.registration, world)
     if rank == 0:
         print(f"[roitr_amd] wrote {args.synthetic} result files under {args.snapshot_dir}/{config.benchmark}; "
               f"correspondences per rank: {counts}")
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def _print_registration(reg, world):
+    """Mean / median RRE and RTE and the share of pairs within 15 deg / 0.3 m, over every rank's pairs (rank 0 prints)."""
+    import numpy as np
+    rows = [(k,) + v for k, v in sorted(reg.items())]
+    if world > 1:
+        allrows = [None] * world
+        torch.distributed.all_gather_object(allrows, rows)
+        rows = [r for part in allrows for r in part]
+    if int(os.environ.get("RANK", 0)) != 0 or not rows:
+        return
+    rre = np.array([r[1] for r in rows])
+    rte = np.array([r[2] for r in rows])
+    ok = float(np.mean((rre < 15.0) & (rte < 0.3)))
+    print(f"[roitr_amd] registration over {len(rows)} pairs: RRE mean {rre.mean():.3f} deg, median {np.median(rre):.3f} deg; "
+          f"RTE mean {rte.mean():.4f} m, median {np.median(rte):.4f} m")
+    print(f"[roitr_amd] pairs with RRE < 15 deg and RTE < 0.3 m: {ok:.4f} (a pose-error success rate, not the 3DMatch-protocol "
+          "registration recall, which needs the benchmark's gt.info)")
 
 
 if __name__ == "__main__":

@@ -28,15 +28,20 @@ def load_pretrain(model, path):
 
 class Tester:
     def __init__(self, config, model, dataset, snapshot_dir="snapshot", pairs_per_forward=8, rank=0, world=1, evaluate=False,
-                 estimate_normals=False, view_point=(0.0, 0.0, 0.0)):
+                 estimate_normals=False, view_point=(0.0, 0.0, 0.0), register=False, ransac=None):
         """evaluate: also compute PIR / IR per pair on the device (lib/loss.py:169-213 Evaluator) and return their means.
         estimate_normals: ignore the dataset's normals and recompute them on the GPU from the points the way the
-        reference's dataset code does (open3d estimate_normals(knn=33) + normal_redirect, dataset/tdmatch.py:120-127)."""
+        reference's dataset code does (open3d estimate_normals(knn=33) + normal_redirect, dataset/tdmatch.py:120-127).
+        register: also estimate every pair's pose on the device (registration.register_handle, keyed on the GLOBAL pair id, so the
+        poses do not depend on sharding or pairs_per_forward; `ransac` holds its keyword arguments) and save it as `est_transform`
+        in the pair's file.  With evaluate as well, `registration` maps this rank's pair ids to (RRE degrees, RTE metres, inliers)."""
         self.config, self.model, self.dataset = config, model, dataset
         self.snapshot_dir = snapshot_dir
         self.pairs_per_forward = pairs_per_forward
         self.rank, self.world = rank, world
         self.evaluate, self.estimate_normals, self.view_point = evaluate, estimate_normals, view_point
+        self.register, self.ransac = register, dict(ransac or {})
+        self.registration = {} if register and evaluate else None
         self.metrics = None
         self.records = None   # rank 0 after test(): shard.GatheredRecords {pair id: match scores}
 
@@ -90,7 +95,18 @@ class Tester:
                     ir, pir, _, _ = evaluator.evaluate_batch(handle)
                     aux = torch.stack([ir.float(), pir.float()], 1)
                 blocks.append(self.model.batch_records(handle, ids, aux))
-                for idx, it, p, o in zip(ids, items, pairs, outs):
+                est = None
+                if self.register:
+                    from .registration import pose_errors, register_handle
+                    reg = register_handle(handle, pair_keys=ids, **self.ransac)
+                    est = reg["T"].cpu()
+                    if self.registration is not None:
+                        rre, rte = pose_errors(est, torch.stack([p["rot"].reshape(3, 3) for p in pairs]),
+                                               torch.stack([p["trans"].reshape(3) for p in pairs]))
+                        inl = reg["inliers"].cpu().tolist()
+                        for k, idx in enumerate(ids):
+                            self.registration[idx] = (float(rre[k]), float(rte[k]), int(inl[k]))
+                for k_pair, (idx, it, p, o) in enumerate(zip(ids, items, pairs, outs)):
                     data = dict()  # lib/tester.py:56-69
                     data["src_raw_pcd"] = p["src_raw_pcd"].cpu()
                     data["src_pcd"], data["tgt_pcd"] = p["src_pcd"].cpu(), p["tgt_pcd"].cpu()
@@ -104,6 +120,8 @@ class Tester:
                     data["rot"], data["trans"] = p["rot"].cpu(), p["trans"].cpu()
                     if benchmark in ("4DMatch", "4DLoMatch") and "metric_index" in it:
                         data["metric_index_list"] = it["metric_index"]
+                    if est is not None:
+                        data["est_transform"] = est[k_pair]
                     torch.save(data, os.path.join(out_dir, f"{idx}.pth"))
         # ---- the one collective of the run: every rank's records -> rank 0 (RCCL over xGMI under torch.distributed.run)
         per_pair = self.model.record_scores_per_pair()
