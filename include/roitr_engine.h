@@ -359,6 +359,10 @@ typedef struct RoitrFine {
     int* pair_starts;                 /* optional (pairs + 1): first output row of every pair, then the total */
 } RoitrFine;
 int roitr_fine_matching(const RoitrFine* a, roitr_stream_t stream);
+/* roitr_optimal_transport(o) followed by roitr_fine_matching(f), bit for bit, with the flag stage done by the transport kernels (the
+ * transport output is not read back, one launch less).  o and f must describe the same patch list (pairs, num_corr, limit, n_corr,
+ * row / column masks, pair_off, slots) and f->ot must be o->out: ROITR_ERR_ARG otherwise. */
+int roitr_matching_tail(const RoitrOT* o, const RoitrFine* f, roitr_stream_t stream);
 
 /* ------------------------------------------------------------------ ground-truth side outputs (need rot/trans) */
 /* Padded clouds for lib/utils.py:506-510: out_pts has n_points + 2*pairs rows -- every cloud followed by its pad row

@@ -1708,14 +1708,11 @@ static int forward_body(void* h, const RoitrForwardIO* io, hipStream_t st)
         }
         CHK(roitr_gemm(&g, st));
     }
-    {
+    {   // optimal transport and fine matching: the transport wave of a patch also sets the patch's flags (roitr_matching_tail)
         RoitrOT o; memset(&o, 0, sizeof(o));
         o.pairs = B; o.num_corr = P_; o.limit = LIM; o.num_iter = 100; o.n_corr = n_corr; o.scores = mscore; o.row_masks = tmask;
         o.col_masks = smask; o.alpha = E.ot_alpha; o.out = ot;
         o.pair_off = pair_off; o.slots = compact ? (int)NP : 0;
-        CHK(roitr_optimal_transport(&o, st));
-    }
-    {
         RoitrFine fm; memset(&fm, 0, sizeof(fm));
         fm.pairs = B; fm.num_corr = P_; fm.limit = LIM; fm.k = E.cfg.fine_topk; fm.mutual = E.cfg.fine_mutual; fm.conf = E.cfg.fine_conf;
         fm.n_corr = n_corr; fm.ot = ot; fm.row_masks = tmask; fm.col_masks = smask; fm.row_pts = tpts; fm.col_pts = spts;
@@ -1723,7 +1720,7 @@ static int forward_body(void* h, const RoitrForwardIO* io, hipStream_t st)
         fm.flags = flags; fm.counts = counts; fm.offsets = offsets; fm.n_out = n_out;
         fm.out_row_pts = o_t; fm.out_col_pts = o_s; fm.out_scores = o_sc; fm.out_patch = io->out_patch; fm.out_cap = (long)cap;
         fm.pair_off = pair_off; fm.slots = compact ? (int)NP : 0; fm.pair_starts = io->pair_starts;
-        CHK(roitr_fine_matching(&fm, st));
+        CHK(roitr_matching_tail(&o, &fm, st));
     }
     roitr_prof_end(ROITR_PROF_PH_MATCH, st);
     roitr_prof_end(ROITR_PROF_PH_FORWARD, st);

@@ -474,6 +474,85 @@ constexpr float OT_FAST_SPREAD = 30.f;   // widest score range of a row (dustbin
 #define OT_BLOCK_FIRST(B, KARR)                                                                                               \
     s0 = fmaf(B, KARR[0], s0); OT_MUL_DPP(s1, B, KARR[1], 1); OT_MUL_DPP(s2, B, KARR[2], 2); OT_MUL_DPP(s3, B, KARR[3], 3);          \
     OT_BLOCK_REST(B, KARR, 0)
+// ------------------------------------------------------------------ flags of a patch by the wave that holds its transport tile
+// fine_flag_kernel's selection done by ONE wave (lane = row, then lane = column) on an LDS tile E = exp(ot[:64, :64]) that the
+// optimal-transport wave filled from the very values it stored: the `ot` read-back (17 KB per patch) and one launch disappear.
+// Same decisions as fine_flag_kernel, bit for bit: the k best by (value descending, index ascending), confidence threshold, row /
+// column masks, mutual and / or, 16-byte flag words, per-patch count.  FK = 1..4: k = FK, the k best in registers; FK = 5: any k
+// by wave maxima (topk_mask).  No LDS besides E: the row mask of row l and the column mask of column l stay in lane l.
+struct OtFlags { int k, mutual; float conf; unsigned char* flags; int* counts; };
+__device__ __forceinline__ unsigned long long topk_mask(float v, int k, float conf);
+
+// One pass over a row (ROWS) or a column of E, the K best kept sorted.  The entries arrive in index order, so a newcomer goes behind
+// every kept entry that is >= it (strict >), and the entries it displaces move down one place without a comparison: they were
+// ordered among themselves.  That is the list fine_flag_kernel's compare-and-swap cascade keeps.
+template <int K, bool ROWS>
+__device__ __forceinline__ unsigned long long topk_regs(const float (*E)[OTN], int lane, float conf)
+{
+    float bv[K]; int bi[K];
+#pragma unroll
+    for (int t = 0; t < K; ++t) { bv[t] = -1.f; bi[t] = 0; }
+#pragma unroll 8
+    for (int j = 0; j < 64; ++j) {
+        const float x = ROWS ? E[lane][j] : E[j][lane];
+        bool c[K];
+#pragma unroll
+        for (int t = 0; t < K; ++t) c[t] = x > bv[t];
+#pragma unroll
+        for (int t = K - 1; t >= 0; --t) {
+            const bool shift = t > 0 && c[t > 0 ? t - 1 : 0];   // the newcomer went in above: take the neighbour's entry
+            const float nv = shift ? bv[t > 0 ? t - 1 : 0] : x;
+            const int ni = shift ? bi[t > 0 ? t - 1 : 0] : j;
+            bv[t] = c[t] ? nv : bv[t]; bi[t] = c[t] ? ni : bi[t];
+        }
+    }
+    unsigned long long m = 0ull;
+#pragma unroll
+    for (int t = 0; t < K; ++t)
+        if (bv[t] >= 0.f && bv[t] > conf) m |= 1ull << bi[t];
+    return m;
+}
+
+// rml: this lane's row is valid; cbits: the valid columns.  All 64 lanes arrive together, E complete.
+template <int FK>
+__device__ __forceinline__ void patch_flags(const float (*E)[OTN], const OtFlags& f, int patch, int lane, bool rml, unsigned long long cbits)
+{
+    unsigned long long rm = 0ull, cm = 0ull;   // lane l: winners of row l (bit = column), winners of column l (bit = row)
+    if constexpr (FK <= 4) {
+        constexpr int K = FK <= 4 ? FK : 1;   // FK = 5 never gets here
+        rm = topk_regs<K, true>(E, lane, f.conf);
+        cm = topk_regs<K, false>(E, lane, f.conf);
+    } else {
+        for (int r = 0; r < 64; ++r) {
+            const unsigned long long mr = topk_mask(E[r][lane], f.k, f.conf);
+            const unsigned long long mc = topk_mask(E[lane][r], f.k, f.conf);
+            if (lane == r) { rm = mr; cm = mc; }
+        }
+    }
+    // the column winners seen from the rows: bit j of lane i = bit i of lane j
+    unsigned long long ct = 0ull;
+#pragma unroll
+    for (int i = 0; i < 64; ++i) {
+        const unsigned long long b = __ballot(((cm >> i) & 1ull) != 0ull);
+        if (lane == i) ct = b;
+    }
+    unsigned long long fm = f.mutual ? (rm & ct) : (rm | ct);
+    fm = rml ? (fm & cbits) : 0ull;
+    const int total = (int)wave_sum((float)__popcll(fm));   // <= 4096: exact
+    // 16-byte word t of the patch = row t / 4, columns 16 (t % 4) ..: consecutive lanes write consecutive words
+    uint4* fl16 = reinterpret_cast<uint4*>(f.flags + (size_t)patch * 64 * 64);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const unsigned long long fr = __shfl(fm, q * 16 + (lane >> 2), 64);
+        const unsigned b16 = (unsigned)(fr >> ((lane & 3) * 16)) & 0xffffu;
+        unsigned w[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) w[u] = (((b16 >> (4 * u)) & 0xfu) * 0x204081u) & 0x01010101u;   // bit n -> byte n
+        fl16[q * 64 + lane] = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    if (lane == 0) f.counts[patch] = total;
+}
+
 // K . x for the lane-distributed 64-vector x: the three other row blocks of x arrive by ds_bpermute (LDS crossbar, no
 // LDS storage), every product is then one DPP-modified FMA -- no LDS reads in the Sinkhorn loop at all
 __device__ __forceinline__ float ot_dot64(const float (&KARR)[64], float x, float init, int lane)
@@ -489,13 +568,20 @@ __device__ __forceinline__ float ot_dot64(const float (&KARR)[64], float x, floa
     OT_BLOCK(x3, KARR, 3);
     return (s0 + s1) + (s2 + s3);
 }
-__global__ __launch_bounds__(64) void ot_kernel(RoitrOT a, unsigned long long* stats)
+// FK = 0: the transport alone.  FK > 0: the patch's fine-matching flags and count too (patch_flags), from an LDS tile of
+// exp(out) in the place of T, which is dead once K' is in registers; dead slots get counts = 0.  A patch handed to ot_log_kernel
+// gets its flags there.  Register / LDS budget: see roitr_matching_tail.
+template <int FK>
+__global__ __launch_bounds__(64) void ot_kernel(RoitrOT a, unsigned long long* stats, OtFlags f)
 {
     __shared__ float T[64][65];
     __shared__ __attribute__((aligned(16))) float av[64];
     const int patch = blockIdx.x;
     const int lane = threadIdx.x;
-    if (a.pair_off ? patch >= a.pair_off[a.pairs] : (patch % a.num_corr) >= a.n_corr[patch / a.num_corr]) return;
+    if (a.pair_off ? patch >= a.pair_off[a.pairs] : (patch % a.num_corr) >= a.n_corr[patch / a.num_corr]) {
+        if (FK && lane == 0) f.counts[patch] = 0;   // the emitter leaves on counts == 0 before it reads the flags of a dead patch
+        return;
+    }
     float* out = a.out + (size_t)patch * OTN * OTN;
     const float alpha = *a.alpha;
     const float* sc = a.scores + (size_t)patch * 64 * 64;
@@ -584,11 +670,17 @@ __global__ __launch_bounds__(64) void ot_kernel(RoitrOT a, unsigned long long* s
 #pragma unroll 8
     for (int i = 0; i < 64; ++i) {
         const float sv = (cml && ((rbits >> i) & 1)) ? sc[i * 64 + lane] : -1e6f;
-        out[i * OTN + lane] = sv + av[i] + vl - norm;
+        const float o = sv + av[i] + vl - norm;
+        out[i * OTN + lane] = o;
+        if (FK) T[i][lane] = expf(o);   // what fine_flag_kernel would read back and exponentiate
     }
     out[64 * OTN + lane] = (cml ? alpha : -1e6f) + u64 + vl - norm;
     out[lane * OTN + 64] = (rml ? alpha : -1e6f) + ul + v64 - norm;
     if (lane == 0) out[64 * OTN + 64] = alpha + u64 + v64 - norm;
+    if constexpr (FK != 0) {
+        __syncthreads();
+        patch_flags<FK>(T, f, patch, lane, rml, cbits);
+    }
 }
 
 // The reference's iteration verbatim, in the log domain (modules.py:21-27): u = log_mu - logsumexp_j(S + v), v = log_nu -
@@ -636,9 +728,11 @@ __device__ __forceinline__ float ot_lse_wave(float x, float extra)
     return mx + __logf(wave_sum(__expf(x - mx)) + __expf(extra - mx));
 }
 
-__global__ __launch_bounds__(64) void ot_log_kernel(RoitrOT a, unsigned long long* stats)
+template <int FK>
+__global__ __launch_bounds__(64) void ot_log_kernel(RoitrOT a, unsigned long long* stats, OtFlags f)
 {
     __shared__ float T[64][65];
+    __shared__ float uv[64];
     const int patch = blockIdx.x;
     const int lane = threadIdx.x;
     if (a.pair_off ? patch >= a.pair_off[a.pairs] : (patch % a.num_corr) >= a.n_corr[patch / a.num_corr]) return;
@@ -683,16 +777,22 @@ __global__ __launch_bounds__(64) void ot_log_kernel(RoitrOT a, unsigned long lon
         vl = vn;
     }
     __syncthreads();
-    T[0][lane] = ul;   // row 0 of the tile is free now: u by row index
+    uv[lane] = ul;   // u by row index
     __syncthreads();
 #pragma unroll 8
     for (int i = 0; i < 64; ++i) {
         const float sv = (cml && ((rbits >> i) & 1)) ? sc[i * 64 + lane] : NINF;
-        out[i * OTN + lane] = sv + T[0][i] + vl - norm;
+        const float o = sv + uv[i] + vl - norm;
+        out[i * OTN + lane] = o;
+        if (FK) T[i][lane] = expf(o);   // the tile is free now
     }
     out[64 * OTN + lane] = sdr + u64 + vl - norm;
     out[lane * OTN + 64] = srd + ul + v64 - norm;
     if (lane == 0) out[64 * OTN + 64] = alpha + u64 + v64 - norm;
+    if constexpr (FK != 0) {
+        __syncthreads();
+        patch_flags<FK>(T, f, patch, lane, rml, cbits);
+    }
 }
 
 // ------------------------------------------------------------------ FineMatching (modules.py:216-324)
@@ -1000,8 +1100,8 @@ extern "C" int roitr_optimal_transport(const RoitrOT* a, hipStream_t stream)
     // data-dependent work of this stage (roitr_ot_stats): live patches, Sinkhorn iterations skipped by the exact fixed-point exit,
     // patches the exponential form handed to the log-domain kernel
     unsigned long long* sd = ot_stats().for_current_device();
-    ot_kernel<<<patches, 64, 0, stream>>>(*a, sd);
-    ot_log_kernel<<<patches, 64, 0, stream>>>(*a, sd);   // the patches the exponential form declined; the others leave at once
+    ot_kernel<0><<<patches, 64, 0, stream>>>(*a, sd, OtFlags{});
+    ot_log_kernel<0><<<patches, 64, 0, stream>>>(*a, sd, OtFlags{});   // the patches the exponential form declined; the others leave at once
     roitr_prof_end(ROITR_PROF_OT, stream);
     ROITR_LAUNCH_CHECK();
     return ROITR_OK;
@@ -1022,6 +1122,57 @@ extern "C" int roitr_fine_matching(const RoitrFine* a, hipStream_t stream)
     fine_scan_kernel<<<1, 1024, 0, stream>>>(patches, a->counts, a->offsets, a->n_out, a->out_cap, a->pairs, a->num_corr, a->pair_off, a->pair_starts);
     ROITR_LAUNCH_CHECK();
     fine_emit_kernel<<<patches, 256, 0, stream>>>(*a);
+    ROITR_LAUNCH_CHECK();
+    return ROITR_OK;
+}
+
+namespace {
+template <int FK>
+void launch_ot_flags(int patches, const RoitrOT& o, unsigned long long* sd, const OtFlags& f, hipStream_t stream)
+{
+    ot_kernel<FK><<<patches, 64, 0, stream>>>(o, sd, f);
+    ot_log_kernel<FK><<<patches, 64, 0, stream>>>(o, sd, f);
+}
+}  // namespace
+
+// roitr_optimal_transport + roitr_fine_matching with the flag stage inside the transport kernels: the wave that stores a patch's
+// 65 x 65 tile derives the patch's flags and count from the values it stores (patch_flags), so `ot` is not read back and
+// fine_flag_kernel is not launched; scan and emit as in roitr_fine_matching.  Bitwise the results of the two calls.
+// The two structs must describe the same patch list; f->ot is o->out.
+// Budget (hipcc resource report, gfx950): ot_kernel<1..5> 154 VGPRs (ot_kernel<0>: 153), no AGPRs, no scratch, 16 896 bytes of LDS
+// (the exp tile takes T's place, the masks stay in registers): 3 waves per SIMD by registers, 9 workgroups per CU by LDS, as before;
+// ot_log_kernel<1..5> 212 VGPRs, no scratch, the same LDS.  The epilogue is ~2.7 k VALU instructions per patch (64 expf, two
+// 64-entry top-k passes, the 64 x 64 bit transpose) on top of the ~19 k of the Sinkhorn loop.
+extern "C" int roitr_matching_tail(const RoitrOT* o, const RoitrFine* f, hipStream_t stream)
+{
+    if (o->pairs != f->pairs || o->num_corr != f->num_corr || o->limit != f->limit || o->n_corr != f->n_corr || o->pair_off != f->pair_off ||
+        o->slots != f->slots || o->row_masks != f->row_masks || o->col_masks != f->col_masks || o->out != f->ot)
+        return ROITR_ERR_ARG;
+    if (o->pairs <= 0) return ROITR_OK;
+    if (o->limit != 64) return ROITR_ERR_UNSUPPORTED;
+    const int patches = o->pair_off ? o->slots : o->pairs * o->num_corr;
+    if (patches <= 0 || f->k < 1) {   // nothing to fuse
+        const int rc = roitr_optimal_transport(o, stream);
+        return rc != ROITR_OK ? rc : roitr_fine_matching(f, stream);
+    }
+    // per patch: scores in, transport tile and flags out
+    const double bytes = (64.0 * 64 + 65.0 * 65) * 4.0 + 64.0 * 64;
+    if (o->pair_off) roitr_prof_begin_live(ROITR_PROF_OT, bytes, 0.0, o->pair_off + o->pairs, stream);
+    else roitr_prof_begin(ROITR_PROF_OT, (double)patches * bytes, stream);
+    unsigned long long* sd = ot_stats().for_current_device();
+    const OtFlags fl = {f->k, f->mutual, f->conf, f->flags, f->counts};
+    switch (f->k) {
+    case 1: launch_ot_flags<1>(patches, *o, sd, fl, stream); break;
+    case 2: launch_ot_flags<2>(patches, *o, sd, fl, stream); break;
+    case 3: launch_ot_flags<3>(patches, *o, sd, fl, stream); break;
+    case 4: launch_ot_flags<4>(patches, *o, sd, fl, stream); break;
+    default: launch_ot_flags<5>(patches, *o, sd, fl, stream); break;
+    }
+    roitr_prof_end(ROITR_PROF_OT, stream);
+    ROITR_LAUNCH_CHECK();
+    fine_scan_kernel<<<1, 1024, 0, stream>>>(patches, f->counts, f->offsets, f->n_out, f->out_cap, f->pairs, f->num_corr, f->pair_off, f->pair_starts);
+    ROITR_LAUNCH_CHECK();
+    fine_emit_kernel<<<patches, 256, 0, stream>>>(*f);
     ROITR_LAUNCH_CHECK();
     return ROITR_OK;
 }
