@@ -360,7 +360,7 @@ typedef struct RoitrFine {
 } RoitrFine;
 int roitr_fine_matching(const RoitrFine* a, roitr_stream_t stream);
 /* roitr_optimal_transport(o) followed by roitr_fine_matching(f), bit for bit, with the flag stage done by the transport kernels (the
- * transport output is not read back, one launch less).  o and f must describe the same patch list (pairs, num_corr, limit, n_corr,
+ * transport output is not read back, one launch less; the selection is the one roitr_fine_matching runs, for every k).  o and f must describe the same patch list (pairs, num_corr, limit, n_corr,
  * row / column masks, pair_off, slots) and f->ot must be o->out: ROITR_ERR_ARG otherwise. */
 int roitr_matching_tail(const RoitrOT* o, const RoitrFine* f, roitr_stream_t stream);
 

@@ -215,3 +215,38 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
     }
     return v;
 }
+
+// Inclusive prefix sum over the 64 lanes of a wave (all lanes call it).
+__device__ __forceinline__ int wave_incl_scan(int v)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(v, o, 64); if (lane >= o) v += t; }
+    return v;
+}
+// Inclusive prefix sum of v over a block of THREADS (a multiple of 64) threads, all of which call it: the sum of v over the thread
+// ids up to the caller's own.  wsum: THREADS / 64 ints of LDS, free again after the caller's next barrier.  One barrier.
+template <int THREADS>
+__device__ __forceinline__ int block_incl_scan(int v, int* wsum)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int incl = wave_incl_scan(v);
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int wb = 0;
+    for (int w = 0; w < wave; ++w) wb += wsum[w];
+    return wb + incl;
+}
+// The same over successive rounds of THREADS values each: everything counted up to and including v (minus v: the position of v's
+// first item in a compaction).  *carry_s (LDS) is the running total: zeroed, with a barrier, before the first round; after the last
+// round it holds the sum of all.  Three barriers.
+template <int THREADS>
+__device__ __forceinline__ int block_running_scan(int v, int* wsum, int* carry_s)
+{
+    const int incl = block_incl_scan<THREADS>(v, wsum);
+    const int end = *carry_s + incl;
+    __syncthreads();
+    if (threadIdx.x == THREADS - 1) *carry_s = end;
+    __syncthreads();
+    return end;
+}

@@ -6,6 +6,7 @@
 #include "common.h"
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include "prof.h"
 #include "roitr_engine.h"
 
@@ -33,14 +34,12 @@ __device__ __forceinline__ float square_distance3(float sx, float sy, float sz, 
 // ------------------------------------------------------------------ point_to_node_partition (lib/utils.py:428-471)
 // A: every point -> nearest node of its cloud (first minimum), distance kept for step B
 __global__ __launch_bounds__(256) void p2n_assign_kernel(int n_points, const float* __restrict__ pts, const int* __restrict__ pt_offset,
-                                                         const int* __restrict__ cloud_of_pt_hint, const float* __restrict__ nodes,
-                                                         const int* __restrict__ node_offset, int b, int* __restrict__ p2n,
-                                                         float* __restrict__ p2n_dist, int* __restrict__ node_masks)
+                                                         const float* __restrict__ nodes, const int* __restrict__ node_offset, int b,
+                                                         int* __restrict__ p2n, float* __restrict__ p2n_dist, int* __restrict__ node_masks)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n_points) return;
     const int c = segment_of(i, pt_offset, b);
-    (void)cloud_of_pt_hint;
     const int ns = c == 0 ? 0 : node_offset[c - 1], ne = node_offset[c];
     const float px = pts[(size_t)i * 3], py = pts[(size_t)i * 3 + 1], pz = pts[(size_t)i * 3 + 2];
     const float p2 = sq_norm3(px, py, pz);
@@ -53,6 +52,26 @@ __global__ __launch_bounds__(256) void p2n_assign_kernel(int n_points, const flo
     p2n[i] = bi - ns;  // node index local to the cloud, as the reference returns it
     p2n_dist[i] = best;
     node_masks[bi] = 1;
+}
+
+// ascending bitonic sort of keys[0..cap) in LDS, cap a power of two, by a block of THREADS threads; the keys are in place (barrier)
+// before the call and sorted (barrier) after it
+template <int THREADS>
+__device__ __forceinline__ void block_bitonic_sort(unsigned long long* keys, int cap, int tid)
+{
+    for (int k = 2; k <= cap; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int e = tid; e < cap; e += THREADS) {
+                const int p = e ^ j;
+                if (p > e) {
+                    const unsigned long long x = keys[e], y = keys[p];
+                    const bool up = (e & k) == 0;
+                    if ((x > y) == up) { keys[e] = y; keys[p] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    }
 }
 
 // B: one block per node: the `limit` nearest OWNED points, ascending (distance, index); pad = n_c (cloud size).
@@ -88,19 +107,7 @@ __global__ __launch_bounds__(256) void p2n_topk_kernel(const int* __restrict__ p
         while (cap < count) cap <<= 1;
         for (int e = count + tid; e < cap; e += 256) keys[e] = ~0ull;
         __syncthreads();
-        for (int k = 2; k <= cap; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int e = tid; e < cap; e += 256) {
-                    const int q = e ^ j;
-                    if (q > e) {
-                        const unsigned long long x = keys[e], y = keys[q];
-                        const bool up = (e & k) == 0;
-                        if ((x > y) == up) { keys[e] = y; keys[q] = x; }
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        block_bitonic_sort<256>(keys, cap, tid);
         for (int t = tid; t < limit; t += 256) {
             const bool ok = t < count;
             knn_idx[(size_t)node * limit + t] = ok ? (int)(unsigned)keys[t] : (pe - ps);
@@ -141,23 +148,6 @@ constexpr int COARSE_LDS_KEYS = 16384;   // 128 KB of 64-bit keys
 // of a 30000-point cloud): the keys are sorted in LDS-sized chunks, every chunk contributes its W = pow2(want) smallest to
 // `spill` (global), and the spilled winners are reduced the same way until they fit -- the result is exactly the
 // `want` smallest keys of the whole set, ascending, in keys[0..want).
-__device__ __forceinline__ void block_bitonic_sort(unsigned long long* keys, int cap, int tid)
-{
-    for (int k = 2; k <= cap; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int e = tid; e < cap; e += 1024) {
-                const int p = e ^ j;
-                if (p > e) {
-                    const unsigned long long x = keys[e], y = keys[p];
-                    const bool up = (e & k) == 0;
-                    if ((x > y) == up) { keys[e] = y; keys[p] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-}
-
 template <typename KeyFn>
 __device__ __forceinline__ void block_select_smallest(KeyFn key_of, int total, int want, unsigned long long* keys, int lds_cap,
                                                       unsigned long long* spill, int tid)
@@ -172,7 +162,7 @@ __device__ __forceinline__ void block_select_smallest(KeyFn key_of, int total, i
             while (cap < count) cap <<= 1;
             for (int e = tid; e < cap; e += 1024) keys[e] = e < count ? (from_spill ? spill[e] : key_of(e)) : ~0ull;
             __syncthreads();
-            block_bitonic_sort(keys, cap, tid);
+            block_bitonic_sort<1024>(keys, cap, tid);
             return;
         }
         const int nchunks = (count + lds_cap - 1) / lds_cap;
@@ -183,7 +173,7 @@ __device__ __forceinline__ void block_select_smallest(KeyFn key_of, int total, i
                 keys[e] = g < count ? (from_spill ? spill[g] : key_of(g)) : ~0ull;
             }
             __syncthreads();
-            block_bitonic_sort(keys, lds_cap, tid);
+            block_bitonic_sort<1024>(keys, lds_cap, tid);
             // chunk c's winners land at spill[c W ..): behind everything this and later chunks still read (W <= lds_cap)
             for (int e = tid; e < W; e += 1024) spill[(size_t)c * W + e] = keys[e];
             __syncthreads();
@@ -289,7 +279,7 @@ __global__ __launch_bounds__(1024) void adaptive_match_kernel(RoitrCoarse a, int
     const int sc = pair, tc = B + pair;
     const int s0 = sc == 0 ? 0 : a.node_offset[sc - 1], nsr = a.node_offset[sc] - s0;
     const int t0 = a.node_offset[tc - 1], nr = a.node_offset[tc] - t0;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     float* M = a.scratch + (size_t)pair * a.scratch_stride;
     const float* XY = a.xy + (size_t)pair * a.xy_stride;
     const int total = nr * nsr;
@@ -335,25 +325,12 @@ __global__ __launch_bounds__(1024) void adaptive_match_kernel(RoitrCoarse a, int
         const int e = base + tid;
         const float v = e < total ? M[e] : -1.f;
         const int f = (v >= 0.f && v <= threshold) ? 1 : 0;
-        int incl = f;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        int wb = 0;
-        for (int w = 0; w < wave; ++w) wb += wsum[w];
-        const int carry = carry_s;
-        if (f) {
-            const int pos = carry + wb + incl - 1;
-            if (pos < a.num_corr) {
-                a.tgt_corr[(size_t)pair * a.num_corr + pos] = e / nsr;
-                a.src_corr[(size_t)pair * a.num_corr + pos] = e % nsr;
-                a.corr_scores[(size_t)pair * a.num_corr + pos] = expf(-v);
-            }
+        const int pos = block_running_scan<1024>(f, wsum, &carry_s) - 1;
+        if (f && pos < a.num_corr) {
+            a.tgt_corr[(size_t)pair * a.num_corr + pos] = e / nsr;
+            a.src_corr[(size_t)pair * a.num_corr + pos] = e % nsr;
+            a.corr_scores[(size_t)pair * a.num_corr + pos] = expf(-v);
         }
-        __syncthreads();
-        if (tid == 1023) carry_s = carry + wb + incl;
-        __syncthreads();
     }
     if (tid == 0) a.n_corr[pair] = min(carry_s, a.num_corr);
 }
@@ -364,17 +341,23 @@ __global__ __launch_bounds__(1024) void adaptive_match_kernel(RoitrCoarse a, int
 // while p < n_corr[pair].  Compacted layout (round 6; the adaptive 4DMatch matching selects anything between 128 and n_t * n_s
 // node pairs per cloud pair, RIGA_v2.py:126-152 runs the tail on the SELECTED ones only): the live patches of all pairs back to
 // back, pair b owns slots [pair_off[b], pair_off[b + 1]); slots from pair_off[pairs] on are dead and never touched.
+// The liveness half alone (no search for the pair): what a per-patch kernel asks before it does anything.  patch_slot calls it inside
+// each branch: hoisted above them, hipcc tests pair_off twice (22 more instructions in patch_gather_kernel).
+__device__ __forceinline__ bool slot_live(int slot, int pairs, int num_corr, const int* __restrict__ n_corr, const int* __restrict__ pair_off)
+{
+    return pair_off ? slot < pair_off[pairs] : (slot % num_corr) < n_corr[slot / num_corr];
+}
 struct PatchSlot { int pair, p; bool live; };
 __device__ __forceinline__ PatchSlot patch_slot(int slot, int pairs, int num_corr, const int* __restrict__ n_corr, const int* __restrict__ pair_off)
 {
     PatchSlot r;
     if (pair_off) {
-        r.live = slot < pair_off[pairs];
+        r.live = slot_live(slot, pairs, num_corr, n_corr, pair_off);
         r.pair = r.live ? segment_of(slot, pair_off + 1, pairs) : 0;
         r.p = slot - pair_off[r.pair];
     } else {
         r.pair = slot / num_corr; r.p = slot % num_corr;
-        r.live = r.p < n_corr[r.pair];
+        r.live = slot_live(slot, pairs, num_corr, n_corr, pair_off);
     }
     return r;
 }
@@ -384,23 +367,13 @@ __global__ __launch_bounds__(1024) void patch_offsets_kernel(int pairs, const in
 {
     __shared__ int wsum[16];
     __shared__ int carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid == 0) { carry_s = 0; pair_off[0] = 0; }
     __syncthreads();
     for (int base = 0; base < pairs; base += 1024) {
         const int i = base + tid;
-        int incl = i < pairs ? n_corr[i] : 0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        int wb = 0;
-        for (int w = 0; w < wave; ++w) wb += wsum[w];
-        const int carry = carry_s;
-        if (i < pairs) pair_off[i + 1] = min(slots, carry + wb + incl);
-        __syncthreads();
-        if (tid == 1023) carry_s = carry + wb + incl;
-        __syncthreads();
+        const int upto = block_running_scan<1024>(i < pairs ? n_corr[i] : 0, wsum, &carry_s);
+        if (i < pairs) pair_off[i + 1] = min(slots, upto);
     }
 }
 
@@ -474,18 +447,34 @@ constexpr float OT_FAST_SPREAD = 30.f;   // widest score range of a row (dustbin
 #define OT_BLOCK_FIRST(B, KARR)                                                                                               \
     s0 = fmaf(B, KARR[0], s0); OT_MUL_DPP(s1, B, KARR[1], 1); OT_MUL_DPP(s2, B, KARR[2], 2); OT_MUL_DPP(s3, B, KARR[3], 3);          \
     OT_BLOCK_REST(B, KARR, 0)
-// ------------------------------------------------------------------ flags of a patch by the wave that holds its transport tile
-// fine_flag_kernel's selection done by ONE wave (lane = row, then lane = column) on an LDS tile E = exp(ot[:64, :64]) that the
-// optimal-transport wave filled from the very values it stored: the `ot` read-back (17 KB per patch) and one launch disappear.
-// Same decisions as fine_flag_kernel, bit for bit: the k best by (value descending, index ascending), confidence threshold, row /
-// column masks, mutual and / or, 16-byte flag words, per-patch count.  FK = 1..4: k = FK, the k best in registers; FK = 5: any k
-// by wave maxima (topk_mask).  No LDS besides E: the row mask of row l and the column mask of column l stay in lane l.
+// ------------------------------------------------------------------ fine-matching flags of a patch (modules.py:216-324)
+// THE flag selection, done by ONE wave (lane = row, then lane = column) on an LDS tile E = exp(ot[:64, :64]): mutual top-k on
+// exp(score), the k best by (value descending, index ascending), confidence threshold, row / column masks, mutual and / or, 16-byte
+// flag words, per-patch count.  Called by the optimal-transport wave on a tile filled from the very values it stored (no `ot`
+// read-back, 17 KB per patch, and no launch of its own) and by fine_flag_kernel on a tile read back from `ot`.  FK = 1..4: k = FK,
+// the k best in registers; FK = 5: any k by wave maxima (topk_mask; k <= 0 selects nothing).  No LDS besides E: the row mask of row l
+// and the column mask of column l stay in lane l.
 struct OtFlags { int k, mutual; float conf; unsigned char* flags; int* counts; };
-__device__ __forceinline__ unsigned long long topk_mask(float v, int k, float conf);
+
+// The wave owns a row (lane = column) or a column (lane = row) of E, one value per lane: the k best are peeled off with k wave maxima
+// (value descending, lower index first among equals -- the rank order the element-wise count would give); the winners above the
+// confidence threshold come back as one 64-bit mask.
+__device__ __forceinline__ unsigned long long topk_mask(float v, int k, float conf)
+{
+    const int lane = threadIdx.x & 63;
+    bool sel = false;
+    for (int t = 0; t < k; ++t) {
+        const float cand = sel ? -1.f : v;   // scores are exp(.) >= 0
+        const float m = wave_max(cand);
+        const unsigned long long eq = __ballot(cand == m);
+        if (m >= 0.f && lane == __ffsll((long long)eq) - 1) sel = true;
+    }
+    return __ballot(sel && v > conf);
+}
 
 // One pass over a row (ROWS) or a column of E, the K best kept sorted.  The entries arrive in index order, so a newcomer goes behind
-// every kept entry that is >= it (strict >), and the entries it displaces move down one place without a comparison: they were
-// ordered among themselves.  That is the list fine_flag_kernel's compare-and-swap cascade keeps.
+// every kept entry that is >= it (strict >: the lower index stays ahead among equals, the order topk_mask peels them off in), and the
+// entries it displaces move down one place without a comparison: they were ordered among themselves.
 template <int K, bool ROWS>
 __device__ __forceinline__ unsigned long long topk_regs(const float (*E)[OTN], int lane, float conf)
 {
@@ -574,11 +563,11 @@ __device__ __forceinline__ float ot_dot64(const float (&KARR)[64], float x, floa
 template <int FK>
 __global__ __launch_bounds__(64) void ot_kernel(RoitrOT a, unsigned long long* stats, OtFlags f)
 {
-    __shared__ float T[64][65];
+    __shared__ float T[64][OTN];
     __shared__ __attribute__((aligned(16))) float av[64];
     const int patch = blockIdx.x;
     const int lane = threadIdx.x;
-    if (a.pair_off ? patch >= a.pair_off[a.pairs] : (patch % a.num_corr) >= a.n_corr[patch / a.num_corr]) {
+    if (!slot_live(patch, a.pairs, a.num_corr, a.n_corr, a.pair_off)) {
         if (FK && lane == 0) f.counts[patch] = 0;   // the emitter leaves on counts == 0 before it reads the flags of a dead patch
         return;
     }
@@ -672,7 +661,7 @@ __global__ __launch_bounds__(64) void ot_kernel(RoitrOT a, unsigned long long* s
         const float sv = (cml && ((rbits >> i) & 1)) ? sc[i * 64 + lane] : -1e6f;
         const float o = sv + av[i] + vl - norm;
         out[i * OTN + lane] = o;
-        if (FK) T[i][lane] = expf(o);   // what fine_flag_kernel would read back and exponentiate
+        if (FK) T[i][lane] = expf(o);   // what fine_flag_kernel reads back and exponentiates
     }
     out[64 * OTN + lane] = (cml ? alpha : -1e6f) + u64 + vl - norm;
     out[lane * OTN + 64] = (rml ? alpha : -1e6f) + ul + v64 - norm;
@@ -731,11 +720,11 @@ __device__ __forceinline__ float ot_lse_wave(float x, float extra)
 template <int FK>
 __global__ __launch_bounds__(64) void ot_log_kernel(RoitrOT a, unsigned long long* stats, OtFlags f)
 {
-    __shared__ float T[64][65];
+    __shared__ float T[64][OTN];
     __shared__ float uv[64];
     const int patch = blockIdx.x;
     const int lane = threadIdx.x;
-    if (a.pair_off ? patch >= a.pair_off[a.pairs] : (patch % a.num_corr) >= a.n_corr[patch / a.num_corr]) return;
+    if (!slot_live(patch, a.pairs, a.num_corr, a.n_corr, a.pair_off)) return;
     float* out = a.out + (size_t)patch * OTN * OTN;
     {
         const float corner = out[64 * OTN + 64];
@@ -796,94 +785,25 @@ __global__ __launch_bounds__(64) void ot_log_kernel(RoitrOT a, unsigned long lon
 }
 
 // ------------------------------------------------------------------ FineMatching (modules.py:216-324)
-// one block per patch: mutual top-k on exp(score) (dustbin dropped, RIGA_v2.py:159-160), threshold, masks
-// One wave owns a row (lane = column) and then a column (lane = row): the k best are peeled off with k wave maxima
-// (value descending, lower index first among equals -- the rank order the element-wise count would give), the winners
-// recorded as one 64-bit mask per row / column; the flag of (i, j) is then two bit tests.
-__device__ __forceinline__ unsigned long long topk_mask(float v, int k, float conf)
-{
-    const int lane = threadIdx.x & 63;
-    bool sel = false;
-    for (int t = 0; t < k; ++t) {
-        const float cand = sel ? -1.f : v;   // scores are exp(.) >= 0
-        const float m = wave_max(cand);
-        const unsigned long long eq = __ballot(cand == m);
-        if (m >= 0.f && lane == __ffsll((long long)eq) - 1) sel = true;
-    }
-    return __ballot(sel && v > conf);
-}
-
+// The flag stage on its own (roitr_fine_matching; roitr_matching_tail has it inside the transport kernels): one block per patch fills
+// E = exp(ot[:64, :64]) (dustbin dropped, RIGA_v2.py:159-160), then one wave runs patch_flags on it.
+template <int FK>
 __global__ __launch_bounds__(256) void fine_flag_kernel(RoitrFine a)
 {
-    __shared__ float E[64][65];
-    __shared__ unsigned long long rowm[64], colm[64];
-    __shared__ int cnt_s[4];
+    __shared__ float E[64][OTN];
     const int patch = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int L = a.limit;   // == 64 (checked by the launcher)
-    unsigned char* fl = a.flags + (size_t)patch * L * L;
-    uint4* fl16 = reinterpret_cast<uint4*>(fl) + tid;   // thread -> row tid/4, 16 columns from (tid%4)*16
-    if (a.pair_off ? patch >= a.pair_off[a.pairs] : (patch % a.num_corr) >= a.n_corr[patch / a.num_corr]) {
+    if (!slot_live(patch, a.pairs, a.num_corr, a.n_corr, a.pair_off)) {
         if (tid == 0) a.counts[patch] = 0;   // the emitter leaves on counts == 0 before it reads the flags of a dead patch
         return;
     }
     const float* sc = a.ot + (size_t)patch * (L + 1) * (L + 1);
     for (int e = tid; e < L * L; e += 256) { const int i = e >> 6, j = e & 63; E[i][j] = expf(sc[i * (L + 1) + j]); }
     __syncthreads();
-    if (a.k <= 4) {
-        // wave 0: lane = row, wave 1: lane = column.  One pass over the 64 entries keeps the k best in registers, ordered by
-        // (value descending, index ascending): the lower index stays ahead among equals, the order topk_mask peels them off in.
-        // The index decides ties explicitly: an entry pushed down the list by a larger newcomer has a LOWER index than an
-        // equal entry met after it, so a plain strict > would leave it behind that entry (and outside the k at the boundary).
-        // E[lane][j] / E[j][lane] are conflict-free (row pitch 65).  ~64 x 16 VALU per wave instead of 96 wave-wide maxima.
-        if (wave < 2) {
-            float bv[4] = {-1.f, -1.f, -1.f, -1.f};
-            int bi[4] = {0, 0, 0, 0};
-#pragma unroll 8
-            for (int j = 0; j < 64; ++j) {
-                float x = wave == 0 ? E[lane][j] : E[j][lane];
-                int xi = j;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const bool up = x > bv[t] || (x == bv[t] && xi < bi[t]);
-                    const float tv = bv[t]; const int ti = bi[t];
-                    bv[t] = up ? x : tv; bi[t] = up ? xi : ti;
-                    x = up ? tv : x; xi = up ? ti : xi;
-                }
-            }
-            unsigned long long m = 0ull;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-                if (t < a.k && bv[t] >= 0.f && bv[t] > a.conf) m |= 1ull << bi[t];
-            if (wave == 0) rowm[lane] = m; else colm[lane] = m;
-        }
-    } else {
-        for (int r = wave; r < 64; r += 4) {
-            const unsigned long long mr = topk_mask(E[r][lane], a.k, a.conf);
-            const unsigned long long mc = topk_mask(E[lane][r], a.k, a.conf);
-            if (lane == 0) { rowm[r] = mr; colm[r] = mc; }
-        }
-    }
-    __syncthreads();
-    const int i = tid >> 2, j0 = (tid & 3) * 16;
-    const int* cm = a.col_masks + (size_t)patch * L;
-    const bool row_ok = a.row_masks[(size_t)patch * L + i] != 0;
-    const unsigned long long rmask = rowm[i];
-    unsigned w[4] = {0, 0, 0, 0};
-    int local = 0;
-#pragma unroll
-    for (int jj = 0; jj < 16; ++jj) {
-        const int j = j0 + jj;
-        const bool rt = (rmask >> j) & 1, ct = (colm[j] >> i) & 1;
-        const bool f = (a.mutual ? (rt && ct) : (rt || ct)) && row_ok && cm[j] != 0;
-        w[jj >> 2] |= (f ? 1u : 0u) << (8 * (jj & 3));
-        local += f ? 1 : 0;
-    }
-    *fl16 = make_uint4(w[0], w[1], w[2], w[3]);
-    local = (int)wave_sum((float)local);
-    if (lane == 0) cnt_s[wave] = local;
-    __syncthreads();
-    if (tid == 0) a.counts[patch] = cnt_s[0] + cnt_s[1] + cnt_s[2] + cnt_s[3];
+    if (tid >= 64) return;
+    const bool rml = a.row_masks[(size_t)patch * L + tid] != 0, cml = a.col_masks[(size_t)patch * L + tid] != 0;
+    patch_flags<FK>(E, OtFlags{a.k, a.mutual, a.conf, a.flags, a.counts}, patch, tid, rml, __ballot(cml));
 }
 
 // exclusive scan of per-patch counts (single block), total -> *n_out
@@ -895,26 +815,16 @@ __global__ __launch_bounds__(1024) void fine_scan_kernel(int n, const int* __res
 {
     __shared__ int wsum[16];
     __shared__ int carry_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid == 0) carry_s = 0;
     __syncthreads();
     for (int base = 0; base < n; base += 1024) {
         const int i = base + tid;
         const int v = i < n ? counts[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        int wb = 0;
-        for (int w = 0; w < wave; ++w) wb += wsum[w];
-        const int carry = carry_s;
+        const int o_ = block_running_scan<1024>(v, wsum, &carry_s) - v;
         // clamped like *n_out: with a caller-chosen out_cap below the true total the offsets of the patches past the cap all
         // read out_cap (their rows are not emitted), so offsets[i+1] - offsets[i] never exceeds what was written
-        if (i < n) { const int o_ = carry + wb + incl - v; offsets[i] = (out_cap > 0 && o_ > out_cap) ? (int)out_cap : o_; }
-        __syncthreads();
-        if (tid == 1023) carry_s = carry + wb + incl;
-        __syncthreads();
+        if (i < n) offsets[i] = (out_cap > 0 && o_ > out_cap) ? (int)out_cap : o_;
     }
     const int total = (out_cap > 0 && carry_s > out_cap) ? (int)out_cap : carry_s;
     if (tid == 0) *n_out = total;
@@ -932,7 +842,7 @@ __global__ __launch_bounds__(256) void fine_emit_kernel(RoitrFine a)
 {
     __shared__ int wsum[4];
     const int patch = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int L = a.limit;
     if (a.counts[patch] == 0) return;
     const unsigned char* fl = a.flags + (size_t)patch * L * L;
@@ -943,13 +853,7 @@ __global__ __launch_bounds__(256) void fine_emit_kernel(RoitrFine a)
     int c = 0;
 #pragma unroll
     for (int u = 0; u < 4; ++u) c += __popc(fw[u]);   // a flag byte is 0 or 1
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int pos = a.offsets[patch] + incl - c;
-    for (int w = 0; w < wave; ++w) pos += wsum[w];
+    int pos = a.offsets[patch] + block_incl_scan<256>(c, wsum) - c;
     float g = 1.0f;
     if (a.global_scores) {   // coarse score of the patch's node pair: (pairs, num_corr), strided in both layouts
         const PatchSlot ps = patch_slot(patch, a.pairs, a.num_corr, a.n_corr, a.pair_off);
@@ -980,7 +884,7 @@ extern "C" int roitr_point_to_node_partition(int b, int n_points, int n_nodes, c
 {
     if (n_points <= 0 || n_nodes <= 0) return ROITR_OK;
     ROITR_HIP(hipMemsetAsync(node_masks, 0, sizeof(int) * (size_t)n_nodes, stream));
-    p2n_assign_kernel<<<div_up(n_points, 256), 256, 0, stream>>>(n_points, pts, pt_offset, nullptr, nodes, node_offset, b, p2n, p2n_dist, node_masks);
+    p2n_assign_kernel<<<div_up(n_points, 256), 256, 0, stream>>>(n_points, pts, pt_offset, nodes, node_offset, b, p2n, p2n_dist, node_masks);
     ROITR_LAUNCH_CHECK();
     p2n_topk_kernel<<<n_nodes, 256, 0, stream>>>(pt_offset, node_offset, cloud_of_node, p2n, p2n_dist, limit, knn_idx, knn_mask);
     ROITR_LAUNCH_CHECK();
@@ -1089,20 +993,55 @@ extern "C" int roitr_ot_stats(int enable, unsigned long long* out)
     return ROITR_OK;
 }
 
+namespace {
+// patch slots of a launch, live or not (RoitrOT / RoitrFine): what the per-patch kernels are launched over
+template <typename Args> int patch_slots(const Args& a) { return a.pair_off ? a.slots : a.pairs * a.num_corr; }
+
+// fn(std::integral_constant<int, FK>) for the flag selection that serves top-k = k: FK = k for 1..4, FK = 5 for every other k
+template <typename Fn>
+void dispatch_fk(int k, Fn fn)
+{
+    switch (k) {
+    case 1: fn(std::integral_constant<int, 1>()); break;
+    case 2: fn(std::integral_constant<int, 2>()); break;
+    case 3: fn(std::integral_constant<int, 3>()); break;
+    case 4: fn(std::integral_constant<int, 4>()); break;
+    default: fn(std::integral_constant<int, 5>()); break;
+    }
+}
+
+// both transport kernels over all patch slots inside the profiler bracket of the stage; bytes: HBM traffic per live patch
+template <int FK>
+void launch_ot(const RoitrOT& o, int patches, double bytes, const OtFlags& f, hipStream_t stream)
+{
+    if (o.pair_off) roitr_prof_begin_live(ROITR_PROF_OT, bytes, 0.0, o.pair_off + o.pairs, stream);   // live patches
+    else roitr_prof_begin(ROITR_PROF_OT, (double)patches * bytes, stream);
+    // data-dependent work of this stage (roitr_ot_stats): live patches, Sinkhorn iterations skipped by the exact fixed-point exit,
+    // patches the exponential form handed to the log-domain kernel
+    unsigned long long* sd = ot_stats().for_current_device();
+    ot_kernel<FK><<<patches, 64, 0, stream>>>(o, sd, f);
+    ot_log_kernel<FK><<<patches, 64, 0, stream>>>(o, sd, f);   // the patches the exponential form declined; the others leave at once
+    roitr_prof_end(ROITR_PROF_OT, stream);
+}
+
+// per-patch counts -> offsets, total and per-pair starts; then the row-major compaction
+int scan_and_emit(const RoitrFine& f, int patches, hipStream_t stream)
+{
+    fine_scan_kernel<<<1, 1024, 0, stream>>>(patches, f.counts, f.offsets, f.n_out, f.out_cap, f.pairs, f.num_corr, f.pair_off, f.pair_starts);
+    ROITR_LAUNCH_CHECK();
+    fine_emit_kernel<<<patches, 256, 0, stream>>>(f);
+    ROITR_LAUNCH_CHECK();
+    return ROITR_OK;
+}
+}  // namespace
+
 extern "C" int roitr_optimal_transport(const RoitrOT* a, hipStream_t stream)
 {
     if (a->pairs <= 0) return ROITR_OK;
     if (a->limit != 64) return ROITR_ERR_UNSUPPORTED;
-    const int patches = a->pair_off ? a->slots : a->pairs * a->num_corr;
+    const int patches = patch_slots(*a);
     if (patches <= 0) return ROITR_OK;
-    if (a->pair_off) roitr_prof_begin_live(ROITR_PROF_OT, (64.0 * 64 + 65.0 * 65) * 4.0, 0.0, a->pair_off + a->pairs, stream);   // live patches
-    else roitr_prof_begin(ROITR_PROF_OT, (double)patches * (64.0 * 64 + 65.0 * 65) * 4.0, stream);
-    // data-dependent work of this stage (roitr_ot_stats): live patches, Sinkhorn iterations skipped by the exact fixed-point exit,
-    // patches the exponential form handed to the log-domain kernel
-    unsigned long long* sd = ot_stats().for_current_device();
-    ot_kernel<0><<<patches, 64, 0, stream>>>(*a, sd, OtFlags{});
-    ot_log_kernel<0><<<patches, 64, 0, stream>>>(*a, sd, OtFlags{});   // the patches the exponential form declined; the others leave at once
-    roitr_prof_end(ROITR_PROF_OT, stream);
+    launch_ot<0>(*a, patches, (64.0 * 64 + 65.0 * 65) * 4.0, OtFlags{}, stream);
     ROITR_LAUNCH_CHECK();
     return ROITR_OK;
 }
@@ -1111,34 +1050,21 @@ extern "C" int roitr_fine_matching(const RoitrFine* a, hipStream_t stream)
 {
     if (a->pairs <= 0) return ROITR_OK;
     if (a->limit != 64) return ROITR_ERR_UNSUPPORTED;
-    const int patches = a->pair_off ? a->slots : a->pairs * a->num_corr;
+    const int patches = patch_slots(*a);
     if (patches <= 0) {
         ROITR_HIP(hipMemsetAsync(a->n_out, 0, sizeof(int), stream));
         if (a->pair_starts) ROITR_HIP(hipMemsetAsync(a->pair_starts, 0, sizeof(int) * ((size_t)a->pairs + 1), stream));
         return ROITR_OK;
     }
-    fine_flag_kernel<<<patches, 256, 0, stream>>>(*a);
+    dispatch_fk(a->k, [&](auto fk) { fine_flag_kernel<decltype(fk)::value><<<patches, 256, 0, stream>>>(*a); });
     ROITR_LAUNCH_CHECK();
-    fine_scan_kernel<<<1, 1024, 0, stream>>>(patches, a->counts, a->offsets, a->n_out, a->out_cap, a->pairs, a->num_corr, a->pair_off, a->pair_starts);
-    ROITR_LAUNCH_CHECK();
-    fine_emit_kernel<<<patches, 256, 0, stream>>>(*a);
-    ROITR_LAUNCH_CHECK();
-    return ROITR_OK;
+    return scan_and_emit(*a, patches, stream);
 }
-
-namespace {
-template <int FK>
-void launch_ot_flags(int patches, const RoitrOT& o, unsigned long long* sd, const OtFlags& f, hipStream_t stream)
-{
-    ot_kernel<FK><<<patches, 64, 0, stream>>>(o, sd, f);
-    ot_log_kernel<FK><<<patches, 64, 0, stream>>>(o, sd, f);
-}
-}  // namespace
 
 // roitr_optimal_transport + roitr_fine_matching with the flag stage inside the transport kernels: the wave that stores a patch's
-// 65 x 65 tile derives the patch's flags and count from the values it stores (patch_flags), so `ot` is not read back and
-// fine_flag_kernel is not launched; scan and emit as in roitr_fine_matching.  Bitwise the results of the two calls.
-// The two structs must describe the same patch list; f->ot is o->out.
+// 65 x 65 tile derives the patch's flags and count from the values it stores (patch_flags, the selection fine_flag_kernel runs on the
+// tile it reads back), so `ot` is not read back and fine_flag_kernel is not launched; scan and emit as in roitr_fine_matching.
+// Bitwise the results of the two calls.  The two structs must describe the same patch list; f->ot is o->out.
 // Budget (hipcc resource report, gfx950): ot_kernel<1..5> 154 VGPRs (ot_kernel<0>: 153), no AGPRs, no scratch, 16 896 bytes of LDS
 // (the exp tile takes T's place, the masks stay in registers): 3 waves per SIMD by registers, 9 workgroups per CU by LDS, as before;
 // ot_log_kernel<1..5> 212 VGPRs, no scratch, the same LDS.  The epilogue is ~2.7 k VALU instructions per patch (64 expf, two
@@ -1150,29 +1076,11 @@ extern "C" int roitr_matching_tail(const RoitrOT* o, const RoitrFine* f, hipStre
         return ROITR_ERR_ARG;
     if (o->pairs <= 0) return ROITR_OK;
     if (o->limit != 64) return ROITR_ERR_UNSUPPORTED;
-    const int patches = o->pair_off ? o->slots : o->pairs * o->num_corr;
-    if (patches <= 0 || f->k < 1) {   // nothing to fuse
-        const int rc = roitr_optimal_transport(o, stream);
-        return rc != ROITR_OK ? rc : roitr_fine_matching(f, stream);
-    }
-    // per patch: scores in, transport tile and flags out
-    const double bytes = (64.0 * 64 + 65.0 * 65) * 4.0 + 64.0 * 64;
-    if (o->pair_off) roitr_prof_begin_live(ROITR_PROF_OT, bytes, 0.0, o->pair_off + o->pairs, stream);
-    else roitr_prof_begin(ROITR_PROF_OT, (double)patches * bytes, stream);
-    unsigned long long* sd = ot_stats().for_current_device();
+    const int patches = patch_slots(*o);
+    if (patches <= 0) return roitr_fine_matching(f, stream);   // no patch: an empty list
     const OtFlags fl = {f->k, f->mutual, f->conf, f->flags, f->counts};
-    switch (f->k) {
-    case 1: launch_ot_flags<1>(patches, *o, sd, fl, stream); break;
-    case 2: launch_ot_flags<2>(patches, *o, sd, fl, stream); break;
-    case 3: launch_ot_flags<3>(patches, *o, sd, fl, stream); break;
-    case 4: launch_ot_flags<4>(patches, *o, sd, fl, stream); break;
-    default: launch_ot_flags<5>(patches, *o, sd, fl, stream); break;
-    }
-    roitr_prof_end(ROITR_PROF_OT, stream);
+    // per patch: scores in, transport tile and flags out
+    dispatch_fk(f->k, [&](auto fk) { launch_ot<decltype(fk)::value>(*o, patches, (64.0 * 64 + 65.0 * 65) * 4.0 + 64.0 * 64, fl, stream); });
     ROITR_LAUNCH_CHECK();
-    fine_scan_kernel<<<1, 1024, 0, stream>>>(patches, f->counts, f->offsets, f->n_out, f->out_cap, f->pairs, f->num_corr, f->pair_off, f->pair_starts);
-    ROITR_LAUNCH_CHECK();
-    fine_emit_kernel<<<patches, 256, 0, stream>>>(*f);
-    ROITR_LAUNCH_CHECK();
-    return ROITR_OK;
+    return scan_and_emit(*f, patches, stream);
 }

@@ -3,10 +3,14 @@ roitr_optimal_transport followed by roitr_fine_matching, on the same inputs: eve
 the transport tiles, flags, counts, offsets, the emitted correspondences (points, scores, patch numbers), the total and the
 per-pair starts.  Buffers start from the same sentinels on both sides, so what a kernel must not write is compared too.
 
+Both sides run the same selection (patch_flags in matching.hip: roitr_fine_matching's flag kernel calls it on the tile it reads back),
+so this file proves the epilogue inside the transport kernels -- tile from the stored values, masks from registers, dead slots --
+and not the selection itself: that is pinned to a float64 restatement in tests/test_matching_tail_gpu.py.
+
 Patches: random scores with masked rows and columns, a patch with every row and one with every column masked, one with all of
 both masked, a patch whose score spread sends it to the log-domain kernel (roitr_ot_stats confirms it went there), constant
-scores and scores on a coarse grid (ties in every row and column: the lower index wins), k = 1 / 2 / 3 / 5 (registers and wave
-maxima) with and without `mutual`, a confidence threshold of 0 and one that cuts.  Layouts: one pair, strided with dead slots,
+scores and scores on a coarse grid (ties in every row and column: the lower index wins), k = 1 / 2 / 3 / 4 / 5 (registers and wave
+maxima) and k = 0 (nothing selected) with and without `mutual`, a confidence threshold of 0 and one that cuts.  Layouts: one pair, strided with dead slots,
 compacted with dead slots past the live count.  The score matrices are generated here; the score product itself is not part of
 the fused launch.
 """
@@ -111,7 +115,7 @@ def _same_bytes(a, b, what):
 
 @pytest.mark.parametrize("layout", sorted(LAYOUTS))
 @pytest.mark.parametrize("mutual", [True, False])
-@pytest.mark.parametrize("k", [1, 2, 3, 5])
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 5])
 def test_fused_tail_is_bitwise_the_two_calls(k, mutual, layout):
     inp = _inputs(1234 + k)
     total = 0
@@ -123,6 +127,21 @@ def test_fused_tail_is_bitwise_the_two_calls(k, mutual, layout):
             assert old["n_out"][0] >= 0
             total += int(old["n_out"][0])
     assert total > 0   # the comparison is not of empty lists
+
+
+@pytest.mark.parametrize("layout", sorted(LAYOUTS))
+def test_fused_tail_with_k_zero_emits_nothing_like_the_two_calls(layout):
+    """k = 0 selects nothing: both forms leave the same bytes (transport tiles, zero flags and counts of the live patches, sentinels
+    elsewhere), an empty list and pair starts of 0."""
+    inp = _inputs(77)
+    for mutual in (True, False):
+        old, _ = _run(False, inp, layout, 0, mutual, 0.0, 1.0)
+        new, _ = _run(True, inp, layout, 0, mutual, 0.0, 1.0)
+        _same_bytes(old, new, f"k=0 mutual={mutual} {layout}")
+        for r in (old, new):
+            assert r["n_out"][0] == 0 and not r["pair_starts"].any()
+            assert (r["counts"] == 0).all() and not (r["flags"] == 1).any()
+            assert np.isnan(r["score"]).all() and (r["patch"] == -7).all()   # nothing emitted
 
 
 def test_fused_tail_serves_the_log_domain_patch_and_keeps_the_counters():
