@@ -22,17 +22,12 @@
 #include <cstdlib>
 #include <map>
 #include <string>
-#include "prof.h"
-#include "roitr_engine.h"
+#include "gemm_host.h"
+#include "gemm_tile.h"
 
-#ifndef GEMM_WIDE_STORE
-#define GEMM_WIDE_STORE 1
-#endif
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int BM = 64, BN = 64, BK = 32, LDR = 20;  // LDR: row pitch (floats) of the [kh][row][kk] LDS image
+constexpr int BK = 32, LDR = 20;  // LDR: row pitch (floats) of the [kh][row][kk] LDS image
 
 // 8 consecutive k of one row into registers (zero row when p == nullptr; scalar tail when unaligned / past K).
 // No arithmetic here: the consumer of these registers is the NEXT iteration's LDS write, so the loads stay in
@@ -74,15 +69,12 @@ __device__ __attribute__((aligned(16))) float g_zero_row[ZERO_ROW_LEN];
 template <bool FAST, int TN, bool LN, bool HA2 = false, bool IL = false>
 __global__ __launch_bounds__(256) void gemm_kernel(RoitrGemm g, int nx, int ny, int T)
 {
-    constexpr bool WIDE_STORE = GEMM_WIDE_STORE != 0;
     constexpr int TBN = BN * TN;
     constexpr int RP = TN == 4 ? 32 : 64;   // rows parked per LayerNorm pass (keeps the static LDS under 64 KB at TN = 4)
     constexpr int STAGE = 2 * BM * LDR + 2 * TBN * LDR, TILE = LN ? RP * (TBN + 1) : 0;
     __shared__ __attribute__((aligned(16))) float smem[STAGE > TILE ? STAGE : TILE];
     float* As = smem;
     float* Bs = smem + 2 * BM * LDR;
-    // 1-D XCD-aware tile grid: XCD x = blockIdx % 8 gets the contiguous tile range [x T/8, (x+1) T/8), N tiles of one
-    // row block adjacent, so the A rows of a row block are fetched into ONE L2 instead of nx different ones
     if (g.batch_live) {   // batch list with a device-side live length: the tile map covers the live tiles only (all eight XCDs stay busy)
         const long tl = (long)*g.batch_live * nx * ny;
         if (tl < T) T = (int)tl;
@@ -103,9 +95,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(RoitrGemm g, int nx, int ny, 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int m0 = by_ * BM, n0 = bx_ * TBN;
-    constexpr bool SPLIT16 = FAST;
     const int r = tid >> 2, kq = (tid & 3) * 8;
-    const int kf = SPLIT16 ? (tid & 3) * 4 : kq;   // staging-load offset inside the slab
+    const int kf = FAST ? (tid & 3) * 4 : kq;   // staging-load offset inside the slab
     if (g.seg_off) {  // ragged batch: this batch's row segments of A and W
         const int ia = g.seg_a0 + bz, iw = g.seg_w0 + bz;
         const int a0 = ia == 0 ? 0 : g.seg_off[ia - 1], w0 = iw == 0 ? 0 : g.seg_off[iw - 1];
@@ -157,7 +148,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(RoitrGemm g, int nx, int ny, 
     // FAST: the four lanes of a row read the slab as two fully used 64-byte segments (lane j: floats 4j.. and 16+4j..), not
     // as interleaved 16-byte pieces of both; which 8 k of the slab a lane stages is free as long as A and W agree.
     auto ld8 = [&](const float* p, float (&d)[8]) {
-        const float4 x = *reinterpret_cast<const float4*>(p), y = *reinterpret_cast<const float4*>(p + (SPLIT16 ? 16 : 4));
+        const float4 x = *reinterpret_cast<const float4*>(p), y = *reinterpret_cast<const float4*>(p + (FAST ? 16 : 4));
         d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w; d[4] = y.x; d[5] = y.y; d[6] = y.z; d[7] = y.w;
     };
     auto fetch = [&](int k) {
@@ -240,7 +231,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(RoitrGemm g, int nx, int ny, 
                         for (int i = 0; i < NS; ++i)
                             if (n == (i * TOT + TOT / 2) / NS) {
                                 __builtin_amdgcn_sched_barrier(0);
-                                const int h = i & 1, o = h ? (SPLIT16 ? 16 : 4) : 0, j = i >> 1;   // half h of staging row j
+                                const int h = i & 1, o = h ? (FAST ? 16 : 4) : 0, j = i >> 1;   // half h of staging row j
                                 const float* src = j == 0 ? an : (HA2 && j == 1) ? ((g.A_cat && kn >= g.k_cat) ? g_zero_row + (kn & 31) : arow2 + kn)
                                                                   : wrow[j - 1 - (HA2 ? 1 : 0)] + kn;
                                 const float4 x = *reinterpret_cast<const float4*>(src + o);
@@ -400,7 +391,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(RoitrGemm g, int nx, int ny, 
         }
         return;
     }
-    if (TN == 1 && WIDE_STORE && n0 + BN <= g.N && (g.ldc & 3) == 0 && (((uintptr_t)C) & 15) == 0) {
+    if (TN == 1 && n0 + BN <= g.N && (g.ldc & 3) == 0 && (((uintptr_t)C) & 15) == 0) {
         // full 64-column tile: transpose through the staging LDS and store 16 bytes per lane (4 store instructions per
         // wave instead of 16 four-byte ones)
         constexpr int TP = BN + 4;   // row pitch: 16-byte aligned rows
@@ -560,6 +551,7 @@ __global__ __launch_bounds__(256) void gemm_small_kernel(RoitrGemm g, int nx, in
 }  // namespace
 
 namespace {
+// ROITR_GEMM_SHAPES (debug): per-shape timing table at exit; every launch is timed with events and waited for
 struct ShapeStat { double ms = 0; long n = 0; };
 struct ShapeLog {
     std::map<std::string, ShapeStat> m;
@@ -567,38 +559,69 @@ struct ShapeLog {
         for (auto& kv : m) fprintf(stderr, "GEMMSHAPE %s launches %ld ms %.4f\n", kv.first.c_str(), kv.second.n, kv.second.ms);
     }
 };
-void shape_log(const RoitrGemm* g, bool fast, float ms)
-{
-    static ShapeLog log;
-    char key[160];
-    snprintf(key, sizeof key, "M %d N %d K %d batch %d gather %d a2 %d relu %d seg %d fast %d ln %d bf16 %d", g->M, g->N, g->K, g->batch, g->a_idx != nullptr,
-             g->A2 != nullptr, g->relu, g->seg_off != nullptr, (int)fast, g->ln_gamma != nullptr, g->bf16);
-    auto& st = log.m[key];
-    st.ms += ms; st.n += 1;
-}
+struct ShapeTimer {
+    const RoitrGemm* g; bool fast; hipStream_t stream;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ShapeTimer(const RoitrGemm* g_, bool fast_, hipStream_t st) : g(g_), fast(fast_), stream(st)
+    {
+        static const bool shapes = getenv("ROITR_GEMM_SHAPES") != nullptr;
+        if (shapes) { (void)hipEventCreate(&e0); (void)hipEventCreate(&e1); (void)hipEventRecord(e0, stream); }
+    }
+    ~ShapeTimer()
+    {
+        if (!e0) return;
+        (void)hipEventRecord(e1, stream); (void)hipEventSynchronize(e1);
+        float ms = 0.f; (void)hipEventElapsedTime(&ms, e0, e1); (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+        static ShapeLog log;
+        char key[160];
+        snprintf(key, sizeof key, "M %d N %d K %d batch %d gather %d a2 %d relu %d seg %d fast %d ln %d bf16 %d", g->M, g->N, g->K, g->batch, g->a_idx != nullptr,
+                 g->A2 != nullptr, g->relu, g->seg_off != nullptr, (int)fast, g->ln_gamma != nullptr, g->bf16);
+        auto& st = log.m[key];
+        st.ms += ms; st.n += 1;
+    }
+};
 }  // namespace
 
 int roitr_gemm_bf16_launch(const RoitrGemm* g, hipStream_t stream);   // gemm_bf16.hip
 int roitr_gemm_x3_launch(const RoitrGemm* g, hipStream_t stream);     // gemm_x3.hip
 
+// What the fp32 launcher below settled on, and what was tried on the way:
+// Measured and dropped (A/B on the forward bench): 64x128 / 128x128 multi-accumulator tiles (19.7 / 22.0 vs 16.9 ms of
+// GEMM per 128-pair forward), two K-slabs per barrier pair (7.9 vs 7.5 ms at 32 pairs), and a persistent-block
+// variant that opens the next tile (row pointers + first slab in flight) before the store epilogue (18.3-19.8 vs
+// 16.9 ms): at K = 64..512 the hardware dispatcher overlapping 7 resident 64x64 blocks per CU beats all of them.
+// Prefetch distance 2 (two alternating register sets) changes nothing either (45.7 vs 45.1 ms per forward): the
+// staging loads are not what the waves wait for.  Nor does distance 3 on the small grids of the one-pair-per-call mode
+// (round 2: 4.68 vs 4.65 ms per pair, bitwise the same results): those launches are not waiting for weight loads either.
+// Round 2, for the short-K layers of levels 1-2 (K = 64 / 128, 1.3 - 5.1 M rows; 1.8 - 3.3 TB/s, 40 - 80 TFLOP/s): a
+// weights-stationary persistent kernel -- the (64 TN x K) weight block staged once per workgroup, row tiles walked with the
+// next tile's rows prefetched across the MFMA block, two barriers per tile instead of two per slab, bitwise the results of
+// this kernel -- measured per shape at 512 pairs: N = 192 / 256 at K = 64 1.57 / 1.96 vs 1.61 / 2.10 ms, N = 384 / 512 at
+// K = 128 1.44 / 1.83 vs 1.30 / 1.68 ms, and the LayerNorm layers (N = 64 / 128, 1 - 2 resident workgroups per CU under
+// 57 - 156 KB of LDS) 1.8 / 1.4 vs 1.07 / 0.72 ms; gemm time per step 65.7 vs 55.2 ms.  Removed: re-staging the weights is
+// not what these launches wait for either.
+// The kernel alone reaches 106 TFLOP/s at K = 2048 and 78 at K = 256 (scripts/bench_gemm.py); the no-memory MFMA
+// ceiling measured on this part is 143-157 TFLOP/s (scripts/micro/mfma_peak.hip).
+// Also measured and removed (round 1-2): an LDS-DMA variant (global_load_lds_dwordx4 into a swizzled row-major image, two
+// stages, one barrier per slab): 98 vs 95 TFLOP/s at K = 2048 and 84 vs 80 at K = 256, but 62 vs 74 at K = 128 and 44 vs
+// 56 at K = 64 (32 KB of LDS per block: 5 instead of 7 resident blocks) -> 19.8 vs 17.9 ms of GEMM per 128-pair forward.
+// Round 3, measured and removed: s_setprio(1) around the 16 MFMAs of a slab (the waves in their MFMA phase first): 38.6 - 39.2 vs
+// 37.8 ms of GEMM per 512-pair step.
+// Round 3, measured and removed: a second kernel for K >= 128 / N >= 192 built like the on-chip GEMMs of local_block.hip
+// (v_mfma_f32_16x16x4_f32, weight fragments as float4 straight from L1 / L2, only A staged: 64 x 64-k slabs, double buffered,
+// one barrier per 64 k).  Correct (float64 test, all shapes of the forward) but 1.35-1.5x SLOWER on every shape it took
+// (M 319488 N 768 K 256: 1.67 vs 1.21 ms; M 1.28 M N 256 K 128: 1.31 vs 0.87 ms; gemm family 48.7 vs 37.6 ms per 512-pair
+// step): a lane's weight float4 comes from its own weight row, so one fragment load touches 16 cache lines at 64 B each --
+// the vector-memory pipe, not LDS, becomes the operand bottleneck once nothing else (attention, LayerNorm) overlaps it.
 extern "C" int roitr_gemm(const RoitrGemm* g, hipStream_t stream)
 {
     if (g->M <= 0 || g->N <= 0 || g->batch <= 0) return ROITR_OK;
     if (g->K <= 0 || !g->A || !g->W || !g->C) { roitr_set_error("roitr_gemm: K <= 0 or a null operand", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-    if (g->bf16) {
-        static const bool shapes_h = getenv("ROITR_GEMM_SHAPES") != nullptr;  // debug: per-shape timing table at exit (synchronous)
-        hipEvent_t h0 = nullptr, h1 = nullptr;
-        if (shapes_h) { hipEventCreate(&h0); hipEventCreate(&h1); hipEventRecord(h0, stream); }
-        const int rc = (g->bf16 & ROITR_BF16_X3) ? roitr_gemm_x3_launch(g, stream) : roitr_gemm_bf16_launch(g, stream);
-        if (shapes_h) {
-            hipEventRecord(h1, stream); hipEventSynchronize(h1);
-            float ms = 0.f; hipEventElapsedTime(&ms, h0, h1);
-            shape_log(g, true, ms);
-            hipEventDestroy(h0); hipEventDestroy(h1);
-        }
-        return rc;
-    }
     auto al16 = [](const void* p, long stride_floats) { return ((uintptr_t)p & 15) == 0 && (stride_floats % 4) == 0; };
+    if (g->bf16) {
+        ShapeTimer timer(g, true, stream);
+        return (g->bf16 & ROITR_BF16_X3) ? roitr_gemm_x3_launch(g, stream) : roitr_gemm_bf16_launch(g, stream);
+    }
     const bool fast = g->K % BK == 0 && g->K <= ZERO_ROW_LEN && g->lda % 4 == 0 && g->ldw % 4 == 0 && al16(g->A, g->sA) && al16(g->W, g->sW) &&
                       (!g->A2 || al16(g->A2, g->sA));
     if (g->A_cat && (!fast || g->batch != 1 || g->seg_off || g->k_cat % BK || g->k_cat <= 0 || g->k_cat >= g->K || g->lda_cat % 4 ||
@@ -607,78 +630,42 @@ extern "C" int roitr_gemm(const RoitrGemm* g, hipStream_t stream)
         return ROITR_ERR_UNSUPPORTED;
     }
     if (g->a_cat_idx && !g->A_cat) { roitr_set_error("roitr_gemm: a_cat_idx without A_cat", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-    const int tn = g->ln_gamma ? g->N / BN : 1;   // LayerNorm epilogue: one block spans the row
-    if (g->ln_gamma && (g->N % BN || (tn != 1 && tn != 2 && tn != 4) || g->batch != 1 || g->seg_off || g->relu || !g->ln_beta)) return ROITR_ERR_UNSUPPORTED;
-    if (g->ip_feat && (!g->ln_gamma || !g->ip_idx || !g->ip_dist2)) { roitr_set_error("roitr_gemm: the interpolation addend rides in the fused LayerNorm epilogue only", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
+    const bool ln = g->ln_gamma != nullptr;
+    const int tn = ln ? g->N / BN : 1;   // LayerNorm epilogue: one block spans the row
+    if (ln && (!gemm_ln_shape_ok(g) || (!fast && tn != 1))) return ROITR_ERR_UNSUPPORTED;
+    if (g->ip_feat && (!ln || !g->ip_idx || !g->ip_dist2)) { roitr_set_error("roitr_gemm: the interpolation addend rides in the fused LayerNorm epilogue only", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
     const int nx = div_up(g->N, BN * tn), ny = div_up(g->M, BM);
-    const long Tl = (long)nx * ny * g->batch;
-    if (Tl > 0x7ffffff0L) return ROITR_ERR_UNSUPPORTED;
-    const int T = (int)Tl;
+    int T;
+    if (!gemm_tile_count(nx, ny, g->batch, &T)) return ROITR_ERR_UNSUPPORTED;
     const unsigned grid = (unsigned)xcd_grid(T);
-    const int prof_cls = roitr_prof_is_enabled() ? roitr_gemm_prof_class(g) : ROITR_PROF_GEMM;
-    if (g->batch_live)   // priced on the LIVE batches (device-side count), not on the capacity of the list
-        roitr_prof_begin_live(prof_cls, 2.0 * g->M * g->N * (double)g->K, roitr_gemm_algorithmic_bytes(g) / g->batch, g->batch_live, stream);
-    else roitr_prof_begin2(prof_cls, 2.0 * g->M * g->N * (double)g->K * g->batch, roitr_gemm_algorithmic_bytes(g), stream);
-    // Measured and dropped (A/B on the forward bench): 64x128 / 128x128 multi-accumulator tiles (19.7 / 22.0 vs 16.9 ms of
-    // GEMM per 128-pair forward), two K-slabs per barrier pair (7.9 vs 7.5 ms at 32 pairs), and a persistent-block
-    // variant that opens the next tile (row pointers + first slab in flight) before the store epilogue (18.3-19.8 vs
-    // 16.9 ms): at K = 64..512 the hardware dispatcher overlapping 7 resident 64x64 blocks per CU beats all of them.
-    // Prefetch distance 2 (two alternating register sets) changes nothing either (45.7 vs 45.1 ms per forward): the
-    // staging loads are not what the waves wait for.  Nor does distance 3 on the small grids of the one-pair-per-call mode
-    // (round 2: 4.68 vs 4.65 ms per pair, bitwise the same results): those launches are not waiting for weight loads either.
-    // Round 2, for the short-K layers of levels 1-2 (K = 64 / 128, 1.3 - 5.1 M rows; 1.8 - 3.3 TB/s, 40 - 80 TFLOP/s): a
-    // weights-stationary persistent kernel -- the (64 TN x K) weight block staged once per workgroup, row tiles walked with the
-    // next tile's rows prefetched across the MFMA block, two barriers per tile instead of two per slab, bitwise the results of
-    // this kernel -- measured per shape at 512 pairs: N = 192 / 256 at K = 64 1.57 / 1.96 vs 1.61 / 2.10 ms, N = 384 / 512 at
-    // K = 128 1.44 / 1.83 vs 1.30 / 1.68 ms, and the LayerNorm layers (N = 64 / 128, 1 - 2 resident workgroups per CU under
-    // 57 - 156 KB of LDS) 1.8 / 1.4 vs 1.07 / 0.72 ms; gemm time per step 65.7 vs 55.2 ms.  Removed: re-staging the weights is
-    // not what these launches wait for either.
-    // The kernel alone reaches 106 TFLOP/s at K = 2048 and 78 at K = 256 (scripts/bench_gemm.py); the no-memory MFMA
-    // ceiling measured on this part is 143-157 TFLOP/s (scripts/micro/mfma_peak.hip).
-    // Also measured and removed (round 1-2): an LDS-DMA variant (global_load_lds_dwordx4 into a swizzled row-major image, two
-    // stages, one barrier per slab): 98 vs 95 TFLOP/s at K = 2048 and 84 vs 80 at K = 256, but 62 vs 74 at K = 128 and 44 vs
-    // 56 at K = 64 (32 KB of LDS per block: 5 instead of 7 resident blocks) -> 19.8 vs 17.9 ms of GEMM per 128-pair forward.
-    // Round 3, measured and removed: s_setprio(1) around the 16 MFMAs of a slab (the waves in their MFMA phase first): 38.6 - 39.2 vs
-    // 37.8 ms of GEMM per 512-pair step.
-    // Round 3, measured and removed: a second kernel for K >= 128 / N >= 192 built like the on-chip GEMMs of local_block.hip
-    // (v_mfma_f32_16x16x4_f32, weight fragments as float4 straight from L1 / L2, only A staged: 64 x 64-k slabs, double buffered,
-    // one barrier per 64 k).  Correct (float64 test, all shapes of the forward) but 1.35-1.5x SLOWER on every shape it took
-    // (M 319488 N 768 K 256: 1.67 vs 1.21 ms; M 1.28 M N 256 K 128: 1.31 vs 0.87 ms; gemm family 48.7 vs 37.6 ms per 512-pair
-    // step): a lane's weight float4 comes from its own weight row, so one fragment load touches 16 cache lines at 64 B each --
-    // the vector-memory pipe, not LDS, becomes the operand bottleneck once nothing else (attention, LayerNorm) overlaps it.
-    static const bool shapes = getenv("ROITR_GEMM_SHAPES") != nullptr;  // debug: per-shape timing table at exit (synchronous)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (shapes) { hipEventCreate(&e0); hipEventCreate(&e1); hipEventRecord(e0, stream); }
+    const int prof_cls = gemm_prof_begin(g, stream);
+    {
+    ShapeTimer timer(g, fast, stream);
     const bool a2 = g->A2 != nullptr;
     const bool il = T >= GEMM_IL_MIN_TILES;   // staging loads spread over the MFMA stream (see the kernel): large grids only
-    if (fast && !g->ln_gamma && T < GEMM_SMALL_MAX_TILES) {   // a fraction of a tile per SIMD: 32 x 32 tiles with 4x shorter accumulator chains
+    if (fast && !ln && T < GEMM_SMALL_MAX_TILES) {   // a fraction of a tile per SIMD: 32 x 32 tiles with 4x shorter accumulator chains
         const int sx = div_up(g->N, SM), sy = div_up(g->M, SM);
         const int ST = sx * sy * g->batch;
         if (a2) gemm_small_kernel<true><<<xcd_grid(ST), 256, 0, stream>>>(*g, sx, sy, ST);
         else gemm_small_kernel<false><<<xcd_grid(ST), 256, 0, stream>>>(*g, sx, sy, ST);
+    } else if (!fast) {
+        if (ln) gemm_kernel<false, 1, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
+        else gemm_kernel<false, 1, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
     } else
-#define GEMM_LAUNCH(F, TN_, LN_) \
-    do { \
-        if (a2 && il) gemm_kernel<F, TN_, LN_, true, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T); \
-        else if (a2) gemm_kernel<F, TN_, LN_, true, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T); \
-        else if (il) gemm_kernel<F, TN_, LN_, false, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T); \
-        else gemm_kernel<F, TN_, LN_, false, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T); \
-    } while (0)
-    if (g->ln_gamma) {
-        if (!fast) { if (tn != 1) return ROITR_ERR_UNSUPPORTED; gemm_kernel<false, 1, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T); }
-        else if (tn == 1) GEMM_LAUNCH(true, 1, true);
-        else if (tn == 2) GEMM_LAUNCH(true, 2, true);
-        else GEMM_LAUNCH(true, 4, true);
-    } else if (fast) GEMM_LAUNCH(true, 1, false);
-    else gemm_kernel<false, 1, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
-#undef GEMM_LAUNCH
-    if (shapes) {
-        hipEventRecord(e1, stream); hipEventSynchronize(e1);
-        float ms = 0; hipEventElapsedTime(&ms, e0, e1); hipEventDestroy(e0); hipEventDestroy(e1);
-        shape_log(g, fast, ms);
+        dispatch_tn(tn, [&](auto tn_) {
+            constexpr int TN = decltype(tn_)::value;
+            auto launch = [&](auto ln_) {
+                constexpr bool LN = decltype(ln_)::value;
+                if (a2 && il) gemm_kernel<true, TN, LN, true, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
+                else if (a2) gemm_kernel<true, TN, LN, true, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
+                else if (il) gemm_kernel<true, TN, LN, false, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
+                else gemm_kernel<true, TN, LN, false, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
+            };
+            if (ln) launch(std::true_type());
+            else if constexpr (TN == 1) launch(std::false_type());   // plain launches: 64 x 64 tiles only
+        });
     }
     roitr_prof_end(prof_cls, stream);
     ROITR_LAUNCH_CHECK();
     return ROITR_OK;
 }
-

@@ -13,26 +13,13 @@
 // bf16 with a 144-byte row pitch: the 16-byte fragment reads of 16 consecutive rows fall on 16 distinct 4-bank groups
 // (36 i mod 64 = 4 (9 i mod 16)), the 16-byte staging writes of a lane octet likewise.  A lane's MFMA operand is 8
 // consecutive k (16 bytes): lanes 0..31 take k = 16 kk .. +7, lanes 32..63 k = 16 kk + 8 .. +7 of k-step kk.
-#include "common.h"
-#include "prof.h"
-#include "roitr_engine.h"
+#include "gemm_host.h"
+#include "gemm_tile.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-constexpr int BM = 64, BN = 64, BK = 64;
+constexpr int BK = 64;
 constexpr int PITCH = 72;   // bf16 elements per LDS row (144 bytes)
-
-__device__ __forceinline__ unsigned pack_bf16(float x, float y)   // low half = x; round to nearest even
-{
-    f32x2 v = {x, y};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ unsigned short to_bf16(float x) { return (unsigned short)(pack_bf16(x, 0.f) & 0xffffu); }
 
 // 16 consecutive k of one row, as 8 packed bf16 pairs.  F32: the source is fp32 (four 16-byte loads, rounded here);
 // otherwise bf16 (two 16-byte loads).  p == nullptr: a zero row.
@@ -334,10 +321,7 @@ extern "C" int roitr_gemm_bf16_supported(const RoitrGemm* g)
     if (g->lda % a_al || g->ldw % 8 || g->sA % a_al || g->sW % 8) return 0;
     if (((uintptr_t)g->A & 15) || ((uintptr_t)g->W & 15) || (g->A2 && (((uintptr_t)g->A2 & 15) || a_h))) return 0;
     if (g->seg_off && (g->lda % a_al || g->ldw % 8)) return 0;
-    if (g->ln_gamma) {
-        const int tn = g->N / BN;
-        if (g->N % BN || (tn != 1 && tn != 2 && tn != 4) || g->batch != 1 || g->seg_off || g->relu || !g->ln_beta) return 0;
-    }
+    if (g->ln_gamma && !gemm_ln_shape_ok(g)) return 0;
     return 1;
 }
 
@@ -358,34 +342,18 @@ int roitr_gemm_bf16_launch(const RoitrGemm* g, hipStream_t stream)
         while (tn > 1 && (long)ny * div_up(g->N, BN * tn) * g->batch < 2048) tn >>= 1;
     }
     const int nx = div_up(g->N, BN * tn);
-    const long Tl = (long)nx * ny * g->batch;
-    if (Tl > 0x7ffffff0L) return ROITR_ERR_UNSUPPORTED;
-    const int T = (int)Tl;
+    int T;
+    if (!gemm_tile_count(nx, ny, g->batch, &T)) return ROITR_ERR_UNSUPPORTED;
     const unsigned grid = (unsigned)xcd_grid(T);
-    const bool a_h = (g->bf16 & ROITR_BF16_A) != 0;
-    const int prof_cls = roitr_prof_is_enabled() ? roitr_gemm_prof_class(g) : ROITR_PROF_GEMM;
-    if (g->batch_live)   // priced on the LIVE batches (device-side count), not on the capacity of the list
-        roitr_prof_begin_live(prof_cls, 2.0 * g->M * g->N * (double)g->K, roitr_gemm_algorithmic_bytes(g) / g->batch, g->batch_live, stream);
-    else roitr_prof_begin2(prof_cls, 2.0 * g->M * g->N * (double)g->K * g->batch, roitr_gemm_algorithmic_bytes(g), stream);
-    if (g->ln_gamma) {
-        if (a_h) {
-            if (tn == 1) gemm_bf16_kernel<false, 1, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
-            else if (tn == 2) gemm_bf16_kernel<false, 2, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
-            else gemm_bf16_kernel<false, 4, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
-        } else {
-            if (tn == 1) gemm_bf16_kernel<true, 1, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
-            else if (tn == 2) gemm_bf16_kernel<true, 2, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
-            else gemm_bf16_kernel<true, 4, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
-        }
-    } else if (a_h) {
-        if (tn == 1) gemm_bf16_kernel<false, 1, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
-        else if (tn == 2) gemm_bf16_kernel<false, 2, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
-        else gemm_bf16_kernel<false, 4, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
-    } else {
-        if (tn == 1) gemm_bf16_kernel<true, 1, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
-        else if (tn == 2) gemm_bf16_kernel<true, 2, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
-        else gemm_bf16_kernel<true, 4, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
-    }
+    const bool a_f32 = (g->bf16 & ROITR_BF16_A) == 0, ln = g->ln_gamma != nullptr;
+    const int prof_cls = gemm_prof_begin(g, stream);
+    dispatch_tn(tn, [&](auto tn_) {
+        constexpr int TN = decltype(tn_)::value;
+        if (a_f32 && ln) gemm_bf16_kernel<true, TN, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
+        else if (a_f32) gemm_bf16_kernel<true, TN, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
+        else if (ln) gemm_bf16_kernel<false, TN, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
+        else gemm_bf16_kernel<false, TN, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
+    });
     roitr_prof_end(prof_cls, stream);
     ROITR_LAUNCH_CHECK();
     return ROITR_OK;

@@ -17,25 +17,14 @@
 // independent of the batch they are computed in, whatever tile a launch picks (tests/test_stages_gpu.py).
 // Same RoitrGemm contract as gemm.hip for what the K >= 256 layers of the path use: row gather (a_idx), zero rows, the addend A2,
 // the K-concatenated operand A_cat (+ a_cat_idx), bias, alpha, ReLU, the LayerNorm epilogue at 64 / 128 / 256 columns.
-#include "common.h"
-#include "prof.h"
-#include "roitr_engine.h"
+#include "gemm_host.h"
+#include "gemm_tile.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-constexpr int BM = 64, BN = 64, BK = 32;
+constexpr int BK = 32;
 constexpr int PITCH = 40;   // bf16 elements per LDS row (80 bytes)
 
-__device__ __forceinline__ unsigned pack_bf16(float x, float y)   // low half = x; round to nearest even
-{
-    f32x2 v = {x, y};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
 // (x, y) -> packed pairs of the three bf16 pieces; the residuals are exact in fp32
 __device__ __forceinline__ void split2(float x, float y, unsigned& h, unsigned& m, unsigned& l)
 {
@@ -45,7 +34,9 @@ __device__ __forceinline__ void split2(float x, float y, unsigned& h, unsigned& 
     l = pack_bf16(rx - __uint_as_float(m << 16), ry - __uint_as_float(m & 0xffff0000u));
 }
 
-// TM x TN accumulators of 32 x 32 per wave: the block tile is 64 TM x 64 TN
+// TM x TN accumulators of 32 x 32 per wave: the block tile is 64 TM x 64 TN.  Only TM = 1 is instantiated (the launcher records why
+// 128-row tiles lost); the parameter stays because the kernel written without it keeps its argument struct in scratch memory (DESIGN.md
+// section 4, "GEMM family: what is shared and what is not")
 template <int TM, int TN, bool LN, bool HA2>
 __global__ __launch_bounds__(256) void gemm_x3_kernel(RoitrGemm g, int nx, int ny, int T)
 {
@@ -304,10 +295,7 @@ extern "C" int roitr_gemm_x3_supported(const RoitrGemm* g)
     if (((uintptr_t)g->A & 15) || ((uintptr_t)g->W & 15) || (g->A2 && ((uintptr_t)g->A2 & 15))) return 0;
     if (g->A_cat && (g->k_cat % BK || g->k_cat <= 0 || g->k_cat >= g->K || g->lda_cat % 4 || ((uintptr_t)g->A_cat & 15))) return 0;
     if (g->a_cat_idx && !g->A_cat) return 0;
-    if (g->ln_gamma) {
-        const int tn = g->N / BN;
-        if (g->N % BN || (tn != 1 && tn != 2 && tn != 4) || g->relu || !g->ln_beta) return 0;
-    }
+    if (g->ln_gamma && !gemm_ln_shape_ok(g)) return 0;
     return 1;
 }
 
@@ -319,33 +307,25 @@ int roitr_gemm_x3_launch(const RoitrGemm* g, hipStream_t stream)
     }
     // tile: whole rows for the LayerNorm epilogue (64 x N); otherwise 64 x 256 where N allows and the grid fills the chip (measured at
     // M = 319 488, K = 256, N = 768: 64 x 64 73, 64 x 128 103, 64 x 256 131, 128 x 64 75, 128 x 128 101, 128 x 256 98 TFLOP/s: an A row
-    // costs more than a W row -- fp32 loads, the split, and two of the four waves repeat none of it) down to 64 x 64 on small grids
-    // (the result bits are the same whatever the tile)
-    int tm = 1, tn = 1;
-    if (g->ln_gamma) tn = g->N / BN;
-    else {
-        tn = g->N % 256 == 0 ? 4 : (g->N % 128 == 0 ? 2 : 1);
-        while (tm * tn > 1 && (long)div_up(g->M, BM * tm) * div_up(g->N, BN * tn) < 512) { if (tm > 1) tm >>= 1; else tn >>= 1; }
-    }
-    const int ny = div_up(g->M, BM * tm), nx = div_up(g->N, BN * tn);
-    const long Tl = (long)nx * ny;
-    if (Tl > 0x7ffffff0L) return ROITR_ERR_UNSUPPORTED;
-    const int T = (int)Tl;
+    // costs more than a W row -- fp32 loads, the split, and two of the four waves repeat none of it -- so 128-row tiles are not launched)
+    // down to 64 x 64 on small grids (the result bits are the same whatever the tile)
+    const bool ln = g->ln_gamma != nullptr;
+    const int ny = div_up(g->M, BM);
+    int tn = ln ? g->N / BN : (g->N % 256 == 0 ? 4 : (g->N % 128 == 0 ? 2 : 1));
+    while (!ln && tn > 1 && (long)ny * div_up(g->N, BN * tn) < 512) tn >>= 1;
+    const int nx = div_up(g->N, BN * tn);
+    int T;
+    if (!gemm_tile_count(nx, ny, 1, &T)) return ROITR_ERR_UNSUPPORTED;
     const unsigned grid = (unsigned)xcd_grid(T);
-    const int prof_cls = roitr_prof_is_enabled() ? roitr_gemm_prof_class(g) : ROITR_PROF_GEMM;
-    roitr_prof_begin2(prof_cls, 2.0 * g->M * g->N * (double)g->K, roitr_gemm_algorithmic_bytes(g), stream);
+    const int prof_cls = gemm_prof_begin(g, stream);
     const bool a2 = g->A2 != nullptr;
-#define X3_LAUNCH(TM_, TN_, LN_) \
-    do { if (a2) gemm_x3_kernel<TM_, TN_, LN_, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T); \
-         else gemm_x3_kernel<TM_, TN_, LN_, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T); } while (0)
-    if (g->ln_gamma) { if (tn == 1) X3_LAUNCH(1, 1, true); else if (tn == 2) X3_LAUNCH(1, 2, true); else X3_LAUNCH(1, 4, true); }
-    else if (tm == 2 && tn == 2) X3_LAUNCH(2, 2, false);
-    else if (tm == 2 && tn == 1) X3_LAUNCH(2, 1, false);
-    else if (tm == 1 && tn == 2) X3_LAUNCH(1, 2, false);
-    else if (tm == 1 && tn == 4) X3_LAUNCH(1, 4, false);
-    else if (tm == 2 && tn == 4) X3_LAUNCH(2, 4, false);
-    else X3_LAUNCH(1, 1, false);
-#undef X3_LAUNCH
+    dispatch_tn(tn, [&](auto tn_) {
+        constexpr int TN = decltype(tn_)::value;
+        if (ln && a2) gemm_x3_kernel<1, TN, true, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
+        else if (ln) gemm_x3_kernel<1, TN, true, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
+        else if (a2) gemm_x3_kernel<1, TN, false, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
+        else gemm_x3_kernel<1, TN, false, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
+    });
     roitr_prof_end(prof_cls, stream);
     ROITR_LAUNCH_CHECK();
     return ROITR_OK;

@@ -65,6 +65,92 @@ def test_gemm_bf16_matches_bf16_rounded_float64(M, N, K, relu):
     assert (np.abs(gh - ref) <= tol + 2.0 ** -8 * np.abs(ref)).all()      # + one bf16 rounding of the result
 
 
+def _gemm_abi(**fields):
+    """roitr_gemm through the C ABI: RoitrGemm fields by name (tensors as device pointers), everything else zero."""
+    import ctypes
+    from roitr_amd import _lib as L
+    from roitr_amd import ops
+    g = ops._Gemm()
+    for k, v in fields.items():
+        setattr(g, k, L.ptr(v) if torch.is_tensor(v) else v)
+    L.check(L.lib().roitr_gemm(ctypes.byref(g), L.stream_ptr()), "gemm")
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("M,N,K,a_h", [(333, 192, 128, False), (70001, 512, 128, False), (517, 256, 64, True)])
+def test_gemm_bf16_gather_zero_rows_and_addend(M, N, K, a_h):
+    """The operand options of the bf16 kernel that the engine uses but ops.linear does not reach: row gather on A with negative and past-the-limit
+    rows (zero rows), the fp32 addend on A (summed in fp32, then rounded), ragged last tiles, 64-, and (70001 rows) 256-column tiles.
+    Same reference and bound as test_gemm_bf16_matches_bf16_rounded_float64."""
+    rng = np.random.default_rng(M + N + K)
+    R = M + 50
+    a = rng.standard_normal((R, K)).astype(np.float32)
+    a2 = None if a_h else rng.standard_normal((R, K)).astype(np.float32)
+    w = (rng.standard_normal((N, K)) / np.sqrt(K)).astype(np.float32)
+    b = rng.standard_normal(N).astype(np.float32)
+    idx = rng.integers(-5, R + 20, M).astype(np.int32)   # < 0 or >= R: zero rows
+    ad, wd = torch.from_numpy(a).cuda(), torch.from_numpy(w).cuda().to(torch.bfloat16)
+    if a_h:
+        ad = ad.to(torch.bfloat16)
+    a2d = None if a2 is None else torch.from_numpy(a2).cuda()
+    out = torch.full((M, N), float("nan"), device="cuda")
+    _gemm_abi(M=M, N=N, K=K, A=ad, lda=K, a_idx=torch.from_numpy(idx).cuda(), a_limit=R, W=wd, ldw=K, bias=torch.from_numpy(b).cuda(), alpha=0.75,
+              relu=1, C=out, ldc=N, batch=1, bf16=1 | (2 if a_h else 0), **({} if a2d is None else {"A2": a2d}))
+    rows = (a if a2 is None else a + a2)[np.clip(idx, 0, R - 1)] * ((idx >= 0) & (idx < R))[:, None]
+    ref = ref_linear(rows, w, b, True, 0.75)
+    tol = 4e-5 * 0.75 * mass(rows, w) + 1e-6
+    got = out.cpu().numpy()
+    assert (np.abs(got - ref) <= tol).all(), float((np.abs(got - ref) / tol).max())
+
+
+def test_gemm_bf16_gathered_batch_list_with_a_live_count():
+    """The matching-score contraction of the bf16 engine (engine.cpp: a batch of 64 x 64 products of gathered rows of ONE stored-bf16
+    matrix, both operands gathered with out-of-range rows, a device-side live batch count): the live batches against float64, the
+    batches past the live count untouched."""
+    rng = np.random.default_rng(11)
+    T1, K, LIM, NB, live = 5000, 256, 64, 40, 29
+    f = rng.standard_normal((T1, K)).astype(np.float32)
+    ia = rng.integers(-3, T1 + 40, (NB, LIM)).astype(np.int32)
+    iw = rng.integers(-3, T1 + 40, (NB, LIM)).astype(np.int32)
+    fd = torch.from_numpy(f).cuda().to(torch.bfloat16)
+    out = torch.full((NB, LIM, LIM), -7.0, device="cuda")
+    _gemm_abi(M=LIM, N=LIM, K=K, A=fd, lda=K, a_idx=torch.from_numpy(ia).cuda(), a_limit=T1, W=fd, ldw=K, w_idx=torch.from_numpy(iw).cuda(), w_limit=T1,
+              alpha=1.0 / 16.0, C=out, ldc=LIM, batch=NB, sC=LIM * LIM, sAidx=LIM, sWidx=LIM, batch_live=torch.tensor([live], dtype=torch.int32).cuda(),
+              bf16=1 | 2)
+    got = out.cpu().numpy()
+    assert (got[live:] == -7.0).all()
+    row = lambda ix: f[np.clip(ix, 0, T1 - 1)] * ((ix >= 0) & (ix < T1))[:, None]
+    for b in range(live):
+        x, w = row(ia[b]), row(iw[b])
+        ref = ref_linear(x, w, None, False, 1.0 / 16.0)
+        tol = 4e-5 / 16.0 * mass(x, w) + 1e-6
+        assert (np.abs(got[b] - ref) <= tol).all(), (b, float((np.abs(got[b] - ref) / tol).max()))
+
+
+def test_gemm_bf16_ragged_batch():
+    """RoitrGemm::seg_off through the bf16 kernel: batch b multiplies row segment B + b of A by row segment b of W (the layout of the
+    coarse node products, engine.cpp), every batch with its own row and column count; entries outside a batch's product untouched."""
+    rng = np.random.default_rng(12)
+    K, B = 128, 3
+    lens = [70, 129, 33, 200, 64, 5]   # W segments 0..2, A segments 3..5
+    off = np.cumsum(lens).astype(np.int32)
+    f = rng.standard_normal((int(off[-1]), K)).astype(np.float32)
+    nmax = max(lens)
+    out = torch.full((B, nmax, nmax), -7.0, device="cuda")
+    fd = torch.from_numpy(f).cuda()
+    _gemm_abi(M=nmax, N=nmax, K=K, A=fd, lda=K, W=fd.to(torch.bfloat16), ldw=K, alpha=0.75, C=out, ldc=nmax, batch=B, sC=nmax * nmax,
+              seg_off=torch.from_numpy(off).cuda(), seg_a0=B, seg_w0=0, bf16=1)
+    got = out.cpu().numpy()
+    start = np.concatenate([[0], off[:-1]])
+    for b in range(B):
+        x, w = f[start[B + b]:off[B + b]], f[start[b]:off[b]]
+        ref = ref_linear(x, w, None, False, 0.75)
+        tol = 4e-5 * 0.75 * mass(x, w) + 1e-6
+        blk = got[b, :x.shape[0], :w.shape[0]]
+        assert (np.abs(blk - ref) <= tol).all(), (b, float((np.abs(blk - ref) / tol).max()))
+        assert (got[b, x.shape[0]:] == -7.0).all() and (got[b, :, w.shape[0]:] == -7.0).all()
+
+
 @pytest.mark.parametrize("N", [64, 128, 256])
 def test_gemm_bf16_layernorm_epilogue(N):
     from roitr_amd import ops
