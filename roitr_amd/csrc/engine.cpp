@@ -18,7 +18,6 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -27,8 +26,6 @@
 #include "prof.h"
 #include "roitr_engine.h"
 #include "roitr_pointops.h"
-
-extern "C" int roitr_build_pfold(int H, int heads, const float* wpe, const float* bpe, float* pfold, hipStream_t stream);
 
 #define CHK(x)                    \
     do {                          \
@@ -50,10 +47,10 @@ struct LocalT {  // LocalPPFTransformer (+ derived weights)
     Lin emb, in_proj, q, k, v, p, vp, lin, out_proj;
     const float* norm_w = nullptr; const float* norm_b = nullptr;
     int in_dim = 0, H = 0, out_dim = 0;
-    float* wqkv = nullptr;  // rows: [Wq (H) ; Wqp (5*HEADS) ; Wk (H) ; Wv (H)] x H
+    float* wqkv = nullptr;  // rows: [Wq (H) ; Wk (H) ; Wv (H)] x H
     unsigned short* wqkv_b = nullptr;   // the same, stored bf16 (operand_dtype = 1)
     float* bqkv = nullptr;
-    // TransitionDown transformers (in_dim != H): [q|qp|k|v] straight from the layer input, W' = Wqkv Win (R x in_dim),
+    // TransitionDown transformers (in_dim != H): [q|k|v] straight from the layer input, W' = Wqkv Win (R x in_dim),
     // b' = Wqkv b_in + bqkv -- in_proj and the q/k/v projections are two linear maps with nothing in between
     float* wqkv_x = nullptr; float* bqkv_x = nullptr; unsigned short* wqkv_x_b = nullptr;
     float* wkT_x = nullptr;                        // (in_dim, H): transpose of the k rows of wqkv_x (TransitionDown fold, fp32)
@@ -63,9 +60,10 @@ struct LocalT {  // LocalPPFTransformer (+ derived weights)
     // block transformers in fp32: linear(att) + in_proj(x) as ONE GEMM over the K-concatenated operand [att | x]:
     // wcat = [Wlin | Win] (H x (H + in_dim)), bcat = b_lin + b_in; f = in_proj(x) is then never materialised
     float* wcat = nullptr; float* bcat = nullptr; unsigned short* wcat_b = nullptr;   // wcat_b: bf16 copy (bf16 operand mode, fused block)
-    // the PPF coefficient rows of the query, qp[h] = [Wpe_h^T q_h, q_h . bpe_h]: computed inside the attention kernel from
-    // wpe (H,4) / bpe (H) (nq = 0: [q|k|v] is 3 H wide = whole 64-column GEMM tiles), or as 5 extra GEMM columns per head (nq = 20)
-    const float* wpe = nullptr; const float* bpe = nullptr; int nq = 0;
+    // the PPF coefficient rows of the query, qp[h] = [Wpe_h^T q_h, q_h . bpe_h], are computed inside the attention kernel from
+    // wpe (H,4) / bpe (H): [q|k|v] is 3 H wide = whole 64-column GEMM tiles (as 5 extra GEMM columns per head it was 212 wide: one
+    // 64-column tile in four was 31 % full)
+    const float* wpe = nullptr; const float* bpe = nullptr;
     float* wvpe = nullptr;  // (H,4)
     float* bvpe = nullptr;  // (H)
     const float* bn2_w = nullptr; const float* bn2_b = nullptr;  // block only
@@ -96,7 +94,7 @@ struct Arena {
     {
         const size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
         if (off + bytes > cap) { fail = true; return (T*)base; }
-        T* p = (T*)(base + off);
+        T* p = base ? (T*)(base + off) : nullptr;   // no base: a counting arena, only `off` advances
         off += bytes;
         return p;
     }
@@ -134,14 +132,29 @@ struct Engine {
     hipEvent_t gend[2] = {nullptr, nullptr};   // recorded on the main stream where the forward that used the arena ends
     bool gend_rec[2] = {false, false};
     bool ahead_off = false;          // the alternating arenas could not be allocated: every call is ordered on the main stream
-    bool garena_short = false;       // an alternating arena ran out INSIDE a call (its size is a hand-kept sum): the wrapper repeats the call on the main-stream path
+    bool garena_short = false;       // an alternating arena ran out INSIDE a call: the wrapper repeats the call on the main-stream path
     static constexpr int RING = 4;   // descriptor staging slots: the host may run RING forwards ahead
     char* pinned[RING] = {nullptr, nullptr, nullptr, nullptr}; size_t pinned_cap[RING] = {0, 0, 0, 0};
     hipEvent_t pinned_ev[RING] = {nullptr, nullptr, nullptr, nullptr};
     int ring_pos = 0;
     hipStream_t side = nullptr;      // the geometry chain (FPS, grids, kNN + PPF of levels 2-4, 3-NN, embedding E, partition, GT outputs)
-    static constexpr int NEV = 12;   // [8]: the error-path join of roitr_engine_forward; [9]: descriptors copied on the geometry stream; [10]: deferred side units; [11]: level-1 groups (ahead mode)
-    hipEvent_t ev[NEV] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // what each event orders ("main" / "geometry": the stream that records it)
+    enum Ev {
+        EV_MAIN_BEGIN,           // main: where this call begins -- inputs + descriptors in place, the shared scratch is free from here
+        EV_LEVEL2_GEOM_DONE,     // geometry: "level l geometry done", levels 2 - 4 -- picks, coordinates, self and TransitionDown
+        EV_LEVEL3_GEOM_DONE,     //           groups + PPF of the level are written (ev_level_done)
+        EV_LEVEL4_GEOM_DONE,
+        EV_LEVEL1_WS_FREE,       // main: the level-1 workspace (grid + retry list) is free for the TransitionDown query
+        EV_EMBED_DONE,           // geometry: E and its index arrays
+        EV_NN3_DONE,             // geometry: the decoder's 3-NN
+        EV_TAIL_DONE,            // geometry: node coordinates, partition and ground-truth outputs (the last join)
+        EV_ERROR_JOIN,           // geometry: the error-path join of roitr_engine_forward
+        EV_DESC_COPIED,          // geometry: descriptors copied (ahead mode)
+        EV_LEVEL1_GROUPS_READY,  // geometry: level-1 groups and PPFs (ahead mode)
+        NEV
+    };
+    static Ev ev_level_done(int l) { return (Ev)(EV_LEVEL2_GEOM_DONE + l - 1); }   // l = 1 .. 3: the 0-based index of levels 2 - 4
+    hipEvent_t ev[NEV] = {};
     bool side_forked = false;        // the current forward has issued work on `side` that `st` has not joined yet
     std::string err;
     hipStream_t fin_stream = nullptr;   // stream of the running finalize (weight conversions are queued on it)
@@ -336,10 +349,7 @@ int resolve_local(Engine& E, LocalT& L, const std::string& pre, int in_dim, int 
 
 int fold_local(Engine& E, LocalT& L, hipStream_t st)
 {
-    // NQ = 0: the PPF coefficient rows qp of the query are formed inside the attention kernel (round 2; as 5 extra GEMM columns
-    // per head, NQ = 20, [q|k|v] was 212 wide: one 64-column tile in four was 31 % full)
-    const int H = L.H, NQ = 0, NQF = 5 * HEADS;
-    L.nq = NQ;
+    const int H = L.H;
     Arena& A = E.warena;
     float* weT = A.get<float>(4 * (size_t)H);
     float* wpeT = A.get<float>(4 * (size_t)H);
@@ -348,9 +358,7 @@ int fold_local(Engine& E, LocalT& L, hipStream_t st)
     float* wvpeT = A.get<float>(4 * (size_t)H);
     L.wvpe = A.get<float>(4 * (size_t)H);
     L.bvpe = A.get<float>(H);
-    float* pfold = A.get<float>((size_t)NQF * H);
-    float* wqT = A.get<float>((size_t)H * H);
-    const int R = 3 * H + NQ;
+    const int R = 3 * H;
     L.wqkv = A.get<float>((size_t)R * H);
     L.bqkv = A.get<float>(R);
     if (A.fail) return ROITR_ERR_ARG;
@@ -363,17 +371,12 @@ int fold_local(Engine& E, LocalT& L, hipStream_t st)
     CHK(gemm(st, 4, H, H, weT, H, L.vp.w, H, nullptr, wvpeT, H));
     CHK(roitr_transpose(4, H, wvpeT, H, L.wvpe, 4, st));
     CHK(gemm(st, 1, H, H, L.emb.b, H, L.vp.w, H, L.vp.b, L.bvpe, H));
-    // Wqp = Pfold @ Wq ; bqp = Pfold @ bq
-    CHK(roitr_build_pfold(H, HEADS, wpe, bpe, pfold, st));
-    CHK(roitr_transpose(H, H, L.q.w, H, wqT, H, st));
     CHK(d2d(st, L.wqkv, L.q.w, sizeof(float) * (size_t)H * H));
-    if (NQ) CHK(gemm(st, NQ, H, H, pfold, H, wqT, H, nullptr, L.wqkv + (size_t)H * H, H));
-    CHK(d2d(st, L.wqkv + (size_t)(H + NQ) * H, L.k.w, sizeof(float) * (size_t)H * H));
-    CHK(d2d(st, L.wqkv + (size_t)(2 * H + NQ) * H, L.v.w, sizeof(float) * (size_t)H * H));
+    CHK(d2d(st, L.wqkv + (size_t)H * H, L.k.w, sizeof(float) * (size_t)H * H));
+    CHK(d2d(st, L.wqkv + (size_t)(2 * H) * H, L.v.w, sizeof(float) * (size_t)H * H));
     CHK(d2d(st, L.bqkv, L.q.b, sizeof(float) * H));
-    if (NQ) CHK(gemm(st, 1, NQ, H, L.q.b, H, pfold, H, nullptr, L.bqkv + H, NQ));
-    CHK(d2d(st, L.bqkv + H + NQ, L.k.b, sizeof(float) * H));
-    CHK(d2d(st, L.bqkv + 2 * H + NQ, L.v.b, sizeof(float) * H));
+    CHK(d2d(st, L.bqkv + H, L.k.b, sizeof(float) * H));
+    CHK(d2d(st, L.bqkv + 2 * H, L.v.b, sizeof(float) * H));
     if (E.cfg.operand_dtype == 1) {   // folded in fp32, stored once in bf16
         L.wqkv_b = A.get<unsigned short>((size_t)R * H);
         if (A.fail) return ROITR_ERR_ARG;
@@ -407,11 +410,11 @@ int fold_local(Engine& E, LocalT& L, hipStream_t st)
         CHK(roitr_transpose(H, I, L.in_proj.w, I, winT, H, st));                       // (in, H)
         CHK(gemm(st, R, I, H, L.wqkv, H, winT, H, nullptr, L.wqkv_x, I));               // (R, in) = Wqkv Win
         CHK(gemm(st, 1, R, H, L.in_proj.b, H, L.wqkv, H, L.bqkv, L.bqkv_x, R));         // Wqkv b_in + bqkv
-        if (E.cfg.operand_dtype != 1 && NQ == 0) {
+        if (E.cfg.operand_dtype != 1) {
             // q~_h = Wk'_h^T q_h needs the k rows transposed: (I, H), head h = columns h c .. (csrc/local_attn.hip, fold form)
             L.wkT_x = A.get<float>((size_t)I * H);
             if (A.fail) return ROITR_ERR_ARG;
-            CHK(roitr_transpose(H, I, L.wqkv_x + (size_t)(H + NQ) * I, I, L.wkT_x, H, st));
+            CHK(roitr_transpose(H, I, L.wqkv_x + (size_t)H * I, I, L.wkT_x, H, st));
             if (I == 64) {
                 // q~_h = Wk'_h^T (Wq'_h x + bq_h): one (H + 4 I) x I weight instead of the q GEMM followed by the batched q~ GEMM --
                 // at I = 64 those were 1.42 + 1.19 ms per 512-pair step for 2 GB of q / q~ rows (two launches of K = 64 / K = 32);
@@ -453,15 +456,27 @@ Ffn ffn(Engine& E, const std::string& pre, int C)
 
 // ---------------------------------------------------------------- per-forward geometry
 struct Levels {
-    int B = 0, NC = 0;                 // pairs, clouds
     std::vector<int> n[4];             // per cloud sizes per level (0-based level index = enc level - 1)
     std::vector<int> off[4];           // cumulative
     int T[4] = {0, 0, 0, 0};
     int nmax[4] = {0, 0, 0, 0};
 };
 
-struct Dev {  // device-resident descriptors
-    int* off[4]; int* cloud_of_node; int* partner; long* eoff; int* cloud_ids;
+// The descriptor block of one forward, staged on the host and copied to the device in one piece:
+// off[4][NC] | cloud_of_node[T4] | partner[NC] | pad | eoff[NC] (long, 16-byte aligned)
+struct Desc {
+    int* off[4]; int* cloud_of_node; int* partner; long* eoff;
+    static size_t eoff_at(size_t NC, size_t T4) { return ((4 * NC + T4 + NC + 8) * sizeof(int) + 15) & ~(size_t)15; }
+    static size_t bytes(size_t NC, size_t T4) { return eoff_at(NC, T4) + NC * sizeof(long); }
+    static Desc at(char* base, size_t NC, size_t T4)   // the fields of a block at `base` (host or device)
+    {
+        Desc D;
+        for (int l = 0; l < 4; ++l) D.off[l] = (int*)base + (size_t)l * NC;
+        D.cloud_of_node = (int*)base + 4 * NC;
+        D.partner = D.cloud_of_node + T4;
+        D.eoff = (long*)(base + eoff_at(NC, T4));
+        return D;
+    }
 };
 
 // LocalPPFTransformer.forward (ppftransformer.py:227-253) on N_in input rows -> M node rows
@@ -471,7 +486,7 @@ int local_transformer(Engine& E, hipStream_t st, const LocalT& L, int N_in, cons
 {
     Arena& A = E.arena;
     const size_t mark = A.off;
-    const int H = L.H, NQ = L.nq;
+    const int H = L.H;
     // TransitionDown with folded projections: q / k / v come straight from x, and f = in_proj(x) is only needed as the
     // LayerNorm residual of the M sampled rows
     // (measured and dropped: the same fold for the first transformer of the network, K = 1 -- an outer-product kernel writing
@@ -486,8 +501,8 @@ int local_transformer(Engine& E, hipStream_t st, const LocalT& L, int N_in, cons
         const int I = L.in_dim;
         float* kv = A.get<float>((size_t)N_in * 2 * H);
         if (A.fail) return ROITR_ERR_ARG;
-        const unsigned short* wkv_b = (E.cfg.operand_dtype == 1 && L.wqkv_x_b && I % 64 == 0) ? L.wqkv_x_b + (size_t)(H + NQ) * I : nullptr;
-        CHK(gemm(st, N_in, 2 * H, I, x, I, L.wqkv_x + (size_t)(H + NQ) * I, I, L.bqkv_x + H + NQ, kv, 2 * H, false, nullptr, nullptr, 1.0f, wkv_b,
+        const unsigned short* wkv_b = (E.cfg.operand_dtype == 1 && L.wqkv_x_b && I % 64 == 0) ? L.wqkv_x_b + (size_t)H * I : nullptr;
+        CHK(gemm(st, N_in, 2 * H, I, x, I, L.wqkv_x + (size_t)H * I, I, L.bqkv_x + H, kv, 2 * H, false, nullptr, nullptr, 1.0f, wkv_b,
                  wkv_b ? ROITR_BF16_C : 0));
         RoitrLocalBlock b;
         memset(&b, 0, sizeof(b));
@@ -505,12 +520,14 @@ int local_transformer(Engine& E, hipStream_t st, const LocalT& L, int N_in, cons
     }
     // TransitionDown in the folded-attention form below with the K-concatenated `linear`: f = in_proj(x[node_idx]) -- only ever the
     // LayerNorm residual -- rides in that GEMM as its second K part (round 4), the gathered (M, H) tensor is never formed
-    const bool td_fold = folded && L.wkT_x && NQ == 0 && roitr_local_attention_fold_supported(L.in_dim, H, K);
+    const bool td_fold = folded && L.wkT_x && roitr_local_attention_fold_supported(L.in_dim, H, K);
     const bool td_cat = td_fold && L.wcat != nullptr;
-    float* f = (catf || td_cat) ? nullptr : A.get<float>((size_t)(folded ? M : N_in) * H);
-    if (catf || td_cat) {}
-    else if (folded) CHK(gemm(st, M, x, L.in_proj, f, false, node_idx));
-    else CHK(gemm(st, N_in, x, L.in_proj, f));
+    float* f = nullptr;
+    if (!catf && !td_cat) {
+        f = A.get<float>((size_t)(folded ? M : N_in) * H);
+        if (folded) CHK(gemm(st, M, x, L.in_proj, f, false, node_idx));
+        else CHK(gemm(st, N_in, x, L.in_proj, f));
+    }
     // TransitionDown in fp32: the k | v projections folded into the query side (csrc/local_attn.hip local_attn_fold_kernel) --
     // q~ = Wk'^T q per head in front, Wv' applied to the attention-weighted INPUT rows behind; the (N_in, 2H) tensor is never formed
     if (td_fold && td_cat && L.wqqt_x && !bn2_res && L.out_dim == H && roitr_local_td_supported(L.in_dim, H, K)) {
@@ -593,29 +610,29 @@ int local_transformer(Engine& E, hipStream_t st, const LocalT& L, int N_in, cons
     const size_t esz = hb ? 2 : 4;
     const float *q, *k, *v; int ldq, ldkv;
     if (!node_idx) {
-        const int R = 3 * H + NQ;
+        const int R = 3 * H;
         float* qkv = A.get<float>((size_t)N_in * R);
         if (A.fail) return ROITR_ERR_ARG;
         if (catf) CHK(gemm(st, N_in, R, L.in_dim, x, L.in_dim, L.wqkv_x, L.in_dim, L.bqkv_x, qkv, R));
         else
         CHK(gemm(st, N_in, R, H, f, H, L.wqkv, H, L.bqkv, qkv, R, false, nullptr, nullptr, 1.0f, L.wqkv_b, cq));
         const char* b0 = (const char*)qkv;
-        q = qkv; k = (const float*)(b0 + (size_t)(H + NQ) * esz); v = (const float*)(b0 + (size_t)(2 * H + NQ) * esz); ldq = R; ldkv = R;
+        q = qkv; k = (const float*)(b0 + (size_t)H * esz); v = (const float*)(b0 + (size_t)(2 * H) * esz); ldq = R; ldkv = R;
     } else {
-        float* qe = A.get<float>((size_t)M * (H + NQ));
+        float* qe = A.get<float>((size_t)M * H);
         float* kv = A.get<float>((size_t)N_in * 2 * H);
         if (A.fail) return ROITR_ERR_ARG;
         if (folded) {
             const int I = L.in_dim;
-            CHK(gemm(st, M, H + NQ, I, x, I, L.wqkv_x, I, L.bqkv_x, qe, H + NQ, false, node_idx, nullptr, 1.0f, L.wqkv_x_b, cq));
-            CHK(gemm(st, N_in, 2 * H, I, x, I, L.wqkv_x + (size_t)(H + NQ) * I, I, L.bqkv_x + H + NQ, kv, 2 * H, false, nullptr, nullptr, 1.0f,
-                     L.wqkv_x_b ? L.wqkv_x_b + (size_t)(H + NQ) * I : nullptr, cq));
+            CHK(gemm(st, M, H, I, x, I, L.wqkv_x, I, L.bqkv_x, qe, H, false, node_idx, nullptr, 1.0f, L.wqkv_x_b, cq));
+            CHK(gemm(st, N_in, 2 * H, I, x, I, L.wqkv_x + (size_t)H * I, I, L.bqkv_x + H, kv, 2 * H, false, nullptr, nullptr, 1.0f,
+                     L.wqkv_x_b ? L.wqkv_x_b + (size_t)H * I : nullptr, cq));
         } else {
-            CHK(gemm(st, M, H + NQ, H, f, H, L.wqkv, H, L.bqkv, qe, H + NQ, false, node_idx, nullptr, 1.0f, L.wqkv_b, cq));
-            CHK(gemm(st, N_in, 2 * H, H, f, H, L.wqkv + (size_t)(H + NQ) * H, H, L.bqkv + H + NQ, kv, 2 * H, false, nullptr, nullptr, 1.0f,
-                     L.wqkv_b ? L.wqkv_b + (size_t)(H + NQ) * H : nullptr, cq));
+            CHK(gemm(st, M, H, H, f, H, L.wqkv, H, L.bqkv, qe, H, false, node_idx, nullptr, 1.0f, L.wqkv_b, cq));
+            CHK(gemm(st, N_in, 2 * H, H, f, H, L.wqkv + (size_t)H * H, H, L.bqkv + H, kv, 2 * H, false, nullptr, nullptr, 1.0f,
+                     L.wqkv_b ? L.wqkv_b + (size_t)H * H : nullptr, cq));
         }
-        q = qe; k = kv; v = (const float*)((const char*)kv + (size_t)H * esz); ldq = H + NQ; ldkv = 2 * H;
+        q = qe; k = kv; v = (const float*)((const char*)kv + (size_t)H * esz); ldq = H; ldkv = 2 * H;
     }
     float* att = A.get<float>((size_t)M * H);
     float* hid = A.get<float>((size_t)M * H);
@@ -626,7 +643,7 @@ int local_transformer(Engine& E, hipStream_t st, const LocalT& L, int N_in, cons
     a.M = M; a.K = K; a.H = H; a.heads = HEADS; a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldkv; a.v = v; a.ldv = ldkv;
     a.group_idx = group; a.ppf = ppf; a.wvpe = L.wvpe; a.bvpe = L.bvpe; a.scale = 1.0f / sqrtf((float)(H / HEADS));
     a.out = att; a.ldo = H; a.node_order = order; a.bf16 = hb ? 3 : 0;
-    if (NQ == 0) { a.wpe = L.wpe; a.bpe = L.bpe; }   // qp computed in the kernel
+    a.wpe = L.wpe; a.bpe = L.bpe;   // qp computed in the kernel
     CHK(roitr_local_attention(&a, st));
     // bf16 operand mode: `y` only feeds out_proj -> the LayerNorm epilogue stores it in bf16 (half the round trip)
     const bool y_h = ln_fuses(H, H, H, H) && bf16_layer(L.lin.wb, H) && bf16_layer(L.out_proj.wb, H);   // independent of M: batch-invariant storage
@@ -1018,41 +1035,41 @@ extern "C" int roitr_engine_geo_table_info(void* h, double* info)
 // scripts/bench_knn_shapes.py: 5.6 -> 6.0 - 6.6 ms for the calls of a 512-pair forward): 6 stays.
 static constexpr float GRID_OCC = 6.0f;
 
-// calls of up to this many pairs run their whole geometry chain ahead of the previous call (RoitrForwardIO::inputs_ready, forward_body)
+// calls of up to this many pairs run their whole geometry chain ahead of the previous call (RoitrForwardIO::inputs_ready, reserve_arenas)
 static constexpr int AHEAD_MAX_PAIRS = 128;
 
-static int forward_body(void* h, const RoitrForwardIO* io, hipStream_t st);
+static int forward_body(Engine& E, const RoitrForwardIO* io, hipStream_t st);
+
+// forward_body with the side stream joined on the error path
+static int forward_joined(Engine& E, const RoitrForwardIO* io, hipStream_t st)
+{
+    E.side_forked = false; E.cur_par = -1; E.garena_short = false;
+    const int rc = forward_body(E, io, st);
+    if (rc != ROITR_OK && E.side_forked && E.side && E.ev[Engine::EV_ERROR_JOIN]) {
+        if (hipEventRecord(E.ev[Engine::EV_ERROR_JOIN], E.side) == hipSuccess) (void)hipStreamWaitEvent(st, E.ev[Engine::EV_ERROR_JOIN], 0);
+        else (void)hipStreamSynchronize(E.side);
+    }
+    return rc;
+}
 
 /* One engine = one main stream at a time: the side stream and its events are per engine, so two forwards of the same engine must
  * be ordered on the caller's stream (the Python side guarantees it: launch_batch uses torch's current stream).  An early return
  * between the fork and the last join (arena exhausted, unsupported shape, a HIP error) would leave side-stream work un-joined --
- * racing with the next forward's arena reuse, or ending a graph capture with an unjoined stream: the wrapper joins it. */
+ * racing with the next forward's arena reuse, or ending a graph capture with an unjoined stream: forward_joined joins it. */
 extern "C" int roitr_engine_forward(void* h, const RoitrForwardIO* io, hipStream_t st)
 {
     Engine& E = *(Engine*)h;
-    E.side_forked = false;
-    E.cur_par = -1;
-    E.garena_short = false;
     g_engine = &E;
-    int rc = forward_body(h, io, st);
-    if (rc != ROITR_OK && E.side_forked && E.side && E.ev[8]) {
-        if (hipEventRecord(E.ev[8], E.side) == hipSuccess) (void)hipStreamWaitEvent(st, E.ev[8], 0);
-        else (void)hipStreamSynchronize(E.side);
-    }
+    int rc = forward_joined(E, io, st);
     if (rc != ROITR_OK && E.garena_short) {
-        // the size estimate of the alternating arena missed a buffer: no hard failure -- drain what the attempt queued and
-        // run the call once more with everything ordered on the main stream; the engine stays on that path (the tests assert that the
-        // estimate holds: test_graph_gpu.py, so this is a safety net, not a mode)
+        // a buffer did not fit the alternating arena: no hard failure -- drain what the attempt queued and run the call once
+        // more with everything ordered on the main stream; the engine stays on that path (the arena is sized by counting the carve
+        // itself and the tests assert that the size holds: test_graph_gpu.py, so this is a safety net, not a mode)
         fprintf(stderr, "roitr: alternating geometry arena too small for this call (%s): falling back to main-stream order\n", roitr_last_error());
         (void)hipStreamSynchronize(st);
         if (E.side) (void)hipStreamSynchronize(E.side);
         E.ahead_off = true;
-        E.side_forked = false; E.cur_par = -1; E.garena_short = false;
-        rc = forward_body(h, io, st);
-        if (rc != ROITR_OK && E.side_forked && E.side && E.ev[8]) {
-            if (hipEventRecord(E.ev[8], E.side) == hipSuccess) (void)hipStreamWaitEvent(st, E.ev[8], 0);
-            else (void)hipStreamSynchronize(E.side);
-        }
+        rc = forward_joined(E, io, st);
     }
     E.side_forked = false;
     if (E.cur_par >= 0 && E.gend[E.cur_par]) {   // the alternating arena is free again where this call ends on the main stream
@@ -1063,18 +1080,56 @@ extern "C" int roitr_engine_forward(void* h, const RoitrForwardIO* io, hipStream
     return rc;
 }
 
-static int forward_body(void* h, const RoitrForwardIO* io, hipStream_t st)
-{
-    Engine& E = *(Engine*)h;
-    if (!E.finalized) { roitr_set_error("engine not finalized", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-    const int B = io->pairs, NC = 2 * B;
-    if (B <= 0) return 0;
-    const int f = E.cfg.factor, C4 = 256 * f, LIM = E.cfg.point_limit;
-    int P_ = E.cfg.num_corr;
+namespace {
 
-    // ---------------- level geometry (host), descriptors to the device
+// ---------------------------------------------------------------- one forward: its plan, its geometry buffers, its stages
+// The host-side plan: sizes, limits, the ordering mode and the stream pair.  plan_sizes and reserve_arenas fill it; every later
+// stage only reads it.
+struct Plan {
     Levels V;
-    V.B = B; V.NC = NC;
+    int B = 0, NC = 0;                        // pairs, clouds
+    int T1 = 0, T4 = 0;                       // rows of the finest / the coarsest level (V.T[0], V.T[3])
+    int C4 = 0, LIM = 0, P_ = 0;              // width of the coarsest level, points per patch, patches per pair
+    size_t NPs = 0; bool compact = false;     // patch slots of the call; compact: the selected patches of all pairs back to back
+    std::vector<long> eoff; long etot = 0;    // per cloud: where its n4 x n4 block of the embedding E starts; entries in all
+    bool ahead = false, knn0_ahead = false, full_ahead = false;   // how much of the geometry chain runs beside the previous call (reserve_arenas)
+    bool e_h = false;                         // E is stored bf16
+    bool gt = false, gt_corr = false;         // ground-truth side outputs (RIGA_v2.py:91-116), only when rot / trans are given; node correspondences
+    int Tp = 0, Tsp = 0, Ttp = 0;             // their padded rows: all, source, target
+    hipStream_t st = nullptr, sd = nullptr;   // main stream, geometry stream
+};
+
+// Everything the geometry chain reads and writes.  carve_geometry takes every buffer; issue_geometry_chain fills them on the
+// geometry stream (level 1's groups: on the stream the mode picks); the feature path reads them behind the chain's events.
+struct GeoBufs {
+    char* desc = nullptr; Desc D;                          // the descriptor block on the device and its fields
+    const float* pts_out = nullptr;                        // coordinates the outputs are made of (io->points_out, or the geometry's own)
+    const float* p[4]; const float* nrm[4];                // coordinates / normals per level ([0]: the inputs)
+    int* down[4] = {nullptr, nullptr, nullptr, nullptr};   // FPS indices into level l-1 (global rows)
+    int* g_self[4]; float* ppf_self[4];                    // self kNN groups (blocks + decoder)
+    int* g_td[4]; float* ppf_td[4];                        // TransitionDown groups (level l nodes over level l-1 points)
+    int* i3[3]; float* d3[3];                              // decoder: 3 nearest level-(l+1) points of every level-l point
+    void* knn_ws[4];
+    bool grid[4];
+    const void* order[4] = {nullptr, nullptr, nullptr, nullptr};  // cell-order visiting order of each level's points
+    float* d_idx = nullptr; float* a_idx = nullptr; float* Emb = nullptr;   // the global transformer's embedding and its index arrays
+    float* node_xyz = nullptr; int* node_masks = nullptr; int* kidx = nullptr; int* kmask = nullptr;   // node outputs (the caller's, or scratch)
+    float* fps_tmp = nullptr; int* fps_tie[4] = {nullptr, nullptr, nullptr, nullptr};   // FPS scratch; per cloud: first pick with a shared arg-max
+    int* c3 = nullptr; int* c4 = nullptr; int* p2n = nullptr; float* p2nd = nullptr;    // partition scratch
+    // ground-truth scratch: padded clouds, their offsets, nearest distances, the two kNN workspaces; node correspondences
+    float* gt_pad = nullptr; int* gt_poff = nullptr; float* gt_d2p = nullptr; void* gt_ws_s = nullptr; void* gt_ws_t = nullptr;
+    float* gt_om = nullptr; float* gt_nt = nullptr; float* gt_nr = nullptr;
+};
+
+// what the feature path hands from stage to stage (main arena): encoder output per level, global transformer output, decoder output per level
+struct Feats { float* xe[4]; float* gfeat; float* xd[4]; };
+
+// ---- stage 1: level sizes (host), patch slots, limits
+int plan_sizes(const Engine& E, const RoitrForwardIO* io, Plan& P)
+{
+    const int B = io->pairs, NC = 2 * B, f = E.cfg.factor;
+    P.B = B; P.NC = NC; P.C4 = 256 * f; P.LIM = E.cfg.point_limit; P.P_ = E.cfg.num_corr;
+    Levels& V = P.V;
     for (int l = 0; l < 4; ++l) { V.n[l].resize(NC); V.off[l].resize(NC); }
     for (int c = 0; c < NC; ++c) {
         int s[4];
@@ -1087,23 +1142,106 @@ static int forward_body(void* h, const RoitrForwardIO* io, hipStream_t st)
         for (int c = 0; c < NC; ++c) { acc += V.n[l][c]; V.off[l][c] = acc; V.nmax[l] = V.n[l][c] > V.nmax[l] ? V.n[l][c] : V.nmax[l]; }
         V.T[l] = acc;
     }
-    const int T1 = V.T[0], T4 = V.T[3];
-    if (E.cfg.adaptive_coarse) P_ = V.nmax[3] * V.nmax[3];  // every node pair may be selected (modules.py:111-112)
+    P.T1 = V.T[0]; P.T4 = V.T[3];
+    P.gt = io->rot && io->trans && (io->gt_node_occ || io->gt_corr_idx);
+    P.gt_corr = P.gt && io->gt_corr_idx && io->gt_corr_overlaps && io->gt_corr_count;
+    P.Tp = P.T1 + NC; P.Tsp = V.off[0][B - 1] + B; P.Ttp = P.Tp - P.Tsp;
+    if (E.cfg.adaptive_coarse) P.P_ = V.nmax[3] * V.nmax[3];  // every node pair may be selected (modules.py:111-112)
     // Patch slots of the call.  3DMatch: exactly B * num_corr, strided.  Adaptive matching: the SELECTED patches of all pairs back to back
     // (roitr_patch_offsets) in as many slots as the caller's per-patch outputs hold (RoitrForwardIO::patch_slots; 0 = the bound B * n^2)
-    const bool compact = E.cfg.adaptive_coarse != 0;
-    size_t NPs = (size_t)B * P_;
-    if (compact && io->patch_slots > 0 && (size_t)io->patch_slots < NPs) NPs = (size_t)io->patch_slots;
-    if (NPs * (size_t)(LIM * LIM) > 0x7fffffffffLL || NPs > 0x7ffffff0u / (size_t)LIM) { roitr_set_error("too many patch slots for one call", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
+    P.compact = E.cfg.adaptive_coarse != 0;
+    P.NPs = (size_t)B * P.P_;
+    if (P.compact && io->patch_slots > 0 && (size_t)io->patch_slots < P.NPs) P.NPs = (size_t)io->patch_slots;
+    const int LIM = P.LIM;
+    if (P.NPs * (size_t)(LIM * LIM) > 0x7fffffffffLL || P.NPs > 0x7ffffff0u / (size_t)LIM) { roitr_set_error("too many patch slots for one call", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
     if (V.nmax[3] > 1024) { roitr_set_error("more than 1024 superpoints per cloud", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
-    std::vector<long> eoff(NC);
-    long etot = 0;
-    for (int c = 0; c < NC; ++c) { eoff[c] = etot; etot += (long)V.n[3][c] * V.n[3][c]; }
+    P.eoff.resize(NC);
+    P.etot = 0;
+    for (int c = 0; c < NC; ++c) { P.eoff[c] = P.etot; P.etot += (long)V.n[3][c] * V.n[3][c]; }
+    // bf16 operand mode: E (an operand of the q~ . E and a' . E contractions of every self layer) is stored bf16 when the
+    // attention kernel for this width reads it (C = 256 / 512, 4 heads, <= 512 superpoints)
+    P.e_h = E.cfg.operand_dtype == 1 && E.proj_d.wb && E.proj_a.wb && (P.C4 == 256 || P.C4 == 512) && V.nmax[3] <= 512;
+    return 0;
+}
 
-    // ---------------- arena sizing (upper bound from the sizes)
+// ---- stage 4 (and the size of the alternating arena in stage 2): EVERY buffer the geometry chain writes, before the encoder's mark /
+// release scopes.  G: what is written before the call begins on the main stream (the alternating arena in the ahead mode); GF: everything
+// else the geometry stream writes.  Run against counting arenas this is also what sizes the alternating arena, so the two cannot differ.
+void carve_geometry(const Engine& E, const RoitrForwardIO* io, const Plan& P, Arena& G, Arena& GF, GeoBufs& S)
+{
+    const Levels& V = P.V; const int NC = P.NC, T1 = P.T1, T4 = P.T4, LIM = P.LIM;
+    S.desc = G.get<char>(Desc::bytes(NC, T4));
+    S.pts_out = io->points_out ? io->points_out : io->points_geom;
+    S.node_xyz = io->node_xyz ? io->node_xyz : GF.get<float>((size_t)T4 * 3);
+    S.node_masks = io->node_masks ? io->node_masks : GF.get<int>(T4);
+    S.kidx = io->node_knn_idx ? io->node_knn_idx : GF.get<int>((size_t)T4 * LIM);
+    S.kmask = io->node_knn_mask ? io->node_knn_mask : GF.get<int>((size_t)T4 * LIM);
+    S.fps_tmp = G.get<float>(T1);
+    S.fps_tie[1] = G.get<int>(NC); S.fps_tie[2] = G.get<int>(NC);
+    S.p[0] = io->points_geom; S.nrm[0] = io->normals;
+    for (int l = 1; l < 4; ++l) {
+        S.down[l] = G.get<int>(V.T[l]);
+        S.p[l] = G.get<float>((size_t)V.T[l] * 3);
+        S.nrm[l] = G.get<float>((size_t)V.T[l] * 3);
+    }
+    for (int l = 0; l < 4; ++l) {
+        const int K = E.nsample[l];
+        const int mcap = l == 0 ? T1 : V.T[l - 1];
+        Arena& GA = (l == 0 && P.knn0_ahead) ? G : GF;
+        S.knn_ws[l] = GA.get<char>(roitr_knn_workspace_bytes(NC, V.T[l], mcap));
+        S.grid[l] = V.T[l] > GRID_MIN_POINTS * NC;
+        S.g_self[l] = GA.get<int>((size_t)V.T[l] * K);
+        S.ppf_self[l] = GA.get<float>((size_t)V.T[l] * K * 4);
+        if (l > 0) {
+            S.g_td[l] = GF.get<int>((size_t)V.T[l] * K);
+            S.ppf_td[l] = GF.get<float>((size_t)V.T[l] * K * 4);
+        } else {
+            S.g_td[0] = S.g_self[0]; S.ppf_td[0] = S.ppf_self[0];  // stride 1: the same kNN (model/model.py:75 vs :31)
+        }
+        if (l < 3) { S.i3[l] = GF.get<int>((size_t)V.T[l] * 3); S.d3[l] = GF.get<float>((size_t)V.T[l] * 3); }
+    }
+    S.d_idx = GF.get<float>(P.etot);
+    S.a_idx = GF.get<float>((size_t)P.etot * 3);
+    S.Emb = GF.get<float>((size_t)P.etot * P.C4);
+    S.c3 = GF.get<int>(V.T[2]);
+    S.c4 = GF.get<int>(T4);
+    S.p2n = GF.get<int>(T1);
+    S.p2nd = GF.get<float>(T1);
+    if (P.gt) {
+        S.gt_pad = GF.get<float>((size_t)P.Tp * 3);
+        S.gt_poff = GF.get<int>((size_t)3 * P.B + 4);
+        S.gt_d2p = GF.get<float>(P.Tp);
+        S.gt_ws_s = GF.get<char>(roitr_knn_workspace_bytes(P.B, P.Tsp, P.Ttp));
+        S.gt_ws_t = GF.get<char>(roitr_knn_workspace_bytes(P.B, P.Ttp, P.Tsp));
+    }
+    if (P.gt_corr) {
+        S.gt_om = GF.get<float>((size_t)P.B * V.nmax[3] * V.nmax[3]);
+        S.gt_nt = GF.get<float>((size_t)T4 * 3);
+        S.gt_nr = GF.get<float>(T4);
+    }
+}
+
+int carve_geometry_buffers(Engine& E, const RoitrForwardIO* io, const Plan& P, GeoBufs& S)
+{
+    Arena& G = P.ahead ? E.garena[E.cur_par] : E.arena;
+    Arena& GF = P.full_ahead ? G : E.arena;
+    carve_geometry(E, io, P, G, GF, S);
+    if (G.fail || GF.fail) {
+        if (P.ahead) E.garena_short = true;   // roitr_engine_forward repeats the call on the main-stream path
+        roitr_set_error("arena exhausted (geometry)", __FILE__, __LINE__);
+        return ROITR_ERR_ARG;
+    }
+    return 0;
+}
+
+// ---- stage 2: the scratch arena (upper bound from the sizes), the geometry stream and its events, the ordering mode and its arena
+int reserve_arenas(Engine& E, const RoitrForwardIO* io, Plan& P)
+{
+    const Levels& V = P.V; hipStream_t st = P.st;
+    const int B = P.B, NC = P.NC, T1 = P.T1, T4 = P.T4, C4 = P.C4, LIM = P.LIM, f = E.cfg.factor;
     {
-        size_t need = (size_t)T1 * 4 * (64 * f * 14 + 256 * f * 2 + 600) + (size_t)etot * (C4 * 4 + 64) /* E once + its index arrays */ + (size_t)T4 * C4 * 4 * 40 +
-                      NPs * (LIM * LIM * 3 + (LIM + 1) * (LIM + 1) + LIM * 16) * 4 + (size_t)B * P_ * 16 + ((size_t)64 << 20);
+        size_t need = (size_t)T1 * 4 * (64 * f * 14 + 256 * f * 2 + 600) + (size_t)P.etot * (C4 * 4 + 64) /* E once + its index arrays */ + (size_t)T4 * C4 * 4 * 40 +
+                      P.NPs * (LIM * LIM * 3 + (LIM + 1) * (LIM + 1) + LIM * 16) * 4 + (size_t)B * P.P_ * 16 + ((size_t)64 << 20);
         if (E.cfg.operand_dtype == 1) need += (size_t)T1 * C4 * 2 + 1024;   // bf16 copy of the point descriptors (patch scores)
         for (int l = 0; l < 4; ++l) need += roitr_knn_workspace_bytes(NC, V.T[l], T1) + 1024;
         need += (size_t)B * (roitr_coarse_scratch_floats(V.nmax[3], V.nmax[3]) + (size_t)2 * V.nmax[3] * V.nmax[3]) * 4 + 1024;
@@ -1118,7 +1256,6 @@ static int forward_body(void* h, const RoitrForwardIO* io, hipStream_t st)
         }
         E.arena.off = 0; E.arena.fail = false;
     }
-    Arena& A = E.arena;
     if (!E.side) {
         // (a lower or higher queue priority for this stream changes nothing measurable: 97.3 / 98.2 / 98.2 ms per 512-pair step)
         // (round 5: the same stream confined to 32 / 64 / 96 / 128 / 192 CUs by hipExtStreamCreateWithCUMask, spread evenly over the XCDs,
@@ -1127,45 +1264,33 @@ static int forward_body(void* h, const RoitrForwardIO* io, hipStream_t st)
         ROITR_HIP(hipStreamCreateWithFlags(&E.side, hipStreamNonBlocking));
         for (int i = 0; i < Engine::NEV; ++i) ROITR_HIP(hipEventCreateWithFlags(&E.ev[i], hipEventDisableTiming));
     }
-    hipStream_t sd = E.side;
+    hipStream_t sd = P.sd = E.side;
 
-    // descriptors: off[4][NC], cloud_of_node[T4], partner[NC], eoff[NC] (long), cloud_ids for rows of level 4
-    const size_t desc_ints = (size_t)4 * NC + T4 + NC + 8;
-    const size_t desc_bytes = ((desc_ints * 4 + 15) & ~(size_t)15) + (size_t)NC * 8;
     // ---------------- sampling ahead of the previous forward's tail (io->inputs_ready, include/roitr_engine.h).  `st` is in order,
     // so everything queued on it for this forward starts after the previous forward has left it -- but the first sampling level
     // (one serial chain per cloud: 0.9 ms for a 5000-point pair, 1/3 of a one-pair forward) needs the input coordinates only.
     // With the inputs ordered by an event instead of by `st`, the geometry stream copies the descriptors and runs that level
     // at once, beside the previous forward; the rest of the geometry chain writes scratch of the shared arena and waits, as
     // before, for the point of `st` where this forward begins.
-    bool ahead = io->inputs_ready != nullptr && E.capture_pin == nullptr && !E.ahead_off;
+    P.ahead = io->inputs_ready != nullptr && E.capture_pin == nullptr && !E.ahead_off;
     // ... and so does the level-1 grid + self kNN (+ PPF) the first transformer starts from: in the ahead mode it runs in front of the
     // sampling level on the geometry stream, its workspace and its group / PPF arrays in the alternating arena too (the previous call's
     // decoder still reads ITS level-1 groups) -- 3 ms per 512-pair step off the main stream's chain
     // up to 128 pairs per call: a small batch is bound by the main stream's chain (one pair per call 2.01 -> 1.87 ms, 64 pairs 12.25 -> 12.04 ms);
     // at 512 pairs the step is bound by the chip's total work and the move only shifts contention onto the GEMMs (5 843 / 5 886 vs 5 906 / 5 862
     // pairs/s, gemm_kernel 37.7 -> 38.9 ms per step)
-    bool knn0_ahead = ahead && B <= AHEAD_MAX_PAIRS;
-    // ... and with it the WHOLE geometry chain (round 4, last step): for calls of up to 128 pairs every buffer the geometry stream writes lives in
+    P.knn0_ahead = P.ahead && B <= AHEAD_MAX_PAIRS;
+    // ... and with it the WHOLE geometry chain: for calls of up to 128 pairs every buffer the geometry stream writes lives in
     // the alternating arena, so the chain of call s + 1 needs nothing from the main stream: it runs beside call s from the first kernel to
     // the last and only waits for the call before that one (same arena) to have ended
-    bool full_ahead = knn0_ahead;
-    if (ahead) {
+    P.full_ahead = P.knn0_ahead;
+    if (P.ahead) {
         Arena& G = E.garena[E.gpar];
-        size_t need = desc_bytes + (size_t)T1 * 4 + (size_t)2 * NC * 4 + 8192;
-        for (int l = 1; l < 4; ++l) need += (size_t)V.T[l] * (4 + 12 + 12) + 1024;
-        if (knn0_ahead) need += roitr_knn_workspace_bytes(NC, V.T[0], T1) + (size_t)V.T[0] * E.nsample[0] * (4 + 16) + 4096;
-        if (full_ahead) {   // everything carved from GA below (each allocation rounds up to 256 bytes)
-            for (int l = 1; l < 4; ++l)
-                need += roitr_knn_workspace_bytes(NC, V.T[l], V.T[l - 1]) + (size_t)V.T[l] * E.nsample[l] * (4 + 16) * 2 + 2048;
-            for (int l = 0; l < 3; ++l) need += (size_t)V.T[l] * 3 * 8 + 1024;
-            need += (size_t)etot * (4 + 12 + (size_t)C4 * 4) + 2048;                                   // d_idx, a_idx, E
-            need += (size_t)T4 * (3 * 4 + 4 + (size_t)LIM * 8) + 2048;                                   // node outputs the caller did not ask for
-            const size_t Tp = (size_t)T1 + NC;
-            need += (size_t)V.T[2] * 4 + (size_t)T4 * 4 + (size_t)T1 * 8 + 2048;                         // partition scratch
-            need += Tp * 16 + (size_t)B * 12 + 2 * roitr_knn_workspace_bytes(B, (int)Tp, (int)Tp) + 4096;   // ground-truth clouds + their kNN
-            need += (size_t)B * V.nmax[3] * V.nmax[3] * 4 + (size_t)T4 * 16 + 2048;                      // node correspondences
-        }
+        Arena cnt, rest;   // the size of the alternating arena: what carve_geometry takes from it (no base: only `off` advances)
+        cnt.cap = rest.cap = ~(size_t)0;
+        GeoBufs unused;
+        carve_geometry(E, io, P, cnt, P.full_ahead ? cnt : rest, unused);
+        const size_t need = cnt.off;
         if (need > G.cap) {
             ROITR_HIP(hipStreamSynchronize(st));
             ROITR_HIP(hipStreamSynchronize(sd));
@@ -1177,24 +1302,32 @@ static int forward_body(void* h, const RoitrForwardIO* io, hipStream_t st)
                 (void)hipGetLastError();
                 G.base = nullptr;
                 E.ahead_off = true;
-                ahead = knn0_ahead = full_ahead = false;
+                P.ahead = P.knn0_ahead = P.full_ahead = false;
             }
         }
     }
-    if (io->inputs_ready && !ahead && E.capture_pin == nullptr) ROITR_HIP(hipStreamWaitEvent(st, (hipEvent_t)io->inputs_ready, 0));   // inputs ordered by the event all the same
-    Arena& G = ahead ? E.garena[E.gpar] : E.arena;
-    if (ahead) {
+    if (io->inputs_ready && !P.ahead && E.capture_pin == nullptr) ROITR_HIP(hipStreamWaitEvent(st, (hipEvent_t)io->inputs_ready, 0));   // inputs ordered by the event all the same
+    if (P.ahead) {
+        Arena& G = E.garena[E.gpar];
         G.off = 0; G.fail = false;
         E.cur_par = E.gpar;
         if (!E.gend[E.gpar]) ROITR_HIP(hipEventCreateWithFlags(&E.gend[E.gpar], hipEventDisableTiming));
-        // the call that used this arena before (two calls back) must have left the main stream: implied by `sd` waiting for ev[0] in the
-        // partial mode, the only ordering left in the full one
+        // the call that used this arena before (two calls back) must have left the main stream: implied by `sd` waiting for
+        // EV_MAIN_BEGIN in the partial mode, the only ordering left in the full one
         if (E.gend_rec[E.gpar]) ROITR_HIP(hipStreamWaitEvent(sd, E.gend[E.gpar], 0));
         E.gpar ^= 1;
         ROITR_HIP(hipStreamWaitEvent(sd, (hipEvent_t)io->inputs_ready, 0));
         E.side_forked = true;
     }
-    hipStream_t st_desc = ahead ? sd : st;   // the stream that stages the descriptors
+    return 0;
+}
+
+// ---- stage 3: the descriptor block, filled in a pinned staging buffer and copied on the stream the mode picks
+int stage_descriptors(Engine& E, const Plan& P, GeoBufs& S)
+{
+    const Levels& V = P.V; const int B = P.B, NC = P.NC; hipStream_t st = P.st, sd = P.sd;
+    const size_t desc_bytes = Desc::bytes(NC, P.T4);
+    hipStream_t st_desc = P.ahead ? sd : st;   // the stream that stages the descriptors
     const int slot = E.ring_pos;
     char* pin = E.capture_pin;   // a captured forward owns its staging buffer (the graph re-reads it at every launch)
     if (!pin) {
@@ -1208,368 +1341,314 @@ static int forward_body(void* h, const RoitrForwardIO* io, hipStream_t st)
         }
         pin = E.pinned[slot];
     }
-    int* hp = (int*)pin;
-    for (int l = 0; l < 4; ++l) memcpy(hp + (size_t)l * NC, V.off[l].data(), sizeof(int) * NC);
-    int* h_con = hp + (size_t)4 * NC;
-    for (int c = 0, r = 0; c < NC; ++c) for (int i = 0; i < V.n[3][c]; ++i) h_con[r++] = c;
-    int* h_partner = h_con + T4;
-    for (int c = 0; c < NC; ++c) h_partner[c] = c < B ? c + B : c - B;
-    long* h_eoff = (long*)(pin + ((desc_ints * 4 + 15) & ~(size_t)15));
-    memcpy(h_eoff, eoff.data(), sizeof(long) * NC);
-    char* ddesc = G.get<char>(desc_bytes);
-    ROITR_HIP(hipMemcpyAsync(ddesc, pin, desc_bytes, hipMemcpyHostToDevice, st_desc));
+    const Desc H = Desc::at(pin, NC, P.T4);
+    for (int l = 0; l < 4; ++l) memcpy(H.off[l], V.off[l].data(), sizeof(int) * NC);
+    for (int c = 0, r = 0; c < NC; ++c) for (int i = 0; i < V.n[3][c]; ++i) H.cloud_of_node[r++] = c;
+    for (int c = 0; c < NC; ++c) H.partner[c] = c < B ? c + B : c - B;
+    memcpy(H.eoff, P.eoff.data(), sizeof(long) * NC);
+    ROITR_HIP(hipMemcpyAsync(S.desc, pin, desc_bytes, hipMemcpyHostToDevice, st_desc));
     if (!E.capture_pin) ROITR_HIP(hipEventRecord(E.pinned_ev[slot], st_desc));
-    if (ahead) {   // `st` reads the descriptors (and the inputs) from here on
-        ROITR_HIP(hipEventRecord(E.ev[9], sd));
-        ROITR_HIP(hipStreamWaitEvent(st, E.ev[9], 0));
+    if (P.ahead) {   // `st` reads the descriptors (and the inputs) from here on
+        ROITR_HIP(hipEventRecord(E.ev[Engine::EV_DESC_COPIED], sd));
+        ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_DESC_COPIED], 0));
     }
-    Dev D;
-    for (int l = 0; l < 4; ++l) D.off[l] = (int*)ddesc + (size_t)l * NC;
-    D.cloud_of_node = (int*)ddesc + (size_t)4 * NC;
-    D.partner = D.cloud_of_node + T4;
-    D.eoff = (long*)(ddesc + ((desc_ints * 4 + 15) & ~(size_t)15));
+    S.D = Desc::at(S.desc, NC, P.T4);
+    return 0;
+}
 
-    roitr_prof_begin(ROITR_PROF_PH_FORWARD, 0.0, st);
-    // ---------------- hierarchy: the GEOMETRY CHAIN on a side stream, the feature path on the main one
-    // (model/model.py:56-80, 30-42, 195-205).  Everything below depends on the input coordinates only: the FPS chain, the
-    // grids, self / TransitionDown kNN groups + PPF of levels 2-4, the decoder's 3-NN, the distance / angle indices and the
-    // embedding E of the global transformer.  These kernels are issue- / latency- / LDS-bound (FPS: one long serial workgroup
-    // per cloud; kNN: VALU issue; geo_table: LDS), the feature path beside them is MFMA- and HBM-bound, so they share the chip
-    // instead of queueing in front of each level (round 3; the FPS chain alone since round 1).  Level 1's grid and self kNN stay on
-    // the main stream (the first transformer needs them at once).  Level l's feature work waits for "level l geometry done" only.
-    const float* p[4]; const float* nrm[4];
-    p[0] = io->points_geom; nrm[0] = io->normals;
-    int* down[4] = {nullptr, nullptr, nullptr, nullptr};  // FPS indices into level l-1 (global rows)
-    int* g_self[4]; float* ppf_self[4];                    // self kNN groups (blocks + decoder)
-    int* g_td[4]; float* ppf_td[4];                        // TransitionDown groups (level l nodes over level l-1 points)
-    int* i3[3]; float* d3[3];                              // decoder: 3 nearest level-(l+1) points of every level-l point
-    void* knn_ws[4];
-    bool grid[4];
-    const void* order[4] = {nullptr, nullptr, nullptr, nullptr};  // cell-order visiting order of each level's points
-    float* xe[4];
-    std::function<int()> issue_geo, issue_tail;   // see the end of the side-stream section
-    const float* pts_out = io->points_out ? io->points_out : io->points_geom;
-    Arena& GF = full_ahead ? G : A;     // everything else the geometry stream writes
-    float* node_xyz = io->node_xyz ? io->node_xyz : GF.get<float>((size_t)T4 * 3);
-    int* node_masks = io->node_masks ? io->node_masks : GF.get<int>(T4);
-    int* kidx = io->node_knn_idx ? io->node_knn_idx : GF.get<int>((size_t)T4 * LIM);
-    int* kmask = io->node_knn_mask ? io->node_knn_mask : GF.get<int>((size_t)T4 * LIM);
-    float* d_idx = nullptr; float* a_idx = nullptr; float* Emb = nullptr;
-    // bf16 operand mode: E (an operand of the q~ . E and a' . E contractions of every self layer) is stored bf16 when the
-    // attention kernel for this width reads it (C = 256 / 512, 4 heads, <= 512 superpoints)
-    const bool e_h = E.cfg.operand_dtype == 1 && E.proj_d.wb && E.proj_a.wb && (C4 == 256 || C4 == 512) && V.nmax[3] <= 512;
-    {
-        float* fps_tmp = G.get<float>(T1);
-        int* fps_tie[4] = {nullptr, G.get<int>(NC), G.get<int>(NC), nullptr};   // per cloud: first pick with a shared arg-max
-        for (int l = 1; l < 4; ++l) {
-            down[l] = G.get<int>(V.T[l]);
-            p[l] = G.get<float>((size_t)V.T[l] * 3);
-            nrm[l] = G.get<float>((size_t)V.T[l] * 3);
-        }
-        if (G.fail) { if (ahead) E.garena_short = true; roitr_set_error("arena exhausted (sampling)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-        // level l's picks and their coordinates / normals: the part of the geometry chain that touches none of the shared scratch
-        auto sample_level = [&](int l) -> int {
-            // tmp = 1e10 (functions/pointops.py:22)
-            ROITR_HIP(hipMemsetD32Async((hipDeviceptr_t)fps_tmp, 0x501502F9 /* bits of 1e10f */, V.T[l - 1], sd));
-            roitr_prof_next_bytes(ROITR_PROF_FPS, 12.0 * V.T[l - 1] + 4.0 * V.T[l] + 8.0 * V.T[l - 1]);
-            // levels 2 and 3 sample the previous level's picks in pick order: answered with the prefix while no arg-max was
-            // shared (pointops_fps.hip), the serial chain of 312 + 78 dependent iterations otherwise
-            CHK(roitr_furthestsampling_ex(NC, V.nmax[l - 1], p[l - 1], D.off[l - 1], D.off[l], fps_tmp, down[l], l > 1 ? fps_tie[l - 1] : nullptr,
-                                          l < 3 ? fps_tie[l] : nullptr, 4, sd));
-            CHK(roitr_gather_rows(V.T[l], 3, p[l - 1], down[l], 0, (float*)p[l], sd));
-            CHK(roitr_gather_rows(V.T[l], 3, nrm[l - 1], down[l], 0, (float*)nrm[l], sd));
-            return ROITR_OK;
-        };
-        // every buffer the side stream writes is carved here, before the encoder's mark / release scopes
-        for (int l = 0; l < 4; ++l) {
-            const int K = E.nsample[l];
-            const int mcap = l == 0 ? T1 : V.T[l - 1];
-            Arena& GA = (l == 0 && knn0_ahead) ? G : GF;
-            knn_ws[l] = GA.get<char>(roitr_knn_workspace_bytes(NC, V.T[l], mcap));
-            grid[l] = V.T[l] > GRID_MIN_POINTS * NC;
-            g_self[l] = GA.get<int>((size_t)V.T[l] * K);
-            ppf_self[l] = GA.get<float>((size_t)V.T[l] * K * 4);
-            if (l > 0) {
-                g_td[l] = GF.get<int>((size_t)V.T[l] * K);
-                ppf_td[l] = GF.get<float>((size_t)V.T[l] * K * 4);
-            } else {
-                g_td[0] = g_self[0]; ppf_td[0] = ppf_self[0];  // stride 1: the same kNN (model/model.py:75 vs :31)
-            }
-            if (l < 3) { i3[l] = GF.get<int>((size_t)V.T[l] * 3); d3[l] = GF.get<float>((size_t)V.T[l] * 3); }
-        }
-        d_idx = GF.get<float>(etot);
-        a_idx = GF.get<float>((size_t)etot * 3);
-        Emb = GF.get<float>((size_t)etot * C4);
-        if (A.fail || G.fail) { if (ahead) E.garena_short = true; roitr_set_error("arena exhausted (geometry)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
+// ---- stage 5: the geometry chain
+// level l's picks and their coordinates / normals: the part of the geometry chain that touches none of the shared scratch
+int sample_level(const Plan& P, const GeoBufs& S, int l)
+{
+    const Levels& V = P.V; hipStream_t sd = P.sd;
+    // tmp = 1e10 (functions/pointops.py:22)
+    ROITR_HIP(hipMemsetD32Async((hipDeviceptr_t)S.fps_tmp, 0x501502F9 /* bits of 1e10f */, V.T[l - 1], sd));
+    roitr_prof_next_bytes(ROITR_PROF_FPS, 12.0 * V.T[l - 1] + 4.0 * V.T[l] + 8.0 * V.T[l - 1]);
+    // levels 2 and 3 sample the previous level's picks in pick order: answered with the prefix while no arg-max was
+    // shared (pointops_fps.hip), the serial chain of 312 + 78 dependent iterations otherwise
+    CHK(roitr_furthestsampling_ex(P.NC, V.nmax[l - 1], S.p[l - 1], S.D.off[l - 1], S.D.off[l], S.fps_tmp, S.down[l], l > 1 ? S.fps_tie[l - 1] : nullptr,
+                                  l < 3 ? S.fps_tie[l] : nullptr, 4, sd));
+    CHK(roitr_gather_rows(V.T[l], 3, S.p[l - 1], S.down[l], 0, (float*)S.p[l], sd));
+    CHK(roitr_gather_rows(V.T[l], 3, S.nrm[l - 1], S.down[l], 0, (float*)S.nrm[l], sd));
+    return ROITR_OK;
+}
 
-        // ---- level-1 grid + self kNN (+ PPF): on the main stream (the first transformer needs them at once), or -- ahead mode -- in
-        // front of everything else on the geometry stream, beside the previous call
-        hipStream_t s0 = knn0_ahead ? sd : st;
-        if (grid[0]) {
-            // 6 points per cell on average: at level 1 (k = 8) the sphere of one cell size then holds ~2.5 (k + 2) points, what
-            // the prefilter kNN kernel's radius rule needs
-            CHK(roitr_knn_build_grid_ex(NC, V.T[0], T1, p[0], D.off[0], knn_ws[0], GRID_OCC, s0));
-            order[0] = roitr_knn_sorted_points(NC, V.T[0], T1, knn_ws[0]);
+// the embedding of the global transformer (positional_encoding.py:139-154): needs the level-4 coordinates only
+int issue_embedding(Engine& E, const Plan& P, const GeoBufs& S)
+{
+    const Desc& D = S.D; const int C4 = P.C4; const long etot = P.etot; hipStream_t sd = P.sd;
+    CHK(roitr_geo_indices(P.T4, S.p[3], D.off[3], D.cloud_of_node, D.eoff, 0.2f, 15.0f, 3, P.V.nmax[3], S.d_idx, S.a_idx, sd));
+    if (E.geo_tab && roitr_geo_embed_table(etot, C4, 3, S.d_idx, S.a_idx, E.geo_tab, E.geo_tab_h, E.geo_tab_nd, E.geo_tab_na, E.geo_div,
+                                           E.proj_d.w, E.proj_d.b, E.proj_a.w, E.proj_a.b, S.Emb, P.e_h ? 1 : 0, sd) != ROITR_OK)
+        E.geo_tab = nullptr;   // e.g. a device that does not grant the table's LDS: this engine serves the GEMM form from now on
+    if (!E.geo_tab) {
+        if (P.e_h)
+            CHK(roitr_geo_embed_bf16_out(etot, C4, 3, S.d_idx, S.a_idx, E.geo_div, E.proj_d.wb, E.proj_d.b, E.proj_a.wb, E.proj_a.b,
+                                         reinterpret_cast<unsigned short*>(S.Emb), sd));
+        else if (E.cfg.operand_dtype == 1 && E.proj_d.wb && E.proj_a.wb)
+            CHK(roitr_geo_embed_bf16(etot, C4, 3, S.d_idx, S.a_idx, E.geo_div, E.proj_d.wb, E.proj_d.b, E.proj_a.wb, E.proj_a.b, S.Emb, sd));
+        else
+            CHK(roitr_geo_embed(etot, C4, 3, S.d_idx, S.a_idx, E.geo_div, E.proj_d.w, E.proj_d.b, E.proj_a.w, E.proj_a.b, S.Emb, sd));
+    }
+    ROITR_HIP(hipEventRecord(E.ev[Engine::EV_EMBED_DONE], sd));
+    return ROITR_OK;
+}
+
+// the chain's tail: the decoder's 3-NN, node coordinates, partition, ground-truth outputs
+int issue_tail(Engine& E, const RoitrForwardIO* io, const Plan& P, const GeoBufs& S)
+{
+    const Levels& V = P.V; const Desc& D = S.D; hipStream_t sd = P.sd;
+    const int B = P.B, NC = P.NC, T1 = P.T1, T4 = P.T4, LIM = P.LIM;
+    // the decoder's 3-NN (pointops.py:168-182 `interpolation`): level-l points among the level-(l+1) points
+    for (int l = 2; l >= 0; --l)
+        CHK(roitr_knnquery_ex(NC, V.T[l + 1], V.T[l], 3, S.p[l + 1], S.p[l], D.off[l + 1], D.off[l], S.i3[l], S.d3[l], nullptr, nullptr, nullptr,
+                              nullptr, S.grid[l + 1] ? 1 : 0, V.T[l], S.knn_ws[l + 1], sd));
+    ROITR_HIP(hipEventRecord(E.ev[Engine::EV_NN3_DONE], sd));
+    // From here on the chain writes the CALLER's output buffers (node_xyz, node_masks, node_knn_*, gt_*).  In the whole-chain-ahead
+    // mode nothing so far has ordered this stream against the previous call on `st` -- but that call's matching phase may still
+    // read ITS outputs through the same pointers (a C caller that reuses one set of buffers; torch's caching allocator handing a
+    // freed block out again): wait for the point where this call begins on `st` (EV_MAIN_BEGIN, recorded behind everything the
+    // previous call queued there).  The kernels below then run beside this call's encoder instead of the previous call's
+    // tail; the matching phase, which needs them, is 1 - 2 ms further down the main stream.
+    if (P.full_ahead) ROITR_HIP(hipStreamWaitEvent(sd, E.ev[Engine::EV_MAIN_BEGIN], 0));
+    // node coordinates (model/model.py:233-235), point-to-node partition (lib/utils.py:428-471) and the ground-truth side
+    // outputs: coordinates, the FPS picks and the given transform only
+    CHK(roitr_compose_idx(V.T[2], S.down[1], S.down[2], S.c3, sd));  // level-3 nodes as level-1 rows
+    CHK(roitr_compose_idx(T4, S.c3, S.down[3], S.c4, sd));
+    CHK(roitr_gather_rows(T4, 3, S.pts_out, S.c4, 0, S.node_xyz, sd));
+    CHK(roitr_point_to_node_partition(NC, T1, T4, S.pts_out, D.off[0], S.node_xyz, D.off[3], D.cloud_of_node, LIM, S.p2n, S.p2nd, S.node_masks,
+                                      S.kidx, S.kmask, sd));
+    // ---------------- ground-truth side outputs (RIGA_v2.py:91-116), only when rot / trans are given
+    if (P.gt) {
+        const int Tsp = P.Tsp, Ttp = P.Ttp;
+        CHK(roitr_build_padded_clouds(B, T1, S.pts_out, D.off[0], io->rot, io->trans, S.gt_pad, S.gt_poff, sd));
+        const float* src_p = S.gt_pad; const float* tgt_p = S.gt_pad + (size_t)Tsp * 3;
+        const int* off_s = S.gt_poff; const int* off_t = S.gt_poff + 2 * B;
+        const int use_grid = (Tsp > GRID_MIN_POINTS * B) ? 1 : 0;
+        if (io->gt_node_occ) {
+            // kNN(1) of every padded target point among the transformed padded source points, and back (l.509-510)
+            float* d2p = S.gt_d2p;
+            if (use_grid) CHK(roitr_knn_build_grid(B, Tsp, Ttp, src_p, off_s, S.gt_ws_s, sd));
+            const float occ_cap2 = E.cfg.occlusion_radius * E.cfg.occlusion_radius * 1.01f;   // only `distance < radius` is read
+            CHK(roitr_knn_within(B, Tsp, Ttp, src_p, tgt_p, off_s, off_t, occ_cap2, d2p + Tsp, use_grid, Ttp, S.gt_ws_s, sd));
+            if (use_grid) CHK(roitr_knn_build_grid(B, Ttp, Tsp, tgt_p, off_t, S.gt_ws_t, sd));
+            CHK(roitr_knn_within(B, Ttp, Tsp, tgt_p, src_p, off_t, off_s, occ_cap2, d2p, use_grid, Tsp, S.gt_ws_t, sd));
+            CHK(roitr_node_occlusion_score(T4, LIM, D.cloud_of_node, D.off[0], S.kidx, S.kmask, S.node_masks, d2p, E.cfg.occlusion_radius,
+                                           io->gt_node_occ, sd));
         }
-        if (!knn0_ahead) ROITR_HIP(hipEventRecord(E.ev[0], st));  // inputs + descriptors are in place
-        CHK(roitr_knnquery_ex(NC, V.T[0], V.T[0], E.nsample[0] + 1, p[0], p[0], D.off[0], D.off[0], nullptr, nullptr, g_self[0], ppf_self[0],
-                              nrm[0], nrm[0], grid[0] ? 1 : 0, T1, knn_ws[0], s0));
-        if (knn0_ahead) {
-            ROITR_HIP(hipEventRecord(E.ev[11], sd));       // the level-1 groups and PPFs are in place
-            ROITR_HIP(hipStreamWaitEvent(st, E.ev[11], 0));
-            ROITR_HIP(hipEventRecord(E.ev[0], st));        // where this call begins on the main stream: the shared scratch is free from here
+        if (P.gt_corr) {
+            const long ms = (long)V.nmax[3] * V.nmax[3];
+            RoitrNodeCorr nc; memset(&nc, 0, sizeof(nc));
+            nc.pairs = B; nc.limit = LIM; nc.max_nodes = V.nmax[3]; nc.pos_radius = E.cfg.matching_radius;
+            nc.nodes = S.node_xyz; nc.node_offset = D.off[3]; nc.node_masks = S.node_masks; nc.points = S.pts_out; nc.pt_offset = D.off[0];
+            nc.knn_idx = S.kidx; nc.knn_mask = S.kmask; nc.rot = io->rot; nc.trans = io->trans; nc.overlap = S.gt_om; nc.mat_stride = ms;
+            nc.out_idx = io->gt_corr_idx; nc.out_overlap = io->gt_corr_overlaps; nc.out_count = io->gt_corr_count;
+            nc.n_nodes = T4; nc.nodes_t = S.gt_nt; nc.radius = S.gt_nr;
+            CHK(roitr_node_correspondences(&nc, sd));
+        }
+    }
+    ROITR_HIP(hipEventRecord(E.ev[Engine::EV_TAIL_DONE], sd));
+    return ROITR_OK;
+}
+
+// hierarchy: the GEOMETRY CHAIN on a side stream, the feature path on the main one
+// (model/model.py:56-80, 30-42, 195-205).  Everything here depends on the input coordinates only: the FPS chain, the
+// grids, self / TransitionDown kNN groups + PPF of levels 2-4, the decoder's 3-NN, the distance / angle indices and the
+// embedding E of the global transformer.  These kernels are issue- / latency- / LDS-bound (FPS: one long serial workgroup
+// per cloud; kNN: VALU issue; geo_table: LDS), the feature path beside them is MFMA- and HBM-bound, so they share the chip
+// instead of queueing in front of each level (round 3; the FPS chain alone since round 1).  Level 1's grid and self kNN stay on
+// the main stream (the first transformer needs them at once).  Level l's feature work waits for "level l geometry done" only.
+int issue_geometry_chain(Engine& E, const RoitrForwardIO* io, const Plan& P, GeoBufs& S)
+{
+    const Levels& V = P.V; const Desc& D = S.D; const int NC = P.NC, T1 = P.T1; hipStream_t st = P.st, sd = P.sd;
+    // ---- level-1 grid + self kNN (+ PPF): on the main stream (the first transformer needs them at once), or -- ahead mode -- in
+    // front of everything else on the geometry stream, beside the previous call
+    hipStream_t s0 = P.knn0_ahead ? sd : st;
+    if (S.grid[0]) {
+        // 6 points per cell on average: at level 1 (k = 8) the sphere of one cell size then holds ~2.5 (k + 2) points, what
+        // the prefilter kNN kernel's radius rule needs
+        CHK(roitr_knn_build_grid_ex(NC, V.T[0], T1, S.p[0], D.off[0], S.knn_ws[0], GRID_OCC, s0));
+        S.order[0] = roitr_knn_sorted_points(NC, V.T[0], T1, S.knn_ws[0]);
+    }
+    if (!P.knn0_ahead) ROITR_HIP(hipEventRecord(E.ev[Engine::EV_MAIN_BEGIN], st));  // inputs + descriptors are in place
+    CHK(roitr_knnquery_ex(NC, V.T[0], V.T[0], E.nsample[0] + 1, S.p[0], S.p[0], D.off[0], D.off[0], nullptr, nullptr, S.g_self[0], S.ppf_self[0],
+                          S.nrm[0], S.nrm[0], S.grid[0] ? 1 : 0, T1, S.knn_ws[0], s0));
+    if (P.knn0_ahead) {
+        ROITR_HIP(hipEventRecord(E.ev[Engine::EV_LEVEL1_GROUPS_READY], sd));   // the level-1 groups and PPFs are in place
+        ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_LEVEL1_GROUPS_READY], 0));
+        ROITR_HIP(hipEventRecord(E.ev[Engine::EV_MAIN_BEGIN], st));            // where this call begins on the main stream: the shared scratch is free from here
+    } else
+        ROITR_HIP(hipEventRecord(E.ev[Engine::EV_LEVEL1_WS_FREE], st));  // the level-1 workspace (grid + retry list) is free for the TransitionDown query
+    if (P.ahead) CHK(sample_level(P, S, 1));
+
+    // ---- side stream
+    if (!P.full_ahead) ROITR_HIP(hipStreamWaitEvent(sd, E.ev[Engine::EV_MAIN_BEGIN], 0));   // (full mode: nothing below touches the shared arena)
+    E.side_forked = true;
+    for (int l = 1; l < 4; ++l) {
+        const int K = E.nsample[l];
+        if (!(P.ahead && l == 1)) CHK(sample_level(P, S, l));
+        // grid over this level's points (refs for: own self-kNN, next level's TD query, finer level's 3-NN)
+        if (S.grid[l]) {
+            CHK(roitr_knn_build_grid_ex(NC, V.T[l], V.T[l - 1], S.p[l], D.off[l], S.knn_ws[l], GRID_OCC, sd));
+            S.order[l] = roitr_knn_sorted_points(NC, V.T[l], V.T[l - 1], S.knn_ws[l]);
+        }
+        CHK(roitr_knnquery_ex(NC, V.T[l], V.T[l], K + 1, S.p[l], S.p[l], D.off[l], D.off[l], nullptr, nullptr, S.g_self[l], S.ppf_self[l], S.nrm[l],
+                              S.nrm[l], S.grid[l] ? 1 : 0, V.T[l - 1], S.knn_ws[l], sd));
+        if (l == 1 && !P.knn0_ahead) ROITR_HIP(hipStreamWaitEvent(sd, E.ev[Engine::EV_LEVEL1_WS_FREE], 0));   // (ahead mode: that query ran on this stream)
+        const int mcap_prev = l - 1 == 0 ? T1 : V.T[l - 2];
+        CHK(roitr_knnquery_ex(NC, V.T[l - 1], V.T[l], K + 1, S.p[l - 1], S.p[l], D.off[l - 1], D.off[l], nullptr, nullptr, S.g_td[l],
+                              S.ppf_td[l], S.nrm[l - 1], S.nrm[l], S.grid[l - 1] ? 1 : 0, mcap_prev, S.knn_ws[l - 1], sd));
+        ROITR_HIP(hipEventRecord(E.ev[Engine::ev_level_done(l)], sd));
+    }
+    // The embedding E and the chain's tail (3-NN, partition, ground-truth outputs).  (Round 4 measured both units queued behind
+    // encoder level 1, 2 or 3 instead of here: no effect on the step)
+    CHK(issue_embedding(E, P, S));
+    return issue_tail(E, io, P, S);
+}
+
+// ---- stage 6: the encoder (model/model.py:195-205), level l behind "level l geometry done"
+int encoder(Engine& E, const RoitrForwardIO* io, const Plan& P, const GeoBufs& S, Feats& F)
+{
+    const Levels& V = P.V; const int T1 = P.T1; hipStream_t st = P.st; Arena& A = E.arena;
+    const float* xin = io->feats;
+    for (int l = 0; l < 4; ++l) {
+        const int K = E.nsample[l], pl = E.planes[l];
+        if (l > 0) {
+            ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::ev_level_done(l)], 0));
+            CHK(tap(E, st, "fps." + std::to_string(l + 1), S.down[l], sizeof(int) * V.T[l]));
+        }
+        CHK(tap(E, st, "group.self." + std::to_string(l + 1), S.g_self[l], sizeof(int) * (size_t)V.T[l] * K));
+        CHK(tap(E, st, "ppf.self." + std::to_string(l + 1), S.ppf_self[l], sizeof(float) * (size_t)V.T[l] * K * 4));
+        if (l > 0) {
+            CHK(tap(E, st, "group.td." + std::to_string(l + 1), S.g_td[l], sizeof(int) * (size_t)V.T[l] * K));
+            CHK(tap(E, st, "ppf.td." + std::to_string(l + 1), S.ppf_td[l], sizeof(float) * (size_t)V.T[l] * K * 4));
+        }
+        // ---- encoder level l
+        float* a = A.get<float>((size_t)V.T[l] * pl);
+        float* b = A.get<float>((size_t)V.T[l] * pl);
+        if (A.fail) break;
+        const int n_in = l == 0 ? T1 : V.T[l - 1];
+        if (l == 0 && E.first_consts && (K == 8 || K == 16)) {
+            // the first transformer of the network: scalar input feature -> rank-1 q | k | v (csrc/local_block.hip)
+            const LocalT& L0 = E.enc[0][0];
+            RoitrLocalFirst lf;
+            memset(&lf, 0, sizeof(lf));
+            lf.M = T1; lf.K = K; lf.x = xin; lf.group_idx = S.g_td[0]; lf.ppf = S.ppf_td[0]; lf.node_order = S.order[0];
+            lf.head_consts = E.first_consts; lf.G = E.first_consts + 64; lf.zero_bias = E.first_consts + 64 + 64 * 32;
+            lf.norm_w = L0.norm_w; lf.norm_b = L0.norm_b; lf.wout = L0.out_proj.w; lf.bout = L0.out_proj.b;
+            lf.scale = 1.0f / sqrtf((float)(L0.H / HEADS)); lf.eps = 1e-5f; lf.out = a;
+            CHK(roitr_local_first(&lf, st));
         } else
-            ROITR_HIP(hipEventRecord(E.ev[4], st));  // the level-1 workspace (grid + retry list) is free for the TransitionDown query
-        if (ahead) CHK(sample_level(1));
-
-        // ---- side stream
-        if (!full_ahead) ROITR_HIP(hipStreamWaitEvent(sd, E.ev[0], 0));   // (full mode: nothing below touches the shared arena)
-        E.side_forked = true;
-        for (int l = 1; l < 4; ++l) {
-            const int K = E.nsample[l];
-            if (!(ahead && l == 1)) CHK(sample_level(l));
-            // grid over this level's points (refs for: own self-kNN, next level's TD query, finer level's 3-NN)
-            if (grid[l]) {
-                CHK(roitr_knn_build_grid_ex(NC, V.T[l], V.T[l - 1], p[l], D.off[l], knn_ws[l], GRID_OCC, sd));
-                order[l] = roitr_knn_sorted_points(NC, V.T[l], V.T[l - 1], knn_ws[l]);
-            }
-            CHK(roitr_knnquery_ex(NC, V.T[l], V.T[l], K + 1, p[l], p[l], D.off[l], D.off[l], nullptr, nullptr, g_self[l], ppf_self[l], nrm[l],
-                                  nrm[l], grid[l] ? 1 : 0, V.T[l - 1], knn_ws[l], sd));
-            if (l == 1 && !knn0_ahead) ROITR_HIP(hipStreamWaitEvent(sd, E.ev[4], 0));   // (ahead mode: that query ran on this stream)
-            const int mcap_prev = l - 1 == 0 ? T1 : V.T[l - 2];
-            CHK(roitr_knnquery_ex(NC, V.T[l - 1], V.T[l], K + 1, p[l - 1], p[l], D.off[l - 1], D.off[l], nullptr, nullptr, g_td[l],
-                                  ppf_td[l], nrm[l - 1], nrm[l], grid[l - 1] ? 1 : 0, mcap_prev, knn_ws[l - 1], sd));
-            ROITR_HIP(hipEventRecord(E.ev[l], sd));
+        CHK(local_transformer(E, st, E.enc[l][0], n_in, xin, V.T[l], l == 0 ? nullptr : S.down[l], S.g_td[l], S.ppf_td[l], K, a, S.order[l]));
+        CHK(tap(E, st, "enc" + std::to_string(l + 1) + ".0", a, sizeof(float) * (size_t)V.T[l] * pl));
+        float* cur = a; float* nxt = b;
+        for (int bi = 1; bi < E.nblocks[l]; ++bi) {
+            CHK(block(E, st, E.enc[l][bi], V.T[l], cur, S.g_self[l], S.ppf_self[l], K, nxt, S.order[l]));
+            CHK(tap(E, st, "enc" + std::to_string(l + 1) + "." + std::to_string(bi), nxt, sizeof(float) * (size_t)V.T[l] * pl));
+            float* t = cur; cur = nxt; nxt = t;
         }
-        // The embedding E and the chain's tail (3-NN, partition, ground-truth outputs).  (Round 4 measured both units ENQUEUED behind
-        // encoder level 1, 2 or 3 instead of here: no effect on the step; the switches are gone.)
-        issue_geo = [&]() -> int {
-            // the embedding of the global transformer (positional_encoding.py:139-154): needs the level-4 coordinates only
-            CHK(roitr_geo_indices(T4, p[3], D.off[3], D.cloud_of_node, D.eoff, 0.2f, 15.0f, 3, V.nmax[3], d_idx, a_idx, sd));
-            if (E.geo_tab && roitr_geo_embed_table(etot, C4, 3, d_idx, a_idx, E.geo_tab, E.geo_tab_h, E.geo_tab_nd, E.geo_tab_na, E.geo_div,
-                                                   E.proj_d.w, E.proj_d.b, E.proj_a.w, E.proj_a.b, Emb, e_h ? 1 : 0, sd) != ROITR_OK)
-                E.geo_tab = nullptr;   // e.g. a device that does not grant the table's LDS: this engine serves the GEMM form from now on
-            if (E.geo_tab) {}
-            else if (e_h)
-                CHK(roitr_geo_embed_bf16_out(etot, C4, 3, d_idx, a_idx, E.geo_div, E.proj_d.wb, E.proj_d.b, E.proj_a.wb, E.proj_a.b,
-                                             reinterpret_cast<unsigned short*>(Emb), sd));
-            else if (E.cfg.operand_dtype == 1 && E.proj_d.wb && E.proj_a.wb)
-                CHK(roitr_geo_embed_bf16(etot, C4, 3, d_idx, a_idx, E.geo_div, E.proj_d.wb, E.proj_d.b, E.proj_a.wb, E.proj_a.b, Emb, sd));
-            else
-                CHK(roitr_geo_embed(etot, C4, 3, d_idx, a_idx, E.geo_div, E.proj_d.w, E.proj_d.b, E.proj_a.w, E.proj_a.b, Emb, sd));
-            ROITR_HIP(hipEventRecord(E.ev[5], sd));
-            return ROITR_OK;
-        };
-        issue_tail = [&]() -> int {
-            // the decoder's 3-NN (pointops.py:168-182 `interpolation`): level-l points among the level-(l+1) points
-            for (int l = 2; l >= 0; --l)
-                CHK(roitr_knnquery_ex(NC, V.T[l + 1], V.T[l], 3, p[l + 1], p[l], D.off[l + 1], D.off[l], i3[l], d3[l], nullptr, nullptr, nullptr,
-                                      nullptr, grid[l + 1] ? 1 : 0, V.T[l], knn_ws[l + 1], sd));
-            ROITR_HIP(hipEventRecord(E.ev[6], sd));
-            // From here on the chain writes the CALLER's output buffers (node_xyz, node_masks, node_knn_*, gt_*).  In the whole-chain-ahead
-            // mode nothing so far has ordered this stream against the previous call on `st` -- but that call's matching phase may still
-            // read ITS outputs through the same pointers (a C caller that reuses one set of buffers; torch's caching allocator handing a
-            // freed block out again): wait for the point where this call begins on `st` (ev[0], recorded behind everything the
-            // previous call queued there).  The kernels below then run beside this call's encoder instead of the previous call's
-            // tail; the matching phase, which needs them, is 1 - 2 ms further down the main stream.
-            if (full_ahead) ROITR_HIP(hipStreamWaitEvent(sd, E.ev[0], 0));
-            // node coordinates (model/model.py:233-235), point-to-node partition (lib/utils.py:428-471) and the ground-truth side
-            // outputs: coordinates, the FPS picks and the given transform only
-            {
-                int* c3 = GF.get<int>(V.T[2]);
-                int* c4 = GF.get<int>(T4);
-                int* p2n = GF.get<int>(T1);
-                float* p2nd = GF.get<float>(T1);
-                if (GF.fail) { if (ahead) E.garena_short = true; roitr_set_error("arena exhausted (partition)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-                CHK(roitr_compose_idx(V.T[2], down[1], down[2], c3, sd));  // level-3 nodes as level-1 rows
-                CHK(roitr_compose_idx(T4, c3, down[3], c4, sd));
-                CHK(roitr_gather_rows(T4, 3, pts_out, c4, 0, node_xyz, sd));
-                CHK(roitr_point_to_node_partition(NC, T1, T4, pts_out, D.off[0], node_xyz, D.off[3], D.cloud_of_node, LIM, p2n, p2nd, node_masks,
-                                                  kidx, kmask, sd));
-            }
-            // ---------------- ground-truth side outputs (RIGA_v2.py:91-116), only when rot / trans are given
-            if (io->rot && io->trans && (io->gt_node_occ || io->gt_corr_idx)) {
-                const int Tp = T1 + NC;                  // padded rows
-                const int Ts = V.off[0][B - 1];          // source rows
-                const int Tsp = Ts + B, Ttp = Tp - Tsp;  // padded source / target rows
-                float* pad = GF.get<float>((size_t)Tp * 3);
-                int* poff = GF.get<int>((size_t)3 * B + 4);
-                float* d2p = GF.get<float>(Tp);
-                void* ws_s = GF.get<char>(roitr_knn_workspace_bytes(B, Tsp, Ttp));
-                void* ws_t = GF.get<char>(roitr_knn_workspace_bytes(B, Ttp, Tsp));
-                if (GF.fail) { if (ahead) E.garena_short = true; roitr_set_error("arena exhausted (gt)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-                CHK(roitr_build_padded_clouds(B, T1, pts_out, D.off[0], io->rot, io->trans, pad, poff, sd));
-                const float* src_p = pad; const float* tgt_p = pad + (size_t)Tsp * 3;
-                const int* off_s = poff; const int* off_t = poff + 2 * B;
-                const int use_grid = (Tsp > GRID_MIN_POINTS * B) ? 1 : 0;
-                if (io->gt_node_occ) {
-                    // kNN(1) of every padded target point among the transformed padded source points, and back (l.509-510)
-                    if (use_grid) CHK(roitr_knn_build_grid(B, Tsp, Ttp, src_p, off_s, ws_s, sd));
-                    const float occ_cap2 = E.cfg.occlusion_radius * E.cfg.occlusion_radius * 1.01f;   // only `distance < radius` is read
-                    CHK(roitr_knn_within(B, Tsp, Ttp, src_p, tgt_p, off_s, off_t, occ_cap2, d2p + Tsp, use_grid, Ttp, ws_s, sd));
-                    if (use_grid) CHK(roitr_knn_build_grid(B, Ttp, Tsp, tgt_p, off_t, ws_t, sd));
-                    CHK(roitr_knn_within(B, Ttp, Tsp, tgt_p, src_p, off_t, off_s, occ_cap2, d2p, use_grid, Tsp, ws_t, sd));
-                    CHK(roitr_node_occlusion_score(T4, LIM, D.cloud_of_node, D.off[0], kidx, kmask, node_masks, d2p, E.cfg.occlusion_radius,
-                                                   io->gt_node_occ, sd));
-                }
-                if (io->gt_corr_idx && io->gt_corr_overlaps && io->gt_corr_count) {
-                    const long ms = (long)V.nmax[3] * V.nmax[3];
-                    float* om = GF.get<float>((size_t)B * ms);
-                    float* nt_ = GF.get<float>((size_t)T4 * 3);
-                    float* nr_ = GF.get<float>(T4);
-                    if (GF.fail) { if (ahead) E.garena_short = true; roitr_set_error("arena exhausted (gt)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-                    RoitrNodeCorr nc; memset(&nc, 0, sizeof(nc));
-                    nc.pairs = B; nc.limit = LIM; nc.max_nodes = V.nmax[3]; nc.pos_radius = E.cfg.matching_radius;
-                    nc.nodes = node_xyz; nc.node_offset = D.off[3]; nc.node_masks = node_masks; nc.points = pts_out; nc.pt_offset = D.off[0];
-                    nc.knn_idx = kidx; nc.knn_mask = kmask; nc.rot = io->rot; nc.trans = io->trans; nc.overlap = om; nc.mat_stride = ms;
-                    nc.out_idx = io->gt_corr_idx; nc.out_overlap = io->gt_corr_overlaps; nc.out_count = io->gt_corr_count;
-                    nc.n_nodes = T4; nc.nodes_t = nt_; nc.radius = nr_;
-                    CHK(roitr_node_correspondences(&nc, sd));
-                }
-            }
-            ROITR_HIP(hipEventRecord(E.ev[7], sd));
-            return ROITR_OK;
-        };
-        CHK(issue_geo());
-        CHK(issue_tail());
-    }
-    roitr_prof_begin(ROITR_PROF_PH_ENC, 0.0, st);
-    {
-        const float* xin = io->feats;
-        for (int l = 0; l < 4; ++l) {
-            const int K = E.nsample[l], pl = E.planes[l];
-            if (l > 0) {
-                ROITR_HIP(hipStreamWaitEvent(st, E.ev[l], 0));
-                CHK(tap(E, st, "fps." + std::to_string(l + 1), down[l], sizeof(int) * V.T[l]));
-            }
-            CHK(tap(E, st, "group.self." + std::to_string(l + 1), g_self[l], sizeof(int) * (size_t)V.T[l] * K));
-            CHK(tap(E, st, "ppf.self." + std::to_string(l + 1), ppf_self[l], sizeof(float) * (size_t)V.T[l] * K * 4));
-            if (l > 0) {
-                CHK(tap(E, st, "group.td." + std::to_string(l + 1), g_td[l], sizeof(int) * (size_t)V.T[l] * K));
-                CHK(tap(E, st, "ppf.td." + std::to_string(l + 1), ppf_td[l], sizeof(float) * (size_t)V.T[l] * K * 4));
-            }
-            // ---- encoder level l
-            float* a = A.get<float>((size_t)V.T[l] * pl);
-            float* b = A.get<float>((size_t)V.T[l] * pl);
-            if (A.fail) break;
-            const int n_in = l == 0 ? T1 : V.T[l - 1];
-            if (l == 0 && E.first_consts && (K == 8 || K == 16)) {
-                // the first transformer of the network: scalar input feature -> rank-1 q | k | v (csrc/local_block.hip)
-                const LocalT& L0 = E.enc[0][0];
-                RoitrLocalFirst lf;
-                memset(&lf, 0, sizeof(lf));
-                lf.M = T1; lf.K = K; lf.x = xin; lf.group_idx = g_td[0]; lf.ppf = ppf_td[0]; lf.node_order = order[0];
-                lf.head_consts = E.first_consts; lf.G = E.first_consts + 64; lf.zero_bias = E.first_consts + 64 + 64 * 32;
-                lf.norm_w = L0.norm_w; lf.norm_b = L0.norm_b; lf.wout = L0.out_proj.w; lf.bout = L0.out_proj.b;
-                lf.scale = 1.0f / sqrtf((float)(L0.H / HEADS)); lf.eps = 1e-5f; lf.out = a;
-                CHK(roitr_local_first(&lf, st));
-            } else
-            CHK(local_transformer(E, st, E.enc[l][0], n_in, xin, V.T[l], l == 0 ? nullptr : down[l], g_td[l], ppf_td[l], K, a, order[l]));
-            CHK(tap(E, st, "enc" + std::to_string(l + 1) + ".0", a, sizeof(float) * (size_t)V.T[l] * pl));
-            float* cur = a; float* nxt = b;
-            for (int bi = 1; bi < E.nblocks[l]; ++bi) {
-                CHK(block(E, st, E.enc[l][bi], V.T[l], cur, g_self[l], ppf_self[l], K, nxt, order[l]));
-                CHK(tap(E, st, "enc" + std::to_string(l + 1) + "." + std::to_string(bi), nxt, sizeof(float) * (size_t)V.T[l] * pl));
-                float* t = cur; cur = nxt; nxt = t;
-            }
-            xe[l] = cur; xin = cur;
-        }
+        F.xe[l] = cur; xin = cur;
     }
     if (A.fail) { roitr_set_error("arena exhausted (encoder)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
+    return 0;
+}
 
-    roitr_prof_end(ROITR_PROF_PH_ENC, st);
-    roitr_prof_begin(ROITR_PROF_PH_GEO, 0.0, st);
-    // ---------------- global geometric transformer (geotransformer.py:94-133), all pairs batched
-    float* gfeat = A.get<float>((size_t)T4 * C4);
-    {
-        const size_t mark = A.off;
-        ROITR_HIP(hipStreamWaitEvent(st, E.ev[5], 0));   // E and its index arrays were written on the side stream
-        CHK(tap(E, st, "geo.d_idx", d_idx, sizeof(float) * etot));
-        CHK(tap(E, st, "geo.a_idx", a_idx, sizeof(float) * etot * 3));
-        CHK(tap(E, st, "geo.emb", Emb, (e_h ? sizeof(unsigned short) : sizeof(float)) * (size_t)etot * C4));   // bf16 mode: the tap holds bf16
+// ---- stage 7: the global geometric transformer (geotransformer.py:94-133), all pairs batched
+int global_transformer(Engine& E, const Plan& P, const GeoBufs& S, Feats& F)
+{
+    const Levels& V = P.V; const Desc& D = S.D; hipStream_t st = P.st; Arena& A = E.arena;
+    const int B = P.B, T4 = P.T4, C4 = P.C4; const long etot = P.etot; const bool e_h = P.e_h;
+    float* gfeat = F.gfeat = A.get<float>((size_t)T4 * C4);
+    const size_t mark = A.off;
+    ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_EMBED_DONE], 0));   // E and its index arrays were written on the side stream
+    CHK(tap(E, st, "geo.d_idx", S.d_idx, sizeof(float) * etot));
+    CHK(tap(E, st, "geo.a_idx", S.a_idx, sizeof(float) * etot * 3));
+    CHK(tap(E, st, "geo.emb", S.Emb, (e_h ? sizeof(unsigned short) : sizeof(float)) * (size_t)etot * C4));   // bf16 mode: the tap holds bf16
 
-        float* fcur = A.get<float>((size_t)T4 * C4);
-        float* pos = A.get<float>((size_t)T4 * C4);
-        float* qkv = A.get<float>((size_t)T4 * 3 * C4);
-        float* qt = A.get<float>((size_t)T4 * HEADS * C4);
-        float* ebar = A.get<float>((size_t)T4 * HEADS * C4);
-        float* hid = A.get<float>((size_t)T4 * C4);
-        float* t1 = A.get<float>((size_t)T4 * C4);
-        float* t2 = A.get<float>((size_t)T4 * C4);
-        if (A.fail) { roitr_set_error("arena exhausted (geo)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-        CHK(gemm(st, T4, xe[3], E.geo_in, fcur));
-        CHK(tap(E, st, "geo.in_proj", fcur, sizeof(float) * (size_t)T4 * C4));
-        const int cpe = C4 / HEADS;
-        const float scale = 1.0f / sqrtf((float)cpe);
-        const int Ts = V.off[3][B - 1];  // source-cloud rows come first
-        for (size_t li = 0; li < E.geo.size(); ++li) {
-            const GeoLayer& L = E.geo[li];
-            if (!L.cross) {
-                CHK(gemm(st, T4, 3 * C4, C4, fcur, C4, L.wqkv, C4, L.bqkv, qkv, 3 * C4, false, nullptr, nullptr, 1.0f, L.wqkv_b));
-                {   // qt[(row,h), :] = Wp_h^T q_h   (batched over heads)
-                    RoitrGemm gq; memset(&gq, 0, sizeof(gq));
-                    gq.M = T4; gq.N = C4; gq.K = cpe; gq.A = qkv; gq.lda = 3 * C4; gq.W = L.wpT; gq.ldw = C4; gq.alpha = 1.f;
-                    gq.C = qt; gq.ldc = HEADS * C4; gq.batch = HEADS; gq.sA = cpe; gq.sW = cpe; gq.sC = C4;
-                    CHK(use_bf16(gq, L.wpT, L.wpT_b, 0));
-                    CHK(roitr_gemm(&gq, st));
-                }
-                RoitrMha m; memset(&m, 0, sizeof(m));
-                m.q_row0 = 0; m.q_rows = T4; m.C = C4; m.heads = HEADS; m.q = qkv; m.ldq = 3 * C4; m.k = qkv + C4; m.ldk = 3 * C4;
-                m.v = qkv + 2 * C4; m.ldv = 3 * C4; m.offset = D.off[3]; m.cloud_of_row = D.cloud_of_node; m.partner = nullptr;
-                m.E = Emb; m.eoff = D.eoff; m.qt = qt; m.bp = L.p.b; m.scale = scale; m.nk_max = V.nmax[3]; m.out = hid; m.ldo = C4; m.ebar = ebar;
-                m.e_bf16 = e_h ? 1 : 0;
-                // algorithmic bytes of the launch: E read once, q | k | v, the folded queries q~, out and ebar written once
-                roitr_prof_next_bytes(ROITR_PROF_MHA, (double)etot * C4 * (e_h ? 2.0 : 4.0) + (double)T4 * C4 * 4.0 * (3 + HEADS + 1 + HEADS));
-                CHK(roitr_mha(&m, st));
-                {   // pos_raw[:, h-slice] = Wvp_h ebar_h + bvp_h
-                    RoitrGemm gp; memset(&gp, 0, sizeof(gp));
-                    gp.M = T4; gp.N = cpe; gp.K = C4; gp.A = ebar; gp.lda = HEADS * C4; gp.W = L.vp.w; gp.ldw = C4; gp.bias = L.vp.b; gp.alpha = 1.f;
-                    gp.C = t2; gp.ldc = C4; gp.batch = HEADS; gp.sA = C4; gp.sW = (long)cpe * C4; gp.sC = cpe; gp.sBias = cpe;
-                    CHK(use_bf16(gp, L.vp.w, L.vp.wb, 0));
-                    CHK(roitr_gemm(&gp, st));
-                }
-                // RPEAttentionLayer tail (geoattention.py:236-244) + AttentionOutput x2 (l.278-280)
-                // (in place is safe for the fused form: a block reads and writes only its own 64 rows)
-                CHK(gemm_ln(st, T4, hid, L.lin, fcur, nullptr, L.n_w, L.n_b, nullptr, false, t1, hid));
-                CHK(ffn_apply(E, st, L.out, T4, C4, hid, fcur));
-                CHK(gemm_ln(st, T4, t2, L.pos_lin, nullptr, nullptr, L.pn_w, L.pn_b, nullptr, false, t1, t2));
-                CHK(ffn_apply(E, st, L.pos, T4, C4, t2, pos));
-                CHK(tap(E, st, "geo.layer" + std::to_string(li) + ".pos", pos, sizeof(float) * (size_t)T4 * C4));
-            } else {
-                // geotransformer.py:45-46: feats0 (src) attends feats1 (tgt), then feats1 attends the UPDATED feats0
-                for (int half = 0; half < 2; ++half) {
-                    const int q0 = half == 0 ? 0 : Ts, qn = half == 0 ? Ts : T4 - Ts;
-                    const int k0 = half == 0 ? Ts : 0, kn = half == 0 ? T4 - Ts : Ts;
-                    float* qb_ = qkv;                          // (T4, C4) region reused: q rows at their own row index
-                    float* kb_ = qkv + (size_t)T4 * C4;
-                    float* vb_ = qkv + (size_t)2 * T4 * C4;
-                    CHK(gemm(st, qn, C4, C4, fcur + (size_t)q0 * C4, C4, L.q.w, C4, L.q.b, qb_ + (size_t)q0 * C4, C4, false, nullptr, pos + (size_t)q0 * C4,
-                             1.0f, L.q.wb));
-                    CHK(gemm(st, kn, C4, C4, fcur + (size_t)k0 * C4, C4, L.k.w, C4, L.k.b, kb_ + (size_t)k0 * C4, C4, false, nullptr, pos + (size_t)k0 * C4,
-                             1.0f, L.k.wb));
-                    CHK(gemm(st, kn, C4, C4, fcur + (size_t)k0 * C4, C4, L.v.w, C4, L.v.b, vb_ + (size_t)k0 * C4, C4, false, nullptr, nullptr, 1.0f, L.v.wb));
-                    RoitrMha m; memset(&m, 0, sizeof(m));
-                    m.q_row0 = q0; m.q_rows = qn; m.C = C4; m.heads = HEADS; m.q = qb_; m.ldq = C4; m.k = kb_; m.ldk = C4; m.v = vb_; m.ldv = C4;
-                    m.offset = D.off[3]; m.cloud_of_row = D.cloud_of_node; m.partner = D.partner; m.scale = scale; m.nk_max = V.nmax[3];
-                    m.out = hid; m.ldo = C4;
-                    roitr_prof_next_bytes(ROITR_PROF_MHA, ((double)qn * 2 + (double)kn * 2) * C4 * 4.0);
-                    CHK(roitr_mha(&m, st));
-                    CHK(gemm_ln(st, qn, hid + (size_t)q0 * C4, L.lin, fcur + (size_t)q0 * C4, nullptr, L.n_w, L.n_b, nullptr, false,
-                                t1 + (size_t)q0 * C4, t2 + (size_t)q0 * C4));
-                    CHK(ffn_apply(E, st, L.out, qn, C4, t2 + (size_t)q0 * C4, fcur + (size_t)q0 * C4));
-                }
+    float* fcur = A.get<float>((size_t)T4 * C4);
+    float* pos = A.get<float>((size_t)T4 * C4);
+    float* qkv = A.get<float>((size_t)T4 * 3 * C4);
+    float* qt = A.get<float>((size_t)T4 * HEADS * C4);
+    float* ebar = A.get<float>((size_t)T4 * HEADS * C4);
+    float* hid = A.get<float>((size_t)T4 * C4);
+    float* t1 = A.get<float>((size_t)T4 * C4);
+    float* t2 = A.get<float>((size_t)T4 * C4);
+    if (A.fail) { roitr_set_error("arena exhausted (geo)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
+    CHK(gemm(st, T4, F.xe[3], E.geo_in, fcur));
+    CHK(tap(E, st, "geo.in_proj", fcur, sizeof(float) * (size_t)T4 * C4));
+    const int cpe = C4 / HEADS;
+    const float scale = 1.0f / sqrtf((float)cpe);
+    const int Ts = V.off[3][B - 1];  // source-cloud rows come first
+    for (size_t li = 0; li < E.geo.size(); ++li) {
+        const GeoLayer& L = E.geo[li];
+        if (!L.cross) {
+            CHK(gemm(st, T4, 3 * C4, C4, fcur, C4, L.wqkv, C4, L.bqkv, qkv, 3 * C4, false, nullptr, nullptr, 1.0f, L.wqkv_b));
+            {   // qt[(row,h), :] = Wp_h^T q_h   (batched over heads)
+                RoitrGemm gq; memset(&gq, 0, sizeof(gq));
+                gq.M = T4; gq.N = C4; gq.K = cpe; gq.A = qkv; gq.lda = 3 * C4; gq.W = L.wpT; gq.ldw = C4; gq.alpha = 1.f;
+                gq.C = qt; gq.ldc = HEADS * C4; gq.batch = HEADS; gq.sA = cpe; gq.sW = cpe; gq.sC = C4;
+                CHK(use_bf16(gq, L.wpT, L.wpT_b, 0));
+                CHK(roitr_gemm(&gq, st));
             }
-            CHK(tap(E, st, "geo.layer" + std::to_string(li), fcur, sizeof(float) * (size_t)T4 * C4));
+            RoitrMha m; memset(&m, 0, sizeof(m));
+            m.q_row0 = 0; m.q_rows = T4; m.C = C4; m.heads = HEADS; m.q = qkv; m.ldq = 3 * C4; m.k = qkv + C4; m.ldk = 3 * C4;
+            m.v = qkv + 2 * C4; m.ldv = 3 * C4; m.offset = D.off[3]; m.cloud_of_row = D.cloud_of_node; m.partner = nullptr;
+            m.E = S.Emb; m.eoff = D.eoff; m.qt = qt; m.bp = L.p.b; m.scale = scale; m.nk_max = V.nmax[3]; m.out = hid; m.ldo = C4; m.ebar = ebar;
+            m.e_bf16 = e_h ? 1 : 0;
+            // algorithmic bytes of the launch: E read once, q | k | v, the folded queries q~, out and ebar written once
+            roitr_prof_next_bytes(ROITR_PROF_MHA, (double)etot * C4 * (e_h ? 2.0 : 4.0) + (double)T4 * C4 * 4.0 * (3 + HEADS + 1 + HEADS));
+            CHK(roitr_mha(&m, st));
+            {   // pos_raw[:, h-slice] = Wvp_h ebar_h + bvp_h
+                RoitrGemm gp; memset(&gp, 0, sizeof(gp));
+                gp.M = T4; gp.N = cpe; gp.K = C4; gp.A = ebar; gp.lda = HEADS * C4; gp.W = L.vp.w; gp.ldw = C4; gp.bias = L.vp.b; gp.alpha = 1.f;
+                gp.C = t2; gp.ldc = C4; gp.batch = HEADS; gp.sA = C4; gp.sW = (long)cpe * C4; gp.sC = cpe; gp.sBias = cpe;
+                CHK(use_bf16(gp, L.vp.w, L.vp.wb, 0));
+                CHK(roitr_gemm(&gp, st));
+            }
+            // RPEAttentionLayer tail (geoattention.py:236-244) + AttentionOutput x2 (l.278-280)
+            // (in place is safe for the fused form: a block reads and writes only its own 64 rows)
+            CHK(gemm_ln(st, T4, hid, L.lin, fcur, nullptr, L.n_w, L.n_b, nullptr, false, t1, hid));
+            CHK(ffn_apply(E, st, L.out, T4, C4, hid, fcur));
+            CHK(gemm_ln(st, T4, t2, L.pos_lin, nullptr, nullptr, L.pn_w, L.pn_b, nullptr, false, t1, t2));
+            CHK(ffn_apply(E, st, L.pos, T4, C4, t2, pos));
+            CHK(tap(E, st, "geo.layer" + std::to_string(li) + ".pos", pos, sizeof(float) * (size_t)T4 * C4));
+        } else {
+            // geotransformer.py:45-46: feats0 (src) attends feats1 (tgt), then feats1 attends the UPDATED feats0
+            for (int half = 0; half < 2; ++half) {
+                const int q0 = half == 0 ? 0 : Ts, qn = half == 0 ? Ts : T4 - Ts;
+                const int k0 = half == 0 ? Ts : 0, kn = half == 0 ? T4 - Ts : Ts;
+                float* qb_ = qkv;                          // (T4, C4) region reused: q rows at their own row index
+                float* kb_ = qkv + (size_t)T4 * C4;
+                float* vb_ = qkv + (size_t)2 * T4 * C4;
+                CHK(gemm(st, qn, C4, C4, fcur + (size_t)q0 * C4, C4, L.q.w, C4, L.q.b, qb_ + (size_t)q0 * C4, C4, false, nullptr, pos + (size_t)q0 * C4,
+                         1.0f, L.q.wb));
+                CHK(gemm(st, kn, C4, C4, fcur + (size_t)k0 * C4, C4, L.k.w, C4, L.k.b, kb_ + (size_t)k0 * C4, C4, false, nullptr, pos + (size_t)k0 * C4,
+                         1.0f, L.k.wb));
+                CHK(gemm(st, kn, C4, C4, fcur + (size_t)k0 * C4, C4, L.v.w, C4, L.v.b, vb_ + (size_t)k0 * C4, C4, false, nullptr, nullptr, 1.0f, L.v.wb));
+                RoitrMha m; memset(&m, 0, sizeof(m));
+                m.q_row0 = q0; m.q_rows = qn; m.C = C4; m.heads = HEADS; m.q = qb_; m.ldq = C4; m.k = kb_; m.ldk = C4; m.v = vb_; m.ldv = C4;
+                m.offset = D.off[3]; m.cloud_of_row = D.cloud_of_node; m.partner = D.partner; m.scale = scale; m.nk_max = V.nmax[3];
+                m.out = hid; m.ldo = C4;
+                roitr_prof_next_bytes(ROITR_PROF_MHA, ((double)qn * 2 + (double)kn * 2) * C4 * 4.0);
+                CHK(roitr_mha(&m, st));
+                CHK(gemm_ln(st, qn, hid + (size_t)q0 * C4, L.lin, fcur + (size_t)q0 * C4, nullptr, L.n_w, L.n_b, nullptr, false,
+                            t1 + (size_t)q0 * C4, t2 + (size_t)q0 * C4));
+                CHK(ffn_apply(E, st, L.out, qn, C4, t2 + (size_t)q0 * C4, fcur + (size_t)q0 * C4));
+            }
         }
-        CHK(gemm(st, T4, fcur, E.geo_out, gfeat));
-        CHK(tap(E, st, "geo.out", gfeat, sizeof(float) * (size_t)T4 * C4));
-        A.off = mark;
+        CHK(tap(E, st, "geo.layer" + std::to_string(li), fcur, sizeof(float) * (size_t)T4 * C4));
     }
+    CHK(gemm(st, T4, fcur, E.geo_out, gfeat));
+    CHK(tap(E, st, "geo.out", gfeat, sizeof(float) * (size_t)T4 * C4));
+    A.off = mark;
+    return 0;
+}
 
-    roitr_prof_end(ROITR_PROF_PH_GEO, st);
-    roitr_prof_begin(ROITR_PROF_PH_DEC, 0.0, st);
-    // ---------------- decoder (model/model.py:223-231)
-    float* xd[4];
+// ---- stage 8: the decoder (model/model.py:223-231)
+int decoder(Engine& E, const Plan& P, const GeoBufs& S, Feats& F)
+{
+    const Levels& V = P.V; const Desc& D = S.D; const int NC = P.NC, T4 = P.T4; hipStream_t st = P.st; Arena& A = E.arena;
+    float** xe = F.xe; float** xd = F.xd;
     {
         // dec4 head: cat(x, linear2(mean).repeat) -> linear1 -> LN -> ReLU   (model/model.py:99-111)
         const int pl = E.planes[3];
@@ -1587,13 +1666,13 @@ static int forward_body(void* h, const RoitrForwardIO* io, hipStream_t st)
         CHK(gemm(st, T4, pl, pl, xe[3], pl, U.l1.w, 2 * pl, nullptr, y, pl, false, nullptr, nullptr, 1.0f, U.l1.wb));
         CHK(roitr_add_layernorm(T4, pl, y, um, D.cloud_of_node, U.l1n_w, U.l1n_b, nullptr, 1, 1e-5f, x0, st));
         CHK(tap(E, st, "dec4.0", x0, sizeof(float) * (size_t)T4 * pl));
-        CHK(block(E, st, E.dec[3], T4, x0, g_self[3], ppf_self[3], E.nsample[3], xd[3], order[3]));
+        CHK(block(E, st, E.dec[3], T4, x0, S.g_self[3], S.ppf_self[3], E.nsample[3], xd[3], S.order[3]));
         CHK(tap(E, st, "dec4.1", xd[3], sizeof(float) * (size_t)T4 * pl));
     }
-    ROITR_HIP(hipStreamWaitEvent(st, E.ev[6], 0));   // the 3-NN of the three TransitionUp layers (side stream)
+    ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_NN3_DONE], 0));   // the 3-NN of the three TransitionUp layers (side stream)
     for (int l = 2; l >= 0; --l) {
         // TransitionUp (model/model.py:112-116): linear1(x1) + interpolation(p2, p1, linear2(x2))
-        const int pl = E.planes[l], pc = E.planes[l + 1];
+        const int pl = E.planes[l];
         const Up& U = E.up[l];
         const int Tl = V.T[l], Tc = V.T[l + 1];
         float* a0 = A.get<float>((size_t)Tl * pl);
@@ -1603,43 +1682,46 @@ static int forward_body(void* h, const RoitrForwardIO* io, hipStream_t st)
         float* x0 = A.get<float>((size_t)Tl * pl);
         xd[l] = A.get<float>((size_t)Tl * pl);
         if (A.fail) { roitr_set_error("arena exhausted (decoder)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-        (void)pc;
         CHK(gemm_ln(st, Tc, xd[l + 1], U.l2, nullptr, nullptr, U.l2n_w, U.l2n_b, nullptr, true, b0, b1));
         if (E.cfg.operand_dtype != 1) {
             // fp32: `linear1(x1) + interpolation(p2, p1, linear2(x2))` in the launch that computes linear1 -- the interpolation rides in
             // the LayerNorm epilogue (after the ReLU), the (Tl, pl) intermediate a1 is never written
-            const Interp3 ip = {b1, i3[l], d3[l]};
+            const Interp3 ip = {b1, S.i3[l], S.d3[l]};
             CHK(gemm_ln(st, Tl, xe[l], U.l1, nullptr, nullptr, U.l1n_w, U.l1n_b, nullptr, true, a0, x0, 0, nullptr, 0, 0, nullptr, &ip));
         } else {
             CHK(gemm_ln(st, Tl, xe[l], U.l1, nullptr, nullptr, U.l1n_w, U.l1n_b, nullptr, true, a0, a1));
-            CHK(roitr_interp3_add(Tl, pl, b1, i3[l], d3[l], a1, x0, st));
+            CHK(roitr_interp3_add(Tl, pl, b1, S.i3[l], S.d3[l], a1, x0, st));
         }
         CHK(tap(E, st, "dec" + std::to_string(l + 1) + ".0", x0, sizeof(float) * (size_t)Tl * pl));
-        CHK(block(E, st, E.dec[l], Tl, x0, g_self[l], ppf_self[l], E.nsample[l], xd[l], order[l]));
+        CHK(block(E, st, E.dec[l], Tl, x0, S.g_self[l], S.ppf_self[l], E.nsample[l], xd[l], S.order[l]));
         CHK(tap(E, st, "dec" + std::to_string(l + 1) + ".1", xd[l], sizeof(float) * (size_t)Tl * pl));
     }
+    return 0;
+}
 
-    roitr_prof_end(ROITR_PROF_PH_DEC, st);
-    roitr_prof_begin(ROITR_PROF_PH_MATCH, 0.0, st);
-    // ---------------- heads (RIGA_v2.py:64-68) and node coordinates (model/model.py:233-235)
-    ROITR_HIP(hipStreamWaitEvent(st, E.ev[7], 0));   // node coordinates, partition and ground-truth side outputs (side stream)
+// ---- stage 9: heads (RIGA_v2.py:64-68), coarse matching, patches, optimal transport, fine matching
+int heads_and_matching(Engine& E, const RoitrForwardIO* io, const Plan& P, const GeoBufs& S, const Feats& F)
+{
+    const Levels& V = P.V; const Desc& D = S.D; hipStream_t st = P.st; Arena& A = E.arena;
+    const int B = P.B, T1 = P.T1, T4 = P.T4, C4 = P.C4, LIM = P.LIM, P_ = P.P_; const bool compact = P.compact;
+    ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_TAIL_DONE], 0));   // node coordinates, partition and ground-truth side outputs (side stream)
     E.side_forked = false;                           // last join: everything the side stream was given is ordered before `st` from here
     float* node_feats = io->node_feats ? io->node_feats : A.get<float>((size_t)T4 * C4);
     float* point_feats = io->point_feats ? io->point_feats : A.get<float>((size_t)T1 * C4);
     {
         float* cp = A.get<float>((size_t)T4 * C4);
         if (A.fail) { roitr_set_error("arena exhausted (heads)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-        CHK(gemm(st, T4, gfeat, E.coarse_proj, cp));
+        CHK(gemm(st, T4, F.gfeat, E.coarse_proj, cp));
         CHK(roitr_l2_normalize(T4, C4, cp, node_feats, st));
-        CHK(gemm(st, T1, xd[0], E.fine_proj, point_feats));
+        CHK(gemm(st, T1, F.xd[0], E.fine_proj, point_feats));
     }
 
-    // ---------------- point-to-node partition, coarse matching, patches, OT, fine matching
+    // ---------------- coarse matching, patches, OT, fine matching
     int* tgt_corr = io->tgt_corr ? io->tgt_corr : A.get<int>((size_t)B * P_);
     int* src_corr = io->src_corr ? io->src_corr : A.get<int>((size_t)B * P_);
     float* cscore = io->corr_scores ? io->corr_scores : A.get<float>((size_t)B * P_);
     int* n_corr = io->n_corr ? io->n_corr : A.get<int>(B);
-    const size_t NP = NPs;
+    const size_t NP = P.NPs;
     int* pair_off = compact ? (io->patch_offsets ? io->patch_offsets : A.get<int>((size_t)B + 1)) : nullptr;
     int* trows = A.get<int>(NP * LIM); int* srows = A.get<int>(NP * LIM);
     int* tmask = io->tgt_knn_masks ? io->tgt_knn_masks : A.get<int>(NP * LIM);
@@ -1671,7 +1753,7 @@ static int forward_body(void* h, const RoitrForwardIO* io, hipStream_t st)
     {
         RoitrCoarse c; memset(&c, 0, sizeof(c));
         c.pairs = B; c.C = C4; c.num_corr = P_; c.dual_norm = 1; c.max_ref = V.nmax[3]; c.max_src = V.nmax[3];
-        c.feats = node_feats; c.node_offset = D.off[3]; c.node_masks = node_masks; c.scratch = cscratch; c.scratch_stride = cstride;
+        c.feats = node_feats; c.node_offset = D.off[3]; c.node_masks = S.node_masks; c.scratch = cscratch; c.scratch_stride = cstride;
         c.tgt_corr = tgt_corr; c.src_corr = src_corr; c.corr_scores = cscore; c.n_corr = n_corr;
         c.xy = cxy; c.xy_stride = xystride; c.xy_ld = V.nmax[3];
         if (E.cfg.adaptive_coarse) CHK(roitr_adaptive_matching(&c, E.cfg.num_corr, 0.75f, st));
@@ -1683,7 +1765,7 @@ static int forward_body(void* h, const RoitrForwardIO* io, hipStream_t st)
     {
         RoitrPatch pg; memset(&pg, 0, sizeof(pg));
         pg.pairs = B; pg.num_corr = P_; pg.limit = LIM; pg.n_corr = n_corr; pg.tgt_corr = tgt_corr; pg.src_corr = src_corr;
-        pg.node_offset = D.off[3]; pg.pt_offset = D.off[0]; pg.knn_idx = kidx; pg.knn_mask = kmask; pg.points = pts_out;
+        pg.node_offset = D.off[3]; pg.pt_offset = D.off[0]; pg.knn_idx = S.kidx; pg.knn_mask = S.kmask; pg.points = S.pts_out;
         pg.tgt_rows = trows; pg.src_rows = srows; pg.tgt_masks = tmask; pg.src_masks = smask; pg.tgt_pts = tpts; pg.src_pts = spts;
         pg.pair_off = pair_off; pg.slots = compact ? (int)NP : 0;
         CHK(roitr_patch_gather(&pg, st));
@@ -1722,7 +1804,29 @@ static int forward_body(void* h, const RoitrForwardIO* io, hipStream_t st)
         fm.pair_off = pair_off; fm.slots = compact ? (int)NP : 0; fm.pair_starts = io->pair_starts;
         CHK(roitr_matching_tail(&o, &fm, st));
     }
-    roitr_prof_end(ROITR_PROF_PH_MATCH, st);
+    return 0;
+}
+}  // namespace
+
+// One forward = this list of stages, no host synchronisation.  The geometry chain is queued whole before the feature path, which joins
+// it stage by stage: encoder level l behind "level l geometry done", the global transformer behind the embedding, the decoder's
+// TransitionUp layers behind the 3-NN, the matching phase behind the chain's tail.
+static int forward_body(Engine& E, const RoitrForwardIO* io, hipStream_t st)
+{
+    if (!E.finalized) { roitr_set_error("engine not finalized", __FILE__, __LINE__); return ROITR_ERR_ARG; }
+    if (io->pairs <= 0) return 0;
+    Plan P; GeoBufs S; Feats F;
+    P.st = st;
+    CHK(plan_sizes(E, io, P));
+    CHK(reserve_arenas(E, io, P));
+    CHK(carve_geometry_buffers(E, io, P, S));   // (host work only; in front of the staging because the descriptor block is one of the buffers)
+    CHK(stage_descriptors(E, P, S));
+    roitr_prof_begin(ROITR_PROF_PH_FORWARD, 0.0, st);
+    CHK(issue_geometry_chain(E, io, P, S));
+    roitr_prof_begin(ROITR_PROF_PH_ENC, 0.0, st);   CHK(encoder(E, io, P, S, F));             roitr_prof_end(ROITR_PROF_PH_ENC, st);
+    roitr_prof_begin(ROITR_PROF_PH_GEO, 0.0, st);   CHK(global_transformer(E, P, S, F));      roitr_prof_end(ROITR_PROF_PH_GEO, st);
+    roitr_prof_begin(ROITR_PROF_PH_DEC, 0.0, st);   CHK(decoder(E, P, S, F));                 roitr_prof_end(ROITR_PROF_PH_DEC, st);
+    roitr_prof_begin(ROITR_PROF_PH_MATCH, 0.0, st); CHK(heads_and_matching(E, io, P, S, F));  roitr_prof_end(ROITR_PROF_PH_MATCH, st);
     roitr_prof_end(ROITR_PROF_PH_FORWARD, st);
     return 0;
 }
@@ -1781,8 +1885,7 @@ extern "C" int roitr_engine_forward_graph(void* h, const RoitrForwardIO* io, hip
         return rc;
     }
     if (!ge->exec) {
-        const size_t nc = 2 * (size_t)io->pairs;
-        const size_t need = (4 * nc + (size_t)t4 + nc + 8) * 4 + 16 + nc * 8 + 64;
+        const size_t need = Desc::bytes(2 * (size_t)io->pairs, (size_t)t4) + 64;
         if (need > ge->pin_cap) {
             if (ge->pin) (void)hipHostFree(ge->pin);
             ge->pin = nullptr; ge->pin_cap = 0;
