@@ -553,6 +553,44 @@ int roitr_ransac_samples(int pairs, const int* n, const unsigned int* pair_keys,
 int roitr_weighted_procrustes(int batch, int n, const float* src_pts, const float* tgt_pts, const float* weights, float weight_thresh,
                               float eps, float* transforms, roitr_stream_t stream);
 
+
+/* ------------------------------------------------------------------ 4DMatch non-rigid evaluation
+ * registration/evaluate_fdmatch.py:50-115: NFMR (non-rigid feature matching recall) of every pair of a batch.  Pair b owns points
+ * [src_offsets[b], src_offsets[b+1]) of src_raw (the undeformed source) and src_deformed (what the model was fed), both (total_src,
+ * 3); correspondences [corr_starts[b], corr_starts[b+1]) of src_corr / tgt_corr (total_corr, 3), the layout
+ * RoitrForwardIO::pair_starts / out_src_pts / out_tgt_pts has; metric points [metric_starts[b], metric_starts[b+1]) of
+ * metric_index (total_metric), indices into the pair's own cloud; rot (pairs, 3, 3), trans (pairs, 3).  All device pointers.
+ *   anchors: idx_c = the nearest point of the pair's DEFORMED cloud to src_corr[c] (fp32 fmaf(dz,dz, fmaf(dy,dy, dx*dx)), the lowest
+ *     index at equal distance), anchor_c = src_raw[idx_c], motion_c = tgt_corr[c] - anchor_c;
+ *   blend: p = src_raw[metric_index[m]]; its 3 nearest anchors (same distance form, the lowest index at equal distance -- the
+ *     reference's np.argpartition leaves that choice open); d < 1e-10 -> 1e-10, d > search_radius -> 1e10, weights (1 / d) / sum,
+ *     flow = sum of weight x motion.  Three anchors beyond the radius weigh 1/3 each and the point still counts, as in the reference;
+ *   err[m] = | p + flow - (rot_b src_deformed[metric_index[m]] + trans_b) |, hits[b] = #{ err < recall_thr }.  NFMR = hits / points.
+ * status[b] (bits below): a pair with fewer than 3 anchors (or an empty cloud) or without metric points gets 0 hits and its bit
+ * (the reference raises there); a metric index outside the pair's cloud is skipped, never dereferenced, and sets BAD_INDEX;
+ * offsets that decrease or leave [0, total] set BAD_OFFSETS and are clamped before use.  err of a skipped point is +inf.
+ * anchor_idx (total_corr, local to the pair) and err (total_metric) may be NULL.  block: lanes per workgroup, 0 (automatic), 64, 128
+ * or 256; results do not depend on it, nor on the batch a pair travels in.  The workspace (device, caller-owned) holds at least
+ * roitr_nfmr_workspace_bytes() bytes.  Refusals (ROITR_ERR_ARG): negative counts, null pointers, thresholds not finite and
+ * positive, another block size, a short workspace. */
+#define ROITR_NFMR_FEW_ANCHORS 1
+#define ROITR_NFMR_NO_METRIC 2
+#define ROITR_NFMR_BAD_INDEX 4
+#define ROITR_NFMR_BAD_OFFSETS 8
+size_t roitr_nfmr_workspace_bytes(int pairs, int total_corr, int total_metric);
+int roitr_nfmr_batch(int pairs, int total_src, const int* src_offsets, const float* src_raw, const float* src_deformed, int total_corr,
+                     const int* corr_starts, const float* src_corr, const float* tgt_corr, int total_metric, const int* metric_starts,
+                     const int* metric_index, const float* rot, const float* trans, float search_radius, float recall_thr, int block,
+                     int* anchor_idx, float* err, int* hits, int* status, void* workspace, size_t workspace_bytes,
+                     roitr_stream_t stream);
+/* blend_anchor_motion (evaluate_fdmatch.py:50-71, knn = 3) alone, batched: queries [query_starts[b], query_starts[b+1]) of
+ * query_loc against references [ref_starts[b], ref_starts[b+1]) of ref_loc / ref_flow -> blended_flow (total_query, 3) and
+ * mask (total_query; 1 where fewer than 3 of the 3 neighbours lie beyond the radius).  Fewer than 3 references: flow 0, mask 0 and
+ * ROITR_NFMR_FEW_ANCHORS in status[b]. */
+int roitr_blend_anchor_motion(int pairs, int total_ref, const int* ref_starts, const float* ref_loc, const float* ref_flow,
+                              int total_query, const int* query_starts, const float* query_loc, float search_radius, int block,
+                              float* blended_flow, int* mask, int* status, roitr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,9 @@ def main():
     ap.add_argument("--estimate-normals", action="store_true", help="recompute the normals on the GPU (open3d knn=33 + normal_redirect)")
     ap.add_argument("--register", action="store_true",
                     help="estimate every pair's pose on the GPU (correspondence RANSAC, registration.py) and save it as est_transform")
+    ap.add_argument("--nonrigid", action="store_true",
+                    help="synthetic 4DMatch-shaped pairs with a real deformation and metric points (synthetic.make_nonrigid_pair); "
+                         "with --evaluate on a 4DMatch config the mean NFMR is reported (nonrigid.py)")
     ap.add_argument("--ransac-iterations", type=int, default=50000)
     ap.add_argument("--ransac-points", type=int, default=1000, help="correspondences drawn per pair (probability ~ confidence)")
     args = ap.parse_args()
@@ -51,7 +54,7 @@ def main():
             if kind == "param":
                 sd[k].copy_(torch.from_numpy(closed_form_param(k, tuple(shape))))
         print("[roitr_amd] no checkpoint given: using closed-form weights (roitr_amd/weights.py)")
-    data = SyntheticPairs(args.synthetic, args.n_points)
+    data = SyntheticPairs(args.synthetic, args.n_points, nonrigid=True) if args.nonrigid else SyntheticPairs(args.synthetic, args.n_points)
     tester = Tester(config, model, data, args.snapshot_dir, args.pairs_per_forward, rank, world, evaluate=args.evaluate,
                     estimate_normals=args.estimate_normals, register=args.register,
                     ransac=dict(iterations=args.ransac_iterations, n_points=args.ransac_points))
@@ -60,6 +63,8 @@ def main():
         print(f"[roitr_amd] PIR {tester.metrics['PIR']:.4f}  IR {tester.metrics['IR']:.4f}  over {tester.metrics['pairs']} pairs")
     if args.register and args.evaluate:
         _print_registration(tester.registration, world)
+    if args.nonrigid and args.evaluate and config.benchmark in ("4DMatch", "4DLoMatch"):   # the same decision on every rank
+        _print_nonrigid(tester.nonrigid or {}, world, float(config.get("eval_acceptance_radius", 0.1)), tester.metrics)
     if rank == 0:
         print(f"[roitr_amd] wrote {args.synthetic} result files under {args.snapshot_dir}/{config.benchmark}; "
               f"correspondences per rank: {counts}")
@@ -84,6 +89,20 @@ def _print_registration(reg, world):
           f"RTE mean {rte.mean():.4f} m, median {np.median(rte):.4f} m")
     print(f"[roitr_amd] pairs with RRE < 15 deg and RTE < 0.3 m: {ok:.4f} (a pose-error success rate, not the 3DMatch-protocol "
           "registration recall, which needs the benchmark's gt.info)")
+
+
+def _print_nonrigid(nonrigid, world, radius, metrics):
+    """Mean NFMR over every rank's pairs next to the mean IR at the config's acceptance radius (rank 0 prints)."""
+    rows = [(k,) + v for k, v in sorted(nonrigid.items())]
+    if world > 1:
+        allrows = [None] * world
+        torch.distributed.all_gather_object(allrows, rows)
+        rows = [r for part in allrows for r in part]
+    if int(os.environ.get("RANK", 0)) != 0 or not rows:
+        return
+    nfmr = sum(r[1] for r in rows) / len(rows)
+    print(f"[roitr_amd] 4DMatch non-rigid evaluation over {len(rows)} pairs: NFMR {nfmr:.4f} (recall threshold 0.04 m, "
+          f"{sum(r[2] for r in rows)} metric points), IR {metrics['IR']:.4f} at {radius:g} m")
 
 
 if __name__ == "__main__":

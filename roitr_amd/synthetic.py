@@ -4,10 +4,11 @@ Input contract of the reference's collate (dataset/common.py:50-126, dataset/tdm
 float32 `src_points (N,3)`, `tgt_points (M,3)`, unit normals flipped toward the view point
 (dataset/common.py:312-320 `normal_redirect`, view point = origin), `feats = ones (.,1)`
 (dataset/tdmatch.py:128-129), `rot (3,3)`, `trans (3,1)` with  tgt ~= src @ rot.T + trans.T,
-`raw_src_pcd = src_points` for 3DMatch.
+`raw_src_pcd = src_points` for 3DMatch.  4DMatch pairs (make_nonrigid_pair) carry a real deformation: `raw_src_pcd` is the undeformed
+source, `src_points` the deformed one, and `metric_index` the points NFMR is measured on (dataset/fdmatch.py:47,94-98).
 
 Seed rule: numpy default_rng(1000 * config + pair_index).  Points ~ U[0,2)^3 m
-(3DMatch fragments are 2-3 m across).  The two clouds are overlapping crops of one scene so the
+(3DMatch fragments are 2-3 m across); make_nonrigid_pair uses config number 8 in that rule.  The two clouds are overlapping crops of one scene so the
 matching stages have real correspondences to find.
 """
 import numpy as np
@@ -143,4 +144,68 @@ def make_pair(n_src, n_tgt=None, config=2, pair_index=0, overlap=0.6, jitter=0.0
         "rot": np.ascontiguousarray(rot, f32),
         "trans": np.ascontiguousarray(trans, f32),
         "raw_src_pcd": np.ascontiguousarray(src, f32),
+    }
+
+
+NONRIGID_CONFIG = 8   # the seed rule's config number of make_nonrigid_pair
+
+
+def smooth_flow(rng, pts, amplitude):
+    """A smooth displacement field of the position: per axis a sum of two seeded low-frequency sines, at most `amplitude` metres per
+    axis (|flow| <= sqrt(3) amplitude), a few centimetres almost everywhere."""
+    ph = rng.uniform(0.0, 2.0 * np.pi, (3, 2))
+    k = rng.uniform(0.8, 2.2, (3, 2, 3))
+    f = np.empty_like(pts)
+    for a in range(3):
+        f[:, a] = 0.6 * np.sin(pts @ k[a, 0] + ph[a, 0]) + 0.4 * np.sin(pts @ k[a, 1] + ph[a, 1])
+    return amplitude * f
+
+
+def make_nonrigid_pair(n_src, n_tgt=None, pair_index=0, overlap=0.6, jitter=0.002, normals="field", amplitude=0.09, n_metric=None):
+    """A 4DMatch-shaped pair (dataset/fdmatch.py): the keys of make_pair with a real deformation, plus `metric_index`.
+    raw_src_pcd ~ U[0,2)^3 is the undeformed source, src_points = raw + smooth_flow(raw) the deformed one (the cloud NFMR searches
+    and the engine reports correspondences in), and inside the shared slab the target re-observes jittered DEFORMED points under
+    rot / trans: tgt[reobserved_tgt] ~= src_points[reobserved_src] @ rot.T + trans.T.  metric_index (int64, sorted): a seeded subset
+    of n_metric (default n_src // 4) source points.  Normals as in make_pair; 'field' normals belong to the undeformed scene position
+    (the backbone's geometry is the raw cloud, model/RIGA_v2.py:62), carried over to the re-observing target points.
+    Seed: default_rng(1000 * NONRIGID_CONFIG + pair_index)."""
+    n_tgt = n_src if n_tgt is None else n_tgt
+    n_metric = max(1, n_src // 4) if n_metric is None else n_metric
+    rng = np.random.default_rng(1000 * NONRIGID_CONFIG + pair_index)
+    shift = 2.0 * (1.0 - overlap)
+    raw = rng.random((n_src, 3)) * 2.0
+    src = raw + smooth_flow(rng, raw, amplitude)
+    tgt_scene = rng.random((n_tgt, 3)) * 2.0
+    tgt_scene[:, 0] += shift
+    tgt_origin = tgt_scene.copy()          # the undeformed scene position every target point belongs to (for the normals)
+    shared_src = np.nonzero(raw[:, 0] >= shift)[0]
+    shared_tgt = np.nonzero(tgt_scene[:, 0] < 2.0)[0]
+    k = min(len(shared_src), len(shared_tgt))
+    pick = rng.permutation(shared_src)[:k]
+    tgt_scene[shared_tgt[:k]] = src[pick] + rng.normal(0.0, jitter, (k, 3))
+    tgt_origin[shared_tgt[:k]] = raw[pick]
+    rot = random_rotation(rng)
+    trans = rng.uniform(-1.0, 1.0, (3, 1))
+    tgt = tgt_scene @ rot.T + trans.T
+    if normals == "field":
+        src_n, tgt_n = field_normals(raw), field_normals(tgt_origin) @ rot.T
+    elif normals == "random":
+        src_n, tgt_n = _normals(rng, raw), _normals(rng, tgt)
+    else:
+        raise ValueError(f"normals must be 'random' or 'field', got {normals!r}")
+    metric_index = np.sort(rng.choice(n_src, size=min(n_metric, n_src), replace=False)).astype(np.int64)
+    f32 = np.float32
+    return {
+        "src_points": np.ascontiguousarray(src, f32),
+        "tgt_points": np.ascontiguousarray(tgt, f32),
+        "src_normals": np.ascontiguousarray(src_n, f32),
+        "tgt_normals": np.ascontiguousarray(tgt_n, f32),
+        "src_feats": np.ones((n_src, 1), f32),
+        "tgt_feats": np.ones((n_tgt, 1), f32),
+        "rot": np.ascontiguousarray(rot, f32),
+        "trans": np.ascontiguousarray(trans, f32),
+        "raw_src_pcd": np.ascontiguousarray(raw, f32),
+        "metric_index": metric_index,
+        "reobserved_src": pick.astype(np.int64),
+        "reobserved_tgt": shared_tgt[:k].astype(np.int64),
     }

@@ -28,13 +28,16 @@ def load_pretrain(model, path):
 
 class Tester:
     def __init__(self, config, model, dataset, snapshot_dir="snapshot", pairs_per_forward=8, rank=0, world=1, evaluate=False,
-                 estimate_normals=False, view_point=(0.0, 0.0, 0.0), register=False, ransac=None):
+                 estimate_normals=False, view_point=(0.0, 0.0, 0.0), register=False, ransac=None, nonrigid=None):
         """evaluate: also compute PIR / IR per pair on the device (lib/loss.py:169-213 Evaluator) and return their means.
         estimate_normals: ignore the dataset's normals and recompute them on the GPU from the points the way the
         reference's dataset code does (open3d estimate_normals(knn=33) + normal_redirect, dataset/tdmatch.py:120-127).
         register: also estimate every pair's pose on the device (registration.register_handle, keyed on the GLOBAL pair id, so the
         poses do not depend on sharding or pairs_per_forward; `ransac` holds its keyword arguments) and save it as `est_transform`
-        in the pair's file.  With evaluate as well, `registration` maps this rank's pair ids to (RRE degrees, RTE metres, inliers)."""
+        in the pair's file.  With evaluate as well, `registration` maps this rank's pair ids to (RRE degrees, RTE metres, inliers).
+        With evaluate on the 4DMatch / 4DLoMatch benchmark and items that carry `metric_index`, the NFMR of every pair is computed
+        on the device (nonrigid.nfmr_handle; `nonrigid` holds its keyword arguments) and `self.nonrigid` maps this rank's pair ids
+        to (NFMR, number of metric points); it stays None otherwise."""
         self.config, self.model, self.dataset = config, model, dataset
         self.snapshot_dir = snapshot_dir
         self.pairs_per_forward = pairs_per_forward
@@ -42,6 +45,8 @@ class Tester:
         self.evaluate, self.estimate_normals, self.view_point = evaluate, estimate_normals, view_point
         self.register, self.ransac = register, dict(ransac or {})
         self.registration = {} if register and evaluate else None
+        self.nonrigid_kw = dict(nonrigid or {})
+        self.nonrigid = None   # {global pair id: (nfmr, n_metric)} once a 4DMatch batch with metric_index has been evaluated
         self.metrics = None
         self.records = None   # rank 0 after test(): shard.GatheredRecords {pair id: match scores}
 
@@ -95,6 +100,13 @@ class Tester:
                     ir, pir, _, _ = evaluator.evaluate_batch(handle)
                     aux = torch.stack([ir.float(), pir.float()], 1)
                 blocks.append(self.model.batch_records(handle, ids, aux))
+                if evaluator is not None and benchmark in ("4DMatch", "4DLoMatch") and all("metric_index" in it for it in items):
+                    from .nonrigid import nfmr_handle
+                    nf = nfmr_handle(handle, [it["metric_index"] for it in items], **self.nonrigid_kw)
+                    if self.nonrigid is None:
+                        self.nonrigid = {}
+                    for idx, r, m in zip(ids, nf["nfmr"].cpu().tolist(), nf["n_metric"].cpu().tolist()):
+                        self.nonrigid[idx] = (float(r), int(m))
                 est = None
                 if self.register:
                     from .registration import pose_errors, register_handle
@@ -119,7 +131,7 @@ class Tester:
                     data["gt_src_node_occ"] = o["gt_src_node_occ"].cpu()
                     data["rot"], data["trans"] = p["rot"].cpu(), p["trans"].cpu()
                     if benchmark in ("4DMatch", "4DLoMatch") and "metric_index" in it:
-                        data["metric_index_list"] = it["metric_index"]
+                        data["metric_index_list"] = it["metric_index"].cpu() if torch.is_tensor(it["metric_index"]) else it["metric_index"]
                     if est is not None:
                         data["est_transform"] = est[k_pair]
                     torch.save(data, os.path.join(out_dir, f"{idx}.pth"))
@@ -150,12 +162,16 @@ class Tester:
 class SyntheticPairs(torch.utils.data.Dataset):
     """Stand-in for dataset/tdmatch.py (no 3DMatch data in this image): seeded synthetic pairs with the same keys."""
 
-    def __init__(self, n_pairs, n_points=5000, config=2):
-        self.n_pairs, self.n_points, self.config = n_pairs, n_points, config
+    def __init__(self, n_pairs, n_points=5000, config=2, nonrigid=False):
+        """nonrigid: 4DMatch-shaped pairs with a real deformation and `metric_index` (synthetic.make_nonrigid_pair; `config` is
+        not used then, the generator has a config number of its own)."""
+        self.n_pairs, self.n_points, self.config, self.nonrigid = n_pairs, n_points, config, nonrigid
 
     def __len__(self):
         return self.n_pairs
 
     def __getitem__(self, i):
-        from .synthetic import make_pair
+        from .synthetic import make_nonrigid_pair, make_pair
+        if self.nonrigid:
+            return {k: torch.from_numpy(v) for k, v in make_nonrigid_pair(self.n_points, pair_index=i).items()}
         return {k: torch.from_numpy(v) for k, v in make_pair(self.n_points, config=self.config, pair_index=i).items()}
