@@ -591,6 +591,38 @@ int roitr_blend_anchor_motion(int pairs, int total_ref, const int* ref_starts, c
                               int total_query, const int* query_starts, const float* query_loc, float search_radius, int block,
                               float* blended_flow, int* mask, int* status, roitr_stream_t stream);
 
+
+/* ------------------------------------------------------------------ descriptor matching
+ * lib/utils.py:99-156 (matching_descriptors, square_distance) and registration/benchmark_utils.py:42-161 (mutual_selection,
+ * get_inlier_ratio, ransac_pose_estimation): the best target of every source descriptor and the best source of every target
+ * descriptor of every pair of a batch, from ONE fp32 MFMA product per pair whose (N, M) score matrix never reaches memory.
+ * Pair b owns rows [src_offsets[b], src_offsets[b+1]) of src_desc (total_src, dim) and rows [tgt_offsets[b], tgt_offsets[b+1]) of
+ * tgt_desc (total_tgt, dim); both may point into one buffer (the engine's point_feats holds the clouds of a call back to back).
+ * The row ranges of different pairs must not overlap on either side.  All device pointers, 16-byte aligned.
+ *   metric 0: score = s . t, the LARGEST wins;  metric 1: score = max((-2 s.t + |s|^2) + |t|^2, 1e-12) (square_distance with
+ *   normalized = False, in its order), the SMALLEST wins.  fp32 operands, fp32 accumulation, a fixed k order: a score does not
+ *   depend on the batch, on the tile it falls into or on the launch geometry.
+ *   THE LOWEST INDEX WINS among equal scores, in both directions (np.argmax / np.argmin / torch.max).
+ * row_idx / row_val (total_src): the best target of every source row, local to the pair, and its score; col_idx / col_val
+ * (total_tgt) likewise.  A row whose pair has nothing on the other side, and every row outside all pairs, gets index -1 and value 0.
+ * Offsets are clamped to [0, total] (and made non-decreasing) before use.  Descriptors are assumed finite; with non-finite input
+ * every index still is -1 or inside its pair and nothing is read out of bounds.  Every output is bitwise independent of the batch
+ * a pair travels in, of the order blocks finish in and of a repeat of the call.
+ * Refusals: dim not a multiple of 4 in [4, 1024] -> ROITR_ERR_UNSUPPORTED; negative counts, null or misaligned pointers, a
+ * workspace below roitr_desc_match_workspace_bytes(), an unknown metric -> ROITR_ERR_ARG. */
+size_t roitr_desc_match_workspace_bytes(int pairs, int total_src, int total_tgt);
+int roitr_desc_match_batch(int pairs, int dim, const int* src_offsets, int total_src, const float* src_desc, const int* tgt_offsets,
+                           int total_tgt, const float* tgt_desc, int metric, int* row_idx, float* row_val, int* col_idx, float* col_val,
+                           void* workspace, size_t workspace_bytes, roitr_stream_t stream);
+/* Ordered compaction of the matches into corr (capacity, 2), local indices (source, target), pair b's at [corr_starts[b],
+ * corr_starts[b+1]):  mode 0 (row-major): (i, row_idx[i]) for every source row i;  mode 1 (col-major): (col_idx[j], j) for every
+ * target row j;  mode 2 (mutual): (i, row_idx[i]) where col_idx[row_idx[i]] == i, in increasing i (the order np.nonzero gives: a
+ * row holds at most one mutual entry).  Entries whose index is -1 or outside the pair are left out.  The offsets are the ones
+ * roitr_desc_match_batch was given (this call has no totals to clamp against).  *n_out: the count NEEDED; rows beyond capacity
+ * are not written.  Refusals (ROITR_ERR_ARG): negative counts, null pointers, an unknown mode. */
+int roitr_desc_match_select(int pairs, const int* src_offsets, const int* tgt_offsets, const int* row_idx, const int* col_idx, int mode,
+                            int* corr_starts, int* corr, int capacity, int* n_out, roitr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,9 @@ def main():
     ap.add_argument("--nonrigid", action="store_true",
                     help="synthetic 4DMatch-shaped pairs with a real deformation and metric points (synthetic.make_nonrigid_pair); "
                          "with --evaluate on a 4DMatch config the mean NFMR is reported (nonrigid.py)")
+    ap.add_argument("--descriptor-eval", action="store_true",
+                    help="with --evaluate: the descriptor-level inlier ratio without / with the mutual check and the feature-matching "
+                         "recall at 0.05, from the point descriptors of every pair (descmatch.py)")
     ap.add_argument("--ransac-iterations", type=int, default=50000)
     ap.add_argument("--ransac-points", type=int, default=1000, help="correspondences drawn per pair (probability ~ confidence)")
     args = ap.parse_args()
@@ -57,10 +60,12 @@ def main():
     data = SyntheticPairs(args.synthetic, args.n_points, nonrigid=True) if args.nonrigid else SyntheticPairs(args.synthetic, args.n_points)
     tester = Tester(config, model, data, args.snapshot_dir, args.pairs_per_forward, rank, world, evaluate=args.evaluate,
                     estimate_normals=args.estimate_normals, register=args.register,
-                    ransac=dict(iterations=args.ransac_iterations, n_points=args.ransac_points))
+                    ransac=dict(iterations=args.ransac_iterations, n_points=args.ransac_points), descriptor_eval=args.descriptor_eval)
     counts = tester.test()
     if rank == 0 and tester.metrics:
         print(f"[roitr_amd] PIR {tester.metrics['PIR']:.4f}  IR {tester.metrics['IR']:.4f}  over {tester.metrics['pairs']} pairs")
+    if args.descriptor_eval and args.evaluate:
+        _print_descriptor(tester.descriptor or {}, world)
     if args.register and args.evaluate:
         _print_registration(tester.registration, world)
     if args.nonrigid and args.evaluate and config.benchmark in ("4DMatch", "4DLoMatch"):   # the same decision on every rank
@@ -89,6 +94,23 @@ def _print_registration(reg, world):
           f"RTE mean {rte.mean():.4f} m, median {np.median(rte):.4f} m")
     print(f"[roitr_amd] pairs with RRE < 15 deg and RTE < 0.3 m: {ok:.4f} (a pose-error success rate, not the 3DMatch-protocol "
           "registration recall, which needs the benchmark's gt.info)")
+
+
+def _print_descriptor(desc, world):
+    """Descriptor-level inlier ratios and feature-matching recall over every rank's pairs (rank 0 prints)."""
+    from .tester import DESC_FMR_THRESHOLD
+    rows = [(k,) + v for k, v in sorted(desc.items())]
+    if world > 1:
+        allrows = [None] * world
+        torch.distributed.all_gather_object(allrows, rows)
+        rows = [r for part in allrows for r in part]
+    if int(os.environ.get("RANK", 0)) != 0 or not rows:
+        return
+    wo = [r[1] for r in rows if r[1] == r[1]]
+    w = [r[2] for r in rows if r[2] == r[2]]
+    print(f"[roitr_amd] descriptor matching over {len(rows)} pairs: IR without mutual check {sum(wo) / max(len(wo), 1):.4f}, with "
+          f"{sum(w) / max(len(w), 1):.4f} ({sum(r[3] for r in rows)} mutual matches), FMR at {DESC_FMR_THRESHOLD:g} "
+          f"{sum(1 for x in wo if x > DESC_FMR_THRESHOLD) / max(len(wo), 1):.4f}")
 
 
 def _print_nonrigid(nonrigid, world, radius, metrics):

@@ -142,6 +142,36 @@ def ransac_pose_estimation_correspondences(src_pcd, tgt_pcd, correspondences, mu
 
 
 @torch.no_grad()
+def ransac_pose_estimation(src_pcd, tgt_pcd, src_feat, tgt_feat, mutual=False, distance_threshold=0.05, ransac_n=3, *,
+                           iterations=50000, seed=0):
+    """registration/benchmark_utils.py:124-161 on the GPU: the pose from descriptor matches.  mutual=True: the pairs that are each
+    other's best under src_feat @ tgt_feat^T (descmatch, the lowest index at equal scores); mutual=False: every source point with
+    its best target (the correspondence list current Open3D's feature-matching RANSAC builds before it runs its correspondence
+    RANSAC).  The matched point pairs then go through ransac_batch(sample="all").  Returns the 4x4 float64 numpy transformation.
+
+    Divergences: Open3D is not part of this project's environment, so parity with it is unpinned (as for
+    ransac_pose_estimation_correspondences); the reference's mutual=True call passes no checkers, the kernel here always runs the
+    edge-length (0.9) and the distance checker; a fixed number of iterations; mutual=False matches under the dot product, as the
+    mutual branch does, where Open3D takes the L2 nearest neighbour in feature space -- the same list for equal-norm descriptors
+    (the model's are unit-normalised), not otherwise (descmatch.match_batch(metric="sqdist", mode="row") gives the L2 list)."""
+    from . import descmatch
+    dev = torch.device("cuda")
+    def dev32(x):
+        t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+        return t.to(device=dev, dtype=torch.float32).contiguous()
+    src, tgt = dev32(src_pcd).reshape(-1, 3), dev32(tgt_pcd).reshape(-1, 3)
+    sf, tf = dev32(src_feat), dev32(tgt_feat)
+    if sf.shape[0] != src.shape[0] or tf.shape[0] != tgt.shape[0]:
+        raise L.RoitrError("ransac_pose_estimation: one descriptor per point is needed")
+    ends = lambda n: torch.tensor([0, n], dtype=torch.int32, device=dev)
+    m = descmatch.match_batch(ends(sf.shape[0]), sf, ends(tf.shape[0]), tf, metric="dot", mode="mutual" if mutual else "row")
+    corr = m["corr"].long()
+    r = ransac_batch(m["corr_starts"], src[corr[:, 0]], tgt[corr[:, 1]], None, sample="all", distance_threshold=distance_threshold,
+                     ransac_n=ransac_n, iterations=iterations, seed=seed)
+    return r["T"][0].cpu().numpy().astype(np.float64)
+
+
+@torch.no_grad()
 def weighted_procrustes(src_points, tgt_points, weights=None, weight_thresh=0., eps=1e-5, return_transform=False):
     """lib/utils.py:159-212 on the GPU (same signature and squeeze rule): (B, N, 3) or (N, 3) -> R, t or the 4x4 transform."""
     squeeze = src_points.ndim == 2

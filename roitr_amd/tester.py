@@ -17,6 +17,10 @@ import torch
 from .shard import assemble_block, gather_result_records, pairs_for_rank, slots_per_rank
 
 
+DESC_INLIER_THRESHOLD = 0.1   # registration/benchmark_utils.py:80 get_inlier_ratio's default, whatever eval_acceptance_radius says
+DESC_FMR_THRESHOLD = 0.05   # registration/evaluate_registration_c2f.py:109: a pair counts when its inlier ratio exceeds it
+
+
 def load_pretrain(model, path):
     """lib/trainer.py:94-130 `_load_pretrain`: state['state_dict'], 'module.' prefixes stripped, strict load."""
     state = torch.load(path, map_location="cpu")
@@ -28,7 +32,7 @@ def load_pretrain(model, path):
 
 class Tester:
     def __init__(self, config, model, dataset, snapshot_dir="snapshot", pairs_per_forward=8, rank=0, world=1, evaluate=False,
-                 estimate_normals=False, view_point=(0.0, 0.0, 0.0), register=False, ransac=None, nonrigid=None):
+                 estimate_normals=False, view_point=(0.0, 0.0, 0.0), register=False, ransac=None, nonrigid=None, descriptor_eval=False):
         """evaluate: also compute PIR / IR per pair on the device (lib/loss.py:169-213 Evaluator) and return their means.
         estimate_normals: ignore the dataset's normals and recompute them on the GPU from the points the way the
         reference's dataset code does (open3d estimate_normals(knn=33) + normal_redirect, dataset/tdmatch.py:120-127).
@@ -37,7 +41,15 @@ class Tester:
         in the pair's file.  With evaluate as well, `registration` maps this rank's pair ids to (RRE degrees, RTE metres, inliers).
         With evaluate on the 4DMatch / 4DLoMatch benchmark and items that carry `metric_index`, the NFMR of every pair is computed
         on the device (nonrigid.nfmr_handle; `nonrigid` holds its keyword arguments) and `self.nonrigid` maps this rank's pair ids
-        to (NFMR, number of metric points); it stays None otherwise."""
+        to (NFMR, number of metric points); it stays None otherwise.
+        descriptor_eval (with evaluate): the descriptor-level evaluation of registration/benchmark_utils.py get_inlier_ratio on
+        the point descriptors of every pair (descmatch.descriptor_handle, one fused matching launch per forward): `self.descriptor`
+        maps this rank's pair ids to (IR without the mutual check, IR with it, number of mutual matches) and `metrics` gains
+        desc_IR_wo (mean over pairs), desc_IR_w (mean over the pairs that have mutual matches: the IR of an empty set is nan, handled
+        as PIR is) and desc_FMR (share of pairs with IR without the mutual check above 0.05, evaluate_registration_c2f.py:109),
+        over the pairs of ALL ranks (one all_gather_object of the per-pair values when world > 1), like IR / PIR.  The inlier
+        distance is get_inlier_ratio's default, 0.1 m, not the config's eval_acceptance_radius.  The result records and their
+        format are untouched."""
         self.config, self.model, self.dataset = config, model, dataset
         self.snapshot_dir = snapshot_dir
         self.pairs_per_forward = pairs_per_forward
@@ -47,6 +59,7 @@ class Tester:
         self.registration = {} if register and evaluate else None
         self.nonrigid_kw = dict(nonrigid or {})
         self.nonrigid = None   # {global pair id: (nfmr, n_metric)} once a 4DMatch batch with metric_index has been evaluated
+        self.descriptor = {} if descriptor_eval and evaluate else None
         self.metrics = None
         self.records = None   # rank 0 after test(): shard.GatheredRecords {pair id: match scores}
 
@@ -107,6 +120,11 @@ class Tester:
                         self.nonrigid = {}
                     for idx, r, m in zip(ids, nf["nfmr"].cpu().tolist(), nf["n_metric"].cpu().tolist()):
                         self.nonrigid[idx] = (float(r), int(m))
+                if self.descriptor is not None:
+                    from .descmatch import descriptor_handle
+                    d = descriptor_handle(handle, "point", DESC_INLIER_THRESHOLD)
+                    for idx, wo, w, nw in zip(ids, d["ir_wo"].cpu().tolist(), d["ir_w"].cpu().tolist(), d["n_w"].cpu().tolist()):
+                        self.descriptor[idx] = (float(wo), float(w), int(nw))
                 est = None
                 if self.register:
                     from .registration import pose_errors, register_handle
@@ -139,6 +157,11 @@ class Tester:
         per_pair = self.model.record_scores_per_pair()
         self.records = gather_result_records(assemble_block(blocks, slots_per_rank(n, self.world), per_pair, device),
                                              slots_per_rank(n, self.world), per_pair)
+        desc_all = self.descriptor
+        if self.descriptor is not None and self.world > 1:   # every rank takes part: IR / PIR below cover all ranks, so must desc_*
+            parts = [None] * self.world
+            torch.distributed.all_gather_object(parts, self.descriptor)
+            desc_all = {k: v for part in parts for k, v in part.items()}
         if self.records is None:     # ranks other than 0
             return None
         if self.records.truncated:
@@ -156,6 +179,11 @@ class Tester:
             pirs = [a[1] for a in self.records.aux.values() if a[1] == a[1]]
             self.metrics = {"IR": sum(irs) / max(len(irs), 1), "PIR": sum(pirs) / max(len(pirs), 1), "pairs": len(irs),
                             "pairs_without_coarse": len(irs) - len(pirs)}
+            if self.descriptor is not None:
+                wo = [v[0] for v in desc_all.values() if v[0] == v[0]]
+                w = [v[1] for v in desc_all.values() if v[1] == v[1]]
+                self.metrics.update(desc_IR_wo=sum(wo) / max(len(wo), 1), desc_IR_w=sum(w) / max(len(w), 1),
+                                    desc_FMR=sum(1 for x in wo if x > DESC_FMR_THRESHOLD) / max(len(wo), 1))
         return counts
 
 
