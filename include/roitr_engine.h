@@ -623,6 +623,52 @@ int roitr_desc_match_batch(int pairs, int dim, const int* src_offsets, int total
 int roitr_desc_match_select(int pairs, const int* src_offsets, const int* tgt_offsets, const int* row_idx, const int* col_idx, int mode,
                             int* corr_starts, int* corr, int capacity, int* n_out, roitr_stream_t stream);
 
+
+/* ------------------------------------------------------------------ validation losses
+ * lib/loss.py:8-166: the forward values of FineMatchingLoss and CoarseMatchingLoss (weighted_circle_loss) for every pair of a batch,
+ * read from the buffers RoitrForwardIO describes, in place.  All device pointers; no host round trip; no float atomics: every output
+ * is bitwise independent of the batch a pair travels in, of the slots its patches sit in and of a repeat of the call.
+ * status[b] is WRITTEN by each call (bits below); the two calls take separate status arrays.
+ *
+ * Fine loss.  Pair b owns patch slots [first_slot[b], first_slot[b] + patch_count[b]) of the per-patch arrays (`slots` slots:
+ * tgt_knn_pts / src_knn_pts (slots, L, 3), tgt_knn_masks / src_knn_masks (slots, L), matching_scores (slots, L+1, L+1)); the ranges
+ * must lie in [0, slots) in increasing order without overlap -- b * num_corr and n_corr[b] in the strided layout, patch_offsets[b] and
+ * the difference to the next entry in the compacted one.  Per patch: src' = src rot_b^T + trans_b (fp32 FMA chain),
+ * gt[i][j] = (d2 < positive_radius^2) & tgt_mask[i] & src_mask[j] with d2 = fmaf(dz,dz, fmaf(dy,dy, dx*dx)) of tgt_i - src'_j (NOT the
+ * reference's |a|^2 + |b|^2 - 2ab: a label can differ where |d2 - r^2| lies inside that form's fp32 error), label (i, L) where a valid
+ * tgt row has no gt, label (L, j) where a valid src column has none.  f_sum[b] = sum of the labelled matching_scores (fp32, summed in
+ * float64 over the pair's patches in slot order), f_count[b] = number of labels, f_loss[b] = -f_sum / f_count; no labels (or no
+ * patches): NaN and ROITR_LOSS_FINE_EMPTY.  A range outside [0, slots): ROITR_LOSS_BAD_OFFSETS, the pair counts as empty, nothing is
+ * read through it; a range that starts before its predecessor's end (the slot-to-pair search needs increasing order): the same for
+ * EVERY pair of the call.  L outside [1, 64] -> ROITR_ERR_UNSUPPORTED; negative counts, null pointers, a radius
+ * not finite and positive, a workspace below roitr_fine_loss_workspace_bytes() -> ROITR_ERR_ARG.
+ *
+ * Coarse loss.  Pair b owns rows [tgt_first[b], tgt_first[b] + tgt_count[b]) of tgt_feats (total_tgt, D) and likewise of src_feats
+ * (both may point into one buffer: the engine's node_feats holds the clouds of a call back to back); at most max_t / max_s rows.
+ * feat_dists = sqrt(max((-2 t.s + |t|^2) + |s|^2, 1e-12)) (square_distance's order, fp32 FMA in k order); overlaps[i][j] from the
+ * pair's gt_count[b] entries of gt_idx (pairs, gt_cap, 2) [tgt, src] / gt_overlaps (pairs, gt_cap), the last entry of a repeated node
+ * pair winning, 0 elsewhere; pos = overlap > pos_overlap, neg = overlap == 0; weighted_circle_loss with pos_scales = sqrt(overlap):
+ * the masked means over rows and columns of softplus(logsumexp_pos + logsumexp_neg) / log_scale, halved.  c_loss[b] is NaN with
+ * ROITR_LOSS_COARSE_EMPTY when no row or no column has both a positive and a negative.  A ground-truth index outside the pair is
+ * skipped, never dereferenced, and sets ROITR_LOSS_BAD_INDEX; a row range outside [0, total] or longer than max_t / max_s empties the
+ * pair and sets ROITR_LOSS_BAD_OFFSETS.  D not a positive multiple of 4, more than 65535 pairs -> ROITR_ERR_UNSUPPORTED; negative
+ * counts, null or misaligned (16 bytes) pointers, log_scale not finite and positive, a short workspace -> ROITR_ERR_ARG. */
+#define ROITR_LOSS_FINE_EMPTY 1
+#define ROITR_LOSS_COARSE_EMPTY 2
+#define ROITR_LOSS_BAD_OFFSETS 4
+#define ROITR_LOSS_BAD_INDEX 8
+size_t roitr_fine_loss_workspace_bytes(int slots);
+int roitr_fine_loss_batch(int pairs, int slots, const int* first_slot, const int* patch_count, int L, const float* tgt_knn_pts,
+                          const float* src_knn_pts, const int* tgt_knn_masks, const int* src_knn_masks, const float* matching_scores,
+                          const float* rot, const float* trans, float positive_radius, float* f_sum, int* f_count, float* f_loss,
+                          int* status, void* workspace, size_t workspace_bytes, roitr_stream_t stream);
+size_t roitr_coarse_loss_workspace_bytes(int pairs, int max_t, int max_s);
+int roitr_coarse_loss_batch(int pairs, int D, const float* tgt_feats, int total_tgt, const int* tgt_first, const int* tgt_count,
+                            const float* src_feats, int total_src, const int* src_first, const int* src_count, int max_t, int max_s,
+                            int gt_cap, const int* gt_idx, const float* gt_overlaps, const int* gt_count, float pos_margin,
+                            float neg_margin, float pos_optimal, float neg_optimal, float log_scale, float pos_overlap, float* c_loss,
+                            int* status, void* workspace, size_t workspace_bytes, roitr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

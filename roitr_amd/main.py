@@ -34,9 +34,13 @@ def main():
     ap.add_argument("--descriptor-eval", action="store_true",
                     help="with --evaluate: the descriptor-level inlier ratio without / with the mutual check and the feature-matching "
                          "recall at 0.05, from the point descriptors of every pair (descmatch.py)")
+    ap.add_argument("--validate", action="store_true",
+                    help="the reference's `val` report: mean loss, c_loss, f_loss, o_loss (lib/loss.py OverallLoss, computed on the device "
+                         "by loss.py), PIR and IR over all pairs; implies --evaluate")
     ap.add_argument("--ransac-iterations", type=int, default=50000)
     ap.add_argument("--ransac-points", type=int, default=1000, help="correspondences drawn per pair (probability ~ confidence)")
     args = ap.parse_args()
+    args.evaluate = args.evaluate or args.validate
     config = Config(load_config(args.config))
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", 0)))
@@ -60,8 +64,12 @@ def main():
     data = SyntheticPairs(args.synthetic, args.n_points, nonrigid=True) if args.nonrigid else SyntheticPairs(args.synthetic, args.n_points)
     tester = Tester(config, model, data, args.snapshot_dir, args.pairs_per_forward, rank, world, evaluate=args.evaluate,
                     estimate_normals=args.estimate_normals, register=args.register,
-                    ransac=dict(iterations=args.ransac_iterations, n_points=args.ransac_points), descriptor_eval=args.descriptor_eval)
+                    ransac=dict(iterations=args.ransac_iterations, n_points=args.ransac_points), descriptor_eval=args.descriptor_eval, validate=args.validate)
     counts = tester.test()
+    if rank == 0 and tester.validation:
+        v = tester.validation
+        print("[roitr_amd] val over %d pairs: " % v["pairs"] + "  ".join(f"{k} {v[k]:.4f}" for k in ("loss", "c_loss", "f_loss", "o_loss", "PIR", "IR")))
+        print("[roitr_amd] val: pairs left out of a mean because their value is nan: " + ", ".join(f"{k} {n}" for k, n in v["skipped"].items()))
     if rank == 0 and tester.metrics:
         print(f"[roitr_amd] PIR {tester.metrics['PIR']:.4f}  IR {tester.metrics['IR']:.4f}  over {tester.metrics['pairs']} pairs")
     if args.descriptor_eval and args.evaluate:

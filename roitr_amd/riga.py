@@ -481,7 +481,7 @@ class RIGA_v2(nn.Module):
         keep = (geom, pout, nrm, feats, rot, trans, arr, meta_dev, ready)   # inputs stay alive until the forward has run
         self.host_ms["launch"] += 1e3 * (time.perf_counter() - t_host)
         self.host_ms["calls"] += 1
-        return dict(pairs=pairs, out=out, B=B, P=P, slots=slots, n_all=n_all, n4=n4, have_gt=have_gt, meta_host=meta_host, done=done, keep=keep,
+        return dict(pairs=pairs, out=out, B=B, P=P, slots=slots, compacted=self.factor != 1, n_all=n_all, n4=n4, have_gt=have_gt, meta_host=meta_host, done=done, keep=keep,
                     relaunch=dict(want_gt=want_gt, inputs_resident=inputs_resident))
 
     def _launch_graph(self, pairs, want_gt):
@@ -539,7 +539,7 @@ class RIGA_v2(nn.Module):
         # these output slots (a plain launch_batch, evaluate_batch, user code on the current stream) behind it
         torch.cuda.current_stream().wait_stream(gs)
         keep = (slot["geom"], slot["pout"], slot["nrm"], slot["feats"], slot["rot"], slot["trans"], slot["arr"], slot["meta_dev"])
-        return dict(pairs=pairs, out=out, B=B, P=P, slots=slots, n_all=n_all, n4=n4, have_gt=have_gt, meta_host=slot["meta_host"], done=done, keep=keep,
+        return dict(pairs=pairs, out=out, B=B, P=P, slots=slots, compacted=self.factor != 1, n_all=n_all, n4=n4, have_gt=have_gt, meta_host=slot["meta_host"], done=done, keep=keep,
                     relaunch=dict(want_gt=want_gt, inputs_resident=False))
 
     def max_scores_per_pair(self):

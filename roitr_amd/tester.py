@@ -32,7 +32,8 @@ def load_pretrain(model, path):
 
 class Tester:
     def __init__(self, config, model, dataset, snapshot_dir="snapshot", pairs_per_forward=8, rank=0, world=1, evaluate=False,
-                 estimate_normals=False, view_point=(0.0, 0.0, 0.0), register=False, ransac=None, nonrigid=None, descriptor_eval=False):
+                 estimate_normals=False, view_point=(0.0, 0.0, 0.0), register=False, ransac=None, nonrigid=None, descriptor_eval=False,
+                 validate=False):
         """evaluate: also compute PIR / IR per pair on the device (lib/loss.py:169-213 Evaluator) and return their means.
         estimate_normals: ignore the dataset's normals and recompute them on the GPU from the points the way the
         reference's dataset code does (open3d estimate_normals(knn=33) + normal_redirect, dataset/tdmatch.py:120-127).
@@ -49,17 +50,25 @@ class Tester:
         as PIR is) and desc_FMR (share of pairs with IR without the mutual check above 0.05, evaluate_registration_c2f.py:109),
         over the pairs of ALL ranks (one all_gather_object of the per-pair values when world > 1), like IR / PIR.  The inlier
         distance is get_inlier_ratio's default, 0.1 m, not the config's eval_acceptance_radius.  The result records and their
-        format are untouched."""
+        format are untouched.
+        validate: the reference's `val` report (lib/trainer.py:335-344: OverallLoss and Evaluator per pair under no_grad); implies
+        evaluate.  The losses of every pair are computed on the device (loss.loss_batch, two batched kernels per forward):
+        `self.losses` maps this rank's pair ids to (loss, c_loss, f_loss, o_loss), and on rank 0 `self.validation` holds the means of
+        loss, c_loss, f_loss, o_loss, PIR and IR over the pairs of ALL ranks (one all_gather_object) plus `skipped`: the reference's
+        AverageMeter turns a whole mean into nan on one nan pair (a pair without fine labels, or without a row and a column that
+        have both a positive and a negative); here such pairs are left out of that key's mean and counted per key."""
         self.config, self.model, self.dataset = config, model, dataset
         self.snapshot_dir = snapshot_dir
         self.pairs_per_forward = pairs_per_forward
         self.rank, self.world = rank, world
-        self.evaluate, self.estimate_normals, self.view_point = evaluate, estimate_normals, view_point
+        self.evaluate, self.estimate_normals, self.view_point = evaluate or validate, estimate_normals, view_point
         self.register, self.ransac = register, dict(ransac or {})
-        self.registration = {} if register and evaluate else None
+        self.registration = {} if register and self.evaluate else None
         self.nonrigid_kw = dict(nonrigid or {})
         self.nonrigid = None   # {global pair id: (nfmr, n_metric)} once a 4DMatch batch with metric_index has been evaluated
-        self.descriptor = {} if descriptor_eval and evaluate else None
+        self.descriptor = {} if descriptor_eval and self.evaluate else None
+        self.losses = {} if validate else None
+        self.validation = None
         self.metrics = None
         self.records = None   # rank 0 after test(): shard.GatheredRecords {pair id: match scores}
 
@@ -120,6 +129,12 @@ class Tester:
                         self.nonrigid = {}
                     for idx, r, m in zip(ids, nf["nfmr"].cpu().tolist(), nf["n_metric"].cpu().tolist()):
                         self.nonrigid[idx] = (float(r), int(m))
+                if self.losses is not None:
+                    from .loss import loss_batch
+                    total, c_loss, f_loss, _, _ = loss_batch(handle, self.config)
+                    rows = torch.stack([total, c_loss, f_loss, 0.0 * f_loss], 1).cpu().tolist()   # o_loss = 0 * f_loss (lib/loss.py:165)
+                    for idx, row in zip(ids, rows):
+                        self.losses[idx] = tuple(float(x) for x in row)
                 if self.descriptor is not None:
                     from .descmatch import descriptor_handle
                     d = descriptor_handle(handle, "point", DESC_INLIER_THRESHOLD)
@@ -162,6 +177,11 @@ class Tester:
             parts = [None] * self.world
             torch.distributed.all_gather_object(parts, self.descriptor)
             desc_all = {k: v for part in parts for k, v in part.items()}
+        losses_all = self.losses
+        if self.losses is not None and self.world > 1:
+            parts = [None] * self.world
+            torch.distributed.all_gather_object(parts, self.losses)
+            losses_all = {k: v for part in parts for k, v in part.items()}
         if self.records is None:     # ranks other than 0
             return None
         if self.records.truncated:
@@ -184,6 +204,13 @@ class Tester:
                 w = [v[1] for v in desc_all.values() if v[1] == v[1]]
                 self.metrics.update(desc_IR_wo=sum(wo) / max(len(wo), 1), desc_IR_w=sum(w) / max(len(w), 1),
                                     desc_FMR=sum(1 for x in wo if x > DESC_FMR_THRESHOLD) / max(len(wo), 1))
+            if losses_all is not None:
+                self.validation = {"PIR": self.metrics["PIR"], "IR": self.metrics["IR"], "pairs": len(losses_all),
+                                   "skipped": {"PIR": self.metrics["pairs_without_coarse"], "IR": 0}}
+                for col, key in enumerate(("loss", "c_loss", "f_loss", "o_loss")):
+                    vals = [v[col] for v in losses_all.values() if v[col] == v[col]]
+                    self.validation[key] = sum(vals) / len(vals) if vals else float("nan")
+                    self.validation["skipped"][key] = len(losses_all) - len(vals)
         return counts
 
 
