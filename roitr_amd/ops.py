@@ -548,3 +548,72 @@ def geo_indices(points, sizes, sigma_d=0.2, sigma_a=15.0, angle_k=3):
                                       L.c_float(sigma_a), int(angle_k), max(sizes), L.ptr(d_idx), L.ptr(a_idx), L.stream_ptr()),
             "geo_indices")
     return d_idx, a_idx
+
+
+# ------------------------------------------------------------------------------------------------
+# Ground-truth side outputs (csrc/gt.hip), batched over pairs; clouds laid out [src_0..src_{B-1}, tgt_0..tgt_{B-1}].
+# ------------------------------------------------------------------------------------------------
+class _NodeCorr(ctypes.Structure):
+    _fields_ = [("pairs", ctypes.c_int), ("limit", ctypes.c_int), ("max_nodes", ctypes.c_int), ("pos_radius", ctypes.c_float),
+                ("nodes", _P), ("node_offset", _P), ("node_masks", _P), ("points", _P), ("pt_offset", _P), ("knn_idx", _P),
+                ("knn_mask", _P), ("rot", _P), ("trans", _P), ("overlap", _P), ("mat_stride", ctypes.c_long), ("out_idx", _P),
+                ("out_overlap", _P), ("out_count", _P), ("n_nodes", ctypes.c_int), ("nodes_t", _P), ("radius", _P)]
+
+
+def build_padded_clouds(points, pt_offset, rot, trans):
+    """roitr_build_padded_clouds (lib/utils.py:505-506 + RIGA_v2.py:86-87): points (n,3) of the 2*pairs clouds, pt_offset (2*pairs,)
+    cumulative, rot (pairs,3,3), trans (pairs,3) -> (padded (n + 2*pairs, 3), offsets (3*pairs,) i32)."""
+    dev = points.device
+    pairs = pt_offset.shape[0] // 2
+    n = points.shape[0]
+    pts, off = points.contiguous().float(), _i32c(pt_offset)
+    r, t = rot.contiguous().float(), trans.contiguous().float()
+    out = torch.empty((n + 2 * pairs, 3), dtype=torch.float32, device=dev)
+    out_off = torch.empty(3 * pairs, dtype=torch.int32, device=dev)
+    L.check(L.lib().roitr_build_padded_clouds(pairs, n, L.ptr(pts), L.ptr(off), L.ptr(r), L.ptr(t), L.ptr(out), L.ptr(out_off),
+                                              L.stream_ptr()), "build_padded_clouds")
+    return out, out_off
+
+
+def node_occlusion_score(cloud_of_node, pt_offset, knn_idx, knn_mask, node_masks, d2_padded, overlap_thres=0.0375):
+    """lib/utils.py:511-527 for all nodes of all clouds: knn_idx / knn_mask (n_nodes, limit) cloud-local with the pad index n_c,
+    d2_padded the squared kNN(1) distance of every padded point to the partner cloud -> scores (n_nodes,) f32."""
+    dev = knn_idx.device
+    n_nodes, limit = knn_idx.shape
+    con, off = _i32c(cloud_of_node), _i32c(pt_offset)
+    ki, km, nm = _i32c(knn_idx), _i32c(knn_mask), _i32c(node_masks)
+    d2 = d2_padded.contiguous().float()
+    out = torch.empty(n_nodes, dtype=torch.float32, device=dev)
+    L.check(L.lib().roitr_node_occlusion_score(n_nodes, limit, L.ptr(con), L.ptr(off), L.ptr(ki), L.ptr(km), L.ptr(nm), L.ptr(d2),
+                                               L.c_float(overlap_thres), L.ptr(out), L.stream_ptr()), "node_occlusion_score")
+    return out
+
+
+def node_correspondences(nodes, node_offset, node_masks, points, pt_offset, knn_idx, knn_mask, rot, trans, pos_radius,
+                         max_nodes=None, mat_stride=None):
+    """lib/utils.py:530-614 get_node_correspondences for `pairs` pairs (ref = tgt, src = src) -> (out_idx (pairs, mat_stride, 2) i32
+    [tgt, src] local node indices in torch.nonzero order, out_overlap (pairs, mat_stride) f32, out_count (pairs,) i32); only the
+    first out_count[p] rows of pair p are written."""
+    dev = nodes.device
+    pairs = node_offset.shape[0] // 2
+    n_nodes, limit = knn_idx.shape
+    noff, poff = _i32c(node_offset), _i32c(pt_offset)
+    if max_nodes is None:
+        ends = [0] + noff.tolist()
+        max_nodes = max(b - a for a, b in zip(ends[:-1], ends[1:]))
+    max_nodes = int(max_nodes)
+    mat_stride = max_nodes * max_nodes if mat_stride is None else int(mat_stride)
+    nd, pts = nodes.contiguous().float(), points.contiguous().float()
+    nm, ki, km = _i32c(node_masks), _i32c(knn_idx), _i32c(knn_mask)
+    r, t = rot.contiguous().float(), trans.contiguous().float()
+    overlap = torch.empty((pairs, mat_stride), dtype=torch.float32, device=dev)
+    out_idx = torch.zeros((pairs, mat_stride, 2), dtype=torch.int32, device=dev)
+    out_ov = torch.zeros((pairs, mat_stride), dtype=torch.float32, device=dev)
+    out_cnt = torch.zeros(pairs, dtype=torch.int32, device=dev)
+    nodes_t = torch.empty((n_nodes, 3), dtype=torch.float32, device=dev)
+    radius = torch.empty(n_nodes, dtype=torch.float32, device=dev)
+    a = _NodeCorr(pairs, limit, max_nodes, float(pos_radius), L.ptr(nd), L.ptr(noff), L.ptr(nm), L.ptr(pts), L.ptr(poff), L.ptr(ki),
+                  L.ptr(km), L.ptr(r), L.ptr(t), L.ptr(overlap), mat_stride, L.ptr(out_idx), L.ptr(out_ov), L.ptr(out_cnt), n_nodes,
+                  L.ptr(nodes_t), L.ptr(radius))
+    L.check(L.lib().roitr_node_correspondences(ctypes.byref(a), L.stream_ptr()), "node_correspondences")
+    return out_idx, out_ov, out_cnt

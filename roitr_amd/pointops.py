@@ -257,3 +257,23 @@ class Interpolation(torch.autograd.Function):
 
 
 interpolation2 = Interpolation.apply
+
+
+def knn_within(xyz, new_xyz, offset, new_offset, cap2, use_grid=None):
+    """roitr_knn_within: squared kNN(1) distance of every query, exact below cap2 and any value >= cap2 otherwise (the radius test of
+    lib/utils.py:508-512) -> (m,) f32."""
+    assert xyz.is_contiguous() and new_xyz.is_contiguous()
+    _need_gpu(xyz, new_xyz, offset, new_offset)
+    offset, new_offset = _i32(offset).contiguous(), _i32(new_offset).contiguous()
+    n, m, b = xyz.shape[0], new_xyz.shape[0], offset.shape[0]
+    if use_grid is None:
+        use_grid = n > GRID_MIN_POINTS * b
+    lib = L.lib()
+    d2 = torch.empty(m, dtype=torch.float32, device=xyz.device)
+    ws = torch.empty(lib.roitr_knn_workspace_bytes(b, n, m), dtype=torch.uint8, device=xyz.device)
+    st = L.stream_ptr()
+    if use_grid:
+        L.check(lib.roitr_knn_build_grid(b, n, m, L.ptr(xyz), L.ptr(offset), L.ptr(ws), st), "knn_build_grid")
+    L.check(lib.roitr_knn_within(b, n, m, L.ptr(xyz), L.ptr(new_xyz), L.ptr(offset), L.ptr(new_offset), L.c_float(cap2), L.ptr(d2),
+                                 1 if use_grid else 0, m, L.ptr(ws), st), "knn_within")
+    return d2

@@ -55,3 +55,36 @@ def test_product_never_imports_the_oracle():
                 text = open(os.path.join(dp, f)).read()
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", text, re.M), f
                 assert "liboracle" not in text and "pointops_cpu" not in text and "roitr_ref" not in text, f
+
+
+def _header_struct(name):
+    """[(field, ctypes type)] of `typedef struct <name> { ... }` in include/roitr_engine.h (scalars int / long / float / size_t and
+    pointers only)."""
+    import re
+    text = open(os.path.join(ROOT, "include", "roitr_engine.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
+    scalars = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
+    fields = []
+    for decl in body.split(";"):
+        decl = decl.strip()
+        if not decl:
+            continue
+        m = re.match(r"(?:const\s+)?(?:unsigned\s+)?([A-Za-z_][A-Za-z0-9_]*)\s*(.*)$", decl, re.S)
+        base, rest = m.group(1), m.group(2)
+        for item in rest.split(","):
+            item = item.strip()
+            if item.startswith("*"):
+                fields.append((item.lstrip("* ").strip(), ctypes.c_void_p))
+            else:
+                fields.append((item, scalars[base]))
+    return fields
+
+
+def test_ctypes_mirrors_match_the_header():
+    """The ctypes structures of roitr_amd/ops.py, field by field (name, type, order, hence offsets) against include/roitr_engine.h."""
+    from roitr_amd import ops
+    for mirror, name in ((ops._NodeCorr, "RoitrNodeCorr"), (ops._OT, "RoitrOT"), (ops._Fine, "RoitrFine"), (ops._Coarse, "RoitrCoarse")):
+        want = _header_struct(name)
+        got = [(f[0], f[1]) for f in mirror._fields_]
+        assert got == want, (name, [(a, b) for a, b in zip(got, want) if a != b], len(got), len(want))

@@ -52,6 +52,9 @@ def test_fdmatch_forward():
     assert frac >= 0.995 and err < 1e-4, (frac, err)
     assert common_order_equal(got, want)
     np.testing.assert_allclose(out["gt_tgt_node_occ"].cpu().numpy(), g["out.gt_tgt_node_occ"], atol=1e-6)
+    np.testing.assert_allclose(out["gt_src_node_occ"].cpu().numpy(), g["out.gt_src_node_occ"], atol=1e-6)
+    assert np.array_equal(out["gt_node_corr_indices"].cpu().numpy(), g["out.gt_node_corr_indices"])
+    np.testing.assert_allclose(out["gt_node_corr_overlaps"].cpu().numpy(), g["out.gt_node_corr_overlaps"], rtol=0, atol=1e-6)
 
 
 def test_patch_list_is_compacted_and_an_overfull_call_is_repeated_exactly():
