@@ -256,6 +256,27 @@ typedef struct RoitrLocalFirst {
 } RoitrLocalFirst;
 int roitr_local_first(const RoitrLocalFirst* a, roitr_stream_t stream);
 
+/* Fragment-ordered copies of the fp32 weights that the on-chip GEMMs of the three launches above read (csrc/local_block.hip
+ * gemm_phase).  Weights stay the same from call to call in real use, so the copy is made once: for every 32-row region and every
+ * 32-k slab of W one 4 KB block of four groups of 64 float4 in the order a wave consumes them, (c, n) = (0,0), (0,1), (1,0), (1,1);
+ * entry 16 g + i of a group holds W[32 region + 16 n + i][32 slab + 16 c + 4 g .. + 3].  A wave's fragment load is then one
+ * contiguous 1 KB read instead of 64 bytes of each of 16 rows.
+ *   prepare: makes (or, for a view prepared before, rewrites) the device copy of the (rows, k) view at W with leading dimension ldw,
+ *            on `stream`, and records it in a library-internal table under (W, rows, k, ldw).  rows and k multiples of 32, ldw >= k.
+ *   release: frees every copy recorded under W (none: a no-op).  Call it before W is freed or its contents change for good; after a
+ *            change in place, prepare again.
+ * A launch takes the fragment path when ALL of its weights are in the table, under exactly these views, and the row-major path
+ * otherwise -- the same bits either way:
+ *   roitr_local_block (fp32 form): (wq, H, H, H), (wcat, H, 2H, 2H), (wout, H, H, H)
+ *   roitr_local_td:    (wqqt, H + 4 in_dim, in_dim, in_dim), (wv, H, in_dim, in_dim), (wcat, H, H + in_dim, H + in_dim), (wout, H, H, H)
+ *   roitr_local_first: (wout, 64, 64, 64)
+ * count: the number of copies the table holds.
+ * reorder_host: the same permutation over host buffers (dst: rows * k floats). */
+int roitr_local_weights_prepare(const float* W, int rows, int k, int ldw, roitr_stream_t stream);
+int roitr_local_weights_release(const float* W);
+int roitr_local_weights_count(void);
+int roitr_local_weights_reorder_host(const float* src, int rows, int k, int ldw, float* dst);
+
 /* ------------------------------------------------------------------ global geometric transformer */
 /* positional_encoding.py:110-137 get_embedding_indices for a batch of clouds.  pts (rows,3) = all nodes,
  * offset (b) cumulative, cloud_of_row (rows), eoff (b) = element offset of cloud c's (n_c, n_c) block.

@@ -174,6 +174,9 @@ struct Engine {
     // operand_dtype = 2: the three bf16 pieces (csrc/gemm_x3.hip) of every weight block a K >= 256 GEMM has multiplied with, made on first
     // use (a warm-up call is never captured), dropped at finalize.  Key: (first element, elements) of the contiguous [N x K] block.
     std::map<std::pair<const float*, long>, unsigned short*> x3;
+    // weights with a fragment-ordered copy for the fused local kernels (roitr_local_weights_prepare): made at finalize, released at
+    // the next finalize (a parameter may have moved or changed) and at destroy
+    std::vector<const float*> frag_weights;
 };
 
 // the engine whose forward / finalize is running on this thread (the GEMM helpers below are free functions)
@@ -347,6 +350,18 @@ int resolve_local(Engine& E, LocalT& L, const std::string& pre, int in_dim, int 
     return E.err.empty() ? 0 : ROITR_ERR_ARG;
 }
 
+int prepare_fragments(Engine& E, const float* W, int rows, int k, hipStream_t st)
+{
+    CHK(roitr_local_weights_prepare(W, rows, k, k, st));
+    E.frag_weights.push_back(W);
+    return 0;
+}
+void release_fragments(Engine& E)
+{
+    for (const float* W : E.frag_weights) (void)roitr_local_weights_release(W);
+    E.frag_weights.clear();
+}
+
 int fold_local(Engine& E, LocalT& L, hipStream_t st)
 {
     const int H = L.H;
@@ -440,6 +455,21 @@ int fold_local(Engine& E, LocalT& L, hipStream_t st)
             L.wqkv_x_b = A.get<unsigned short>((size_t)R * I);
             if (A.fail) return ROITR_ERR_ARG;
             CHK(roitr_f32_to_bf16((long)R * I, L.wqkv_x, L.wqkv_x_b, st));
+        }
+    }
+    // fp32 levels that run in the fused kernels of csrc/local_block.hip: their on-chip GEMMs read fragment-ordered weight copies,
+    // under exactly the views local_transformer() hands over
+    if (E.cfg.operand_dtype != 1 && L.wcat && L.wqkv_x && L.out_dim == H) {
+        const int I = L.in_dim;
+        if (I == H && (H == 64 || H == 128)) {                                  // roitr_local_block
+            CHK(prepare_fragments(E, L.wqkv_x, H, H, st));
+            CHK(prepare_fragments(E, L.wcat, H, 2 * H, st));
+            CHK(prepare_fragments(E, L.out_proj.w, H, H, st));
+        } else if (L.wqqt_x && roitr_local_td_supported(I, H, 16)) {           // roitr_local_td
+            CHK(prepare_fragments(E, L.wqqt_x, H + HEADS * I, I, st));
+            CHK(prepare_fragments(E, L.wqkv_x + (size_t)(2 * H) * I, H, I, st));
+            CHK(prepare_fragments(E, L.wcat, H, H + I, st));
+            CHK(prepare_fragments(E, L.out_proj.w, H, H, st));
         }
     }
     return 0;
@@ -751,6 +781,7 @@ int build_local_first(Engine& E, const LocalT& L, hipStream_t st)
     ROITR_HIP(hipMemcpy(E.first_consts, hc.data(), sizeof(float) * 64, hipMemcpyHostToDevice));
     ROITR_HIP(hipMemcpy(E.first_consts + 64, G.data(), sizeof(float) * G.size(), hipMemcpyHostToDevice));
     ROITR_HIP(hipMemcpy(E.first_consts + 64 + (size_t)H * 32, zb.data(), sizeof(float) * H, hipMemcpyHostToDevice));
+    if (L.out_dim == H) CHK(prepare_fragments(E, L.out_proj.w, H, H, st));   // roitr_local_first's out_proj
     return 0;
 }
 }  // namespace
@@ -784,6 +815,7 @@ extern "C" void roitr_engine_destroy(void* h)
         if (g.pin) (void)hipHostFree(g.pin);
     }
     for (auto& kv : E->x3) (void)hipFree(kv.second);
+    release_fragments(*E);
     if (E->side) (void)hipStreamDestroy(E->side);
     for (int i = 0; i < Engine::NEV; ++i) if (E->ev[i]) (void)hipEventDestroy(E->ev[i]);
     for (int i = 0; i < Engine::RING; ++i) {
@@ -832,6 +864,7 @@ extern "C" int roitr_engine_finalize(void* h, hipStream_t st)
         for (auto& kv : E.x3) (void)hipFree(kv.second);
         E.x3.clear();
     }
+    release_fragments(E);   // of the previous weights (the release waits for forwards that still read them)
     const int f = E.cfg.factor;
     const int C4 = 256 * f;
     if (E.cfg.operand_dtype < 0 || E.cfg.operand_dtype > 2) { roitr_set_error("operand_dtype must be 0 (fp32), 1 (bf16) or 2 (fp32 by three-way bf16 split)", __FILE__, __LINE__); return ROITR_ERR_ARG; }

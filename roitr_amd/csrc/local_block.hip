@@ -15,10 +15,13 @@
 // Matrix work: v_mfma_f32_16x16x4_f32 (exact fp32 FMA chains, the fp32 vector rate).  A wave owns a 32 x 32 region = 2 x 2 tiles
 // of the TM x H output (TM = 64 at H = 64: 2 x 2 regions; TM = 32 at H = 128: 1 x 4 regions).  Activation images live row-major in
 // LDS (pitch H + 4 floats: the 16 rows a ds_read_b128 fragment load touches fall on 16 different 16-byte slots); the weight
-// fragments of a wave's 32 output columns come straight from L1 / L2 into registers (no LDS staging).  Lane (i = l & 15, g = l >> 4) reads ONE float4 = k 16c+4g .. +3 of its row
-// per operand and 16-k chunk and feeds component s to the s-th MFMA of the chunk: the MFMA sums k over g, the four steps over s --
-// every k once, A and B agreeing by construction.  A row's result depends on its own operands only, in a fixed order: a node's
-// output does not depend on the tile or batch it is in.
+// fragments of a wave's 32 output columns come straight from L1 / L2 into registers (no LDS staging).  Lane (i = l & 15, g = l >> 4)
+// holds ONE float4 = k 16c+4g .. +3 of its row per operand and 16-k chunk and feeds component s to the s-th MFMA of the chunk: the
+// MFMA sums k over g, the four steps over s -- every k once, A and B agreeing by construction.  The weight float4 comes from the
+// row-major matrix (64 bytes of each of 16 rows per wave-load) or, when the weights of the launch were prepared
+// (roitr_local_weights_prepare), from a copy laid out in the order the lanes consume it: one contiguous 1 KB read per wave-load.
+// The values in the registers, and every operation on them, are the same in both forms.  A row's result depends on its own
+// operands only, in a fixed order: a node's output does not depend on the tile or batch it is in.
 //
 // Attention: LPN = H / 4 lanes per node (a lane owns 4 consecutive channels, a head = LPN / 4 lanes), 64 / LPN nodes per wave at a
 // time; q comes from the LDS tile, the result goes back into the same slots (each wave reads and writes only its own rows).
@@ -26,6 +29,8 @@
 #include "common.h"
 #include "prof.h"
 #include "roitr_engine.h"
+#include <mutex>
+#include <vector>
 
 namespace {
 
@@ -68,25 +73,36 @@ __device__ __forceinline__ void acc_zero(Acc& a)
 // slab are fetched once and used RT times.  The on-chip GEMMs are not bound by the matrix pipe (busy 0.61 / 0.66 of the time at
 // H = 64 / 128 without the attention phase, profiles/r06_local_block_sq.txt: every tile re-fetches all weight fragments, 4 loads per
 // 32 MFMAs of a slab), so MFMAs per fetched fragment is what counts.
-template <int H, int AP, int RT = 1>
+// FR: W is a fragment-ordered copy (lb_frag_src below; roitr_local_weights_prepare) of a (rows, ldw) matrix: the four fragment loads
+// of a slab are four contiguous 1 KB reads of the wave, `ldw` is the width of the copied matrix.  Row-major (FR = false), lane
+// (i, g) loads 16 bytes of row c0 + i: a wave-load touches 16 cache lines and uses 64 bytes of each, and the other k half of the
+// slab touches the same 16 lines again -- 64 line look-ups for the 4 KB of a slab.  Same values into the same registers either way.
+// APF: the A fragments of the next (c, t) step are read from LDS into a second register pair while the 16 MFMAs of the current
+// step issue (8 more VGPRs); without it the ds_read_b128 pair sits right in front of the MFMAs that wait for it.
+template <int H, int AP, int RT = 1, bool FR = false, bool APF = false>
 __device__ __forceinline__ void gemm_phase(Acc (&acc)[RT], const float* __restrict__ A, int Ka, const float* __restrict__ W, int ldw, int k_w0,
                                            int r0, int c0, int tid)
 {
     const int lane = tid & 63, i = lane & 15, g = lane >> 4;
-    const float* w0 = W + (size_t)(c0 + i) * ldw + k_w0 + 4 * g;
-    const float* w1 = W + (size_t)(c0 + 16 + i) * ldw + k_w0 + 4 * g;
+    // the float4 of this lane for (slab s, 16-k chunk c, column half n) is wl + s * os + c * oc + n * on
+    const float* wl = FR ? W + ((size_t)(c0 >> 5) * (ldw >> 5) + (k_w0 >> 5)) * 1024 + 4 * lane : W + (size_t)(c0 + i) * ldw + k_w0 + 4 * g;
+    const int os = FR ? 1024 : 32, oc = FR ? 512 : 16, on = FR ? 256 : 16 * ldw;
+    const float* al = A + (r0 + i) * AP + 4 * g;
     float4 bn[2][2];
 #pragma unroll
-    for (int c = 0; c < 2; ++c) { bn[c][0] = *reinterpret_cast<const float4*>(w0 + 16 * c); bn[c][1] = *reinterpret_cast<const float4*>(w1 + 16 * c); }
+    for (int c = 0; c < 2; ++c) { bn[c][0] = *reinterpret_cast<const float4*>(wl + c * oc); bn[c][1] = *reinterpret_cast<const float4*>(wl + c * oc + on); }
+    float4 an0, an1;
+    if (APF) { an0 = *reinterpret_cast<const float4*>(al); an1 = *reinterpret_cast<const float4*>(al + 16 * AP); }
     for (int k0 = 0; k0 < Ka; k0 += 32) {
         float4 bc[2][2];
 #pragma unroll
         for (int c = 0; c < 2; ++c) { bc[c][0] = bn[c][0]; bc[c][1] = bn[c][1]; }
         if (k0 + 32 < Ka) {
+            const float* wn = wl + (size_t)((k0 >> 5) + 1) * os;
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                bn[c][0] = *reinterpret_cast<const float4*>(w0 + k0 + 32 + 16 * c);
-                bn[c][1] = *reinterpret_cast<const float4*>(w1 + k0 + 32 + 16 * c);
+                bn[c][0] = *reinterpret_cast<const float4*>(wn + c * oc);
+                bn[c][1] = *reinterpret_cast<const float4*>(wn + c * oc + on);
             }
         }
 #pragma unroll
@@ -94,8 +110,21 @@ __device__ __forceinline__ void gemm_phase(Acc (&acc)[RT], const float* __restri
             const float4 b0 = bc[c][0], b1 = bc[c][1];
 #pragma unroll
             for (int t = 0; t < RT; ++t) {
-                const float4 a0 = *reinterpret_cast<const float4*>(A + (r0 + 32 * t + i) * AP + k0 + 16 * c + 4 * g);
-                const float4 a1 = *reinterpret_cast<const float4*>(A + (r0 + 32 * t + 16 + i) * AP + k0 + 16 * c + 4 * g);
+                float4 a0, a1;
+                if (APF) {
+                    a0 = an0; a1 = an1;
+                    // the step after (k0, c, t): (k0, c, t + 1), (k0, 1, 0), (k0 + 32, 0, 0)
+                    const bool last = t + 1 == RT && c == 1;
+                    const int tn = t + 1 < RT ? t + 1 : 0, kn = last ? k0 + 32 : k0 + (t + 1 < RT ? 16 * c : 16);
+                    if (!last || k0 + 32 < Ka) {
+                        an0 = *reinterpret_cast<const float4*>(al + 32 * tn * AP + kn);
+                        an1 = *reinterpret_cast<const float4*>(al + (32 * tn + 16) * AP + kn);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);   // the reads above are issued BEFORE this step's MFMAs, not sunk in front of their use
+                } else {
+                    a0 = *reinterpret_cast<const float4*>(al + 32 * t * AP + k0 + 16 * c);
+                    a1 = *reinterpret_cast<const float4*>(al + (32 * t + 16) * AP + k0 + 16 * c);
+                }
 #define LB_STEP(S)                                                                                                  \
                 acc[t].t[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.S, b0.S, acc[t].t[0][0], 0, 0, 0);          \
                 acc[t].t[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.S, b1.S, acc[t].t[0][1], 0, 0, 0);          \
@@ -108,11 +137,11 @@ __device__ __forceinline__ void gemm_phase(Acc (&acc)[RT], const float* __restri
     }
 }
 // one region (local_td_kernel, local_first_kernel)
-template <int H, int AP>
-__device__ __forceinline__ void gemm_phase(Acc& acc, const float* __restrict__ A, int Ka, const float* __restrict__ W, int ldw, int k_w0,
+template <int H, int AP, bool FR = false, bool APF = false>
+__device__ __forceinline__ void gemm_phase1(Acc& acc, const float* __restrict__ A, int Ka, const float* __restrict__ W, int ldw, int k_w0,
                                            int r0, int c0, int tid)
 {
-    gemm_phase<H, AP, 1>(reinterpret_cast<Acc (&)[1]>(acc), A, Ka, W, ldw, k_w0, r0, c0, tid);
+    gemm_phase<H, AP, 1, FR, APF>(reinterpret_cast<Acc (&)[1]>(acc), A, Ka, W, ldw, k_w0, r0, c0, tid);
 }
 
 // D[row][col] = acc + bias[col] into a row-major LDS tile (pitch DP); 16x16 C/D map: col = lane & 15, row = 4 (lane >> 4) + reg
@@ -187,12 +216,12 @@ template <bool MB, int RT> __device__ __forceinline__ void region_zero(RegionAcc
         } else acc_zero(r.a[t]);
     }
 }
-template <bool MB, int H, int AP, int RT>
+template <bool MB, int H, int AP, int RT, bool FR, bool APF>
 __device__ __forceinline__ void region_gemm(RegionAcc<MB, RT>& r, const float* __restrict__ A, int Ka, const float* __restrict__ W,
                                             const unsigned short* __restrict__ Wb, int ldw, int k_w0, int r0, int c0, int tid)
 {
     if constexpr (MB) gemm_phase_bf16<AP, RT>(r.a, A, Ka, Wb, ldw, k_w0, r0, c0, tid);
-    else gemm_phase<H, AP, RT>(r.a, A, Ka, W, ldw, k_w0, r0, c0, tid);
+    else gemm_phase<H, AP, RT, FR, APF>(r.a, A, Ka, W, ldw, k_w0, r0, c0, tid);
 }
 template <bool MB, int DP, int RT>
 __device__ __forceinline__ void region_store(const RegionAcc<MB, RT>& r, const float* __restrict__ bias, float* __restrict__ D, int r0, int c0, int lane)
@@ -218,7 +247,8 @@ __device__ __forceinline__ float4 ld_kv4(const float* kv, size_t row, int ld, in
 
 // DBG (tuning only, scripts/bench_local_block.py): 0 = the kernel; 1 = without the attention phase; 2 = attention only
 // MB: bf16 matrix operands in the three on-chip GEMMs (RoitrLocalBlock::wq_h / wcat_h / wout_h; the engine's bf16 operand mode)
-template <int H, int K, int TM, int DBG = 0, bool KVH = false, bool MB = false>
+// FR: wq / wcat / wout point to fragment-ordered copies (the launcher found all three in the table of roitr_local_weights_prepare)
+template <int H, int K, int TM, int DBG = 0, bool KVH = false, bool MB = false, bool FR = false>
 __global__ __launch_bounds__(256, (K <= 8 && TM * H <= 4096) ? 3 : 2) void local_block_kernel(RoitrLocalBlock a)
 {
     constexpr int AP = H + 4;                 // activation image pitch
@@ -257,6 +287,9 @@ __global__ __launch_bounds__(256, (K <= 8 && TM * H <= 4096) ? 3 : 2) void local
     }
     // the TM x H output is (TM / 32) x (H / 32) regions of 32 x 32: a wave takes ONE 32-column strip and RT row regions under each other
     constexpr int NC = H / 32, RT = TM * H / (32 * 32 * 4);
+    // A fragments a step ahead where it was measured to pay: the 64-row tiles at H = 128 (two row regions per wave).  With one region
+    // per wave at H = 64 it cost time (3.04 -> 3.10 ms per level-1 launch alone, profiles/local_block_fragments_alone.txt).
+    constexpr bool APF = H == 128 && RT == 2;
     int r0 = (wave / NC) * 32 * RT;
     int c0 = (wave % NC) * 32;
     RegionAcc<MB, RT> acc;
@@ -265,7 +298,7 @@ __global__ __launch_bounds__(256, (K <= 8 && TM * H <= 4096) ? 3 : 2) void local
     // ---- P1: q = x Wq^T + bq -> R2
     __syncthreads();                                              // the x image is complete
     zero_all();
-    if (DBG != 2) region_gemm<MB, H, AP, RT>(acc, R1, H, a.wq, a.wq_h, H, 0, r0, c0, tid);
+    if (DBG != 2) region_gemm<MB, H, AP, RT, FR, APF>(acc, R1, H, a.wq, a.wq_h, H, 0, r0, c0, tid);
     store_all(a.bq);
     __syncthreads();
     // ---- P2: attention, in place on R2 (a wave touches only the rows of its own nodes)
@@ -374,8 +407,8 @@ __global__ __launch_bounds__(256, (K <= 8 && TM * H <= 4096) ? 3 : 2) void local
     __syncthreads();                                              // the attention rows of every wave are in place
     zero_all();
     if (DBG != 2) {
-    region_gemm<MB, H, AP, RT>(acc, R2, H, a.wcat, a.wcat_h, 2 * H, 0, r0, c0, tid);
-    region_gemm<MB, H, AP, RT>(acc, R1, H, a.wcat, a.wcat_h, 2 * H, H, r0, c0, tid);
+    region_gemm<MB, H, AP, RT, FR, APF>(acc, R2, H, a.wcat, a.wcat_h, 2 * H, 0, r0, c0, tid);
+    region_gemm<MB, H, AP, RT, FR, APF>(acc, R1, H, a.wcat, a.wcat_h, 2 * H, H, r0, c0, tid);
     }
     __syncthreads();                                              // every wave is done reading R1 / R2
     store_all(a.bcat);
@@ -424,7 +457,7 @@ __global__ __launch_bounds__(256, (K <= 8 && TM * H <= 4096) ? 3 : 2) void local
     }
     __syncthreads();                                              // the y image is complete
     zero_all();
-    if (DBG != 2) region_gemm<MB, H, AP, RT>(acc, R1, H, a.wout, a.wout_h, H, 0, r0, c0, tid);
+    if (DBG != 2) region_gemm<MB, H, AP, RT, FR, APF>(acc, R1, H, a.wout, a.wout_h, H, 0, r0, c0, tid);
     __syncthreads();                                              // every wave is done reading the y image
     store_all(a.bout);
     __syncthreads();
@@ -476,7 +509,7 @@ __global__ __launch_bounds__(256, (K <= 8 && TM * H <= 4096) ? 3 : 2) void local
 // bytes instead of 512), no in_proj launch: per node the kernel reads x, K indices, K neighbour scalars and the PPFs, forms g_i
 // (one thread per (node, head)), and finishes with the two on-chip GEMMs of the block kernel: z = G g -> LayerNorm -> out_proj.
 // Constants: RoitrLocalFirst (built by the engine at finalize in float64 from the layer's weights).
-template <int K>
+template <int K, bool FR>
 __global__ __launch_bounds__(256) void local_first_kernel(RoitrLocalFirst a)
 {
     constexpr int H = 64, TM = 64, AP = H + 4, HV = 1;
@@ -544,7 +577,7 @@ __global__ __launch_bounds__(256) void local_first_kernel(RoitrLocalFirst a)
     // ---- z = G g (K = 32, the bias rides in column 21) -> LayerNorm -> y
     __syncthreads();                                              // the g rows are complete
     acc_zero(acc);
-    gemm_phase<H, AP>(acc, R2, 32, a.G, 32, 0, r0, c0, tid);
+    gemm_phase1<H, AP, false, false>(acc, R2, 32, a.G, 32, 0, r0, c0, tid);
     __syncthreads();
     acc_store<AP>(acc, a.zero_bias, R2, r0, c0, lane);
     __syncthreads();
@@ -566,7 +599,7 @@ __global__ __launch_bounds__(256) void local_first_kernel(RoitrLocalFirst a)
     // ---- out = y Wout^T + bout
     __syncthreads();                                              // the y image is complete
     acc_zero(acc);
-    gemm_phase<H, AP>(acc, R1, H, a.wout, H, 0, r0, c0, tid);
+    gemm_phase1<H, AP, FR, false>(acc, R1, H, a.wout, H, 0, r0, c0, tid);
     __syncthreads();
     acc_store<AP>(acc, a.bout, R2, r0, c0, lane);
     __syncthreads();
@@ -609,6 +642,7 @@ __device__ __forceinline__ float td_row_allmax(float v)
     return v;
 }
 
+template <bool FR>
 __global__ __launch_bounds__(256, 3) void local_td_kernel(RoitrLocalTd a)
 {
     constexpr int I = 64, H = 128, K = 16, TM = 32, HQ = 2, HV = 2;
@@ -620,6 +654,7 @@ __global__ __launch_bounds__(256, 3) void local_td_kernel(RoitrLocalTd a)
     __shared__ __attribute__((aligned(16))) float R3[TM * P3];   // q~ -> xbar -> [y (columns 0..127) | x_n (columns 128..191)]
     __shared__ __attribute__((aligned(16))) float probs[4][64];  // per wave: [head][neighbour]
     __shared__ int ids[TM];
+    // (every on-chip GEMM below reads its A fragments a step ahead, gemm_phase APF: 2.86 -> 2.82 ms per level-2 launch alone)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ntiles = (a.M + TM - 1) / TM;
     const int tile = xcd_block_id(ntiles);
@@ -652,7 +687,7 @@ __global__ __launch_bounds__(256, 3) void local_td_kernel(RoitrLocalTd a)
         for (int pass = 0; pass < 3; ++pass) {
             Acc acc;
             acc_zero(acc);
-            gemm_phase<H, P2>(acc, R2, I, a.wqqt, I, 0, 0, 128 * pass + c0, tid);
+            gemm_phase1<H, P2, FR, true>(acc, R2, I, a.wqqt, I, 0, 0, 128 * pass + c0, tid);
             if (pass == 0) accq = acc;
             else {
                 // columns 128 pass + c0 of [q | q~] = columns 128 (pass - 1) + c0 of q~
@@ -762,7 +797,7 @@ __global__ __launch_bounds__(256, 3) void local_td_kernel(RoitrLocalTd a)
     {   // ---- P2b: val_h = Wv'_h xbar_h (wave = head); att = vpart + val + bv' in place on R2
         Acc acc;
         acc_zero(acc);
-        gemm_phase<H, P3>(acc, R3 + I * wave, I, a.wv, I, 0, 0, c0, tid);
+        gemm_phase1<H, P3, FR, true>(acc, R3 + I * wave, I, a.wv, I, 0, 0, c0, tid);
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
             const int col = c0 + 16 * n + (lane & 15);
@@ -789,9 +824,9 @@ __global__ __launch_bounds__(256, 3) void local_td_kernel(RoitrLocalTd a)
     Acc acc;
     // ---- P3: y = LN([att | x_n] Wcat^T + bcat) -> R3 columns 0..127
     acc_zero(acc);
-    gemm_phase<H, P2>(acc, R2, H, a.wcat, H + I, 0, 0, c0, tid);
+    gemm_phase1<H, P2, FR, true>(acc, R2, H, a.wcat, H + I, 0, 0, c0, tid);
     __syncthreads();                                              // the x_n columns are complete; every wave is done reading R2
-    gemm_phase<H, P3>(acc, R3 + 2 * I, I, a.wcat, H + I, H, 0, c0, tid);
+    gemm_phase1<H, P3, FR, true>(acc, R3 + 2 * I, I, a.wcat, H + I, H, 0, c0, tid);
     acc_store<P2>(acc, a.bcat, R2, 0, c0, lane);
     __syncthreads();
     {
@@ -826,7 +861,7 @@ __global__ __launch_bounds__(256, 3) void local_td_kernel(RoitrLocalTd a)
     __syncthreads();                                              // the y image is complete
     // ---- P4: out = y Wout^T + bout
     acc_zero(acc);
-    gemm_phase<H, P3>(acc, R3, H, a.wout, H, 0, 0, c0, tid);
+    gemm_phase1<H, P3, FR, true>(acc, R3, H, a.wout, H, 0, 0, c0, tid);
     acc_store<P2>(acc, a.bout, R2, 0, c0, lane);                   // R2 was last read before the barrier above
     __syncthreads();
     {
@@ -843,11 +878,104 @@ __global__ __launch_bounds__(256, 3) void local_td_kernel(RoitrLocalTd a)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Fragment-ordered weight copies (roitr_local_weights_prepare).  For every 32-row region and every 32-k slab of W one 4 KB block of
+// four groups of 64 float4 in the order gemm_phase reads them, (c, n) = (0,0), (0,1), (1,0), (1,1): entry lane = 16 g + i of a group
+// holds W[32 region + 16 n + i][32 slab + 16 c + 4 g .. + 3].  Float offset into W of float4 `d` of the copy:
+__host__ __device__ inline size_t lb_frag_src(size_t d, int k, int ldw)
+{
+    const int lane = (int)(d & 63), q = (int)((d >> 6) & 3), nslab = k >> 5;
+    const size_t blk = d >> 8, region = blk / nslab, slab = blk % nslab;
+    const int i = lane & 15, g = lane >> 4, c = q >> 1, n = q & 1;
+    return (32 * region + 16 * n + i) * (size_t)ldw + 32 * slab + 16 * c + 4 * g;
+}
+__global__ __launch_bounds__(256) void lb_reorder_kernel(const float* __restrict__ W, int rows, int k, int ldw, float4* __restrict__ dst)
+{
+    const size_t d = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (d < (size_t)rows * k / 4) dst[d] = *reinterpret_cast<const float4*>(W + lb_frag_src(d, k, ldw));
+}
+bool lb_frag_shape_ok(int rows, int k, int ldw) { return rows > 0 && k > 0 && rows % 32 == 0 && k % 32 == 0 && ldw >= k && ldw % 4 == 0; }
+
+struct FragEntry { const float* W; int rows, k, ldw; float* frag; };
+std::mutex g_frag_mutex;
+std::vector<FragEntry> g_frags;   // a few dozen entries (the engine's fp32 levels): a linear walk per launch
+
+// the copy of the (rows, k) view at W with leading dimension ldw, or nullptr
+const float* lb_frag(const float* W, int rows, int k, int ldw)
+{
+    std::lock_guard<std::mutex> lock(g_frag_mutex);
+    for (const FragEntry& e : g_frags)
+        if (e.W == W && e.rows == rows && e.k == k && e.ldw == ldw) return e.frag;
+    return nullptr;
+}
+
 }  // namespace
+
+extern "C" int roitr_local_weights_reorder_host(const float* src, int rows, int k, int ldw, float* dst)
+{
+    if (!src || !dst || !lb_frag_shape_ok(rows, k, ldw)) { roitr_set_error("roitr_local_weights_reorder_host: rows and k multiples of 32, ldw >= k", __FILE__, __LINE__); return ROITR_ERR_ARG; }
+    const size_t n4 = (size_t)rows * k / 4;
+    for (size_t d = 0; d < n4; ++d) { const float* s4 = src + lb_frag_src(d, k, ldw); for (int e = 0; e < 4; ++e) dst[4 * d + e] = s4[e]; }
+    return ROITR_OK;
+}
+
+extern "C" int roitr_local_weights_prepare(const float* W, int rows, int k, int ldw, hipStream_t stream)
+{
+    if (!W || ((uintptr_t)W & 15) != 0 || !lb_frag_shape_ok(rows, k, ldw)) {
+        roitr_set_error("roitr_local_weights_prepare: W 16-byte aligned, rows and k multiples of 32, ldw >= k and a multiple of 4", __FILE__, __LINE__);
+        return ROITR_ERR_ARG;
+    }
+    float* frag = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(g_frag_mutex);
+        for (const FragEntry& e : g_frags)
+            if (e.W == W && e.rows == rows && e.k == k && e.ldw == ldw) frag = e.frag;   // prepared before: the copy is written again
+        if (!frag) {
+            ROITR_HIP(hipMalloc((void**)&frag, sizeof(float) * (size_t)rows * k));
+            g_frags.push_back(FragEntry{W, rows, k, ldw, frag});
+        }
+    }
+    lb_reorder_kernel<<<div_up(rows * k / 4, 256), 256, 0, stream>>>(W, rows, k, ldw, reinterpret_cast<float4*>(frag));
+    ROITR_LAUNCH_CHECK();
+    return ROITR_OK;
+}
+
+extern "C" int roitr_local_weights_count(void)
+{
+    std::lock_guard<std::mutex> lock(g_frag_mutex);
+    return (int)g_frags.size();
+}
+
+extern "C" int roitr_local_weights_release(const float* W)
+{
+    std::vector<float*> drop;
+    {
+        std::lock_guard<std::mutex> lock(g_frag_mutex);
+        for (size_t j = 0; j < g_frags.size();) {
+            if (g_frags[j].W == W) { drop.push_back(g_frags[j].frag); g_frags.erase(g_frags.begin() + j); }
+            else ++j;
+        }
+    }
+    for (float* f : drop) ROITR_HIP(hipFree(f));   // hipFree waits for the launches that still read the copy
+    return ROITR_OK;
+}
 
 extern "C" int roitr_local_block_supported(int H, int K)
 {
     return ((H == 64 && K == 8) || (H == 64 && K == 16) || (H == 128 && K == 16) || (H == 128 && K == 8)) ? 1 : 0;
+}
+
+// The fragment path of a launch: every fp32 weight its on-chip GEMMs read has a fragment-ordered copy -> the pointers of `b` are
+// replaced by the copies' (the struct is the launch's own).  One missing: the row-major path, `b` as the caller gave it.
+static bool lb_block_fragments(RoitrLocalBlock& b)
+{
+    if (b.wq_h || b.kv_bf16) return false;   // the bf16 forms keep their own fetch
+    const float* wq = lb_frag(b.wq, b.H, b.H, b.H);
+    const float* wcat = lb_frag(b.wcat, b.H, 2 * b.H, 2 * b.H);
+    const float* wout = lb_frag(b.wout, b.H, b.H, b.H);
+    if (!wq || !wcat || !wout) return false;
+    b.wq = wq; b.wcat = wcat; b.wout = wout;
+    return true;
 }
 
 // tuning hook of scripts/bench_local_block.py (not part of include/*.h): the kernel with a phase left out
@@ -858,16 +986,20 @@ extern "C" int roitr_local_block_dbg(const RoitrLocalBlock* a, int variant, hipS
     const int big = variant / 10, ph = variant % 10;
     const int tm = (a->H == 64 ? 64 : 32) * (big ? 2 : 1);
     const int grid = xcd_grid(div_up(a->M, tm));
-#define LB_DBG(HH, KK, TT)                                                                     \
-    do {                                                                                       \
-        if (ph == 1) local_block_kernel<HH, KK, TT, 1><<<grid, 256, 0, stream>>>(*a);     \
-        else if (ph == 2) local_block_kernel<HH, KK, TT, 2><<<grid, 256, 0, stream>>>(*a); \
-        else local_block_kernel<HH, KK, TT, 0><<<grid, 256, 0, stream>>>(*a);                  \
+    RoitrLocalBlock b = *a;
+    const bool fr = lb_block_fragments(b);
+#define LB_DBG_(HH, KK, TT, FR_)                                                                                    \
+    do {                                                                                                            \
+        if (ph == 1) local_block_kernel<HH, KK, TT, 1, false, false, FR_><<<grid, 256, 0, stream>>>(b);             \
+        else if (ph == 2) local_block_kernel<HH, KK, TT, 2, false, false, FR_><<<grid, 256, 0, stream>>>(b);        \
+        else local_block_kernel<HH, KK, TT, 0, false, false, FR_><<<grid, 256, 0, stream>>>(b);                     \
     } while (0)
+#define LB_DBG(HH, KK, TT) do { if (fr) LB_DBG_(HH, KK, TT, true); else LB_DBG_(HH, KK, TT, false); } while (0)
     if (a->H == 64 && a->K == 8) { if (big) LB_DBG(64, 8, 128); else LB_DBG(64, 8, 64); }   // 128-row tiles at H = 64: this hook only
     else if (a->H == 128 && a->K == 16) { if (big) LB_DBG(128, 16, 64); else LB_DBG(128, 16, 32); }
     else return ROITR_ERR_UNSUPPORTED;
 #undef LB_DBG
+#undef LB_DBG_
     ROITR_LAUNCH_CHECK();
     return ROITR_OK;
 }
@@ -900,12 +1032,15 @@ extern "C" int roitr_local_block(const RoitrLocalBlock* a, hipStream_t stream)
     constexpr int LB_BIG_MIN_TILES = 1024;
     const bool big = a->H == 128 && div_up(a->M, 64) >= LB_BIG_MIN_TILES;
     const int grid = xcd_grid(div_up(a->M, a->H == 64 ? 64 : (big ? 64 : 32)));
-#define LB_GO(HH, KK, TT, KVH_) local_block_kernel<HH, KK, TT, 0, KVH_><<<grid, 256, 0, stream>>>(*a)
-#define LB_GO_MB(HH, KK, TT) local_block_kernel<HH, KK, TT, 0, true, true><<<grid, 256, 0, stream>>>(*a)
+    RoitrLocalBlock b = *a;
+    const bool fr = lb_block_fragments(b);
+#define LB_GO(HH, KK, TT, KVH_) local_block_kernel<HH, KK, TT, 0, KVH_><<<grid, 256, 0, stream>>>(b)
+#define LB_GO_MB(HH, KK, TT) local_block_kernel<HH, KK, TT, 0, true, true><<<grid, 256, 0, stream>>>(b)
 #define LB_PICK(HH, KK, TT)                                   \
     do {                                                      \
         if (mb) LB_GO_MB(HH, KK, TT);                         \
         else if (a->kv_bf16) LB_GO(HH, KK, TT, true);         \
+        else if (fr) local_block_kernel<HH, KK, TT, 0, false, false, true><<<grid, 256, 0, stream>>>(b); \
         else LB_GO(HH, KK, TT, false);                        \
     } while (0)
     if (a->H == 64) { if (a->K == 8) LB_PICK(64, 8, 64); else LB_PICK(64, 16, 64); }
@@ -934,7 +1069,18 @@ extern "C" int roitr_local_td(const RoitrLocalTd* a, hipStream_t stream)
     // algorithmic bytes: the node row in, 16 gathered input rows, ppf + indices, one row out; FLOPs of the on-chip GEMMs in aux
     const double I = a->in_dim, H = a->H;
     roitr_prof_begin2(ROITR_PROF_LOCAL_BLOCK, (double)a->M * (I * 4 + 16.0 * (I * 4 + 20.0) + H * 4), 2.0 * a->M * ((H + 4 * I) * I + H * I + H * (H + I) + H * H), stream);
-    local_td_kernel<<<xcd_grid(div_up(a->M, 32)), 256, 0, stream>>>(*a);
+    RoitrLocalTd b = *a;
+    {
+        const int Hi = a->H, Ii = a->in_dim;
+        const float* wqqt = lb_frag(b.wqqt, Hi + 4 * Ii, Ii, Ii);
+        const float* wv = lb_frag(b.wv, Hi, Ii, Ii);
+        const float* wcat = lb_frag(b.wcat, Hi, Hi + Ii, Hi + Ii);
+        const float* wout = lb_frag(b.wout, Hi, Hi, Hi);
+        if (wqqt && wv && wcat && wout) {
+            b.wqqt = wqqt; b.wv = wv; b.wcat = wcat; b.wout = wout;
+            local_td_kernel<true><<<xcd_grid(div_up(a->M, 32)), 256, 0, stream>>>(b);
+        } else local_td_kernel<false><<<xcd_grid(div_up(a->M, 32)), 256, 0, stream>>>(b);
+    }
     roitr_prof_end(ROITR_PROF_LOCAL_BLOCK, stream);
     ROITR_LAUNCH_CHECK();
     return ROITR_OK;
@@ -952,8 +1098,16 @@ extern "C" int roitr_local_first(const RoitrLocalFirst* a, hipStream_t stream)
     // algorithmic bytes: x, K indices, K neighbour scalars (4 B each), the PPFs, one row out; FLOPs of the two on-chip GEMMs in aux
     roitr_prof_begin2(ROITR_PROF_LOCAL_BLOCK, (double)a->M * (4.0 + a->K * (4.0 + 4.0 + 16.0) + 64.0 * 4), 2.0 * a->M * 64.0 * (32.0 + 64.0), stream);
     const int grid = xcd_grid(div_up(a->M, 64));
-    if (a->K == 8) local_first_kernel<8><<<grid, 256, 0, stream>>>(*a);
-    else local_first_kernel<16><<<grid, 256, 0, stream>>>(*a);
+    RoitrLocalFirst b = *a;
+    const float* wout = lb_frag(b.wout, 64, 64, 64);
+    if (wout) {
+        b.wout = wout;
+        if (a->K == 8) local_first_kernel<8, true><<<grid, 256, 0, stream>>>(b);
+        else local_first_kernel<16, true><<<grid, 256, 0, stream>>>(b);
+    } else {
+        if (a->K == 8) local_first_kernel<8, false><<<grid, 256, 0, stream>>>(b);
+        else local_first_kernel<16, false><<<grid, 256, 0, stream>>>(b);
+    }
     roitr_prof_end(ROITR_PROF_LOCAL_BLOCK, stream);
     ROITR_LAUNCH_CHECK();
     return ROITR_OK;

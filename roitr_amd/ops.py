@@ -472,6 +472,68 @@ def local_block(x, kv, group_idx, ppf, w, node_order=None, variant=None, bf16_we
     return out
 
 
+class _LocalFirst(ctypes.Structure):
+    _fields_ = [("M", ctypes.c_int), ("K", ctypes.c_int),
+                ("x", ctypes.c_void_p), ("group_idx", ctypes.c_void_p), ("ppf", ctypes.c_void_p), ("node_order", ctypes.c_void_p),
+                ("head_consts", ctypes.c_void_p), ("G", ctypes.c_void_p), ("zero_bias", ctypes.c_void_p),
+                ("norm_w", ctypes.c_void_p), ("norm_b", ctypes.c_void_p), ("wout", ctypes.c_void_p), ("bout", ctypes.c_void_p),
+                ("scale", ctypes.c_float), ("eps", ctypes.c_float), ("out", ctypes.c_void_p)]
+
+
+def local_first(x, group_idx, ppf, w, node_order=None):
+    """The first local transformer of the network in its rank-1 form (csrc/local_block.hip local_first_kernel;
+    include/roitr_engine.h RoitrLocalFirst).  x (M,) the scalar input feature, group_idx (M, K) int32, K in {8, 16}, ppf (M, K, 4);
+    w: dict of head_consts (64), G (64, 32), zero_bias (64), norm_w, norm_b, wout (64, 64), bout.  Returns (M, 64)."""
+    f = lambda t: t.contiguous().float()
+    x, ppf = f(x), f(ppf)
+    group_idx = _i32c(group_idx)
+    w = {k: f(v) for k, v in w.items()}
+    M, K = int(x.shape[0]), int(group_idx.shape[1])
+    out = torch.empty((M, 64), dtype=torch.float32, device=x.device)
+    a = _LocalFirst()
+    a.M, a.K = M, K
+    a.x, a.group_idx, a.ppf = L.ptr(x), L.ptr(group_idx), L.ptr(ppf)
+    no = f(node_order) if node_order is not None else None
+    a.node_order = L.ptr(no)
+    for k in ("head_consts", "G", "zero_bias", "norm_w", "norm_b", "wout", "bout"):
+        setattr(a, k, L.ptr(w[k]))
+    a.scale, a.eps, a.out = 0.25, 1e-5, L.ptr(out)
+    L.check(L.lib().roitr_local_first(ctypes.byref(a), L.stream_ptr()), "local_first")
+    return out
+
+
+def _weight_view(t):
+    if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1:
+        raise L.RoitrError("local weights: a 2-D float32 tensor with contiguous rows")
+    return int(t.shape[0]), int(t.shape[1]), int(t.stride(0))
+
+
+def local_weights_prepare(w):
+    """roitr_local_weights_prepare: a fragment-ordered device copy of the (rows, k) weight `w` (a device tensor, or a row / column
+    slice of one), kept by the library under w's address until local_weights_release(w).  local_block / local_td / local_first take
+    the fragment path when all of their weights are prepared (include/roitr_engine.h); the caller keeps `w` alive and unchanged."""
+    rows, k, ldw = _weight_view(w)
+    L.check(L.lib().roitr_local_weights_prepare(L.ptr(w), rows, k, ldw, L.stream_ptr()), "local_weights_prepare")
+
+
+def local_weights_release(w):
+    """roitr_local_weights_release: frees every copy kept under w's address (none: a no-op)."""
+    L.check(L.lib().roitr_local_weights_release(L.ptr(w)), "local_weights_release")
+
+
+def local_weights_count():
+    """roitr_local_weights_count: the number of fragment-ordered copies the library holds."""
+    return int(L.lib().roitr_local_weights_count())
+
+
+def local_weights_reorder_host(w):
+    """roitr_local_weights_reorder_host: the fragment order of a HOST weight (rows, k) (rows may be strided), as a flat host tensor."""
+    rows, k, ldw = _weight_view(w)
+    dst = torch.empty(rows * k, dtype=torch.float32)
+    L.check(L.lib().roitr_local_weights_reorder_host(L.host_ptr(w), rows, k, ldw, L.host_ptr(dst)), "local_weights_reorder_host")
+    return dst
+
+
 # ------------------------------------------------------------------------------------------------
 # Global geometric transformer (csrc/geo_attn.hip)
 # ------------------------------------------------------------------------------------------------

@@ -1,11 +1,14 @@
 """Micro-benchmark of csrc/local_block.hip local_td_kernel at the level-2 shape of the 512-pair step (tuning aid):
-    python scripts/bench_local_td.py [pairs]"""
+    python scripts/bench_local_td.py [pairs] [--prepared]
+--prepared: the weights get their fragment-ordered copies first (ops.local_weights_prepare), so the launches take the fragment path."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from roitr_amd import ops
 
-pairs = int(sys.argv[1]) if len(sys.argv) > 1 else 512
+prepared = "--prepared" in sys.argv
+argv = [a for a in sys.argv[1:] if a != "--prepared"]
+pairs = int(argv[0]) if argv else 512
 dev = "cuda"
 g = torch.Generator(device=dev).manual_seed(0)
 I, H, n_in, n_out = 64, 128, 5000, 1250
@@ -22,6 +25,9 @@ ppf = torch.rand((M, 16, 4), device=dev, generator=g)
 r = lambda *s: torch.randn(s, device=dev, generator=g) / (s[-1] ** 0.5)
 w = dict(wqqt=r(H + 4 * I, I), bqqt=r(H + 4 * I), wv=r(H, I), bv=r(H), wpe=r(H, 4), wvpe=r(H, 4), bvpe=r(H), wcat=r(H, H + I), bcat=r(H),
          norm_w=1 + 0.1 * r(H), norm_b=0.1 * r(H), wout=r(H, H), bout=r(H))
+if prepared:
+    for k in ("wqqt", "wv", "wcat", "wout"):
+        ops.local_weights_prepare(w[k])
 for _ in range(2):
     ops.local_td(x, node_idx, grp, ppf, w)
 torch.cuda.synchronize()
@@ -32,4 +38,4 @@ for _ in range(5):
 e1.record(); torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / 5
 flops = 2.0 * M * ((H + 4 * I) * I + H * I + H * (H + I) + H * H)
-print(f"local_td M={M} N_in={N_in}: {ms:7.3f} ms per launch ({flops / ms / 1e9:6.1f} TFLOP/s on the on-chip GEMMs)")
+print(f"local_td M={M} N_in={N_in}{' prepared' if prepared else ''}: {ms:7.3f} ms per launch ({flops / ms / 1e9:6.1f} TFLOP/s on the on-chip GEMMs)")
