@@ -511,6 +511,15 @@ int roitr_engine_forward(void* engine, const RoitrForwardIO* io, roitr_stream_t 
  * The caller keeps the io buffers at fixed addresses and re-fills them between calls. */
 int roitr_engine_forward_graph(void* engine, const RoitrForwardIO* io, roitr_stream_t stream);
 int roitr_engine_graph_count(void* engine);
+/* Behind the encoder the global transformer and the coarse front of the matching phase (coarse head, coarse matching, patch arrays)
+ * depend on nothing the decoder writes, and the decoder on nothing of theirs.  on == 1 (the default): for calls with enough superpoints
+ * for it to pay they run on a stream of the engine's own beside the decoder, joined in front of the patch score product; smaller calls
+ * keep them on the caller's stream.  on == 2: on the engine's stream for every call.  on == 0: never -- the same launches, on the same
+ * buffers, queued on the caller's stream in front of the decoder.  The results are the same bytes in every mode. */
+int roitr_engine_set_phase_overlap(void* engine, int on);
+/* Diagnostics: out5 = {capacity of the main scratch arena in bytes, its largest fill since it was allocated, capacity of the branch arena,
+ * its fill in the last call, 1 if the last forward queued its branch on the engine's own stream (0: on the caller's)}. */
+int roitr_engine_scratch_info(void* engine, long* out5);
 /* Test taps: after stage `name` its output tensor is copied to `device_ptr` (NULL removes the tap);
  * inject: the stage output is REPLACED by the tensor at device_ptr before the forward continues. */
 int roitr_engine_set_tap(void* engine, const char* name, void* device_ptr);

@@ -88,7 +88,7 @@ struct GeoLayer {
 };
 
 struct Arena {
-    char* base = nullptr; size_t cap = 0, off = 0;
+    char* base = nullptr; size_t cap = 0, off = 0, peak = 0;   // peak: the largest `off` since it was last zeroed
     bool fail = false;
     template <typename T> T* get(size_t count)
     {
@@ -96,6 +96,7 @@ struct Arena {
         if (off + bytes > cap) { fail = true; return (T*)base; }
         T* p = base ? (T*)(base + off) : nullptr;   // no base: a counting arena, only `off` advances
         off += bytes;
+        if (off > peak) peak = off;
         return p;
     }
 };
@@ -123,6 +124,9 @@ struct Engine {
     float* first_consts = nullptr;   // head_consts (64) | G (64 x 32) | zero bias (64)
     Arena warena;  // derived weights
     Arena arena;   // per-forward scratch
+    // scratch of the branch (the global transformer and the coarse front of the matching phase, queued beside the decoder): a region
+    // of its own, carved once per call with no release inside the call -- the decoder reuses main-arena addresses while the branch runs
+    Arena barena;
     // sampling-ahead mode (RoitrForwardIO::inputs_ready): descriptors, FPS scratch, pick indices and the coarser levels' coordinates /
     // normals of forward s+1 are written on the geometry stream while forward s still runs on the main one, so they cannot live in
     // the (stream-ordered, single) scratch arena: two small arenas used alternately
@@ -151,11 +155,19 @@ struct Engine {
         EV_ERROR_JOIN,           // geometry: the error-path join of roitr_engine_forward
         EV_DESC_COPIED,          // geometry: descriptors copied (ahead mode)
         EV_LEVEL1_GROUPS_READY,  // geometry: level-1 groups and PPFs (ahead mode)
+        EV_ENCODER_DONE,         // main: the encoder's outputs are written (where the branch forks)
+        EV_BRANCH_DONE,          // branch: global features, coarse correspondences and patch arrays (joined in front of the score product)
+        EV_BRANCH_ERROR_JOIN,    // branch: the error-path join of roitr_engine_forward
         NEV
     };
     static Ev ev_level_done(int l) { return (Ev)(EV_LEVEL2_GEOM_DONE + l - 1); }   // l = 1 .. 3: the 0-based index of levels 2 - 4
     hipEvent_t ev[NEV] = {};
     bool side_forked = false;        // the current forward has issued work on `side` that `st` has not joined yet
+    hipStream_t branch = nullptr;    // the global transformer and the coarse front, beside the decoder on the main stream
+    int phase_overlap = 1;           // roitr_engine_set_phase_overlap: 0 = the branch's launches are queued on the main stream, in front of the decoder;
+                                     // 1 = on the branch stream for calls of at least BRANCH_MIN_NODES superpoints; 2 = on the branch stream always
+    bool branch_forked = false;      // the current forward has issued work on `branch` that `st` has not joined yet
+    bool on_branch = false;          // the last forward queued its branch on the branch stream (roitr_engine_scratch_info)
     std::string err;
     hipStream_t fin_stream = nullptr;   // stream of the running finalize (weight conversions are queued on it)
     // ---- captured forwards (roitr_engine_forward_graph): one hipGraphExec per (sizes, io pointers) key
@@ -705,13 +717,13 @@ int block(Engine& E, hipStream_t st, const LocalT& L, int M, const float* x, con
     return 0;
 }
 
-int ffn_apply(Engine& E, hipStream_t st, const Ffn& F, int M, int C, const float* x, float* out)
+// scratch from `A` (the arena of the stream the launches are queued on), released on return
+int ffn_apply(Arena& A, hipStream_t st, const Ffn& F, int M, int C, const float* x, float* out)
 {
-    Arena& A = E.arena;
     const size_t mark = A.off;
     float* e = A.get<float>((size_t)M * 2 * C);
     float* s = A.get<float>((size_t)M * C);
-    if (A.fail) return ROITR_ERR_ARG;
+    if (A.fail) { roitr_set_error("arena exhausted (ffn)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
     // bf16 operand mode: the (M, 2C) hidden activation lives in bf16 between the two GEMMs
     const bool e_h = bf16_layer(F.expand.wb, C) && bf16_layer(F.squeeze.wb, 2 * C);
     CHK(gemm(st, M, x, F.expand, e, true, nullptr, nullptr, e_h ? ROITR_BF16_C : 0));
@@ -807,6 +819,8 @@ extern "C" void roitr_engine_destroy(void* h)
     if (g_engine == E) g_engine = nullptr;
     if (E->warena.base) (void)hipFree(E->warena.base);
     if (E->arena.base) (void)hipFree(E->arena.base);
+    if (E->branch) (void)hipStreamSynchronize(E->branch);
+    if (E->barena.base) (void)hipFree(E->barena.base);
     for (int i = 0; i < 2; ++i) if (E->garena[i].base) (void)hipFree(E->garena[i].base);
     for (int i = 0; i < 2; ++i) if (E->gend[i]) (void)hipEventDestroy(E->gend[i]);
     for (auto& g : E->graphs) {
@@ -817,6 +831,7 @@ extern "C" void roitr_engine_destroy(void* h)
     for (auto& kv : E->x3) (void)hipFree(kv.second);
     release_fragments(*E);
     if (E->side) (void)hipStreamDestroy(E->side);
+    if (E->branch) (void)hipStreamDestroy(E->branch);
     for (int i = 0; i < Engine::NEV; ++i) if (E->ev[i]) (void)hipEventDestroy(E->ev[i]);
     for (int i = 0; i < Engine::RING; ++i) {
         if (E->pinned[i]) (void)hipHostFree(E->pinned[i]);
@@ -858,6 +873,7 @@ extern "C" int roitr_engine_finalize(void* h, hipStream_t st)
         if (g.pin) (void)hipHostFree(g.pin);
     }
     E.graphs.clear();
+    if (E.branch) ROITR_HIP(hipStreamSynchronize(E.branch));   // a forward's branch may still read the weights this call replaces
     if (!E.x3.empty()) {   // split copies of the previous weights: a forward may still read them
         ROITR_HIP(hipStreamSynchronize(st));
         if (E.side) ROITR_HIP(hipStreamSynchronize(E.side));
@@ -1068,6 +1084,14 @@ extern "C" int roitr_engine_geo_table_info(void* h, double* info)
 // scripts/bench_knn_shapes.py: 5.6 -> 6.0 - 6.6 ms for the calls of a 512-pair forward): 6 stays.
 static constexpr float GRID_OCC = 6.0f;
 
+// Calls with fewer superpoints (rows of the global transformer) keep the branch's launches on the main stream, in the single-stream order
+// (global transformer, decoder, coarse front).  Measured (profiles/phase_overlap_ab.txt): with the third stream one 5 000-point pair per call
+// (156 rows), two calls in flight, was slower, 1.84 -> 1.91 ms per pair; calls of 9 984 (64 pairs), 16 000 (config 4) and 79 872 rows (config 2)
+// were faster.  Nothing was measured between 156 and 9 984 rows: 8192 is a choice inside that gap, not a measured break-even.  The cause at
+// one pair was not traced (expected: the geometry stream runs the NEXT call's whole chain beside this call, and a third stream competes with it).
+// Every kernel's rows are independent of the row count, so the choice changes no result.
+static constexpr int BRANCH_MIN_NODES = 8192;
+
 // calls of up to this many pairs run their whole geometry chain ahead of the previous call (RoitrForwardIO::inputs_ready, reserve_arenas)
 static constexpr int AHEAD_MAX_PAIRS = 128;
 
@@ -1076,8 +1100,13 @@ static int forward_body(Engine& E, const RoitrForwardIO* io, hipStream_t st);
 // forward_body with the side stream joined on the error path
 static int forward_joined(Engine& E, const RoitrForwardIO* io, hipStream_t st)
 {
-    E.side_forked = false; E.cur_par = -1; E.garena_short = false;
+    E.side_forked = false; E.branch_forked = false; E.cur_par = -1; E.garena_short = false;
     const int rc = forward_body(E, io, st);
+    // (the branch first: it may itself wait for events of the geometry stream)
+    if (rc != ROITR_OK && E.branch_forked && E.branch && E.ev[Engine::EV_BRANCH_ERROR_JOIN]) {
+        if (hipEventRecord(E.ev[Engine::EV_BRANCH_ERROR_JOIN], E.branch) == hipSuccess) (void)hipStreamWaitEvent(st, E.ev[Engine::EV_BRANCH_ERROR_JOIN], 0);
+        else (void)hipStreamSynchronize(E.branch);
+    }
     if (rc != ROITR_OK && E.side_forked && E.side && E.ev[Engine::EV_ERROR_JOIN]) {
         if (hipEventRecord(E.ev[Engine::EV_ERROR_JOIN], E.side) == hipSuccess) (void)hipStreamWaitEvent(st, E.ev[Engine::EV_ERROR_JOIN], 0);
         else (void)hipStreamSynchronize(E.side);
@@ -1087,8 +1116,8 @@ static int forward_joined(Engine& E, const RoitrForwardIO* io, hipStream_t st)
 
 /* One engine = one main stream at a time: the side stream and its events are per engine, so two forwards of the same engine must
  * be ordered on the caller's stream (the Python side guarantees it: launch_batch uses torch's current stream).  An early return
- * between the fork and the last join (arena exhausted, unsupported shape, a HIP error) would leave side-stream work un-joined --
- * racing with the next forward's arena reuse, or ending a graph capture with an unjoined stream: forward_joined joins it. */
+ * between a fork and the last join (arena exhausted, unsupported shape, a HIP error) would leave side- or branch-stream work un-joined --
+ * racing with the next forward's arena reuse, or ending a graph capture with an unjoined stream: forward_joined joins both. */
 extern "C" int roitr_engine_forward(void* h, const RoitrForwardIO* io, hipStream_t st)
 {
     Engine& E = *(Engine*)h;
@@ -1101,10 +1130,11 @@ extern "C" int roitr_engine_forward(void* h, const RoitrForwardIO* io, hipStream
         fprintf(stderr, "roitr: alternating geometry arena too small for this call (%s): falling back to main-stream order\n", roitr_last_error());
         (void)hipStreamSynchronize(st);
         if (E.side) (void)hipStreamSynchronize(E.side);
+        if (E.branch) (void)hipStreamSynchronize(E.branch);
         E.ahead_off = true;
         rc = forward_joined(E, io, st);
     }
-    E.side_forked = false;
+    E.side_forked = false; E.branch_forked = false;
     if (E.cur_par >= 0 && E.gend[E.cur_par]) {   // the alternating arena is free again where this call ends on the main stream
         if (hipEventRecord(E.gend[E.cur_par], st) == hipSuccess) E.gend_rec[E.cur_par] = true;
         else { (void)hipStreamSynchronize(st); E.gend_rec[E.cur_par] = false; }
@@ -1130,6 +1160,7 @@ struct Plan {
     bool gt = false, gt_corr = false;         // ground-truth side outputs (RIGA_v2.py:91-116), only when rot / trans are given; node correspondences
     int Tp = 0, Tsp = 0, Ttp = 0;             // their padded rows: all, source, target
     hipStream_t st = nullptr, sd = nullptr;   // main stream, geometry stream
+    hipStream_t sb = nullptr;                 // the stream of the branch: the engine's third stream, or `st` with the phase overlap off
 };
 
 // Everything the geometry chain reads and writes.  carve_geometry takes every buffer; issue_geometry_chain fills them on the
@@ -1156,6 +1187,51 @@ struct GeoBufs {
 
 // what the feature path hands from stage to stage (main arena): encoder output per level, global transformer output, decoder output per level
 struct Feats { float* xe[4]; float* gfeat; float* xd[4]; };
+
+// Everything the branch (global_transformer, then coarse_front) writes: all of it in the branch arena, taken once per call by
+// carve_branch -- what the matching tail reads behind the join (correspondences, patch rows / masks / points) therefore lives as
+// long as the call.  The caller's own output buffers are used where given.
+struct BranchBufs {
+    float *gfeat, *fcur, *pos, *qkv, *qt, *ebar, *hid, *t1, *t2;   // global transformer
+    float *node_feats, *cp, *cscratch, *cxy; long cstride, xystride;   // coarse head and matching
+    int *tgt_corr, *src_corr, *n_corr, *pair_off; float* cscore;
+    int *trows, *srows, *tmask, *smask; float *tpts, *spts;            // patch arrays
+};
+
+// Run against a counting arena this is also what sizes the branch arena (its `peak`), so the two cannot differ.
+void carve_branch(const RoitrForwardIO* io, const Plan& P, Arena& A, BranchBufs& R)
+{
+    const size_t T4 = P.T4, C4 = P.C4, B = P.B, LIM = P.LIM, P_ = P.P_, NP = P.NPs, n4 = P.V.nmax[3];
+    R.gfeat = A.get<float>(T4 * C4);
+    R.fcur = A.get<float>(T4 * C4);
+    R.pos = A.get<float>(T4 * C4);
+    R.qkv = A.get<float>(T4 * 3 * C4);
+    R.qt = A.get<float>(T4 * HEADS * C4);
+    R.ebar = A.get<float>(T4 * HEADS * C4);
+    R.hid = A.get<float>(T4 * C4);
+    R.t1 = A.get<float>(T4 * C4);
+    R.t2 = A.get<float>(T4 * C4);
+    R.node_feats = io->node_feats ? io->node_feats : A.get<float>(T4 * C4);
+    R.cp = A.get<float>(T4 * C4);
+    R.tgt_corr = io->tgt_corr ? io->tgt_corr : A.get<int>(B * P_);
+    R.src_corr = io->src_corr ? io->src_corr : A.get<int>(B * P_);
+    R.cscore = io->corr_scores ? io->corr_scores : A.get<float>(B * P_);
+    R.n_corr = io->n_corr ? io->n_corr : A.get<int>(B);
+    R.pair_off = P.compact ? (io->patch_offsets ? io->patch_offsets : A.get<int>(B + 1)) : nullptr;
+    R.trows = A.get<int>(NP * LIM); R.srows = A.get<int>(NP * LIM);
+    R.tmask = io->tgt_knn_masks ? io->tgt_knn_masks : A.get<int>(NP * LIM);
+    R.smask = io->src_knn_masks ? io->src_knn_masks : A.get<int>(NP * LIM);
+    R.tpts = io->tgt_knn_pts ? io->tgt_knn_pts : A.get<float>(NP * LIM * 3);
+    R.spts = io->src_knn_pts ? io->src_knn_pts : A.get<float>(NP * LIM * 3);
+    R.cstride = (long)roitr_coarse_scratch_floats((int)n4, (int)n4);
+    R.cscratch = A.get<float>(B * (size_t)R.cstride);
+    R.xystride = (long)(n4 * n4);
+    R.cxy = A.get<float>(B * (size_t)R.xystride);
+    // the hidden pair of ffn_apply over all T4 rows: the only scratch the branch takes and releases inside the call
+    const size_t mark = A.off;
+    (void)A.get<float>(T4 * 2 * C4); (void)A.get<float>(T4 * C4);
+    A.off = mark;
+}
 
 // ---- stage 1: level sizes (host), patch slots, limits
 int plan_sizes(const Engine& E, const RoitrForwardIO* io, Plan& P)
@@ -1273,18 +1349,19 @@ int reserve_arenas(Engine& E, const RoitrForwardIO* io, Plan& P)
     const Levels& V = P.V; hipStream_t st = P.st;
     const int B = P.B, NC = P.NC, T1 = P.T1, T4 = P.T4, C4 = P.C4, LIM = P.LIM, f = E.cfg.factor;
     {
-        size_t need = (size_t)T1 * 4 * (64 * f * 14 + 256 * f * 2 + 600) + (size_t)P.etot * (C4 * 4 + 64) /* E once + its index arrays */ + (size_t)T4 * C4 * 4 * 40 +
-                      P.NPs * (LIM * LIM * 3 + (LIM + 1) * (LIM + 1) + LIM * 16) * 4 + (size_t)B * P.P_ * 16 + ((size_t)64 << 20);
+        size_t need = (size_t)T1 * 4 * (64 * f * 14 + 256 * f * 2 + 600) + (size_t)P.etot * (C4 * 4 + 64) /* E once + its index arrays */ + (size_t)T4 * C4 * 4 * 18 +
+                      P.NPs * (LIM * LIM * 3 + (LIM + 1) * (LIM + 1) + LIM * 6) * 4 + ((size_t)64 << 20);
+        // (the global transformer's 20 (T4, C4) tensors, the coarse head's two, the coarse scratch, the correspondence and the patch row / mask /
+        // point arrays are not in this bound: they live in the branch arena, sized below by counting)
         if (E.cfg.operand_dtype == 1) need += (size_t)T1 * C4 * 2 + 1024;   // bf16 copy of the point descriptors (patch scores)
         for (int l = 0; l < 4; ++l) need += roitr_knn_workspace_bytes(NC, V.T[l], T1) + 1024;
-        need += (size_t)B * (roitr_coarse_scratch_floats(V.nmax[3], V.nmax[3]) + (size_t)2 * V.nmax[3] * V.nmax[3]) * 4 + 1024;
         need += 2 * roitr_knn_workspace_bytes(B, T1 + NC, T1 + NC) + (size_t)(T1 + NC) * 16 + 4096;
         if (need > E.arena.cap) {
             ROITR_HIP(hipStreamSynchronize(st));
             if (E.arena.base) ROITR_HIP(hipFree(E.arena.base));
             E.arena.base = nullptr; E.arena.cap = 0;
             ROITR_HIP(hipMalloc((void**)&E.arena.base, need));
-            E.arena.cap = need;
+            E.arena.cap = need; E.arena.peak = 0;
             E.arena_epoch++;
         }
         E.arena.off = 0; E.arena.fail = false;
@@ -1295,9 +1372,26 @@ int reserve_arenas(Engine& E, const RoitrForwardIO* io, Plan& P)
         // with the main stream off the null stream so that the masked -- "blocking" -- stream does not serialise with it: 3 927 /
         // 5 768 / 6 004 / 5 969 / 5 949 pairs/s against 5 905 - 6 005 unmasked.  Confinement buys nothing: DESIGN.md section 4.)
         ROITR_HIP(hipStreamCreateWithFlags(&E.side, hipStreamNonBlocking));
+        ROITR_HIP(hipStreamCreateWithFlags(&E.branch, hipStreamNonBlocking));
         for (int i = 0; i < Engine::NEV; ++i) ROITR_HIP(hipEventCreateWithFlags(&E.ev[i], hipEventDisableTiming));
     }
     hipStream_t sd = P.sd = E.side;
+    P.sb = (E.phase_overlap == 2 || (E.phase_overlap == 1 && T4 >= BRANCH_MIN_NODES)) ? E.branch : st;
+    {   // the branch arena: exactly what carve_branch takes (counted the same way as the alternating arenas below)
+        Arena cnt; cnt.cap = ~(size_t)0;
+        BranchBufs unused;
+        carve_branch(io, P, cnt, unused);
+        if (cnt.peak > E.barena.cap) {
+            ROITR_HIP(hipStreamSynchronize(st));
+            ROITR_HIP(hipStreamSynchronize(E.branch));
+            if (E.barena.base) ROITR_HIP(hipFree(E.barena.base));
+            E.barena.base = nullptr; E.barena.cap = 0;
+            ROITR_HIP(hipMalloc((void**)&E.barena.base, cnt.peak));
+            E.barena.cap = cnt.peak;
+            E.arena_epoch++;
+        }
+        E.barena.off = 0; E.barena.peak = 0; E.barena.fail = false;
+    }
 
     // ---------------- sampling ahead of the previous forward's tail (io->inputs_ready, include/roitr_engine.h).  `st` is in order,
     // so everything queued on it for this forward starts after the previous forward has left it -- but the first sampling level
@@ -1587,26 +1681,19 @@ int encoder(Engine& E, const RoitrForwardIO* io, const Plan& P, const GeoBufs& S
 }
 
 // ---- stage 7: the global geometric transformer (geotransformer.py:94-133), all pairs batched
-int global_transformer(Engine& E, const Plan& P, const GeoBufs& S, Feats& F)
+// Queued on the branch's stream (P.sb), in the branch's buffers: it reads the encoder's last level and E, and only the coarse head reads
+// its output, so it runs beside the decoder.
+int global_transformer(Engine& E, const Plan& P, const GeoBufs& S, Feats& F, const BranchBufs& R)
 {
-    const Levels& V = P.V; const Desc& D = S.D; hipStream_t st = P.st; Arena& A = E.arena;
+    const Levels& V = P.V; const Desc& D = S.D; hipStream_t st = P.sb; Arena& A = E.barena;
     const int B = P.B, T4 = P.T4, C4 = P.C4; const long etot = P.etot; const bool e_h = P.e_h;
-    float* gfeat = F.gfeat = A.get<float>((size_t)T4 * C4);
-    const size_t mark = A.off;
+    float* gfeat = F.gfeat = R.gfeat;
     ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_EMBED_DONE], 0));   // E and its index arrays were written on the side stream
     CHK(tap(E, st, "geo.d_idx", S.d_idx, sizeof(float) * etot));
     CHK(tap(E, st, "geo.a_idx", S.a_idx, sizeof(float) * etot * 3));
     CHK(tap(E, st, "geo.emb", S.Emb, (e_h ? sizeof(unsigned short) : sizeof(float)) * (size_t)etot * C4));   // bf16 mode: the tap holds bf16
 
-    float* fcur = A.get<float>((size_t)T4 * C4);
-    float* pos = A.get<float>((size_t)T4 * C4);
-    float* qkv = A.get<float>((size_t)T4 * 3 * C4);
-    float* qt = A.get<float>((size_t)T4 * HEADS * C4);
-    float* ebar = A.get<float>((size_t)T4 * HEADS * C4);
-    float* hid = A.get<float>((size_t)T4 * C4);
-    float* t1 = A.get<float>((size_t)T4 * C4);
-    float* t2 = A.get<float>((size_t)T4 * C4);
-    if (A.fail) { roitr_set_error("arena exhausted (geo)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
+    float *fcur = R.fcur, *pos = R.pos, *qkv = R.qkv, *qt = R.qt, *ebar = R.ebar, *hid = R.hid, *t1 = R.t1, *t2 = R.t2;
     CHK(gemm(st, T4, F.xe[3], E.geo_in, fcur));
     CHK(tap(E, st, "geo.in_proj", fcur, sizeof(float) * (size_t)T4 * C4));
     const int cpe = C4 / HEADS;
@@ -1641,9 +1728,9 @@ int global_transformer(Engine& E, const Plan& P, const GeoBufs& S, Feats& F)
             // RPEAttentionLayer tail (geoattention.py:236-244) + AttentionOutput x2 (l.278-280)
             // (in place is safe for the fused form: a block reads and writes only its own 64 rows)
             CHK(gemm_ln(st, T4, hid, L.lin, fcur, nullptr, L.n_w, L.n_b, nullptr, false, t1, hid));
-            CHK(ffn_apply(E, st, L.out, T4, C4, hid, fcur));
+            CHK(ffn_apply(A, st, L.out, T4, C4, hid, fcur));
             CHK(gemm_ln(st, T4, t2, L.pos_lin, nullptr, nullptr, L.pn_w, L.pn_b, nullptr, false, t1, t2));
-            CHK(ffn_apply(E, st, L.pos, T4, C4, t2, pos));
+            CHK(ffn_apply(A, st, L.pos, T4, C4, t2, pos));
             CHK(tap(E, st, "geo.layer" + std::to_string(li) + ".pos", pos, sizeof(float) * (size_t)T4 * C4));
         } else {
             // geotransformer.py:45-46: feats0 (src) attends feats1 (tgt), then feats1 attends the UPDATED feats0
@@ -1666,14 +1753,13 @@ int global_transformer(Engine& E, const Plan& P, const GeoBufs& S, Feats& F)
                 CHK(roitr_mha(&m, st));
                 CHK(gemm_ln(st, qn, hid + (size_t)q0 * C4, L.lin, fcur + (size_t)q0 * C4, nullptr, L.n_w, L.n_b, nullptr, false,
                             t1 + (size_t)q0 * C4, t2 + (size_t)q0 * C4));
-                CHK(ffn_apply(E, st, L.out, qn, C4, t2 + (size_t)q0 * C4, fcur + (size_t)q0 * C4));
+                CHK(ffn_apply(A, st, L.out, qn, C4, t2 + (size_t)q0 * C4, fcur + (size_t)q0 * C4));
             }
         }
         CHK(tap(E, st, "geo.layer" + std::to_string(li), fcur, sizeof(float) * (size_t)T4 * C4));
     }
     CHK(gemm(st, T4, fcur, E.geo_out, gfeat));
     CHK(tap(E, st, "geo.out", gfeat, sizeof(float) * (size_t)T4 * C4));
-    A.off = mark;
     return 0;
 }
 
@@ -1732,35 +1818,64 @@ int decoder(Engine& E, const Plan& P, const GeoBufs& S, Feats& F)
     return 0;
 }
 
-// ---- stage 9: heads (RIGA_v2.py:64-68), coarse matching, patches, optimal transport, fine matching
-int heads_and_matching(Engine& E, const RoitrForwardIO* io, const Plan& P, const GeoBufs& S, const Feats& F)
+// ---- stage 9a: the coarse front of the matching phase (RIGA_v2.py:64-66, 118-125): coarse head, coarse matching, patch slots and patch
+// arrays.  It needs the global features and the geometry chain's tail only, so it follows the global transformer on the branch's stream.
+int coarse_front(Engine& E, const Plan& P, const GeoBufs& S, const Feats& F, const BranchBufs& R)
 {
-    const Levels& V = P.V; const Desc& D = S.D; hipStream_t st = P.st; Arena& A = E.arena;
-    const int B = P.B, T1 = P.T1, T4 = P.T4, C4 = P.C4, LIM = P.LIM, P_ = P.P_; const bool compact = P.compact;
-    ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_TAIL_DONE], 0));   // node coordinates, partition and ground-truth side outputs (side stream)
-    E.side_forked = false;                           // last join: everything the side stream was given is ordered before `st` from here
-    float* node_feats = io->node_feats ? io->node_feats : A.get<float>((size_t)T4 * C4);
-    float* point_feats = io->point_feats ? io->point_feats : A.get<float>((size_t)T1 * C4);
-    {
-        float* cp = A.get<float>((size_t)T4 * C4);
-        if (A.fail) { roitr_set_error("arena exhausted (heads)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-        CHK(gemm(st, T4, F.gfeat, E.coarse_proj, cp));
-        CHK(roitr_l2_normalize(T4, C4, cp, node_feats, st));
-        CHK(gemm(st, T1, F.xd[0], E.fine_proj, point_feats));
-    }
-
-    // ---------------- coarse matching, patches, OT, fine matching
-    int* tgt_corr = io->tgt_corr ? io->tgt_corr : A.get<int>((size_t)B * P_);
-    int* src_corr = io->src_corr ? io->src_corr : A.get<int>((size_t)B * P_);
-    float* cscore = io->corr_scores ? io->corr_scores : A.get<float>((size_t)B * P_);
-    int* n_corr = io->n_corr ? io->n_corr : A.get<int>(B);
+    const Levels& V = P.V; const Desc& D = S.D; hipStream_t st = P.sb;
+    const int B = P.B, T4 = P.T4, C4 = P.C4, LIM = P.LIM, P_ = P.P_; const bool compact = P.compact;
     const size_t NP = P.NPs;
-    int* pair_off = compact ? (io->patch_offsets ? io->patch_offsets : A.get<int>((size_t)B + 1)) : nullptr;
-    int* trows = A.get<int>(NP * LIM); int* srows = A.get<int>(NP * LIM);
-    int* tmask = io->tgt_knn_masks ? io->tgt_knn_masks : A.get<int>(NP * LIM);
-    int* smask = io->src_knn_masks ? io->src_knn_masks : A.get<int>(NP * LIM);
-    float* tpts = io->tgt_knn_pts ? io->tgt_knn_pts : A.get<float>(NP * LIM * 3);
-    float* spts = io->src_knn_pts ? io->src_knn_pts : A.get<float>(NP * LIM * 3);
+    ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_TAIL_DONE], 0));   // node masks, partition and ground-truth side outputs (side stream)
+    CHK(gemm(st, T4, F.gfeat, E.coarse_proj, R.cp));
+    CHK(roitr_l2_normalize(T4, C4, R.cp, R.node_feats, st));
+    {   // all tgt_b x src_b feature dot products in one ragged-batched GEMM (rows: tgt cloud B+b, cols: src cloud b)
+        RoitrGemm g; memset(&g, 0, sizeof(g));
+        g.M = V.nmax[3]; g.N = V.nmax[3]; g.K = C4; g.A = R.node_feats; g.lda = C4; g.W = R.node_feats; g.ldw = C4; g.alpha = 1.f;
+        g.C = R.cxy; g.ldc = V.nmax[3]; g.batch = B; g.sC = R.xystride; g.seg_off = D.off[3]; g.seg_a0 = B; g.seg_w0 = 0;
+        CHK(roitr_gemm(&g, st));
+    }
+    {
+        RoitrCoarse c; memset(&c, 0, sizeof(c));
+        c.pairs = B; c.C = C4; c.num_corr = P_; c.dual_norm = 1; c.max_ref = V.nmax[3]; c.max_src = V.nmax[3];
+        c.feats = R.node_feats; c.node_offset = D.off[3]; c.node_masks = S.node_masks; c.scratch = R.cscratch; c.scratch_stride = R.cstride;
+        c.tgt_corr = R.tgt_corr; c.src_corr = R.src_corr; c.corr_scores = R.cscore; c.n_corr = R.n_corr;
+        c.xy = R.cxy; c.xy_stride = R.xystride; c.xy_ld = V.nmax[3];
+        if (E.cfg.adaptive_coarse) CHK(roitr_adaptive_matching(&c, E.cfg.num_corr, 0.75f, st));
+        else CHK(roitr_coarse_matching(&c, st));
+    }
+    // the tail runs on the selected patches only (RIGA_v2.py:126-152): their slots, pair after pair
+    if (compact) CHK(roitr_patch_offsets(B, R.n_corr, (int)NP, R.pair_off, st));
+    {
+        RoitrPatch pg; memset(&pg, 0, sizeof(pg));
+        pg.pairs = B; pg.num_corr = P_; pg.limit = LIM; pg.n_corr = R.n_corr; pg.tgt_corr = R.tgt_corr; pg.src_corr = R.src_corr;
+        pg.node_offset = D.off[3]; pg.pt_offset = D.off[0]; pg.knn_idx = S.kidx; pg.knn_mask = S.kmask; pg.points = S.pts_out;
+        pg.tgt_rows = R.trows; pg.src_rows = R.srows; pg.tgt_masks = R.tmask; pg.src_masks = R.smask; pg.tgt_pts = R.tpts; pg.src_pts = R.spts;
+        pg.pair_off = R.pair_off; pg.slots = compact ? (int)NP : 0;
+        CHK(roitr_patch_gather(&pg, st));
+    }
+    return 0;
+}
+
+// ---- stage 9b: the fine head (RIGA_v2.py:67-68) behind the decoder, then -- behind the branch -- patch scores, optimal transport, fine matching
+int heads_and_matching(Engine& E, const RoitrForwardIO* io, const Plan& P, const Feats& F, const BranchBufs& R)
+{
+    hipStream_t st = P.st; Arena& A = E.arena;
+    const int B = P.B, T1 = P.T1, C4 = P.C4, LIM = P.LIM, P_ = P.P_; const bool compact = P.compact;
+    float* point_feats = io->point_feats ? io->point_feats : A.get<float>((size_t)T1 * C4);
+    if (A.fail) { roitr_set_error("arena exhausted (heads)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
+    CHK(gemm(st, T1, F.xd[0], E.fine_proj, point_feats));
+    // the last join: the branch, and the geometry chain's tail (the branch waited for it; the main stream waits for it as well, so
+    // that a capture sees every stream joined by the stream it began on)
+    if (P.sb != st) {
+        ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_BRANCH_DONE], 0));
+        ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_TAIL_DONE], 0));
+    }
+    // everything the other two streams were given is ordered before `st` from here (on one stream coarse_front, queued just in front of this
+    // function, took the EV_TAIL_DONE wait on `st`)
+    E.side_forked = false; E.branch_forked = false;
+    const int* n_corr = R.n_corr; const int* pair_off = R.pair_off; const float* cscore = R.cscore;
+    const int *trows = R.trows, *srows = R.srows, *tmask = R.tmask, *smask = R.smask; const float *tpts = R.tpts, *spts = R.spts;
+    const size_t NP = P.NPs;
     float* mscore = A.get<float>(NP * LIM * LIM);
     float* ot = io->matching_scores ? io->matching_scores : A.get<float>(NP * (LIM + 1) * (LIM + 1));
     unsigned char* flags = A.get<unsigned char>(NP * LIM * LIM);
@@ -1771,38 +1886,8 @@ int heads_and_matching(Engine& E, const RoitrForwardIO* io, const Plan& P, const
     float* o_t = io->out_tgt_pts ? io->out_tgt_pts : A.get<float>(cap * 3);
     float* o_s = io->out_src_pts ? io->out_src_pts : A.get<float>(cap * 3);
     float* o_sc = io->out_scores ? io->out_scores : A.get<float>(cap);
-    const long cstride = (long)roitr_coarse_scratch_floats(V.nmax[3], V.nmax[3]);
-    float* cscratch = A.get<float>((size_t)B * cstride);
-    const long xystride = (long)V.nmax[3] * V.nmax[3];
-    float* cxy = A.get<float>((size_t)B * xystride);
     if (A.fail) { roitr_set_error("arena exhausted (matching)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-
-    {   // all tgt_b x src_b feature dot products in one ragged-batched GEMM (rows: tgt cloud B+b, cols: src cloud b)
-        RoitrGemm g; memset(&g, 0, sizeof(g));
-        g.M = V.nmax[3]; g.N = V.nmax[3]; g.K = C4; g.A = node_feats; g.lda = C4; g.W = node_feats; g.ldw = C4; g.alpha = 1.f;
-        g.C = cxy; g.ldc = V.nmax[3]; g.batch = B; g.sC = xystride; g.seg_off = D.off[3]; g.seg_a0 = B; g.seg_w0 = 0;
-        CHK(roitr_gemm(&g, st));
-    }
-    {
-        RoitrCoarse c; memset(&c, 0, sizeof(c));
-        c.pairs = B; c.C = C4; c.num_corr = P_; c.dual_norm = 1; c.max_ref = V.nmax[3]; c.max_src = V.nmax[3];
-        c.feats = node_feats; c.node_offset = D.off[3]; c.node_masks = S.node_masks; c.scratch = cscratch; c.scratch_stride = cstride;
-        c.tgt_corr = tgt_corr; c.src_corr = src_corr; c.corr_scores = cscore; c.n_corr = n_corr;
-        c.xy = cxy; c.xy_stride = xystride; c.xy_ld = V.nmax[3];
-        if (E.cfg.adaptive_coarse) CHK(roitr_adaptive_matching(&c, E.cfg.num_corr, 0.75f, st));
-        else CHK(roitr_coarse_matching(&c, st));
-    }
-    // the tail runs on the selected patches only (RIGA_v2.py:126-152): their slots, pair after pair
-    if (compact) CHK(roitr_patch_offsets(B, n_corr, (int)NP, pair_off, st));
     const int* live_patches = compact ? pair_off + B : nullptr;
-    {
-        RoitrPatch pg; memset(&pg, 0, sizeof(pg));
-        pg.pairs = B; pg.num_corr = P_; pg.limit = LIM; pg.n_corr = n_corr; pg.tgt_corr = tgt_corr; pg.src_corr = src_corr;
-        pg.node_offset = D.off[3]; pg.pt_offset = D.off[0]; pg.knn_idx = S.kidx; pg.knn_mask = S.kmask; pg.points = S.pts_out;
-        pg.tgt_rows = trows; pg.src_rows = srows; pg.tgt_masks = tmask; pg.src_masks = smask; pg.tgt_pts = tpts; pg.src_pts = spts;
-        pg.pair_off = pair_off; pg.slots = compact ? (int)NP : 0;
-        CHK(roitr_patch_gather(&pg, st));
-    }
     {   // matching_scores = einsum('bnd,bmd->bnm', tgt, src) / sqrt(C)   (RIGA_v2.py:150-152)
         RoitrGemm g; memset(&g, 0, sizeof(g));
         g.M = LIM; g.N = LIM; g.K = C4; g.A = point_feats; g.lda = C4; g.a_idx = trows; g.a_limit = T1; g.W = point_feats; g.ldw = C4;
@@ -1843,25 +1928,69 @@ int heads_and_matching(Engine& E, const RoitrForwardIO* io, const Plan& P, const
 
 // One forward = this list of stages, no host synchronisation.  The geometry chain is queued whole before the feature path, which joins
 // it stage by stage: encoder level l behind "level l geometry done", the global transformer behind the embedding, the decoder's
-// TransitionUp layers behind the 3-NN, the matching phase behind the chain's tail.
+// TransitionUp layers behind the 3-NN, the coarse front behind the chain's tail.  Behind the encoder the feature path forks once more:
+// the global transformer and the coarse front (the branch, on the engine's third stream) run beside the decoder and the fine head, and
+// the main stream joins the branch in front of the patch score product.  The host queues the branch first (the other order measures the
+// same at 512 pairs per call: DESIGN.md section 4, "Global transformer beside the decoder").
 static int forward_body(Engine& E, const RoitrForwardIO* io, hipStream_t st)
 {
     if (!E.finalized) { roitr_set_error("engine not finalized", __FILE__, __LINE__); return ROITR_ERR_ARG; }
     if (io->pairs <= 0) return 0;
-    Plan P; GeoBufs S; Feats F;
+    Plan P; GeoBufs S; Feats F; BranchBufs R;
     P.st = st;
     CHK(plan_sizes(E, io, P));
     CHK(reserve_arenas(E, io, P));
     CHK(carve_geometry_buffers(E, io, P, S));   // (host work only; in front of the staging because the descriptor block is one of the buffers)
+    carve_branch(io, P, E.barena, R);
+    if (E.barena.fail) { roitr_set_error("arena exhausted (branch)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
     CHK(stage_descriptors(E, P, S));
+    hipStream_t sb = P.sb;
     roitr_prof_begin(ROITR_PROF_PH_FORWARD, 0.0, st);
     CHK(issue_geometry_chain(E, io, P, S));
     roitr_prof_begin(ROITR_PROF_PH_ENC, 0.0, st);   CHK(encoder(E, io, P, S, F));             roitr_prof_end(ROITR_PROF_PH_ENC, st);
-    roitr_prof_begin(ROITR_PROF_PH_GEO, 0.0, st);   CHK(global_transformer(E, P, S, F));      roitr_prof_end(ROITR_PROF_PH_GEO, st);
+    if (sb != st) {   // fork: the branch starts where the encoder's outputs are written
+        ROITR_HIP(hipEventRecord(E.ev[Engine::EV_ENCODER_DONE], st));
+        ROITR_HIP(hipStreamWaitEvent(sb, E.ev[Engine::EV_ENCODER_DONE], 0));
+        E.branch_forked = true;
+    }
+    const bool forked = sb != st;
+    E.on_branch = forked;
+    roitr_prof_begin(ROITR_PROF_PH_GEO, 0.0, sb);
+    CHK(global_transformer(E, P, S, F, R));
+    if (forked) CHK(coarse_front(E, P, S, F, R));
+    roitr_prof_end(ROITR_PROF_PH_GEO, sb);
+    if (forked) ROITR_HIP(hipEventRecord(E.ev[Engine::EV_BRANCH_DONE], sb));
     roitr_prof_begin(ROITR_PROF_PH_DEC, 0.0, st);   CHK(decoder(E, P, S, F));                 roitr_prof_end(ROITR_PROF_PH_DEC, st);
-    roitr_prof_begin(ROITR_PROF_PH_MATCH, 0.0, st); CHK(heads_and_matching(E, io, P, S, F));  roitr_prof_end(ROITR_PROF_PH_MATCH, st);
+    roitr_prof_begin(ROITR_PROF_PH_MATCH, 0.0, st);
+    // one stream: the single-stream order of before -- global transformer, decoder, coarse front (inside the matching phase, behind the
+    // decoder, so that the main stream meets the wait for the geometry chain's tail as late as it used to)
+    if (!forked) CHK(coarse_front(E, P, S, F, R));
+    CHK(heads_and_matching(E, io, P, F, R));
+    roitr_prof_end(ROITR_PROF_PH_MATCH, st);
     roitr_prof_end(ROITR_PROF_PH_FORWARD, st);
     return 0;
+}
+
+/* The global transformer and the coarse front beside the decoder on the branch stream (2: always; 1, the default: for calls of at least
+ * BRANCH_MIN_NODES superpoints) or on the main stream in the single-stream order (0, and small calls in mode 1): the same launches on the same
+ * buffers either way, so the results are the same bytes -- which is what modes 0 and 2 are for (tests).  Captured forwards hold the order they
+ * were captured with: a change re-captures them. */
+/* {main arena capacity, its largest fill since it was allocated, branch arena capacity, its fill in the last call, 1 if the last forward queued its
+ * branch on the branch stream} -- diagnostics (tests, the footprint figures of DESIGN.md) */
+extern "C" int roitr_engine_scratch_info(void* h, long* out5)
+{
+    Engine& E = *(Engine*)h;
+    out5[0] = (long)E.arena.cap; out5[1] = (long)E.arena.peak; out5[2] = (long)E.barena.cap; out5[3] = (long)E.barena.peak;
+    out5[4] = E.on_branch ? 1 : 0;
+    return ROITR_OK;
+}
+
+extern "C" int roitr_engine_set_phase_overlap(void* h, int on)
+{
+    Engine& E = *(Engine*)h;
+    const int mode = on == 0 ? 0 : on == 2 ? 2 : 1;
+    if (E.phase_overlap != mode) { E.phase_overlap = mode; E.arena_epoch++; }
+    return ROITR_OK;
 }
 
 

@@ -290,6 +290,20 @@ class RIGA_v2(nn.Module):
         self._injects[name] = tensor
         L.lib().roitr_engine_set_inject(self._engine, name.encode(), L.ptr(tensor))
 
+    def set_phase_overlap(self, on=1):
+        """Global transformer + coarse front on the engine's branch stream beside the decoder: 1 (default) for calls large enough for it to
+        pay, 2 for every call, 0 never (the same launches on the main stream).  The results are the same bytes in every mode."""
+        self._ensure_engine()
+        L.check(L.lib().roitr_engine_set_phase_overlap(self._engine, ctypes.c_int(int(on))), "set_phase_overlap")
+
+    def scratch_info(self):
+        """Diagnostics of the engine's scratch: capacities and fills of the main and the branch arena in bytes, and whether the last forward
+        queued its branch (global transformer + coarse front) on the engine's branch stream."""
+        self._ensure_engine()
+        out = (ctypes.c_long * 5)()
+        L.check(L.lib().roitr_engine_scratch_info(self._engine, out), "scratch_info")
+        return {"main_cap": out[0], "main_peak": out[1], "branch_cap": out[2], "branch_fill": out[3], "on_branch_stream": bool(out[4])}
+
     PROF_CLASSES = {"fps_kernel": 0, "knn_query_kernel": 1, "grid_build_kernel": 2, "knn_replay_kernel": 3, "phase.geometry": 4,
                     "phase.encoder": 5, "phase.global_transformer": 6, "phase.decoder": 7, "phase.matching": 8,
                     "phase.forward": 9, "ot_kernel": 10, "local_attn_kernel": 11, "gemm_kernel.mfma_roofed": 12, "mha_kernel": 13,
