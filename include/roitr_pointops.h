@@ -105,6 +105,32 @@ int roitr_estimate_normals(int b, int n, const float* xyz, const int* offset, in
 int roitr_normal_redirect(int n, const float* xyz, const float* normals_in, const float* view_point, float* normals_out,
                           roitr_stream_t stream);
 
+/* ------------------------------------------------------------------ raw scans: voxel grid + point cap
+ * Open3D's voxel_down_sample restated (parity with the original is unpinned, as for the normals).  Per cloud, in float64 on the fp32
+ * inputs: vmb = min_bound - voxel_size / 2, ijk = floor((p - vmb) / voxel_size); one output point per occupied voxel = the sum of its
+ * points in INPUT order / their count, rounded once to fp32.  Output order (Open3D's is a hash map's): clouds in input order, voxels
+ * ascending in (ix, iy, iz).  offset (b) cumulative int32 with offset[b-1] == n; empty clouds are legal.
+ *   out_xyz (n,3), out_count (n), out_attr (n,c): capacity buffers, the first new_offset[b-1] rows are written
+ *   new_offset (b): cumulative voxel counts;  inverse (n): output row of every input point (-1 in a cloud with a status bit)
+ *   attr (n,c) / out_attr: optional per-point channels and their per-voxel means (same summation); c = 0 or NULL: none
+ *   status (b): bit 1 = an axis needs a voxel index above 65535 (the key holds 16 bits per axis), bit 2 = a non-finite coordinate.
+ *               Such a cloud yields zero voxels; the other clouds of the call are unaffected.
+ * Host-side errors (nothing is launched): voxel_size not finite or not positive, b outside 1..65536 (16 bits of cloud id), null
+ * pointers.  ws: roitr_voxel_workspace_bytes(b, n, c).  No host synchronisation inside. */
+size_t roitr_voxel_workspace_bytes(int b, int n, int c);
+int roitr_voxel_downsample(int b, int n, const float* xyz, const int* offset, double voxel_size, int c, const float* attr,
+                           float* out_xyz, int* new_offset, int* out_count, int* inverse, float* out_attr, int* status, void* ws,
+                           roitr_stream_t stream);
+/* The point cap of dataset/tdmatch.py:72-78 (np.random.permutation(n)[:points_lim]) as a distribution: uniform without replacement.
+ * Point j (cloud-local) of a cloud with key k draws u = splitmix64(seed ^ 0xE7037ED1A0B428DB ^ splitmix64(k << 32 | j)) >> 16; a cloud
+ * with more than `limit` points keeps the `limit` points of smallest (u, j), a smaller one keeps all.  idx (capacity n): the kept GLOBAL
+ * rows, ascending (the reference keeps permutation order); new_offset (b) cumulative.  cloud_keys (b, device, optional): k per cloud,
+ * default the cloud's position in the call.  The selection depends on (seed, k, cloud size, limit) only.
+ * ws: roitr_subsample_workspace_bytes(b, n). */
+size_t roitr_subsample_workspace_bytes(int b, int n);
+int roitr_random_subsample(int b, int n, const int* offset, int limit, unsigned long long seed, const int* cloud_keys, int* idx,
+                           int* new_offset, void* ws, roitr_stream_t stream);
+
 /* kNN(1) distances for a radius test (lib/utils.py:509-521 get_node_occlusion_score): exact when < cap2, otherwise any
  * value >= cap2.  Same workspace / grid rules as roitr_knnquery_ex. */
 int roitr_knn_within(int b, int n, int m, const float* xyz, const float* new_xyz, const int* offset, const int* new_offset,

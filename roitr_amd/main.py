@@ -37,6 +37,12 @@ def main():
     ap.add_argument("--validate", action="store_true",
                     help="the reference's `val` report: mean loss, c_loss, f_loss, o_loss (lib/loss.py OverallLoss, computed on the device "
                          "by loss.py), PIR and IR over all pairs; implies --evaluate")
+    ap.add_argument("--voxel-size", type=float, default=None,
+                    help="voxel-grid downsample every cloud on the GPU first (metres; 0.025 is what the 3DMatch files went through); the "
+                         "normals are then re-estimated on the new points")
+    ap.add_argument("--points-lim", type=int, default=None,
+                    help="cap every cloud at N points, uniform without replacement, on the GPU (the reference's points_lim / max_points)")
+    ap.add_argument("--subsample-seed", type=int, default=0, help="seed of the cap's counter-based stream")
     ap.add_argument("--ransac-iterations", type=int, default=50000)
     ap.add_argument("--ransac-points", type=int, default=1000, help="correspondences drawn per pair (probability ~ confidence)")
     args = ap.parse_args()
@@ -64,7 +70,8 @@ def main():
     data = SyntheticPairs(args.synthetic, args.n_points, nonrigid=True) if args.nonrigid else SyntheticPairs(args.synthetic, args.n_points)
     tester = Tester(config, model, data, args.snapshot_dir, args.pairs_per_forward, rank, world, evaluate=args.evaluate,
                     estimate_normals=args.estimate_normals, register=args.register,
-                    ransac=dict(iterations=args.ransac_iterations, n_points=args.ransac_points), descriptor_eval=args.descriptor_eval, validate=args.validate)
+                    ransac=dict(iterations=args.ransac_iterations, n_points=args.ransac_points), descriptor_eval=args.descriptor_eval, validate=args.validate,
+                    voxel_size=args.voxel_size, points_lim=args.points_lim, subsample_seed=args.subsample_seed)
     counts = tester.test()
     if rank == 0 and tester.validation:
         v = tester.validation

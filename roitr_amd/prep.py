@@ -4,7 +4,12 @@ Mirrors the reference's dataset code: `pcd.estimate_normals(search_param=o3d.geo
 followed by `normal_redirect(points, normals, view_point)` (dataset/tdmatch.py:120-127, dataset/fdmatch.py:83-90,
 dataset/common.py:312-320).  Open3D (0.13.0, requirements.txt:64) is not part of the reference tree; its algorithm is
 restated in csrc/prep.hip.  No CPU fallback.
+
+In front of the normals, for raw scans (csrc/voxel.hip): `voxel_down_sample` (the 2.5 cm voxel grid the
+reference's 3DMatch files went through beforehand; Open3D's voxel_down_sample restated, with a DEFINED output order) and
+`random_subsample` (the `points_lim` cap of dataset/tdmatch.py:72-78 and dataset/fdmatch.py:49-56 as a distribution).
 """
+import collections
 import ctypes
 
 import torch
@@ -51,3 +56,82 @@ def normal_redirect(points, normals, view_point):
     L.check(L.lib().roitr_normal_redirect(int(points.shape[0]), L.ptr(points), L.ptr(normals), _vp(view_point), L.ptr(out), L.stream_ptr()),
             "normal_redirect")
     return out
+
+
+VoxelResult = collections.namedtuple("VoxelResult", "points offset attr inverse counts status")
+VOXEL_STATUS_RANGE, VOXEL_STATUS_NONFINITE = 1, 2
+
+
+def voxel_down_sample(xyz, offset, voxel_size, attr=None, strict=True):
+    """Voxel-grid downsampling of b concatenated clouds: xyz (n,3) fp32 device tensor, offset (b) cumulative int32.
+
+    Per cloud, in float64 on the fp32 inputs: vmb = min_bound - voxel_size / 2, ijk = floor((p - vmb) / voxel_size); one output point
+    per occupied voxel, the sum of its points in input order over their count, rounded once to fp32 (Open3D's voxel_down_sample
+    restated; parity with the original is unpinned).  Open3D leaves the output order to a hash map; here clouds keep their order and
+    the voxels of a cloud ascend in (ix, iy, iz).  Returns VoxelResult:
+      points (m,3), offset (b) cumulative int32, attr (m,c) per-voxel means of `attr` (n,c) or None, inverse (n) int32 output row of
+      every input point (Open3D's `_and_trace`), counts (m) int32 points per voxel, status (b) int32 per cloud: bit 1 = an axis needs
+      a voxel index above 65535, bit 2 = a non-finite coordinate; such a cloud yields no voxels and inverse = -1.
+    strict: raise RoitrError naming the first cloud with a status bit.  One host read (the total, to slice the capacity buffers; the
+    status words travel with it)."""
+    if not xyz.is_cuda:
+        raise L.RoitrError("roitr_amd.prep needs ROCm device tensors (no CPU fallback)")
+    xyz = xyz.contiguous().float()
+    offset = offset.to(device=xyz.device, dtype=torch.int32).contiguous()
+    n, b = int(xyz.shape[0]), int(offset.shape[0])
+    c = 0
+    if attr is not None:
+        c = int(attr[0].numel()) if n else int(torch.Size(attr.shape[1:]).numel())
+        attr = attr.to(xyz.device).contiguous().float().reshape(n, c)
+    dev = xyz.device
+    out_xyz = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    out_attr = torch.empty((n, c), dtype=torch.float32, device=dev) if attr is not None else None
+    counts = torch.empty((n,), dtype=torch.int32, device=dev)
+    inverse = torch.empty((n,), dtype=torch.int32, device=dev)
+    tail = torch.empty((2 * b,), dtype=torch.int32, device=dev)   # new_offset, status: one host read for both
+    new_offset, status = tail[:b], tail[b:]
+    lib = L.lib()
+    lib.roitr_voxel_workspace_bytes.restype = ctypes.c_size_t
+    ws = torch.empty(lib.roitr_voxel_workspace_bytes(b, n, c), dtype=torch.uint8, device=dev)
+    L.check(lib.roitr_voxel_downsample(b, n, L.ptr(xyz), L.ptr(offset), ctypes.c_double(float(voxel_size)), c, L.ptr(attr), L.ptr(out_xyz),
+                                       L.ptr(new_offset), L.ptr(counts), L.ptr(inverse), L.ptr(out_attr), L.ptr(status), L.ptr(ws),
+                                       L.stream_ptr()), "voxel_down_sample")
+    host = tail.cpu()
+    if strict and bool(host[b:].any()):
+        k = int(torch.nonzero(host[b:])[0])
+        what = [w for bit, w in ((VOXEL_STATUS_RANGE, "an axis needs a voxel index above 65535 (voxel_size too small for its extent)"),
+                                 (VOXEL_STATUS_NONFINITE, "a non-finite coordinate")) if int(host[b + k]) & bit]
+        raise L.RoitrError(f"voxel_down_sample: cloud {k}: " + " and ".join(what))
+    m = int(host[b - 1])
+    return VoxelResult(out_xyz[:m], new_offset, out_attr[:m] if out_attr is not None else None, inverse, counts[:m], status)
+
+
+def random_subsample(offset, limit, seed=0, cloud_keys=None):
+    """The point cap: offset (b) cumulative int32 device tensor -> (idx, new_offset).
+
+    A cloud with more than `limit` points keeps `limit` of them, uniform without replacement: point j of a cloud with key k draws
+    u = splitmix64(seed ^ DOMAIN ^ splitmix64(k << 32 | j)) >> 16 and the points of smallest (u, j) stay; a smaller cloud keeps all.
+    idx: the kept GLOBAL rows (int32), ascending -- the reference's np.random.permutation(n)[:points_lim] keeps permutation order and
+    its stream cannot be reproduced on a device; the distribution of the kept set is the same.  cloud_keys (b ints): k per cloud
+    (default: the cloud's position); the selection depends on (seed, k, cloud size, limit) only, not on the rest of the call."""
+    if not offset.is_cuda:
+        raise L.RoitrError("roitr_amd.prep needs ROCm device tensors (no CPU fallback)")
+    offset = offset.to(torch.int32).contiguous()
+    dev = offset.device
+    b = int(offset.shape[0])
+    keys = None
+    if cloud_keys is not None:
+        keys = torch.as_tensor(cloud_keys).to(device=dev, dtype=torch.int32).contiguous()
+        if int(keys.shape[0]) != b:
+            raise L.RoitrError("random_subsample: one cloud key per cloud")
+    host = offset.cpu()
+    n = int(host[-1]) if b else 0
+    idx = torch.empty((n,), dtype=torch.int32, device=dev)
+    new_offset = torch.empty((b,), dtype=torch.int32, device=dev)
+    lib = L.lib()
+    lib.roitr_subsample_workspace_bytes.restype = ctypes.c_size_t
+    ws = torch.empty(lib.roitr_subsample_workspace_bytes(b, n), dtype=torch.uint8, device=dev)
+    L.check(lib.roitr_random_subsample(b, n, L.ptr(offset), int(limit), ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), L.ptr(keys),
+                                       L.ptr(idx), L.ptr(new_offset), L.ptr(ws), L.stream_ptr()), "random_subsample")
+    sizes = torch.diff(host, prepend=host.new_zeros(1)).clamp(max=int(limit))   # the total follows from the sizes: no second read
+    return idx[:int(sizes.sum())], new_offset

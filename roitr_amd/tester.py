@@ -33,7 +33,7 @@ def load_pretrain(model, path):
 class Tester:
     def __init__(self, config, model, dataset, snapshot_dir="snapshot", pairs_per_forward=8, rank=0, world=1, evaluate=False,
                  estimate_normals=False, view_point=(0.0, 0.0, 0.0), register=False, ransac=None, nonrigid=None, descriptor_eval=False,
-                 validate=False):
+                 validate=False, voxel_size=None, points_lim=None, subsample_seed=0):
         """evaluate: also compute PIR / IR per pair on the device (lib/loss.py:169-213 Evaluator) and return their means.
         estimate_normals: ignore the dataset's normals and recompute them on the GPU from the points the way the
         reference's dataset code does (open3d estimate_normals(knn=33) + normal_redirect, dataset/tdmatch.py:120-127).
@@ -56,11 +56,16 @@ class Tester:
         `self.losses` maps this rank's pair ids to (loss, c_loss, f_loss, o_loss), and on rank 0 `self.validation` holds the means of
         loss, c_loss, f_loss, o_loss, PIR and IR over the pairs of ALL ranks (one all_gather_object) plus `skipped`: the reference's
         AverageMeter turns a whole mean into nan on one nan pair (a pair without fine labels, or without a row and a column that
-        have both a positive and a negative); here such pairs are left out of that key's mean and counted per key."""
+        have both a positive and a negative); here such pairs are left out of that key's mean and counted per key.
+        voxel_size / points_lim / subsample_seed: raw scans in front of the model, on the device (prep.voxel_down_sample,
+        prep.random_subsample; see _prepare).  With either one set the normals are always re-estimated on the new points (the dataset's
+        normals no longer belong to them) and the features are rebuilt as ones."""
         self.config, self.model, self.dataset = config, model, dataset
         self.snapshot_dir = snapshot_dir
         self.pairs_per_forward = pairs_per_forward
         self.rank, self.world = rank, world
+        self.voxel_size, self.points_lim, self.subsample_seed = voxel_size, points_lim, subsample_seed
+        estimate_normals = estimate_normals or voxel_size is not None or points_lim is not None
         self.evaluate, self.estimate_normals, self.view_point = evaluate or validate, estimate_normals, view_point
         self.register, self.ransac = register, dict(ransac or {})
         self.registration = {} if register and self.evaluate else None
@@ -78,6 +83,57 @@ class Tester:
             out[k] = v.to(device) if torch.is_tensor(v) else v
         return out
 
+    def _prepare(self, ids, items, device):
+        """The reference's preparation of a raw scan, for all clouds of one forward: the voxel grid its 3DMatch files went through
+        beforehand (one batched call for the source clouds, on `raw_src_pcd` with `src_points` as the attribute -- the identity for
+        rigid items, the deformed cloud of 4DMatch as the per-voxel mean of the deformed points -- and one for the targets), then the
+        `points_lim` cap of dataset/tdmatch.py:72-78 / dataset/fdmatch.py:49-56 (one batched call; cloud keys 2 * GLOBAL pair id and
+        2 * id + 1, so the kept rows do not depend on sharding or pairs_per_forward; kept rows stay in input order where the reference
+        keeps permutation order).  `metric_index` becomes unique(inverse[metric_index]) under the grid and the kept ones of its rows,
+        renumbered, under the cap (the reference leaves it pointing into the uncapped cloud)."""
+        from .prep import random_subsample, voxel_down_sample
+        k = len(items)
+
+        def offsets(clouds):
+            return torch.tensor([c.shape[0] for c in clouds]).cumsum(0).to(device=device, dtype=torch.int32)
+
+        raw = [it["raw_src_pcd"].float() for it in items]
+        deformed = [it["src_points"].float() for it in items]
+        tgt = [it["tgt_points"].float() for it in items]
+        metric = [it["metric_index"].to(device).long() if torch.is_tensor(it.get("metric_index")) else None for it in items]
+        if self.voxel_size is not None:
+            off_in = offsets(raw)
+            rs = voxel_down_sample(torch.cat(raw), off_in, self.voxel_size, attr=torch.cat(deformed))
+            rt = voxel_down_sample(torch.cat(tgt), offsets(tgt), self.voxel_size)
+            lo_in, lo_s, lo_t = [0] + off_in.tolist(), [0] + rs.offset.tolist(), [0] + rt.offset.tolist()
+            for j in range(k):
+                if metric[j] is not None:
+                    metric[j] = torch.unique(rs.inverse[metric[j] + lo_in[j]].long()) - lo_s[j]
+            raw = [rs.points[lo_s[j]:lo_s[j + 1]] for j in range(k)]
+            deformed = [rs.attr[lo_s[j]:lo_s[j + 1]] for j in range(k)]
+            tgt = [rt.points[lo_t[j]:lo_t[j + 1]] for j in range(k)]
+        if self.points_lim is not None:
+            off = offsets(raw + tgt)
+            idx, new_off = random_subsample(off, self.points_lim, self.subsample_seed, [2 * i for i in ids] + [2 * i + 1 for i in ids])
+            idx, lo, cut = idx.long(), [0] + off.tolist(), [0] + new_off.tolist()
+            for j in range(2 * k):
+                kept = idx[cut[j]:cut[j + 1]] - lo[j]
+                if j >= k:
+                    tgt[j - k] = tgt[j - k][kept]
+                    continue
+                if metric[j] is not None:
+                    pos = torch.full((raw[j].shape[0],), -1, dtype=torch.long, device=device)
+                    pos[kept] = torch.arange(kept.shape[0], device=device)
+                    m = pos[metric[j]]
+                    metric[j] = m[m >= 0]
+                raw[j], deformed[j] = raw[j][kept], deformed[j][kept]
+        for j, it in enumerate(items):
+            it["raw_src_pcd"], it["src_points"], it["tgt_points"] = raw[j], deformed[j], tgt[j]
+            it["src_feats"] = torch.ones((raw[j].shape[0], 1), dtype=torch.float32, device=device)
+            it["tgt_feats"] = torch.ones((tgt[j].shape[0], 1), dtype=torch.float32, device=device)
+            if metric[j] is not None:
+                it["metric_index"] = metric[j]
+
     def test(self, limit=None):
         benchmark = self.config["benchmark"] if isinstance(self.config, dict) else self.config.benchmark
         out_dir = os.path.join(self.snapshot_dir, str(benchmark))
@@ -89,6 +145,8 @@ class Tester:
         def load(s):
             ids = mine[s:s + self.pairs_per_forward]
             items = [self._to_device(self.dataset[i], device) for i in ids]
+            if self.voxel_size is not None or self.points_lim is not None:
+                self._prepare(ids, items, device)
             if self.estimate_normals:   # one batched call for all clouds of this forward
                 from .prep import estimate_normals
                 clouds = [it["raw_src_pcd"] for it in items] + [it["tgt_points"] for it in items]
