@@ -136,6 +136,39 @@ int roitr_random_subsample(int b, int n, const int* offset, int limit, unsigned 
 int roitr_knn_within(int b, int n, int m, const float* xyz, const float* new_xyz, const int* offset, const int* new_offset,
                      float cap2, float* dist2, int use_grid, int m_capacity, void* ws, roitr_stream_t stream);
 
+/* ------------------------------------------------------------------ pair ground truth: radius search under the gt transform
+ * lib/utils.py:72-96 get_correspondences (an Open3D KD-tree radius search per source point, optional idx[:K]) restated, with the overlap
+ * ratio of gt_overlap.log and the 6x6 information matrix of gt.info as reductions on top.  B ragged pairs: src (n,3) / tgt (m,3) fp32
+ * with cumulative int32 offsets src_offset / tgt_offset (B); rot (B,3,3), trans (B,3) fp32, source to target: p' = R p + t.
+ * PRECONDITION (not checked: the offsets are device memory): 0 <= offset[0] <= ... <= offset[B-1], src_offset[B-1] == n,
+ * tgt_offset[B-1] == m.  The kernels index with them; offsets that break this read out of bounds.
+ * The decision, in float64 on the fp32 inputs, every product and sum rounded on its own (no FMA):
+ *     p'[c] = ((R[c][0] px + R[c][1] py) + R[c][2] pz) + t[c];   d2 = ((p'x - qx)^2 + (p'y - qy)^2) + (p'z - qz)^2
+ *     (i, j) is a correspondence iff d2 < (double)radius * (double)radius            (strict; Open3D's boundary is unpinned)
+ *   inverse != 0 (roitr_pairgt_stats): the queries are moved by q'[c] = (R[0][c] dx + R[1][c] dy) + R[2][c] dz, d = q - t, instead:
+ *     call it with the target clouds as `src` and the source clouds as `tgt` for the target-side overlap.
+ *   count (n), nn_idx (n), nn_dist2 (n, float64): per query the number of searched points within the radius, the nearest one
+ *     (pair-local, ties to the lower index; -1 / +inf when none).  Each optional (NULL).
+ *   n_hit (B), overlap (B, float64) = n_hit / n_src, info (B,6,6 float64, optional): sum over the hit queries of G^T G,
+ *     G = [ I3 | -2 [p]x ], p the query in its own frame: Redwood's gt.info layout (translation block first), info[0][0] = n_hit.
+ *     Summed in float64 in a fixed tree per pair: bitwise the same for a pair alone and anywhere in a batch.
+ *   status (B): bit 1 = a non-finite coordinate or transform, bit 2 = an empty cloud, bit 4 = list overflow.  A pair with bit 1 or 2 has
+ *     no correspondences (count 0, nn -1 / +inf, n_hit 0, overlap NaN, info 0); the other pairs of the call are unaffected.
+ * roitr_pairgt_correspondences: corr (capacity, 2) int32 rows (i, j), pair-local, pairs in input order, ascending i, within an i
+ *   ascending (d2, j); k > 0 keeps the first k rows of every i (idx[:K]), k = 0 all.  corr_offset (B) cumulative (saturates at INT_MAX),
+ *   total (2 x int64, device): [0] rows of the list, [1] candidates before the cap = the capacity the call needs.  Candidates pass
+ *   through a buffer of `capacity` entries inside ws: when total[1] > capacity the pairs whose candidates do not all fit carry bit 4 and
+ *   their rows are not written (corr_offset and total stay exact): repeat with capacity = total[1].
+ * Host-side errors (nothing is launched): radius not finite or not positive, k < 0, B outside 1..65536, capacity outside 0..2^31-1, null
+ * pointers.  ws: roitr_pairgt_workspace_bytes(B, n, m, capacity) (capacity 0 for roitr_pairgt_stats).  No host synchronisation. */
+size_t roitr_pairgt_workspace_bytes(int b, int n, int m, long long capacity);
+int roitr_pairgt_stats(int b, int n, int m, const float* src, const int* src_offset, const float* tgt, const int* tgt_offset,
+                       const float* rot, const float* trans, float radius, int inverse, int* count, int* nn_idx, double* nn_dist2,
+                       int* n_hit, double* overlap, double* info, int* status, void* ws, roitr_stream_t stream);
+int roitr_pairgt_correspondences(int b, int n, int m, const float* src, const int* src_offset, const float* tgt, const int* tgt_offset,
+                                 const float* rot, const float* trans, float radius, int k, long long capacity, int* corr,
+                                 int* corr_offset, long long* total, int* status, void* ws, roitr_stream_t stream);
+
 int roitr_grouping_forward(int m, int nsample, int c, const float* input, const int* idx, float* output, roitr_stream_t stream);
 int roitr_grouping_backward(int m, int nsample, int c, const float* grad_output, const int* idx, float* grad_input, roitr_stream_t stream);
 int roitr_interpolation_forward(int n, int c, int k, const float* input, const int* idx, const float* weight, float* output, roitr_stream_t stream);

@@ -23,19 +23,13 @@
 //     second kernel REPLAYS the reference algorithm for them exactly -- index-order scan, max-heap,
 //     heap_sort -- wave-cooperatively (64 distances per step, ballot-pruned against the heap root).
 #include "common.h"
+#include "knn_grid.h"   // RoitrGrid, GRID_MAX_CELLS, GRID_MAX_DIM
 #include "prof.h"
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 
 #define KNN_FILL 1e10f  // knnquery_cuda_kernel.cu:89
-#define GRID_MAX_CELLS 16384
-#define GRID_MAX_DIM 255
-
-struct RoitrGrid {  // one per cloud
-    float ox, oy, oz, h, inv_h;
-    int nx, ny, nz;
-};
 
 namespace {
 
@@ -1679,6 +1673,12 @@ extern "C" int roitr_knn_build_grid_ex(int b, int n, int m_capacity, const float
 extern "C" const void* roitr_knn_sorted_points(int b, int n, int m_capacity, void* ws)
 {
     return carve(ws, b, n, m_capacity).sorted;
+}
+
+RoitrGridView roitr_knn_grid_view(int b, int n, int m_capacity, void* ws)
+{
+    const WsView v = carve(ws, b, n, m_capacity);
+    return RoitrGridView{v.grids, v.cell_start, v.sorted};
 }
 
 // The general entry point.  use_grid != 0 requires a prior roitr_knn_build_grid on the same ws.

@@ -43,10 +43,20 @@ def main():
     ap.add_argument("--points-lim", type=int, default=None,
                     help="cap every cloud at N points, uniform without replacement, on the GPU (the reference's points_lim / max_points)")
     ap.add_argument("--subsample-seed", type=int, default=0, help="seed of the cap's counter-based stream")
+    ap.add_argument("--recall", action="store_true",
+                    help="the 3DMatch-protocol registration recall on the run's own pairs: overlap ratios and gt.info matrices computed "
+                         "on the GPU (pairgt.py), RR overall and per overlap bin; implies --register and --evaluate")
+    ap.add_argument("--overlap-radius", type=float, default=0.0375, help="radius of the ground-truth overlap / information matrix (metres)")
+    ap.add_argument("--write-gt", default=None, metavar="DIR",
+                    help="write gt.log, gt.info, gt_overlap.log and est.log for the run's pairs into DIR (the reference's benchmark() reads "
+                         "them); pair k is the fragment pair (k, k + 2) behind one filler record, because the reference never tests the "
+                         "record at index 0; implies --recall")
     ap.add_argument("--ransac-iterations", type=int, default=50000)
     ap.add_argument("--ransac-points", type=int, default=1000, help="correspondences drawn per pair (probability ~ confidence)")
     args = ap.parse_args()
-    args.evaluate = args.evaluate or args.validate
+    args.recall = args.recall or args.write_gt is not None
+    args.register = args.register or args.recall
+    args.evaluate = args.evaluate or args.validate or args.recall
     config = Config(load_config(args.config))
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", 0)))
@@ -71,7 +81,8 @@ def main():
     tester = Tester(config, model, data, args.snapshot_dir, args.pairs_per_forward, rank, world, evaluate=args.evaluate,
                     estimate_normals=args.estimate_normals, register=args.register,
                     ransac=dict(iterations=args.ransac_iterations, n_points=args.ransac_points), descriptor_eval=args.descriptor_eval, validate=args.validate,
-                    voxel_size=args.voxel_size, points_lim=args.points_lim, subsample_seed=args.subsample_seed)
+                    voxel_size=args.voxel_size, points_lim=args.points_lim, subsample_seed=args.subsample_seed,
+                    recall=args.recall, overlap_radius=args.overlap_radius)
     counts = tester.test()
     if rank == 0 and tester.validation:
         v = tester.validation
@@ -83,6 +94,22 @@ def main():
         _print_descriptor(tester.descriptor or {}, world)
     if args.register and args.evaluate:
         _print_registration(tester.registration, world)
+    if args.recall and rank == 0 and tester.metrics:
+        m = tester.metrics
+        print(f"[roitr_amd] registration recall (RMSE <= 0.2 m, overlap radius {args.overlap_radius:g} m) {m['RR']:.4f} over {m['RR_pairs']} "
+              f"pairs ({m['pairs_without_overlap']} without overlap left out); overlap >= 0.3: {m['RR_overlap_ge_0.3']:.4f} "
+              f"({m['RR_overlap_ge_0.3_pairs']}), 0.1 .. 0.3: {m['RR_overlap_0.1_0.3']:.4f} ({m['RR_overlap_0.1_0.3_pairs']}), "
+              f"< 0.1: {m['RR_overlap_lt_0.1']:.4f} ({m['RR_overlap_lt_0.1_pairs']})")
+    if args.write_gt is not None:
+        gt = tester.gt
+        if world > 1:
+            parts = [None] * world
+            torch.distributed.all_gather_object(parts, tester.gt)
+            gt = {k: v for part in parts for k, v in part.items()}
+        if rank == 0:
+            from .tester import write_gt
+            write_gt(args.write_gt, gt)
+            print(f"[roitr_amd] wrote gt.log, gt.info, gt_overlap.log and est.log for {len(gt)} pairs under {args.write_gt}")
     if args.nonrigid and args.evaluate and config.benchmark in ("4DMatch", "4DLoMatch"):   # the same decision on every rank
         _print_nonrigid(tester.nonrigid or {}, world, float(config.get("eval_acceptance_radius", 0.1)), tester.metrics)
     if rank == 0:

@@ -19,6 +19,8 @@ from .shard import assemble_block, gather_result_records, pairs_for_rank, slots_
 
 DESC_INLIER_THRESHOLD = 0.1   # registration/benchmark_utils.py:80 get_inlier_ratio's default, whatever eval_acceptance_radius says
 DESC_FMR_THRESHOLD = 0.05   # registration/evaluate_registration_c2f.py:109: a pair counts when its inlier ratio exceeds it
+RECALL_RMSE = 0.2            # registration/benchmark.py:217 evaluate_registration: a pair is registered when p <= 0.2 ** 2
+OVERLAP_BINS = (("overlap_ge_0.3", 0.3, float("inf")), ("overlap_0.1_0.3", 0.1, 0.3), ("overlap_lt_0.1", float("-inf"), 0.1))
 
 
 def load_pretrain(model, path):
@@ -33,7 +35,7 @@ def load_pretrain(model, path):
 class Tester:
     def __init__(self, config, model, dataset, snapshot_dir="snapshot", pairs_per_forward=8, rank=0, world=1, evaluate=False,
                  estimate_normals=False, view_point=(0.0, 0.0, 0.0), register=False, ransac=None, nonrigid=None, descriptor_eval=False,
-                 validate=False, voxel_size=None, points_lim=None, subsample_seed=0):
+                 validate=False, voxel_size=None, points_lim=None, subsample_seed=0, recall=False, overlap_radius=0.0375):
         """evaluate: also compute PIR / IR per pair on the device (lib/loss.py:169-213 Evaluator) and return their means.
         estimate_normals: ignore the dataset's normals and recompute them on the GPU from the points the way the
         reference's dataset code does (open3d estimate_normals(knn=33) + normal_redirect, dataset/tdmatch.py:120-127).
@@ -59,7 +61,16 @@ class Tester:
         have both a positive and a negative); here such pairs are left out of that key's mean and counted per key.
         voxel_size / points_lim / subsample_seed: raw scans in front of the model, on the device (prep.voxel_down_sample,
         prep.random_subsample; see _prepare).  With either one set the normals are always re-estimated on the new points (the dataset's
-        normals no longer belong to them) and the features are rebuilt as ones."""
+        normals no longer belong to them) and the features are rebuilt as ones.
+        recall: the 3DMatch-protocol registration recall on the run's own pairs; implies register and evaluate.  Per forward ONE batched
+        pairgt.pairgt_handle call on the clouds the model saw gives every pair's overlap ratios and gt.info matrix at `overlap_radius`;
+        `self.recall` maps this rank's pair ids to (overlap_src, overlap_tgt, p, success) with p = compute_transformation_err(
+        inv(T_gt) @ T_est, info) and success = p <= 0.2 ** 2 (p is nan for a pair without a source point within the radius: it has
+        no information matrix).  On rank 0 `metrics` gains RR / RR_pairs over the pairs of ALL ranks that have a p, the same per
+        overlap bin of overlap_src (RR_overlap_ge_0.3: the 3DMatch range, RR_overlap_0.1_0.3: 3DLoMatch, RR_overlap_lt_0.1, each
+        with its _pairs count; nan for an empty bin) and pairs_without_overlap, the pairs left out.  Every pair's file additionally
+        holds gt_overlap (2, float64: source side, target side) and gt_info (6,6 float64); `self.gt` keeps (T_gt, info,
+        overlap_src, T_est) per pair id for write_gt.  With recall off, files, records and metrics are what they are without it."""
         self.config, self.model, self.dataset = config, model, dataset
         self.snapshot_dir = snapshot_dir
         self.pairs_per_forward = pairs_per_forward
@@ -67,8 +78,13 @@ class Tester:
         self.voxel_size, self.points_lim, self.subsample_seed = voxel_size, points_lim, subsample_seed
         estimate_normals = estimate_normals or voxel_size is not None or points_lim is not None
         self.evaluate, self.estimate_normals, self.view_point = evaluate or validate, estimate_normals, view_point
+        register = register or recall
+        self.evaluate = self.evaluate or recall
         self.register, self.ransac = register, dict(ransac or {})
         self.registration = {} if register and self.evaluate else None
+        self.recall = {} if recall else None
+        self.gt = {} if recall else None
+        self.overlap_radius = overlap_radius
         self.nonrigid_kw = dict(nonrigid or {})
         self.nonrigid = None   # {global pair id: (nfmr, n_metric)} once a 4DMatch batch with metric_index has been evaluated
         self.descriptor = {} if descriptor_eval and self.evaluate else None
@@ -133,6 +149,25 @@ class Tester:
             it["tgt_feats"] = torch.ones((tgt[j].shape[0], 1), dtype=torch.float32, device=device)
             if metric[j] is not None:
                 it["metric_index"] = metric[j]
+
+    def _recall_rows(self, handle, ids, pairs, est):
+        """One pairgt call for the forward: fills self.recall / self.gt and returns per pair (gt_overlap, gt_info) for its file."""
+        import numpy as np
+        from .pairgt import pairgt_handle
+        gt = pairgt_handle(handle, self.overlap_radius)
+        ov = torch.stack([gt.overlap_src, gt.overlap_tgt], 1).cpu()
+        info, hits = gt.info.cpu(), gt.n_src_hit.cpu().tolist()
+        rows = []
+        for k, idx in enumerate(ids):
+            T_gt = np.eye(4)
+            T_gt[:3, :3] = pairs[k]["rot"].reshape(3, 3).double().cpu().numpy()
+            T_gt[:3, 3] = pairs[k]["trans"].reshape(3).double().cpu().numpy()
+            T_est = est[k].double().numpy()
+            p = recall_error(T_gt, T_est, info[k].numpy()) if hits[k] > 0 else float("nan")
+            self.recall[idx] = (float(ov[k, 0]), float(ov[k, 1]), p, bool(p <= RECALL_RMSE ** 2))
+            self.gt[idx] = (T_gt, info[k].numpy(), float(ov[k, 0]), T_est)
+            rows.append((ov[k].clone(), info[k].clone()))
+        return rows
 
     def test(self, limit=None):
         benchmark = self.config["benchmark"] if isinstance(self.config, dict) else self.config.benchmark
@@ -209,6 +244,9 @@ class Tester:
                         inl = reg["inliers"].cpu().tolist()
                         for k, idx in enumerate(ids):
                             self.registration[idx] = (float(rre[k]), float(rte[k]), int(inl[k]))
+                gt_rows = None
+                if self.recall is not None:
+                    gt_rows = self._recall_rows(handle, ids, pairs, est)
                 for k_pair, (idx, it, p, o) in enumerate(zip(ids, items, pairs, outs)):
                     data = dict()  # lib/tester.py:56-69
                     data["src_raw_pcd"] = p["src_raw_pcd"].cpu()
@@ -225,6 +263,8 @@ class Tester:
                         data["metric_index_list"] = it["metric_index"].cpu() if torch.is_tensor(it["metric_index"]) else it["metric_index"]
                     if est is not None:
                         data["est_transform"] = est[k_pair]
+                    if gt_rows is not None:
+                        data["gt_overlap"], data["gt_info"] = gt_rows[k_pair]
                     torch.save(data, os.path.join(out_dir, f"{idx}.pth"))
         # ---- the one collective of the run: every rank's records -> rank 0 (RCCL over xGMI under torch.distributed.run)
         per_pair = self.model.record_scores_per_pair()
@@ -240,6 +280,11 @@ class Tester:
             parts = [None] * self.world
             torch.distributed.all_gather_object(parts, self.losses)
             losses_all = {k: v for part in parts for k, v in part.items()}
+        recall_all = self.recall
+        if self.recall is not None and self.world > 1:
+            parts = [None] * self.world
+            torch.distributed.all_gather_object(parts, self.recall)
+            recall_all = {k: v for part in parts for k, v in part.items()}
         if self.records is None:     # ranks other than 0
             return None
         if self.records.truncated:
@@ -262,6 +307,8 @@ class Tester:
                 w = [v[1] for v in desc_all.values() if v[1] == v[1]]
                 self.metrics.update(desc_IR_wo=sum(wo) / max(len(wo), 1), desc_IR_w=sum(w) / max(len(w), 1),
                                     desc_FMR=sum(1 for x in wo if x > DESC_FMR_THRESHOLD) / max(len(wo), 1))
+            if recall_all is not None:
+                self.metrics.update(recall_metrics(recall_all))
             if losses_all is not None:
                 self.validation = {"PIR": self.metrics["PIR"], "IR": self.metrics["IR"], "pairs": len(losses_all),
                                    "skipped": {"PIR": self.metrics["pairs_without_coarse"], "IR": 0}}
@@ -270,6 +317,45 @@ class Tester:
                     self.validation[key] = sum(vals) / len(vals) if vals else float("nan")
                     self.validation["skipped"][key] = len(losses_all) - len(vals)
         return counts
+
+
+def recall_error(T_gt, T_est, info):
+    """registration/benchmark.py:260: p = computeTransformationErr(inv(T_gt) @ T_est, info), the value compared with 0.2 ** 2."""
+    import numpy as np
+    from .registration import compute_transformation_err
+    return compute_transformation_err(np.linalg.inv(T_gt) @ T_est, info)
+
+
+def recall_metrics(recall):
+    """{pair id: (overlap_src, overlap_tgt, p, success)} -> RR over the pairs that have a p, and per bin of overlap_src."""
+    rows = [v for v in recall.values() if v[2] == v[2]]
+    rate = lambda sel: sum(1 for v in sel if v[3]) / len(sel) if sel else float("nan")
+    out = {"RR": rate(rows), "RR_pairs": len(rows), "pairs_without_overlap": len(recall) - len(rows)}
+    for name, lo, hi in OVERLAP_BINS:
+        sel = [v for v in rows if lo <= v[0] < hi]
+        out["RR_" + name], out["RR_" + name + "_pairs"] = rate(sel), len(sel)
+    return out
+
+
+def write_gt(directory, gt):
+    """gt.log, gt.info, gt_overlap.log and est.log for {pair id: (T_gt, info, overlap_src, T_est)} in the layouts
+    registration.read_trajectory / read_trajectory_info read and the `i,j,ratio` lines of the reference's gt_overlap.log.  Pair id k is
+    written as the fragment pair (k, k + 2) of k_max + 3 fragments: registration/benchmark.py only tests non-consecutive pairs.  It
+    also marks the tested pairs by their POSITIVE index into gt.log (`gt_mask[i, j] = idx`, `> 0`), so whatever stands at index 0 is
+    never tested: the first record of gt.log, gt.info and est.log is a filler, the consecutive pair (0, 1) with identity matrices,
+    and every pair of the run is tested.  gt_overlap.log holds the run's pairs only."""
+    import numpy as np
+    from .registration import write_trajectory, write_trajectory_info
+    os.makedirs(directory, exist_ok=True)
+    ids = sorted(gt)
+    n_frag = (ids[-1] + 3) if ids else 2
+    meta = [(0, 1, n_frag)] + [(k, k + 2, n_frag) for k in ids]
+    write_trajectory(np.stack([np.eye(4)] + [gt[k][0] for k in ids]), meta, os.path.join(directory, "gt.log"))
+    write_trajectory_info(np.stack([np.eye(6)] + [gt[k][1] for k in ids]), meta, os.path.join(directory, "gt.info"))
+    write_trajectory(np.stack([np.eye(4)] + [gt[k][3] for k in ids]), meta, os.path.join(directory, "est.log"))
+    with open(os.path.join(directory, "gt_overlap.log"), "w") as f:
+        for k in ids:
+            f.write(f"{k},{k + 2},{gt[k][2]:.4f}\n")
 
 
 class SyntheticPairs(torch.utils.data.Dataset):
