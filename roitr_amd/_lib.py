@@ -5,6 +5,7 @@ importing an operator raises.  (The CPU restatement lives under oracle/ and is t
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libroitr_hip.so")
@@ -13,6 +14,46 @@ _lib = None
 
 class RoitrError(RuntimeError):
     pass
+
+
+# The entry points of the evaluation and preparation modules (registration, nonrigid, descmatch, loss, pairgt, prep, evaluate): their
+# restype / argtypes are read from the prototypes of include/*.h at load, so a call cannot disagree with the header about a type.
+# (The calls of the timed path -- ops, pointops, riga -- convert their arguments themselves.)
+BOUND = ("roitr_registration_workspace_bytes roitr_ransac_correspondences roitr_ransac_samples roitr_weighted_procrustes "
+         "roitr_nfmr_workspace_bytes roitr_nfmr_batch roitr_blend_anchor_motion "
+         "roitr_desc_match_workspace_bytes roitr_desc_match_batch roitr_desc_match_select "
+         "roitr_fine_loss_workspace_bytes roitr_fine_loss_batch roitr_coarse_loss_workspace_bytes roitr_coarse_loss_batch "
+         "roitr_pairgt_workspace_bytes roitr_pairgt_stats roitr_pairgt_correspondences "
+         "roitr_normals_workspace_bytes roitr_estimate_normals roitr_normal_redirect "
+         "roitr_voxel_workspace_bytes roitr_voxel_downsample roitr_subsample_workspace_bytes roitr_random_subsample "
+         "roitr_inlier_counts roitr_coarse_hits").split()
+_CTYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t, "long": ctypes.c_long,
+           "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_uint64, "unsigned int": ctypes.c_uint,
+           "unsigned": ctypes.c_uint, "roitr_stream_t": ctypes.c_void_p, "void": None}
+
+
+def _ctype(decl, named):
+    """ctypes type of a C parameter or return declaration; any pointer is a c_void_p.  named: the last word may be the parameter's name."""
+    if "*" in decl or "[" in decl:
+        return ctypes.c_void_p
+    words = [w for w in decl.split() if w != "const"]
+    if named and len(words) > 1 and " ".join(words) not in _CTYPES:
+        words.pop()
+    return _CTYPES[" ".join(words)]   # KeyError: a type this table does not know
+
+
+def header_prototypes():
+    """{function name: (restype, [argtypes])} of every prototype in include/roitr_pointops.h and include/roitr_engine.h."""
+    protos = {}
+    for h in ("roitr_pointops.h", "roitr_engine.h"):
+        text = open(os.path.join(os.path.dirname(_HERE), "include", h)).read()
+        text = re.sub(r"/\*.*?\*/|//[^\n]*|^\s*#[^\n]*|extern \"C\" \{", "", text, flags=re.S | re.M)
+        while re.search(r"\{[^{}]*\}", text):   # struct bodies
+            text = re.sub(r"\{[^{}]*\}", "", text)
+        for ret, name, params in re.findall(r"([\w\s\*]+?)\b(\w+)\s*\(([^()]*)\)\s*;", text):
+            params = [p.strip() for p in params.split(",") if p.strip() not in ("", "void")]
+            protos[name] = (_ctype(ret.strip(), False), [_ctype(p, True) for p in params])
+    return protos
 
 
 def lib():
@@ -33,6 +74,9 @@ def lib():
         for name in ("roitr_engine_create",):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = ctypes.c_void_p
+        protos = header_prototypes()
+        for name in BOUND:
+            getattr(_lib, name).restype, getattr(_lib, name).argtypes = protos[name]
     return _lib
 
 

@@ -106,6 +106,48 @@ __device__ __forceinline__ int segment_of(int i, const int* __restrict__ off, in
     return lo;
 }
 
+// Rows of pair p in a concatenated buffer of `total` rows, in the two forms the batched operators take.
+// Starts form (pairs + 1 entries): [off[p], off[p + 1]) clamped into [0, total] before anything is read through it, and whether the
+// clamp had to change it.
+__device__ __forceinline__ int2 starts_range(const int* __restrict__ off, int p, int total)
+{
+    const int s = min(max(off[p], 0), total);
+    return make_int2(s, min(max(off[p + 1], s), total));
+}
+__device__ __forceinline__ bool starts_bad(const int* __restrict__ off, int p, int total)
+{
+    return off[p] < 0 || off[p + 1] < off[p] || off[p + 1] > total;
+}
+// (first, count) form: (first row, rows) of pair b; a range that leaves [0, total] or is longer than cap (where the buffer it is
+// copied to has a stride) is bad and has no rows.
+__device__ __forceinline__ bool count_bad(const int* __restrict__ first, const int* __restrict__ count, int b, int total)
+{
+    const long long f = first[b], c = count[b];
+    return f < 0 || c < 0 || f + c > total;
+}
+__device__ __forceinline__ bool count_bad(const int* __restrict__ first, const int* __restrict__ count, int b, int total, int cap)
+{
+    const long long f = first[b], c = count[b];
+    return f < 0 || c < 0 || c > cap || f + c > total;
+}
+__device__ __forceinline__ int2 count_range(const int* __restrict__ first, const int* __restrict__ count, int b, int total, int cap)
+{
+    const long long f = first[b], c = count[b];
+    if (f < 0 || c < 0 || c > cap || f + c > total) return make_int2(0, 0);
+    return make_int2((int)f, (int)c);
+}
+
+// Order-preserving image of a float in an unsigned, a < b <=> float_image(a) < float_image(b), and its inverse.
+__device__ __forceinline__ unsigned float_image(float v)
+{
+    const unsigned u = __float_as_uint(v);
+    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float image_float(unsigned o)
+{
+    return __uint_as_float(o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu));
+}
+
 // Sum over the 16 lanes of a DPP row (result in every lane of the row).
 template <int CTRL>
 __device__ __forceinline__ float row_dpp_add(float v)

@@ -32,6 +32,7 @@
 #include "common.h"
 #include "roitr_engine.h"
 #include "gemm_tile.h"
+#include "workspace.h"
 
 #include <math.h>
 #include <stdint.h>
@@ -43,39 +44,22 @@ typedef unsigned long long dm_key;
 
 __device__ __attribute__((aligned(16))) float dm_zero4[4];
 
-size_t dm_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct DmWorkspace { dm_key* row_keys; dm_key* col_keys; float* norm_s; float* norm_t; int* tiles; size_t bytes; };
 
-struct DmLayout { size_t row_keys, col_keys, norm_s, norm_t, tiles, bytes; };
-
-DmLayout dm_layout(int pairs, int total_src, int total_tgt)
+DmWorkspace dm_carve(void* ws, int pairs, int total_src, int total_tgt)
 {
-    DmLayout l;
-    size_t o = 0;
-    l.row_keys = o; o += dm_align256((size_t)total_src * sizeof(dm_key));
-    l.col_keys = o; o += dm_align256((size_t)total_tgt * sizeof(dm_key));
-    l.norm_s = o; o += dm_align256((size_t)total_src * sizeof(float));
-    l.norm_t = o; o += dm_align256((size_t)total_tgt * sizeof(float));
-    l.tiles = o; o += dm_align256((size_t)(pairs + 1) * sizeof(int));
-    l.bytes = o;
-    return l;
+    Carve c(ws);
+    DmWorkspace w;
+    w.row_keys = c.take<dm_key>(total_src);
+    w.col_keys = c.take<dm_key>(total_tgt);
+    w.norm_s = c.take<float>(total_src);
+    w.norm_t = c.take<float>(total_tgt);
+    w.tiles = c.take<int>((size_t)pairs + 1);
+    w.bytes = c.bytes;
+    return w;
 }
 
-__device__ __forceinline__ int2 dm_range(const int* __restrict__ off, int p, int total)
-{
-    const int s = min(max(off[p], 0), total);
-    return make_int2(s, min(max(off[p + 1], s), total));
-}
-
-__device__ __forceinline__ unsigned dm_ord(float v)
-{
-    const unsigned u = __float_as_uint(v);
-    return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ __forceinline__ float dm_unord(unsigned o)
-{
-    return __uint_as_float(o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-}
-__device__ __forceinline__ dm_key dm_make_key(float v, int idx) { return ((dm_key)dm_ord(v) << 32) | (unsigned)~idx; }
+__device__ __forceinline__ dm_key dm_make_key(float v, int idx) { return ((dm_key)float_image(v) << 32) | (unsigned)~idx; }
 
 // keys only grow: a value read earlier is a lower bound of the value now, so skipping on `key <= seen` never loses a maximum
 __device__ __forceinline__ void dm_raise(dm_key* __restrict__ slot, dm_key key)
@@ -121,7 +105,7 @@ __global__ __launch_bounds__(256) void dm_tiles_kernel(int pairs, const int* __r
     const int chunk = (pairs + 255) / 256;
     const int lo = min(threadIdx.x * chunk, pairs), hi = min(lo + chunk, pairs);
     int s = 0;
-    for (int p = lo; p < hi; ++p) { const int2 r = dm_range(src_offsets, p, total_src); s += (r.y - r.x + 63) >> 6; }
+    for (int p = lo; p < hi; ++p) { const int2 r = starts_range(src_offsets, p, total_src); s += (r.y - r.x + 63) >> 6; }
     part[threadIdx.x] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -133,7 +117,7 @@ __global__ __launch_bounds__(256) void dm_tiles_kernel(int pairs, const int* __r
     int run = part[threadIdx.x];
     for (int p = lo; p < hi; ++p) {
         tile_starts[p] = run;
-        const int2 r = dm_range(src_offsets, p, total_src);
+        const int2 r = starts_range(src_offsets, p, total_src);
         run += (r.y - r.x + 63) >> 6;
     }
 }
@@ -151,7 +135,7 @@ __global__ __launch_bounds__(256) void dm_match_kernel(int pairs, int dim, const
     const int tile = blockIdx.x;
     if (tile >= tile_starts[pairs]) return;   // block-uniform
     const int p = segment_of(tile, tile_starts + 1, pairs);
-    const int2 sr = dm_range(src_offsets, p, total_src), tr = dm_range(tgt_offsets, p, total_tgt);
+    const int2 sr = starts_range(src_offsets, p, total_src), tr = starts_range(tgt_offsets, p, total_tgt);
     const int n = sr.y - sr.x, m = tr.y - tr.x;
     const int m0 = (tile - tile_starts[p]) * 64;
     const int nct = (m + 63) >> 6, S = gridDim.y;
@@ -284,7 +268,7 @@ __global__ __launch_bounds__(256) void dm_decode_kernel(int total_src, int total
     float val = 0.f;
     if (k != 0) {   // no real key is 0: ~index of an index below 2^31 has its top bit set
         idx = (int)~(unsigned)(k & 0xFFFFFFFFu);
-        val = dm_unord((unsigned)(k >> 32));
+        val = image_float((unsigned)(k >> 32));
         if (metric == 1) val = -val;
     }
     (is_src ? row_idx : col_idx)[r] = idx;
@@ -366,44 +350,35 @@ __global__ __launch_bounds__(256) void dm_scan_kernel(int pairs, int* __restrict
     for (int p = lo; p < hi; ++p) { run += corr_starts[p + 1]; corr_starts[p + 1] = run; }
 }
 
-int dm_refuse(int code, const char* msg)
-{
-    roitr_set_error(msg, __FILE__, __LINE__);
-    return code;
-}
-
 }  // namespace
 
 extern "C" size_t roitr_desc_match_workspace_bytes(int pairs, int total_src, int total_tgt)
 {
     if (pairs < 0 || total_src < 0 || total_tgt < 0) return 0;
-    return dm_layout(pairs, total_src, total_tgt).bytes;
+    return dm_carve(nullptr, pairs, total_src, total_tgt).bytes;
 }
 
 extern "C" int roitr_desc_match_batch(int pairs, int dim, const int* src_offsets, int total_src, const float* src_desc,
                                       const int* tgt_offsets, int total_tgt, const float* tgt_desc, int metric, int* row_idx, float* row_val,
                                       int* col_idx, float* col_val, void* workspace, size_t workspace_bytes, hipStream_t stream)
 {
-    if (pairs < 0 || total_src < 0 || total_tgt < 0) return dm_refuse(ROITR_ERR_ARG, "roitr_desc_match_batch: negative count");
-    if (metric != 0 && metric != 1) return dm_refuse(ROITR_ERR_ARG, "roitr_desc_match_batch: metric must be 0 (dot product) or 1 (squared distance)");
+    if (pairs < 0 || total_src < 0 || total_tgt < 0) return refuse(ROITR_ERR_ARG, "roitr_desc_match_batch: negative count");
+    if (metric != 0 && metric != 1) return refuse(ROITR_ERR_ARG, "roitr_desc_match_batch: metric must be 0 (dot product) or 1 (squared distance)");
     if (dim < 4 || dim > 1024 || dim % 4 != 0)
-        return dm_refuse(ROITR_ERR_UNSUPPORTED, "roitr_desc_match_batch: dim must be a multiple of 4 in [4, 1024]");
+        return refuse(ROITR_ERR_UNSUPPORTED, "roitr_desc_match_batch: dim must be a multiple of 4 in [4, 1024]");
     if ((pairs > 0 && (!src_offsets || !tgt_offsets)) || (total_src > 0 && (!src_desc || !row_idx || !row_val)) ||
         (total_tgt > 0 && (!tgt_desc || !col_idx || !col_val)))
-        return dm_refuse(ROITR_ERR_ARG, "roitr_desc_match_batch: null pointer");
+        return refuse(ROITR_ERR_ARG, "roitr_desc_match_batch: null pointer");
     if ((((uintptr_t)src_desc) | ((uintptr_t)tgt_desc)) & 15)
-        return dm_refuse(ROITR_ERR_ARG, "roitr_desc_match_batch: descriptors must be 16-byte aligned");
-    const DmLayout l = dm_layout(pairs, total_src, total_tgt);
-    if (workspace_bytes < l.bytes || !workspace)
-        return dm_refuse(ROITR_ERR_ARG, "roitr_desc_match_batch: workspace smaller than roitr_desc_match_workspace_bytes()");
+        return refuse(ROITR_ERR_ARG, "roitr_desc_match_batch: descriptors must be 16-byte aligned");
+    const DmWorkspace w = dm_carve(workspace, pairs, total_src, total_tgt);
+    if (workspace_bytes < w.bytes || !workspace)
+        return refuse(ROITR_ERR_ARG, "roitr_desc_match_batch: workspace smaller than roitr_desc_match_workspace_bytes()");
     const long rows = (long)total_src + total_tgt;
     if (rows == 0) return ROITR_OK;
-    char* ws = (char*)workspace;
-    dm_key* row_keys = (dm_key*)(ws + l.row_keys);
-    dm_key* col_keys = (dm_key*)(ws + l.col_keys);
-    float* norm_s = (float*)(ws + l.norm_s);
-    float* norm_t = (float*)(ws + l.norm_t);
-    int* tiles = (int*)(ws + l.tiles);
+    dm_key *row_keys = w.row_keys, *col_keys = w.col_keys;
+    float *norm_s = w.norm_s, *norm_t = w.norm_t;
+    int* tiles = w.tiles;
     dm_prep_kernel<<<div_up(rows * 16, 256), 256, 0, stream>>>(dim, total_src, src_desc, total_tgt, tgt_desc, metric, row_keys, col_keys, norm_s,
                                                                norm_t);
     ROITR_LAUNCH_CHECK();
@@ -432,10 +407,10 @@ extern "C" int roitr_desc_match_batch(int pairs, int dim, const int* src_offsets
 extern "C" int roitr_desc_match_select(int pairs, const int* src_offsets, const int* tgt_offsets, const int* row_idx, const int* col_idx, int mode,
                                        int* corr_starts, int* corr, int capacity, int* n_out, hipStream_t stream)
 {
-    if (pairs < 0 || capacity < 0) return dm_refuse(ROITR_ERR_ARG, "roitr_desc_match_select: negative count");
-    if (mode < 0 || mode > 2) return dm_refuse(ROITR_ERR_ARG, "roitr_desc_match_select: mode must be 0 (row-major), 1 (col-major) or 2 (mutual)");
+    if (pairs < 0 || capacity < 0) return refuse(ROITR_ERR_ARG, "roitr_desc_match_select: negative count");
+    if (mode < 0 || mode > 2) return refuse(ROITR_ERR_ARG, "roitr_desc_match_select: mode must be 0 (row-major), 1 (col-major) or 2 (mutual)");
     if (!corr_starts || !n_out || (pairs > 0 && (!src_offsets || !tgt_offsets || !row_idx || !col_idx)) || (capacity > 0 && !corr))
-        return dm_refuse(ROITR_ERR_ARG, "roitr_desc_match_select: null pointer");
+        return refuse(ROITR_ERR_ARG, "roitr_desc_match_select: null pointer");
     if (pairs > 0) {
         dm_select_kernel<false><<<pairs, 256, 0, stream>>>(src_offsets, tgt_offsets, row_idx, col_idx, mode, corr_starts, (int*)nullptr, 0);
         ROITR_LAUNCH_CHECK();

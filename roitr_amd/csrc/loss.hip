@@ -30,28 +30,16 @@
 // Ranges and indices are checked before anything is read through them; a bad range empties the pair and sets a status bit.
 #include "common.h"
 #include "roitr_engine.h"
+#include "workspace.h"
 
 #include <math.h>
 
 namespace {
 
-size_t ls_align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-int ls_refuse(int code, const char* msg)
-{
-    roitr_set_error(msg, __FILE__, __LINE__);
-    return code;
-}
-
 // ------------------------------------------------------------------------------------------------ fine loss
 
-// pair b's slots [first[b], first[b] + count[b]) must lie in [0, slots) ...
-__device__ __forceinline__ bool fl_bad(const int* __restrict__ first, const int* __restrict__ count, int b, int slots)
-{
-    const long long f = first[b], c = count[b];
-    return f < 0 || c < 0 || f + c > slots;
-}
-// ... and behind pair b - 1's: what the binary search of fine_patch_kernel stands on
+// pair b's slots [first[b], first[b] + count[b]) must lie in [0, slots) (common.h count_bad) and behind pair b - 1's: what the
+// binary search of fine_patch_kernel stands on
 __device__ __forceinline__ bool fl_unordered(const int* __restrict__ first, const int* __restrict__ count, int b)
 {
     return b > 0 && first[b] < (long long)first[b - 1] + max(count[b - 1], 0);
@@ -75,7 +63,7 @@ __global__ __launch_bounds__(64) void fine_patch_kernel(int pairs, int slots, co
     }
     const int b = lo;
     const int f = first[b];
-    if (s < f || s - f >= count[b] || fl_bad(first, count, b, slots)) return;   // block-uniform: a dead slot, never summed
+    if (s < f || s - f >= count[b] || count_bad(first, count, b, slots)) return;   // block-uniform: a dead slot, never summed
     const float* R = rot + (size_t)b * 9;
     const float* t = trans + (size_t)b * 3;
     bool sm = false, tm = false;
@@ -137,7 +125,7 @@ __global__ __launch_bounds__(256) void fine_reduce_kernel(int pairs, int slots, 
     const int b = blockIdx.x;
     int unordered = 0;   // anywhere in the call: a slot may then have been resolved to another pair and its partial left unwritten
     for (int p = threadIdx.x; p < pairs; p += 256) unordered |= fl_unordered(first, count, p) ? 1 : 0;
-    const bool bad = __syncthreads_or(unordered) != 0 || fl_bad(first, count, b, slots);
+    const bool bad = __syncthreads_or(unordered) != 0 || count_bad(first, count, b, slots);
     const int f = bad ? 0 : first[b], c = bad ? 0 : count[b];
     double acc = 0.0;
     int cnt = 0;
@@ -165,19 +153,6 @@ constexpr int CK = 16;   // k per LDS chunk
 
 struct CircleConst { float pos_margin, neg_margin, pos_optimal, neg_optimal, log_scale, pos_overlap; };
 
-// (first row, rows) of pair b on one side; rows = 0 when the range is not inside [0, total] or longer than the stride
-__device__ __forceinline__ int2 cl_range(const int* __restrict__ first, const int* __restrict__ count, int b, int total, int cap)
-{
-    const long long f = first[b], c = count[b];
-    if (f < 0 || c < 0 || c > cap || f + c > total) return make_int2(0, 0);
-    return make_int2((int)f, (int)c);
-}
-__device__ __forceinline__ bool cl_bad(const int* __restrict__ first, const int* __restrict__ count, int b, int total, int cap)
-{
-    const long long f = first[b], c = count[b];
-    return f < 0 || c < 0 || c > cap || f + c > total;
-}
-
 __global__ __launch_bounds__(256) void coarse_dist_kernel(int D, const float* __restrict__ tgt_feats, int total_t, const int* __restrict__ t_first,
                                                           const int* __restrict__ t_count, const float* __restrict__ src_feats, int total_s,
                                                           const int* __restrict__ s_first, const int* __restrict__ s_count, int max_t, int max_s,
@@ -187,7 +162,7 @@ __global__ __launch_bounds__(256) void coarse_dist_kernel(int D, const float* __
     __shared__ __align__(16) float Bt[CK][CT + 4];
     __shared__ float s_nt[CT], s_ns[CT];
     const int b = blockIdx.z;
-    const int2 tr = cl_range(t_first, t_count, b, total_t, max_t), sr = cl_range(s_first, s_count, b, total_s, max_s);
+    const int2 tr = count_range(t_first, t_count, b, total_t, max_t), sr = count_range(s_first, s_count, b, total_s, max_s);
     const int i0 = blockIdx.y * CT, j0 = blockIdx.x * CT;
     if (i0 >= tr.y || j0 >= sr.y) return;   // block-uniform
     const int tid = threadIdx.x, lr = tid >> 2, kq = tid & 3, ty = tid >> 4, tx = tid & 15;
@@ -244,7 +219,7 @@ __global__ __launch_bounds__(256) void coarse_status_kernel(int pairs, int total
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= pairs) return;
-    status[b] = cl_bad(t_first, t_count, b, total_t, max_t) || cl_bad(s_first, s_count, b, total_s, max_s) ? ROITR_LOSS_BAD_OFFSETS : 0;
+    status[b] = count_bad(t_first, t_count, b, total_t, max_t) || count_bad(s_first, s_count, b, total_s, max_s) ? ROITR_LOSS_BAD_OFFSETS : 0;
 }
 
 __global__ __launch_bounds__(256) void coarse_scatter_kernel(int gt_cap, const int* __restrict__ gt_idx, const int* __restrict__ gt_count,
@@ -254,7 +229,7 @@ __global__ __launch_bounds__(256) void coarse_scatter_kernel(int gt_cap, const i
 {
     const int b = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x;
     if (e >= min(gt_count[b], gt_cap)) return;
-    const int nt = cl_range(t_first, t_count, b, total_t, max_t).y, ns = cl_range(s_first, s_count, b, total_s, max_s).y;
+    const int nt = count_range(t_first, t_count, b, total_t, max_t).y, ns = count_range(s_first, s_count, b, total_s, max_s).y;
     const int i = gt_idx[((size_t)b * gt_cap + e) * 2], j = gt_idx[((size_t)b * gt_cap + e) * 2 + 1];
     if (i < 0 || i >= nt || j < 0 || j >= ns) { atomicOr(status + b, ROITR_LOSS_BAD_INDEX); return; }   // never dereferenced
     atomicMax(slot + (size_t)b * max_t * max_s + (size_t)i * max_s + j, e);
@@ -313,7 +288,7 @@ __global__ __launch_bounds__(256) void coarse_row_kernel(int total_t, const int*
                                                          int* __restrict__ row_valid)
 {
     const int b = blockIdx.y, i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int nt = cl_range(t_first, t_count, b, total_t, max_t).y, ns = cl_range(s_first, s_count, b, total_s, max_s).y;
+    const int nt = count_range(t_first, t_count, b, total_t, max_t).y, ns = count_range(s_first, s_count, b, total_s, max_s).y;
     if (i >= nt || ns == 0) return;   // wave-uniform; no barrier below
     const size_t base = (size_t)b * max_t * max_s + (size_t)i * max_s;
     const float* gt_ov = gt_overlaps + (size_t)b * gt_cap;
@@ -340,7 +315,7 @@ __global__ __launch_bounds__(256) void coarse_col_kernel(int total_t, const int*
     __shared__ float s_m[2][4][64], s_s[2][4][64];
     __shared__ int s_any[4][64];
     const int b = blockIdx.y, cx = threadIdx.x & 63, seg = threadIdx.x >> 6, j = blockIdx.x * 64 + cx;
-    const int nt = cl_range(t_first, t_count, b, total_t, max_t).y, ns = cl_range(s_first, s_count, b, total_s, max_s).y;
+    const int nt = count_range(t_first, t_count, b, total_t, max_t).y, ns = count_range(s_first, s_count, b, total_s, max_s).y;
     if (blockIdx.x * 64 >= ns || nt == 0) return;   // block-uniform
     const int chunk = (nt + 3) >> 2, r0 = seg * chunk, r1 = min(nt, r0 + chunk);   // the quarters depend on the pair alone
     const size_t base = (size_t)b * max_t * max_s;
@@ -391,7 +366,7 @@ __global__ __launch_bounds__(256) void coarse_final_kernel(int total_t, const in
     __shared__ double s_sum[256];
     __shared__ int s_cnt[256];
     const int b = blockIdx.x;
-    int nt = cl_range(t_first, t_count, b, total_t, max_t).y, ns = cl_range(s_first, s_count, b, total_s, max_s).y;
+    int nt = count_range(t_first, t_count, b, total_t, max_t).y, ns = count_range(s_first, s_count, b, total_s, max_s).y;
     if (nt == 0 || ns == 0) nt = ns = 0;   // the row / column kernels wrote nothing
     int nr = 0, nc = 0;
     const double mr = cl_masked_mean(row_loss + (size_t)b * max_t, row_valid + (size_t)b * max_t, nt, s_sum, s_cnt, &nr);
@@ -402,12 +377,36 @@ __global__ __launch_bounds__(256) void coarse_final_kernel(int total_t, const in
     }
 }
 
+struct FineWs { float* part_sum; int* part_cnt; size_t bytes; };   // (sum, count) per slot
+FineWs fine_ws(void* base, int slots)
+{
+    Carve c(base);
+    FineWs w;
+    w.part_sum = c.take<float>(slots);
+    w.part_cnt = c.take<int>(slots);
+    w.bytes = c.bytes;
+    return w;
+}
+
+struct CoarseWs { float* dist; int* slot; float* row_loss; int* row_valid; float* col_loss; int* col_valid; size_t bytes; };
+CoarseWs coarse_ws(void* base, int pairs, int max_t, int max_s)
+{
+    const size_t mat = (size_t)pairs * max_t * max_s, rows = (size_t)pairs * max_t, cols = (size_t)pairs * max_s;
+    Carve c(base);
+    CoarseWs w;
+    w.dist = c.take<float>(mat); w.slot = c.take<int>(mat);
+    w.row_loss = c.take<float>(rows); w.row_valid = c.take<int>(rows);
+    w.col_loss = c.take<float>(cols); w.col_valid = c.take<int>(cols);
+    w.bytes = c.bytes;
+    return w;
+}
+
 }  // namespace
 
 extern "C" size_t roitr_fine_loss_workspace_bytes(int slots)
 {
     if (slots < 0) return 0;
-    return 2 * ls_align256((size_t)slots * sizeof(float));   // (sum, count) per slot
+    return fine_ws(nullptr, slots).bytes;
 }
 
 extern "C" int roitr_fine_loss_batch(int pairs, int slots, const int* first_slot, const int* patch_count, int L, const float* tgt_knn_pts,
@@ -415,44 +414,27 @@ extern "C" int roitr_fine_loss_batch(int pairs, int slots, const int* first_slot
                                      const float* matching_scores, const float* rot, const float* trans, float positive_radius, float* f_sum,
                                      int* f_count, float* f_loss, int* status, void* workspace, size_t workspace_bytes, hipStream_t stream)
 {
-    if (pairs < 0 || slots < 0) return ls_refuse(ROITR_ERR_ARG, "roitr_fine_loss_batch: negative count");
-    if (L < 1 || L > 64) return ls_refuse(ROITR_ERR_UNSUPPORTED, "roitr_fine_loss_batch: point_limit L must lie in [1, 64]");
+    if (pairs < 0 || slots < 0) return refuse(ROITR_ERR_ARG, "roitr_fine_loss_batch: negative count");
+    if (L < 1 || L > 64) return refuse(ROITR_ERR_UNSUPPORTED, "roitr_fine_loss_batch: point_limit L must lie in [1, 64]");
     if (pairs == 0) return ROITR_OK;
     if (!(positive_radius > 0.f) || !isfinite(positive_radius))
-        return ls_refuse(ROITR_ERR_ARG, "roitr_fine_loss_batch: positive_radius must be finite and positive");
+        return refuse(ROITR_ERR_ARG, "roitr_fine_loss_batch: positive_radius must be finite and positive");
     if (!first_slot || !patch_count || !rot || !trans || !f_sum || !f_count || !f_loss || !status ||
         (slots > 0 && (!tgt_knn_pts || !src_knn_pts || !tgt_knn_masks || !src_knn_masks || !matching_scores)))
-        return ls_refuse(ROITR_ERR_ARG, "roitr_fine_loss_batch: null pointer");
-    if (workspace_bytes < roitr_fine_loss_workspace_bytes(slots) || (slots > 0 && !workspace))
-        return ls_refuse(ROITR_ERR_ARG, "roitr_fine_loss_batch: workspace smaller than roitr_fine_loss_workspace_bytes()");
-    float* part_sum = (float*)workspace;
-    int* part_cnt = (int*)((char*)workspace + ls_align256((size_t)slots * sizeof(float)));
+        return refuse(ROITR_ERR_ARG, "roitr_fine_loss_batch: null pointer");
+    const FineWs w = fine_ws(workspace, slots);
+    if (workspace_bytes < w.bytes || (slots > 0 && !workspace))
+        return refuse(ROITR_ERR_ARG, "roitr_fine_loss_batch: workspace smaller than roitr_fine_loss_workspace_bytes()");
     const float r2 = (float)((double)positive_radius * (double)positive_radius);
     if (slots > 0) {
         fine_patch_kernel<<<slots, 64, 0, stream>>>(pairs, slots, first_slot, patch_count, tgt_knn_pts, src_knn_pts, tgt_knn_masks, src_knn_masks,
-                                                    matching_scores, rot, trans, r2, L, part_sum, part_cnt);
+                                                    matching_scores, rot, trans, r2, L, w.part_sum, w.part_cnt);
         ROITR_LAUNCH_CHECK();
     }
-    fine_reduce_kernel<<<pairs, 256, 0, stream>>>(pairs, slots, first_slot, patch_count, part_sum, part_cnt, f_sum, f_count, f_loss, status);
+    fine_reduce_kernel<<<pairs, 256, 0, stream>>>(pairs, slots, first_slot, patch_count, w.part_sum, w.part_cnt, f_sum, f_count, f_loss, status);
     ROITR_LAUNCH_CHECK();
     return ROITR_OK;
 }
-
-namespace {
-struct CoarseWs { float* dist; int* slot; float* row_loss; int* row_valid; float* col_loss; int* col_valid; size_t bytes; };
-CoarseWs coarse_ws(void* base, int pairs, int max_t, int max_s)
-{
-    const size_t mat = ls_align256((size_t)pairs * max_t * max_s * 4), rows = ls_align256((size_t)pairs * max_t * 4),
-                 cols = ls_align256((size_t)pairs * max_s * 4);
-    char* p = (char*)base;
-    CoarseWs w;
-    w.dist = (float*)p; w.slot = (int*)(p + mat);
-    w.row_loss = (float*)(p + 2 * mat); w.row_valid = (int*)(p + 2 * mat + rows);
-    w.col_loss = (float*)(p + 2 * mat + 2 * rows); w.col_valid = (int*)(p + 2 * mat + 2 * rows + cols);
-    w.bytes = 2 * mat + 2 * rows + 2 * cols;
-    return w;
-}
-}  // namespace
 
 extern "C" size_t roitr_coarse_loss_workspace_bytes(int pairs, int max_t, int max_s)
 {
@@ -467,18 +449,18 @@ extern "C" int roitr_coarse_loss_batch(int pairs, int D, const float* tgt_feats,
                                        int* status, void* workspace, size_t workspace_bytes, hipStream_t stream)
 {
     if (pairs < 0 || total_tgt < 0 || total_src < 0 || max_t < 0 || max_s < 0 || gt_cap < 0)
-        return ls_refuse(ROITR_ERR_ARG, "roitr_coarse_loss_batch: negative count");
-    if (D < 4 || D % 4 != 0) return ls_refuse(ROITR_ERR_UNSUPPORTED, "roitr_coarse_loss_batch: the descriptor width must be a positive multiple of 4");
-    if (pairs > 65535) return ls_refuse(ROITR_ERR_UNSUPPORTED, "roitr_coarse_loss_batch: at most 65535 pairs per call");
+        return refuse(ROITR_ERR_ARG, "roitr_coarse_loss_batch: negative count");
+    if (D < 4 || D % 4 != 0) return refuse(ROITR_ERR_UNSUPPORTED, "roitr_coarse_loss_batch: the descriptor width must be a positive multiple of 4");
+    if (pairs > 65535) return refuse(ROITR_ERR_UNSUPPORTED, "roitr_coarse_loss_batch: at most 65535 pairs per call");
     if (pairs == 0) return ROITR_OK;
-    if (!(log_scale > 0.f) || !isfinite(log_scale)) return ls_refuse(ROITR_ERR_ARG, "roitr_coarse_loss_batch: log_scale must be finite and positive");
+    if (!(log_scale > 0.f) || !isfinite(log_scale)) return refuse(ROITR_ERR_ARG, "roitr_coarse_loss_batch: log_scale must be finite and positive");
     if (!tgt_first || !tgt_count || !src_first || !src_count || !gt_count || !c_loss || !status || (total_tgt > 0 && !tgt_feats) ||
         (total_src > 0 && !src_feats) || (gt_cap > 0 && (!gt_idx || !gt_overlaps)))
-        return ls_refuse(ROITR_ERR_ARG, "roitr_coarse_loss_batch: null pointer");
-    if (((uintptr_t)tgt_feats | (uintptr_t)src_feats) & 15) return ls_refuse(ROITR_ERR_ARG, "roitr_coarse_loss_batch: descriptors must be 16-byte aligned");
+        return refuse(ROITR_ERR_ARG, "roitr_coarse_loss_batch: null pointer");
+    if (((uintptr_t)tgt_feats | (uintptr_t)src_feats) & 15) return refuse(ROITR_ERR_ARG, "roitr_coarse_loss_batch: descriptors must be 16-byte aligned");
     const CoarseWs w = coarse_ws(workspace, pairs, max_t, max_s);
     if (workspace_bytes < w.bytes || (w.bytes > 0 && !workspace))
-        return ls_refuse(ROITR_ERR_ARG, "roitr_coarse_loss_batch: workspace smaller than roitr_coarse_loss_workspace_bytes()");
+        return refuse(ROITR_ERR_ARG, "roitr_coarse_loss_batch: workspace smaller than roitr_coarse_loss_workspace_bytes()");
     const CircleConst k = {pos_margin, neg_margin, pos_optimal, neg_optimal, log_scale, pos_overlap};
     coarse_status_kernel<<<div_up(pairs, 256), 256, 0, stream>>>(pairs, total_tgt, tgt_first, tgt_count, total_src, src_first, src_count, max_t,
                                                                  max_s, status);

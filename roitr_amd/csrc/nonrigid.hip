@@ -24,24 +24,13 @@
 // of the block size.  Offsets are clamped to the totals the host was given before anything is read through them.
 #include "common.h"
 #include "roitr_engine.h"
+#include "workspace.h"
 
 #include <math.h>
 
 namespace {
 
 constexpr int NF_TILE = 1024;   // candidates per LDS tile (16 KB)
-
-size_t nf_align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-__device__ __forceinline__ int2 nf_range(const int* __restrict__ off, int p, int total)
-{
-    const int s = min(max(off[p], 0), total);
-    return make_int2(s, min(max(off[p + 1], s), total));
-}
-__device__ __forceinline__ bool nf_bad(const int* __restrict__ off, int p, int total)
-{
-    return off[p] < 0 || off[p + 1] < off[p] || off[p + 1] > total;
-}
 
 // one thread per pair: status word and zeroed hit count.  ref_need: anchors a pair must have (3); need_src: the anchors come from
 // a search in the pair's source cloud, an empty cloud leaves none
@@ -52,12 +41,12 @@ __global__ __launch_bounds__(256) void nfmr_status_kernel(int pairs, int total_s
     const int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= pairs) return;
     int st = 0;
-    int n_ref = nf_range(ref_starts, p, total_ref).y - nf_range(ref_starts, p, total_ref).x;
-    const int2 q = nf_range(q_starts, p, total_q);
-    if (nf_bad(ref_starts, p, total_ref) || nf_bad(q_starts, p, total_q)) st |= ROITR_NFMR_BAD_OFFSETS;
+    int n_ref = starts_range(ref_starts, p, total_ref).y - starts_range(ref_starts, p, total_ref).x;
+    const int2 q = starts_range(q_starts, p, total_q);
+    if (starts_bad(ref_starts, p, total_ref) || starts_bad(q_starts, p, total_q)) st |= ROITR_NFMR_BAD_OFFSETS;
     if (src_offsets) {
-        if (nf_bad(src_offsets, p, total_src)) st |= ROITR_NFMR_BAD_OFFSETS;
-        const int2 s = nf_range(src_offsets, p, total_src);
+        if (starts_bad(src_offsets, p, total_src)) st |= ROITR_NFMR_BAD_OFFSETS;
+        const int2 s = starts_range(src_offsets, p, total_src);
         if (s.y == s.x) n_ref = 0;
     }
     if (n_ref < 3) st |= ROITR_NFMR_FEW_ANCHORS;
@@ -81,9 +70,9 @@ __global__ __launch_bounds__(THREADS) void nfmr_anchor_kernel(int pairs, int tot
     if (live) { qx = src_corr[(size_t)c * 3]; qy = src_corr[(size_t)c * 3 + 1]; qz = src_corr[(size_t)c * 3 + 2]; }
     const int p_first = segment_of(c_lo, corr_starts + 1, pairs), p_last = segment_of(c_hi - 1, corr_starts + 1, pairs);
     for (int p = p_first; p <= p_last; ++p) {   // block-uniform
-        const int2 cr = nf_range(corr_starts, p, total_corr);
+        const int2 cr = starts_range(corr_starts, p, total_corr);
         if (cr.y <= c_lo || cr.x >= c_hi) continue;
-        const int2 sr = nf_range(src_offsets, p, total_src);
+        const int2 sr = starts_range(src_offsets, p, total_src);
         const int n = sr.y - sr.x;
         float best = INFINITY;
         int bi = 0;
@@ -138,11 +127,11 @@ __global__ __launch_bounds__(THREADS) void nfmr_blend_kernel(int pairs, int tota
     const bool live = m < total_q;
     const int p_first = segment_of(m_lo, q_starts + 1, pairs), p_last = segment_of(m_hi - 1, q_starts + 1, pairs);
     for (int p = p_first; p <= p_last; ++p) {   // block-uniform
-        const int2 qr = nf_range(q_starts, p, total_q);
+        const int2 qr = starts_range(q_starts, p, total_q);
         if (qr.y <= m_lo || qr.x >= m_hi) continue;
-        const int2 rr = nf_range(ref_starts, p, total_ref);
+        const int2 rr = starts_range(ref_starts, p, total_ref);
         int2 sr = make_int2(0, 0);
-        if (metric_index) sr = nf_range(src_offsets, p, total_src);
+        if (metric_index) sr = starts_range(src_offsets, p, total_src);
         const int n_src = sr.y - sr.x;
         const int n_ref = (metric_index && n_src == 0) ? 0 : rr.y - rr.x;   // no cloud: the anchor pass wrote nothing
         const bool mine = live && m >= qr.x && m < qr.y;
@@ -252,10 +241,16 @@ __global__ __launch_bounds__(THREADS) void nfmr_blend_kernel(int pairs, int tota
     }
 }
 
-int nf_refuse(int code, const char* msg)
+struct NfWorkspace { float* anchor; float* motion; size_t bytes; };   // (total_corr, 3) each
+
+NfWorkspace nf_carve(void* ws, int total_corr)
 {
-    roitr_set_error(msg, __FILE__, __LINE__);
-    return code;
+    Carve c(ws);
+    NfWorkspace w;
+    w.anchor = c.take<float>((size_t)total_corr * 3);
+    w.motion = c.take<float>((size_t)total_corr * 3);
+    w.bytes = c.bytes;
+    return w;
 }
 
 int nf_block(int block, int rows)
@@ -291,7 +286,7 @@ extern "C" size_t roitr_nfmr_workspace_bytes(int pairs, int total_corr, int tota
 {
     (void)pairs; (void)total_metric;
     if (total_corr < 0) return 0;
-    return 2 * nf_align256((size_t)total_corr * 3 * sizeof(float));   // anchors, motions
+    return nf_carve(nullptr, total_corr).bytes;
 }
 
 extern "C" int roitr_nfmr_batch(int pairs, int total_src, const int* src_offsets, const float* src_raw, const float* src_deformed,
@@ -301,29 +296,28 @@ extern "C" int roitr_nfmr_batch(int pairs, int total_src, const int* src_offsets
                                 void* workspace, size_t workspace_bytes, hipStream_t stream)
 {
     if (pairs < 0 || total_src < 0 || total_corr < 0 || total_metric < 0)
-        return nf_refuse(ROITR_ERR_ARG, "roitr_nfmr_batch: negative count");
+        return refuse(ROITR_ERR_ARG, "roitr_nfmr_batch: negative count");
     if (pairs == 0) return ROITR_OK;
     if (!(search_radius > 0.f) || !isfinite(search_radius) || !(recall_thr > 0.f) || !isfinite(recall_thr))
-        return nf_refuse(ROITR_ERR_ARG, "roitr_nfmr_batch: search_radius and recall_thr must be finite and positive");
-    if (!nf_block_ok(block)) return nf_refuse(ROITR_ERR_ARG, "roitr_nfmr_batch: block must be 0 (automatic), 64, 128 or 256");
+        return refuse(ROITR_ERR_ARG, "roitr_nfmr_batch: search_radius and recall_thr must be finite and positive");
+    if (!nf_block_ok(block)) return refuse(ROITR_ERR_ARG, "roitr_nfmr_batch: block must be 0 (automatic), 64, 128 or 256");
     if (!src_offsets || !corr_starts || !metric_starts || !rot || !trans || !hits || !status || (total_src > 0 && (!src_raw || !src_deformed)) ||
         (total_corr > 0 && (!src_corr || !tgt_corr)) || (total_metric > 0 && !metric_index))
-        return nf_refuse(ROITR_ERR_ARG, "roitr_nfmr_batch: null pointer");
-    if (workspace_bytes < roitr_nfmr_workspace_bytes(pairs, total_corr, total_metric) || (total_corr > 0 && !workspace))
-        return nf_refuse(ROITR_ERR_ARG, "roitr_nfmr_batch: workspace smaller than roitr_nfmr_workspace_bytes()");
-    float* anchor = (float*)workspace;
-    float* motion = (float*)((char*)workspace + nf_align256((size_t)total_corr * 3 * sizeof(float)));
+        return refuse(ROITR_ERR_ARG, "roitr_nfmr_batch: null pointer");
+    const NfWorkspace w = nf_carve(workspace, total_corr);
+    if (workspace_bytes < w.bytes || (total_corr > 0 && !workspace))
+        return refuse(ROITR_ERR_ARG, "roitr_nfmr_batch: workspace smaller than roitr_nfmr_workspace_bytes()");
     nfmr_status_kernel<<<div_up(pairs, 256), 256, 0, stream>>>(pairs, total_src, src_offsets, total_corr, corr_starts, total_metric,
                                                                metric_starts, hits, status);
     ROITR_LAUNCH_CHECK();
     if (total_corr > 0) {
         launch_anchor(nf_block(block, total_corr), total_corr, stream, pairs, total_src, src_offsets, src_raw, src_deformed, total_corr,
-                      corr_starts, src_corr, tgt_corr, anchor_idx, anchor, motion);
+                      corr_starts, src_corr, tgt_corr, anchor_idx, w.anchor, w.motion);
         ROITR_LAUNCH_CHECK();
     }
     if (total_metric > 0) {
-        launch_blend(nf_block(block, total_metric), total_metric, stream, pairs, total_corr, corr_starts, (const float*)anchor,
-                     (const float*)motion, total_metric, metric_starts, (const float*)nullptr, metric_index, total_src, src_offsets, src_raw,
+        launch_blend(nf_block(block, total_metric), total_metric, stream, pairs, total_corr, corr_starts, (const float*)w.anchor,
+                     (const float*)w.motion, total_metric, metric_starts, (const float*)nullptr, metric_index, total_src, src_offsets, src_raw,
                      src_deformed, rot, trans, search_radius, recall_thr, (float*)nullptr, (int*)nullptr, err, hits, status);
         ROITR_LAUNCH_CHECK();
     }
@@ -334,14 +328,14 @@ extern "C" int roitr_blend_anchor_motion(int pairs, int total_ref, const int* re
                                          int total_query, const int* query_starts, const float* query_loc, float search_radius, int block,
                                          float* blended_flow, int* mask, int* status, hipStream_t stream)
 {
-    if (pairs < 0 || total_ref < 0 || total_query < 0) return nf_refuse(ROITR_ERR_ARG, "roitr_blend_anchor_motion: negative count");
+    if (pairs < 0 || total_ref < 0 || total_query < 0) return refuse(ROITR_ERR_ARG, "roitr_blend_anchor_motion: negative count");
     if (pairs == 0) return ROITR_OK;
     if (!(search_radius > 0.f) || !isfinite(search_radius))
-        return nf_refuse(ROITR_ERR_ARG, "roitr_blend_anchor_motion: search_radius must be finite and positive");
-    if (!nf_block_ok(block)) return nf_refuse(ROITR_ERR_ARG, "roitr_blend_anchor_motion: block must be 0 (automatic), 64, 128 or 256");
+        return refuse(ROITR_ERR_ARG, "roitr_blend_anchor_motion: search_radius must be finite and positive");
+    if (!nf_block_ok(block)) return refuse(ROITR_ERR_ARG, "roitr_blend_anchor_motion: block must be 0 (automatic), 64, 128 or 256");
     if (!ref_starts || !query_starts || !status || (total_ref > 0 && (!ref_loc || !ref_flow)) ||
         (total_query > 0 && (!query_loc || !blended_flow || !mask)))
-        return nf_refuse(ROITR_ERR_ARG, "roitr_blend_anchor_motion: null pointer");
+        return refuse(ROITR_ERR_ARG, "roitr_blend_anchor_motion: null pointer");
     nfmr_status_kernel<<<div_up(pairs, 256), 256, 0, stream>>>(pairs, 0, (const int*)nullptr, total_ref, ref_starts, total_query, query_starts,
                                                                (int*)nullptr, status);
     ROITR_LAUNCH_CHECK();

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "knn_grid.h"
 #include "roitr_pointops.h"
+#include "workspace.h"
 #include <cmath>
 
 #define PG_NONFINITE 1
@@ -54,20 +55,18 @@ struct PgWs {
 
 PgWs carve(void* ws, int b, int n, int m, i64 capacity)
 {
-    uintptr_t p = ((uintptr_t)ws + 255) & ~(uintptr_t)255;
-    const uintptr_t p0 = (uintptr_t)ws;
-    auto take = [&](size_t bytes) { uintptr_t r = p; p += (bytes + 255) & ~(size_t)255; return r; };
+    Carve c(Carve::aligned(ws));
     PgWs w;
     const int ntile = div_up(n > 0 ? n : 1, PG_TILE);
-    w.knn = (void*)take(roitr_knn_workspace_bytes(b, m, 0));
-    w.clean = (float*)take((size_t)m * 12);
-    w.cnt = (int*)take((size_t)n * 4);
-    w.upos = (i64*)take((size_t)n * 8);
-    w.cpos = (i64*)take((size_t)n * 8);
-    w.tile = (i64*)take((size_t)ntile * 16);
-    w.cand_d2 = (double*)take((size_t)capacity * 8);
-    w.cand_j = (int*)take((size_t)capacity * 4);
-    w.bytes = (size_t)(p - p0) + 256;
+    w.knn = c.take<char>(roitr_knn_workspace_bytes(b, m, 0));
+    w.clean = c.take<float>((size_t)m * 3);
+    w.cnt = c.take<int>(n);
+    w.upos = c.take<i64>(n);
+    w.cpos = c.take<i64>(n);
+    w.tile = c.take<i64>((size_t)ntile * 2);
+    w.cand_d2 = c.take<double>(capacity);
+    w.cand_j = c.take<int>(capacity);
+    w.bytes = c.bytes + 256;   // room to align the caller's pointer
     return w;
 }
 

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "registration_math.h"
 #include "roitr_engine.h"
+#include "workspace.h"
 
 #include <limits.h>
 
@@ -29,8 +30,6 @@ constexpr int RG_TARGET_BLOCKS = 2048;   // hypothesis blocks the automatic chun
 constexpr int RG_MAX_ITER = 1 << 28;     // iteration << 4 must fit the low 32 bits of the counter
 
 enum { RG_SEL_ALL = 0, RG_SEL_TOPK = 1, RG_SEL_WEIGHTED = 2 };
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int ransac_chunks(int pairs, int iterations, int chunks_req)
 {
@@ -46,23 +45,19 @@ struct RgWorkspace {
     float4* sel_t;               // (total_rows) x, y, z, 0
     unsigned long long* keys;    // (total_rows) ordered selection keys
     int4* best;                  // (pairs, chunks) {count, sum d^2 bits, iteration, valid hypotheses}
+    size_t bytes;
 };
 
 RgWorkspace carve(void* ws, int pairs, int total_rows, int chunks)
 {
-    char* p = (char*)ws;
+    Carve c(ws);
     RgWorkspace w;
-    w.sel_s = (float4*)p; p += align256((size_t)total_rows * sizeof(float4));
-    w.sel_t = (float4*)p; p += align256((size_t)total_rows * sizeof(float4));
-    w.keys = (unsigned long long*)p; p += align256((size_t)total_rows * 8);
-    w.best = (int4*)p;
+    w.sel_s = c.take<float4>(total_rows);
+    w.sel_t = c.take<float4>(total_rows);
+    w.keys = c.take<unsigned long long>(total_rows);
+    w.best = c.take<int4>((size_t)pairs * chunks);
+    w.bytes = c.bytes;
     return w;
-}
-
-size_t workspace_bytes(int pairs, int total_rows, int chunks)
-{
-    return align256((size_t)total_rows * sizeof(float4)) * 2 + align256((size_t)total_rows * 8) +
-           align256((size_t)pairs * chunks * sizeof(int4));
 }
 
 __device__ __forceinline__ int wave_sum_i(int v)
@@ -408,18 +403,12 @@ __global__ void ransac_samples_kernel(int pairs, const int* __restrict__ n, cons
     out[3 * i] = a0; out[3 * i + 1] = a1; out[3 * i + 2] = a2;
 }
 
-int refuse(int code, const char* msg)
-{
-    roitr_set_error(msg, __FILE__, __LINE__);
-    return code;
-}
-
 }  // namespace
 
 extern "C" size_t roitr_registration_workspace_bytes(int pairs, int total_rows, int iterations, int chunks)
 {
     if (pairs <= 0 || total_rows < 0 || iterations < 1) return 0;
-    return workspace_bytes(pairs, total_rows, ransac_chunks(pairs, iterations, chunks));
+    return carve(nullptr, pairs, total_rows, ransac_chunks(pairs, iterations, chunks)).bytes;
 }
 
 extern "C" int roitr_ransac_correspondences(int pairs, const int* starts, int total_rows, const float* src_pts, const float* tgt_pts,
@@ -446,9 +435,9 @@ extern "C" int roitr_ransac_correspondences(int pairs, const int* starts, int to
         (total_rows > 0 && (!src_pts || !tgt_pts)))
         return refuse(ROITR_ERR_ARG, "roitr_ransac_correspondences: null pointer");
     const int ch = ransac_chunks(pairs, iterations, chunks);
-    if (workspace_bytes_given < workspace_bytes(pairs, total_rows, ch))
-        return refuse(ROITR_ERR_ARG, "roitr_ransac_correspondences: workspace smaller than roitr_registration_workspace_bytes()");
     const RgWorkspace ws = carve(workspace, pairs, total_rows, ch);
+    if (workspace_bytes_given < ws.bytes)
+        return refuse(ROITR_ERR_ARG, "roitr_ransac_correspondences: workspace smaller than roitr_registration_workspace_bytes()");
     const float thr2 = distance_threshold * distance_threshold;
     ransac_select_kernel<<<pairs, RG_THREADS, 0, stream>>>(starts, total_rows, src_pts, tgt_pts, scores, sample_mode, n_points, seed,
                                                            pair_keys, ws, n_used, selected);

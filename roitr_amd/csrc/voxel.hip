@@ -22,6 +22,7 @@
 #include "common.h"
 #include "registration_math.h"
 #include "roitr_pointops.h"
+#include "workspace.h"
 
 #include <cmath>
 
@@ -53,40 +54,35 @@ struct Workspace {
     size_t bytes;
 };
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static Workspace carve(void* ws, int b, int n)
 {
     const size_t nblk = (size_t)div_up(n > 0 ? n : 1, VX_TILE);
-    char* p = static_cast<char*>(ws);
-    size_t o = 0;
+    Carve c(Carve::aligned(ws));
     Workspace w;
-    auto take = [&](size_t bytes) { char* q = p ? p + o : nullptr; o += align256(bytes); return q; };
-    w.key[0] = reinterpret_cast<u64*>(take((size_t)n * 8));
-    w.key[1] = reinterpret_cast<u64*>(take((size_t)n * 8));
-    w.pay[0] = reinterpret_cast<unsigned*>(take((size_t)n * 4));
-    w.pay[1] = reinterpret_cast<unsigned*>(take((size_t)n * 4));
-    w.hist = reinterpret_cast<int*>(take((size_t)VX_RADIX * nblk * 4));
-    w.bintotal = reinterpret_cast<int*>(take(VX_RADIX * 4));
-    w.andor = reinterpret_cast<u64*>(take(16));
-    w.bounds = reinterpret_cast<unsigned*>(take((size_t)(b > 0 ? b : 1) * 12));
-    w.flag = reinterpret_cast<unsigned char*>(take(nblk * VX_TILE));
-    w.blocksum = reinterpret_cast<int*>(take((nblk + 1) * 4));
-    w.start = reinterpret_cast<int*>(take((size_t)n * 4));
-    w.bytes = o + 256;   // room to align the caller's pointer
+    w.key[0] = c.take<u64>(n);
+    w.key[1] = c.take<u64>(n);
+    w.pay[0] = c.take<unsigned>(n);
+    w.pay[1] = c.take<unsigned>(n);
+    w.hist = c.take<int>((size_t)VX_RADIX * nblk);
+    w.bintotal = c.take<int>(VX_RADIX);
+    w.andor = c.take<u64>(2);
+    w.bounds = c.take<unsigned>((size_t)(b > 0 ? b : 1) * 3);
+    w.flag = c.take<unsigned char>(nblk * VX_TILE);
+    w.blocksum = c.take<int>(nblk + 1);
+    w.start = c.take<int>(n);
+    w.bytes = c.bytes + 256;   // room to align the caller's pointer
     return w;
 }
 
-static void* aligned_ws(void* ws) { return reinterpret_cast<void*>(align256(reinterpret_cast<size_t>(ws))); }
-
 // ------------------------------------------------------------------ small device helpers
-// order-preserving image of a float in an unsigned: a < b  <=>  image(a) < image(b)
-__device__ __forceinline__ unsigned float_image(float f)
+// common.h float_image written with a select: the same function, kept for voxel_bounds_kernel alone, whose generated code differs
+// with the shared xor form (614 instead of 639 instructions, 25 instead of 24 VGPRs: not measured on a device, so not taken in a change
+// that promises identical device code; profiles/eval_layer_refactor_isa.txt)
+__device__ __forceinline__ unsigned bounds_image(float f)
 {
     const unsigned u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
-__device__ __forceinline__ float image_float(unsigned o) { return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o); }
 
 __device__ __forceinline__ bool pass_live(const u64* __restrict__ andor, int p) { return (((andor[0] ^ andor[1]) >> (8 * p)) & 0xffu) != 0; }
 // number of live passes below p: its parity names the buffer that holds the order pass p reads
@@ -142,7 +138,7 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_bounds_kernel(int b, int n, 
             unsigned nf = 0;
             if (valid) {
                 const float x = xyz[(size_t)i * 3], y = xyz[(size_t)i * 3 + 1], z = xyz[(size_t)i * 3 + 2];
-                if (isfinite(x) && isfinite(y) && isfinite(z)) { v[0] = float_image(x); v[1] = float_image(y); v[2] = float_image(z); }
+                if (isfinite(x) && isfinite(y) && isfinite(z)) { v[0] = bounds_image(x); v[1] = bounds_image(y); v[2] = bounds_image(z); }
                 else nf = 1;
             }
             const int cf = __builtin_amdgcn_readfirstlane(c);
@@ -168,7 +164,7 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_bounds_kernel(int b, int n, 
         const int i = base + r * VX_THREADS + threadIdx.x;
         if (i >= n) break;
         const float x = xyz[(size_t)i * 3], y = xyz[(size_t)i * 3 + 1], z = xyz[(size_t)i * 3 + 2];
-        if (isfinite(x) && isfinite(y) && isfinite(z)) { m[0] = min(m[0], float_image(x)); m[1] = min(m[1], float_image(y)); m[2] = min(m[2], float_image(z)); }
+        if (isfinite(x) && isfinite(y) && isfinite(z)) { m[0] = min(m[0], bounds_image(x)); m[1] = min(m[1], bounds_image(y)); m[2] = min(m[2], bounds_image(z)); }
         else bad = 1;
     }
 #pragma unroll
@@ -600,7 +596,7 @@ extern "C" int roitr_voxel_downsample(int b, int n, const float* xyz, const int*
         ROITR_HIP(hipMemsetAsync(new_offset, 0, (size_t)b * 4, stream));
         return ROITR_OK;
     }
-    const Workspace w = carve(aligned_ws(ws), b, n);
+    const Workspace w = carve(ws, b, n);
     const int nblk = div_up(n, VX_TILE);
     ROITR_HIP(hipMemsetAsync(w.bounds, 0xff, (size_t)b * 12, stream));
     int rc = init_andor(w, stream);
@@ -641,7 +637,7 @@ extern "C" int roitr_random_subsample(int b, int n, const int* offset, int limit
         ROITR_HIP(hipMemsetAsync(new_offset, 0, (size_t)b * 4, stream));
         return ROITR_OK;
     }
-    const Workspace w = carve(aligned_ws(ws), b, n);
+    const Workspace w = carve(ws, b, n);
     const int nblk = div_up(n, VX_TILE);
     int rc = init_andor(w, stream);
     if (rc != ROITR_OK) return rc;

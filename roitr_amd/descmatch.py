@@ -10,47 +10,21 @@ Differences from the reference, by design: among equal scores THE LOWEST INDEX w
 torch.max give, so there is none on finite input); scores are fp32 MFMA sums in a fixed k order where the reference has a BLAS
 product, so an index can differ where two scores lie within rounding of each other (tests/descmatch_util.py states the bound).
 """
-import ctypes
-
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib as L
+from .riga import handle_layout, handle_poses
 
 METRICS = {"dot": 0, "sqdist": 1}
 MODES = {"row": 0, "col": 1, "mutual": 2}
 
 
-def _sig():
-    lib = L.lib()
-    if getattr(lib, "_dm_sig", False):
-        return lib
-    vp, ci = ctypes.c_void_p, ctypes.c_int
-    lib.roitr_desc_match_workspace_bytes.restype = ctypes.c_size_t
-    lib.roitr_desc_match_workspace_bytes.argtypes = [ci] * 3
-    lib.roitr_desc_match_batch.argtypes = [ci, ci, vp, ci, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-    lib.roitr_desc_match_select.argtypes = [ci, vp, vp, vp, vp, ci, vp, vp, ci, vp, vp]
-    lib._dm_sig = True
-    return lib
-
-
-def _dev(t, dtype, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise L.RoitrError(f"{what}: roitr_amd needs ROCm device tensors (no CPU fallback)")
-    return t.to(dtype).contiguous()
-
-
 def _desc(t, what):
-    t = _dev(t, torch.float32, what)
+    t = A.dev(t, torch.float32, what)
     if t.dim() != 2:
         raise L.RoitrError(f"{what} must be (rows, dim), got {tuple(t.shape)}")
-    return t
-
-
-def _offsets(t, what, B=None):
-    t = _dev(t, torch.int32, what).reshape(-1)
-    if t.numel() < 1 or (B is not None and t.numel() != B + 1):
-        raise L.RoitrError(f"{what} must hold pairs + 1 entries, got {t.numel()}" + ("" if B is None else f" for {B} pairs"))
     return t
 
 
@@ -61,10 +35,10 @@ def select(src_offsets, tgt_offsets, row_idx, col_idx, mode="mutual", capacity=N
     mode's upper bound, which never cuts) limits the rows written; `needed` is the count the full list has."""
     if mode not in MODES:
         raise L.RoitrError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
-    src_offsets = _offsets(src_offsets, "src_offsets")
+    src_offsets = A.starts(src_offsets, "src_offsets")
     B = int(src_offsets.numel()) - 1
-    tgt_offsets = _offsets(tgt_offsets, "tgt_offsets", B)
-    row_idx, col_idx = _dev(row_idx, torch.int32, "row_idx"), _dev(col_idx, torch.int32, "col_idx")
+    tgt_offsets = A.starts(tgt_offsets, "tgt_offsets", B)
+    row_idx, col_idx = A.dev(row_idx, torch.int32, "row_idx"), A.dev(col_idx, torch.int32, "col_idx")
     dev = row_idx.device
     if row_idx.numel() == 0:   # a side without rows is never read, but the entry point refuses a null pointer
         row_idx = torch.full((1,), -1, dtype=torch.int32, device=dev)
@@ -75,9 +49,9 @@ def select(src_offsets, tgt_offsets, row_idx, col_idx, mode="mutual", capacity=N
     corr_starts = torch.empty((B + 1,), dtype=torch.int32, device=dev)
     corr = torch.full((max(cap, 1), 2), -1, dtype=torch.int32, device=dev)
     n_out = torch.empty((1,), dtype=torch.int32, device=dev)
-    L.check(_sig().roitr_desc_match_select(B, src_offsets.data_ptr(), tgt_offsets.data_ptr(), row_idx.data_ptr(), col_idx.data_ptr(),
-                                           MODES[mode], corr_starts.data_ptr(), corr.data_ptr(), cap, n_out.data_ptr(),
-                                           L.stream_ptr().value), "desc_match_select")
+    L.check(L.lib().roitr_desc_match_select(B, src_offsets.data_ptr(), tgt_offsets.data_ptr(), row_idx.data_ptr(), col_idx.data_ptr(),
+                                            MODES[mode], corr_starts.data_ptr(), corr.data_ptr(), cap, n_out.data_ptr(),
+                                            L.stream_ptr().value), "desc_match_select")
     needed = int(n_out.item())   # the one host round trip: the capacity check
     return corr_starts, corr[:min(needed, cap)], needed
 
@@ -96,9 +70,9 @@ def match_batch(src_offsets, src_desc, tgt_offsets, tgt_desc, *, metric="dot", m
         raise L.RoitrError(f"metric must be one of {sorted(METRICS)}, got {metric!r}")
     if mode not in MODES:
         raise L.RoitrError(f"mode must be one of {sorted(MODES)}, got {mode!r}")
-    src_offsets = _offsets(src_offsets, "src_offsets")
+    src_offsets = A.starts(src_offsets, "src_offsets")
     B = int(src_offsets.numel()) - 1
-    tgt_offsets = _offsets(tgt_offsets, "tgt_offsets", B)
+    tgt_offsets = A.starts(tgt_offsets, "tgt_offsets", B)
     src_desc, tgt_desc = _desc(src_desc, "src_desc"), _desc(tgt_desc, "tgt_desc")
     if src_desc.shape[1] != tgt_desc.shape[1]:
         raise L.RoitrError(f"src_desc / tgt_desc: dim {src_desc.shape[1]} against {tgt_desc.shape[1]}")
@@ -108,9 +82,9 @@ def match_batch(src_offsets, src_desc, tgt_offsets, tgt_desc, *, metric="dot", m
     row_val = torch.empty((n_src,), dtype=torch.float32, device=dev)
     col_idx = torch.empty((n_tgt,), dtype=torch.int32, device=dev)
     col_val = torch.empty((n_tgt,), dtype=torch.float32, device=dev)
-    lib = _sig()
+    lib = L.lib()
     nbytes = int(lib.roitr_desc_match_workspace_bytes(B, n_src, n_tgt))
-    ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+    ws = A.workspace(nbytes, dev)
     L.check(lib.roitr_desc_match_batch(B, dim, src_offsets.data_ptr(), n_src, src_desc.data_ptr(), tgt_offsets.data_ptr(), n_tgt,
                                        tgt_desc.data_ptr(), METRICS[metric], row_idx.data_ptr(), row_val.data_ptr(), col_idx.data_ptr(),
                                        col_val.data_ptr(), ws.data_ptr(), nbytes, L.stream_ptr().value), "desc_match_batch")
@@ -118,18 +92,9 @@ def match_batch(src_offsets, src_desc, tgt_offsets, tgt_desc, *, metric="dot", m
     return dict(row_idx=row_idx, row_val=row_val, col_idx=col_idx, col_val=col_val, corr_starts=corr_starts, corr=corr)
 
 
-def _cuda(x, dtype=torch.float32):
-    t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-    return t.to(device="cuda", dtype=dtype).contiguous()
-
-
-def _ends(n):
-    return torch.tensor([0, n], dtype=torch.int32, device="cuda")
-
-
 def _match_one(src_desc, tgt_desc, metric, mode):
-    s, t = _cuda(src_desc), _cuda(tgt_desc)
-    return match_batch(_ends(s.shape[0]), s, _ends(t.shape[0]), t, metric=metric, mode=mode), s.shape[0], t.shape[0]
+    s, t = A.upload(src_desc), A.upload(tgt_desc)
+    return match_batch(A.cumulative([s.shape[0]], "cuda"), s, A.cumulative([t.shape[0]], "cuda"), t, metric=metric, mode=mode), s.shape[0], t.shape[0]
 
 
 @torch.no_grad()
@@ -175,8 +140,8 @@ def get_inlier_ratio(src_pcd, tgt_pcd, src_feat, tgt_feat, rot, trans, inlier_di
     mutual check: the distances (numpy) between rot src + trans and the matched target points, and the share below the threshold
     (a 0-dim tensor; nan for an empty mutual set, the mean of nothing, as in the reference)."""
     r, n, m = _match_one(src_feat, tgt_feat, "dot", "mutual")
-    src, tgt = _cuda(src_pcd).reshape(-1, 3), _cuda(tgt_pcd).reshape(-1, 3)
-    rot, trans = _cuda(rot).reshape(3, 3), _cuda(trans).reshape(3, 1)
+    src, tgt = A.upload(src_pcd).reshape(-1, 3), A.upload(tgt_pcd).reshape(-1, 3)
+    rot, trans = A.upload(rot).reshape(3, 3), A.upload(trans).reshape(3, 1)
     src = (torch.matmul(rot, src.transpose(0, 1)) + trans).transpose(0, 1)
     results = {"w": {}, "wo": {}}
     for key, si, ti in (("wo", torch.arange(n, device="cuda"), r["row_idx"].long()), ("w", r["corr"][:, 0].long(), r["corr"][:, 1].long())):
@@ -197,24 +162,14 @@ def descriptor_handle(handle, which="point", inlier_distance_threshold=0.1):
     points in the layout registration.ransac_batch takes: starts (B + 1) int32, src_pts / tgt_pts (n, 3) (source points NOT
     transformed), plus corr (n, 2) their local indices."""
     from .evaluate import _inlier_counts
-    if which not in ("point", "node"):
-        raise L.RoitrError(f"which must be 'point' or 'node', got {which!r}")
-    if not handle["have_gt"]:
-        raise L.RoitrError("descriptor_handle needs ground-truth transforms (rot / trans) in the pairs")
-    out, B = handle["out"], handle["B"]
-    sizes = handle["n_all"] if which == "point" else handle["n4"]
-    desc = out["point_feats"] if which == "point" else out["node_feats"]
-    pts = handle["keep"][1] if which == "point" else out["node_xyz"]   # the clouds the model was fed: src_pcd then tgt_pcd
-    rot, trans = handle["keep"][4], handle["keep"][5]
+    pts, src_off, tgt_off = handle_layout(handle, which)
+    rot, trans = handle_poses(handle, "descriptor_handle")
+    B = handle["B"]
+    desc = handle["out"]["point_feats" if which == "point" else "node_feats"][:pts.shape[0]]
     dev = desc.device
-    o = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    total = int(o[-1])
-    desc, pts = desc[:total], pts[:total]
-    src_off = torch.tensor(o[:B + 1].astype(np.int32), device=dev)
-    tgt_off = torch.tensor(o[B:2 * B + 1].astype(np.int32), device=dev)
     r = match_batch(src_off, desc, tgt_off, desc, metric="dot", mode="mutual")
-    n_src_rows = int(o[B])
-    n_src = torch.tensor(np.diff(o[:B + 1]), device=dev)
+    n_src_rows = sum(handle["n_all" if which == "point" else "n4"][:B])
+    n_src = src_off[1:] - src_off[:-1]
     # without the mutual check: source row i of pair b against target tgt_off[b] + row_idx[i]
     pair_of_row = torch.repeat_interleave(torch.arange(B, device=dev), n_src, output_size=n_src_rows)
     ri = r["row_idx"][:n_src_rows].long()
@@ -223,7 +178,7 @@ def descriptor_handle(handle, which="point", inlier_distance_threshold=0.1):
     # a pair without targets has no matches: its rows are compared with a point at infinity and count as outliers
     tgt_wo = torch.where(has[:, None], pts[tgt_abs], torch.full_like(pts[tgt_abs], float("inf")))
     inl_wo = _inlier_counts(src_off, pts[:n_src_rows].contiguous(), tgt_wo.contiguous(), rot, trans, inlier_distance_threshold)
-    n_wo = n_src.to(torch.int32)
+    n_wo = n_src
     ir_wo = torch.where(n_wo > 0, inl_wo.float() / n_wo.clamp_min(1).float(), torch.full((B,), float("nan"), device=dev))
     # with it
     corr, starts = r["corr"].long(), r["corr_starts"]

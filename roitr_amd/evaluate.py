@@ -6,7 +6,9 @@ registration/benchmark_utils.py:69-77.  `evaluate_batch` does the same for all p
 """
 import torch
 
+from . import _args as A
 from . import _lib as L
+from .riga import handle_poses
 
 
 def _cfg(cfg, k, d=None):
@@ -24,10 +26,8 @@ def _inlier_counts(starts, src_pts, tgt_pts, rot, trans, radius):
 def get_inlier_ratio_correspondence(src_node, tgt_node, rot, trans, inlier_distance_threshold=0.1):
     """registration/benchmark_utils.py:69-77 (inliers / number of correspondences)."""
     n = int(src_node.shape[0])
-    dev = src_node.device
-    starts = torch.tensor([0, n], dtype=torch.int32, device=dev)
-    cnt = _inlier_counts(starts, src_node.contiguous().float(), tgt_node.contiguous().float(), rot.reshape(1, 3, 3).contiguous().float(),
-                         trans.reshape(1, 3).contiguous().float(), inlier_distance_threshold)
+    cnt = _inlier_counts(A.cumulative([n], src_node.device), src_node.contiguous().float(), tgt_node.contiguous().float(),
+                         rot.reshape(1, 3, 3).contiguous().float(), trans.reshape(1, 3).contiguous().float(), inlier_distance_threshold)
     return cnt[0].float() / n
 
 
@@ -77,9 +77,7 @@ class Evaluator(torch.nn.Module):
         Returns (ir (B,), pir (B,), n_corr_fine (B,), n_corr_coarse (B,)) as device tensors; empty sets give IR 0 / PIR nan."""
         out, B, P = handle["out"], handle["B"], handle["P"]
         dev = out["n_out"].device
-        if not handle["have_gt"]:
-            raise L.RoitrError("evaluate_batch needs ground-truth transforms (rot / trans) in the pairs")
-        rot, trans = handle["keep"][4], handle["keep"][5]
+        rot, trans = handle_poses(handle, "evaluate_batch")
         # first output row of every pair, then the total: written by the engine in the strided (3DMatch) and the compacted
         # (4DMatch) patch layout alike -- fine_offsets is per patch SLOT, and pair b's first slot is b * P in the first only
         starts = out["pair_starts"]

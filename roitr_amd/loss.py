@@ -10,12 +10,12 @@ Differences from the reference, by design: the fine loss measures point distance
 |a|^2 + |b|^2 - 2ab expansion (a label can differ where |d^2 - r^2| lies inside that form's rounding error); sums run in a fixed order
 (partly in float64), so a value differs from torch's in the last bits and does not depend on the batch.
 """
-import ctypes
-
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib as L
+from .riga import handle_poses, handle_starts
 
 FINE_EMPTY, COARSE_EMPTY, BAD_OFFSETS, BAD_INDEX = 1, 2, 4, 8
 
@@ -27,28 +27,6 @@ DEFAULTS = dict(coarse_loss_positive_margin=0.1, coarse_loss_negative_margin=1.4
 def _cfg(cfg, key):
     v = cfg.get(key) if isinstance(cfg, dict) else getattr(cfg, key, None)
     return DEFAULTS[key] if v is None else v
-
-
-def _sig():
-    lib = L.lib()
-    if getattr(lib, "_loss_sig", False):
-        return lib
-    vp, ci, cf, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
-    lib.roitr_fine_loss_workspace_bytes.restype = sz
-    lib.roitr_fine_loss_workspace_bytes.argtypes = [ci]
-    lib.roitr_fine_loss_batch.argtypes = [ci, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, sz, vp]
-    lib.roitr_coarse_loss_workspace_bytes.restype = sz
-    lib.roitr_coarse_loss_workspace_bytes.argtypes = [ci] * 3
-    lib.roitr_coarse_loss_batch.argtypes = [ci, ci, vp, ci, vp, vp, vp, ci, vp, vp, ci, ci, ci, vp, vp, vp, cf, cf, cf, cf, cf, cf, vp, vp,
-                                            vp, sz, vp]
-    lib._loss_sig = True
-    return lib
-
-
-def _dev(t, dtype, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise L.RoitrError(f"{what}: roitr_amd needs ROCm device tensors (no CPU fallback)")
-    return t.to(dtype).contiguous()
 
 
 def _ints(values, dev):
@@ -63,26 +41,24 @@ def fine_loss_batch(first_slot, patch_count, tgt_knn_pts, src_knn_pts, tgt_knn_m
     trans (B,3).  Device tensors.  Returns (f_loss, f_sum, f_count, status), each (B,); a pair without labels has f_loss NaN and
     FINE_EMPTY in its status."""
     i32, f32 = torch.int32, torch.float32
-    first_slot, patch_count = _dev(first_slot, i32, "first_slot").reshape(-1), _dev(patch_count, i32, "patch_count").reshape(-1)
+    first_slot, patch_count = A.dev(first_slot, i32, "first_slot").reshape(-1), A.dev(patch_count, i32, "patch_count").reshape(-1)
     B = int(first_slot.numel())
-    scores = _dev(matching_scores, f32, "matching_scores")
+    scores = A.dev(matching_scores, f32, "matching_scores")
     slots, Lp = int(scores.shape[0]), int(scores.shape[-1]) - 1
     if scores.dim() != 3 or scores.shape[1] != scores.shape[2] or patch_count.numel() != B:
         raise L.RoitrError(f"fine_loss_batch: matching_scores {tuple(scores.shape)}, {B} first slots, {patch_count.numel()} counts")
-    tp, sp = _dev(tgt_knn_pts, f32, "tgt_knn_pts"), _dev(src_knn_pts, f32, "src_knn_pts")
-    tm, sm = _dev(tgt_knn_masks, i32, "tgt_knn_masks"), _dev(src_knn_masks, i32, "src_knn_masks")
+    tp, sp = A.dev(tgt_knn_pts, f32, "tgt_knn_pts"), A.dev(src_knn_pts, f32, "src_knn_pts")
+    tm, sm = A.dev(tgt_knn_masks, i32, "tgt_knn_masks"), A.dev(src_knn_masks, i32, "src_knn_masks")
     if tuple(tp.shape) != (slots, Lp, 3) or tp.shape != sp.shape or tuple(tm.shape) != (slots, Lp) or tm.shape != sm.shape:
         raise L.RoitrError(f"fine_loss_batch: points {tuple(tp.shape)} / {tuple(sp.shape)} and masks {tuple(tm.shape)} / {tuple(sm.shape)} "
                            f"do not match scores {tuple(scores.shape)}")
-    rot, trans = _dev(rot, f32, "rot").reshape(-1, 3, 3), _dev(trans, f32, "trans").reshape(-1, 3)
-    if rot.shape[0] != B or trans.shape[0] != B:
-        raise L.RoitrError(f"rot / trans: {rot.shape[0]} / {trans.shape[0]} poses for {B} pairs")
+    rot, trans = A.poses(rot, trans, B)
     dev = scores.device
     f_sum, f_loss = torch.empty((B,), dtype=f32, device=dev), torch.empty((B,), dtype=f32, device=dev)
     f_count, status = torch.empty((B,), dtype=i32, device=dev), torch.empty((B,), dtype=i32, device=dev)
-    lib = _sig()
+    lib = L.lib()
     nbytes = int(lib.roitr_fine_loss_workspace_bytes(slots))
-    ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+    ws = A.workspace(nbytes, dev)
     L.check(lib.roitr_fine_loss_batch(B, slots, first_slot.data_ptr(), patch_count.data_ptr(), Lp, tp.data_ptr(), sp.data_ptr(),
                                       tm.data_ptr(), sm.data_ptr(), scores.data_ptr(), rot.data_ptr(), trans.data_ptr(),
                                       float(positive_radius), f_sum.data_ptr(), f_count.data_ptr(), f_loss.data_ptr(), status.data_ptr(),
@@ -99,20 +75,20 @@ def coarse_loss_batch(tgt_feats, tgt_first, tgt_count, src_feats, src_first, src
     same tensor); gt_idx (B, cap, 2) [tgt node, src node], gt_overlaps (B, cap), gt_count (B,).  Device tensors.
     Returns (c_loss, status), each (B,)."""
     i32, f32 = torch.int32, torch.float32
-    tf, sf = _dev(tgt_feats, f32, "tgt_feats"), _dev(src_feats, f32, "src_feats")
+    tf, sf = A.dev(tgt_feats, f32, "tgt_feats"), A.dev(src_feats, f32, "src_feats")
     if tf.dim() != 2 or sf.dim() != 2 or tf.shape[1] != sf.shape[1]:
         raise L.RoitrError(f"coarse_loss_batch: descriptors {tuple(tf.shape)} / {tuple(sf.shape)}")
-    t0, tc = _dev(tgt_first, i32, "tgt_first").reshape(-1), _dev(tgt_count, i32, "tgt_count").reshape(-1)
-    s0, sc = _dev(src_first, i32, "src_first").reshape(-1), _dev(src_count, i32, "src_count").reshape(-1)
+    t0, tc = A.dev(tgt_first, i32, "tgt_first").reshape(-1), A.dev(tgt_count, i32, "tgt_count").reshape(-1)
+    s0, sc = A.dev(src_first, i32, "src_first").reshape(-1), A.dev(src_count, i32, "src_count").reshape(-1)
     B = int(t0.numel())
-    gi, go, gc = _dev(gt_idx, i32, "gt_idx"), _dev(gt_overlaps, f32, "gt_overlaps"), _dev(gt_count, i32, "gt_count").reshape(-1)
+    gi, go, gc = A.dev(gt_idx, i32, "gt_idx"), A.dev(gt_overlaps, f32, "gt_overlaps"), A.dev(gt_count, i32, "gt_count").reshape(-1)
     if not (tc.numel() == s0.numel() == sc.numel() == gc.numel() == B) or gi.dim() != 3 or tuple(gi.shape) != (B, go.shape[-1], 2) or go.shape[0] != B:
         raise L.RoitrError(f"coarse_loss_batch: {B} pairs, gt_idx {tuple(gi.shape)}, gt_overlaps {tuple(go.shape)}")
     dev = tf.device
     c_loss, status = torch.empty((B,), dtype=f32, device=dev), torch.empty((B,), dtype=i32, device=dev)
-    lib = _sig()
+    lib = L.lib()
     nbytes = int(lib.roitr_coarse_loss_workspace_bytes(B, int(max_t), int(max_s)))
-    ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+    ws = A.workspace(nbytes, dev)
     L.check(lib.roitr_coarse_loss_batch(B, int(tf.shape[1]), tf.data_ptr(), int(tf.shape[0]), t0.data_ptr(), tc.data_ptr(), sf.data_ptr(),
                                         int(sf.shape[0]), s0.data_ptr(), sc.data_ptr(), int(max_t), int(max_s), int(go.shape[1]),
                                         gi.data_ptr(), go.data_ptr(), gc.data_ptr(), float(positive_margin), float(negative_margin),
@@ -144,15 +120,11 @@ def loss_batch(handle, cfg):
     Returns device tensors (loss, c_loss, f_loss, f_count, status), each (B,): loss = coarse_loss_weight * c_loss + fine_loss_weight *
     f_loss; status holds FINE_EMPTY / COARSE_EMPTY where a loss is NaN (the reference's mean of an empty selection)."""
     out, B, P, n4 = handle["out"], handle["B"], handle["P"], handle["n4"]
-    if not handle["have_gt"]:
-        raise L.RoitrError("loss_batch needs ground-truth transforms (rot / trans) in the pairs")
-    rot, trans = handle["keep"][4], handle["keep"][5]
-    dev = out["n_corr"].device
+    rot, trans = handle_poses(handle, "loss_batch")
     n_corr = out["n_corr"]
-    if "loss_index" not in handle:   # host-known layout of the call, uploaded once per handle
-        o_nod = np.concatenate([[0], np.cumsum(n4)])   # node rows: src_0 .. src_{B-1}, tgt_0 .. tgt_{B-1}
-        index = _ints(np.stack([o_nod[B:2 * B], n4[B:], o_nod[:B], n4[:B], np.arange(B) * P]), dev)
-        handle["loss_index"] = tuple(index[k] for k in range(5))
+    if "loss_index" not in handle:   # host-known layout of the call, built once per handle
+        s, t = handle_starts(handle, "node")
+        handle["loss_index"] = (t[:-1], t[1:] - t[:-1], s[:-1], s[1:] - s[:-1], _ints(np.arange(B) * P, n_corr.device))
     tgt_first, tgt_count, src_first, src_count, strided_first = handle["loss_index"]
     if handle["compacted"]:   # the selected patches of all pairs back to back (roitr_patch_offsets)
         first = torch.cumsum(n_corr, 0, dtype=torch.int32) - n_corr

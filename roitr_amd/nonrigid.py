@@ -9,48 +9,13 @@ reference's np.argpartition leaves the choice among repeated anchors open, so pa
 distances are differences in fp32, not the |a|^2 + |b|^2 - 2ab expansion; a pair with fewer than 3 anchors or without metric points
 has NFMR 0 and a status bit where the reference raises; only knn = 3.
 """
-import ctypes
-
-import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib as L
+from .riga import handle_poses
 
 FEW_ANCHORS, NO_METRIC, BAD_INDEX, BAD_OFFSETS = 1, 2, 4, 8
-
-
-def _sig():
-    lib = L.lib()
-    if getattr(lib, "_nf_sig", False):
-        return lib
-    vp, ci, cf = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    lib.roitr_nfmr_workspace_bytes.restype = ctypes.c_size_t
-    lib.roitr_nfmr_workspace_bytes.argtypes = [ci] * 3
-    lib.roitr_nfmr_batch.argtypes = [ci, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, vp, vp,
-                                     ctypes.c_size_t, vp]
-    lib.roitr_blend_anchor_motion.argtypes = [ci, ci, vp, vp, vp, ci, vp, vp, cf, ci, vp, vp, vp, vp]
-    lib._nf_sig = True
-    return lib
-
-
-def _dev(t, dtype, what):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise L.RoitrError(f"{what}: roitr_amd needs ROCm device tensors (no CPU fallback)")
-    return t.to(dtype).contiguous()
-
-
-def _pts(t, what):
-    t = _dev(t, torch.float32, what)
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise L.RoitrError(f"{what} must be (n, 3), got {tuple(t.shape)}")
-    return t
-
-
-def _offsets(t, what, B=None):
-    t = _dev(t, torch.int32, what).reshape(-1)
-    if t.numel() < 1 or (B is not None and t.numel() != B + 1):
-        raise L.RoitrError(f"{what} must hold pairs + 1 entries, got {t.numel()}" + ("" if B is None else f" for {B} pairs"))
-    return t
 
 
 def _check_status(status, what):
@@ -76,30 +41,27 @@ def nfmr_batch(src_offsets, src_raw, src_deformed, corr_starts, src_corr, tgt_co
     Returns a dict of device tensors: nfmr (B,) float32, hits, n_metric, status (B,) int32 (FEW_ANCHORS / NO_METRIC pairs have
     NFMR 0) and, with return_errors, anchor_idx (rows of src_corr; local to the pair) and err (per metric point, metres).
     block: lanes per workgroup (0: automatic); the result does not depend on it, nor on the batch a pair travels in."""
-    src_offsets = _offsets(src_offsets, "src_offsets")
+    src_offsets = A.starts(src_offsets, "src_offsets")
     B = int(src_offsets.numel()) - 1
-    corr_starts, metric_starts = _offsets(corr_starts, "corr_starts", B), _offsets(metric_starts, "metric_starts", B)
-    src_raw, src_deformed = _pts(src_raw, "src_raw"), _pts(src_deformed, "src_deformed")
-    src_corr, tgt_corr = _pts(src_corr, "src_corr"), _pts(tgt_corr, "tgt_corr")
+    corr_starts, metric_starts = A.starts(corr_starts, "corr_starts", B), A.starts(metric_starts, "metric_starts", B)
+    src_raw, src_deformed = A.points(src_raw, "src_raw"), A.points(src_deformed, "src_deformed")
+    src_corr, tgt_corr = A.points(src_corr, "src_corr"), A.points(tgt_corr, "tgt_corr")
     if src_raw.shape != src_deformed.shape or src_corr.shape != tgt_corr.shape:
         raise L.RoitrError("src_raw / src_deformed and src_corr / tgt_corr must have the same shapes")
     if not torch.is_tensor(metric_index) or not metric_index.is_cuda:
         raise L.RoitrError("metric_index: roitr_amd needs ROCm device tensors (no CPU fallback)")
     # int64 indices beyond the int32 range stay out of range (-1 / 2^31 - 1) instead of wrapping into it
     metric_index = metric_index.reshape(-1).clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
-    rot = _dev(rot, torch.float32, "rot").reshape(-1, 3, 3)
-    trans = _dev(trans, torch.float32, "trans").reshape(-1, 3)
-    if rot.shape[0] != B or trans.shape[0] != B:
-        raise L.RoitrError(f"rot / trans: {rot.shape[0]} / {trans.shape[0]} poses for {B} pairs")
+    rot, trans = A.poses(rot, trans, B)
     dev = src_raw.device
     n_src, n_corr, n_met = int(src_raw.shape[0]), int(src_corr.shape[0]), int(metric_index.shape[0])
     hits = torch.empty((B,), dtype=torch.int32, device=dev)
     status = torch.empty((B,), dtype=torch.int32, device=dev)
     anchor_idx = torch.full((n_corr,), -1, dtype=torch.int32, device=dev) if return_errors else None
     err = torch.full((n_met,), float("inf"), dtype=torch.float32, device=dev) if return_errors else None
-    lib = _sig()
+    lib = L.lib()
     nbytes = int(lib.roitr_nfmr_workspace_bytes(B, n_corr, n_met))
-    ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+    ws = A.workspace(nbytes, dev)
     L.check(lib.roitr_nfmr_batch(B, n_src, src_offsets.data_ptr(), src_raw.data_ptr(), src_deformed.data_ptr(), n_corr,
                                  corr_starts.data_ptr(), src_corr.data_ptr(), tgt_corr.data_ptr(), n_met, metric_starts.data_ptr(),
                                  metric_index.data_ptr(), rot.data_ptr(), trans.data_ptr(), float(search_radius), float(recall_thr),
@@ -115,23 +77,16 @@ def nfmr_batch(src_offsets, src_raw, src_deformed, corr_starts, src_corr, tgt_co
     return out
 
 
-def _cuda(x, dtype):
-    t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-    return t.to(device="cuda", dtype=dtype).contiguous()
-
-
 @torch.no_grad()
 def compute_nrfmr(data, recall_thr=0.04):
     """registration/evaluate_fdmatch.py:74-115 on the GPU: the NFMR of one saved result file (the dict lib/tester.py:56-69 writes,
     with `metric_index_list`), as a 0-dim tensor like the reference's."""
-    f32, i32 = torch.float32, torch.int32
-    raw, deformed = _cuda(data["src_raw_pcd"], f32).reshape(-1, 3), _cuda(data["src_pcd"], f32).reshape(-1, 3)
-    src_corr, tgt_corr = _cuda(data["src_corr_pts"], f32).reshape(-1, 3), _cuda(data["tgt_corr_pts"], f32).reshape(-1, 3)
-    index = _cuda(torch.as_tensor(data["metric_index_list"]).reshape(-1), torch.int64)
-    def ends(n):
-        return torch.tensor([0, n], dtype=i32, device="cuda")
-    r = nfmr_batch(ends(raw.shape[0]), raw, deformed, ends(src_corr.shape[0]), src_corr, tgt_corr, ends(index.shape[0]), index,
-                   _cuda(data["rot"], f32).reshape(1, 3, 3), _cuda(data["trans"], f32).reshape(1, 3), recall_thr=recall_thr)
+    raw, deformed = A.upload(data["src_raw_pcd"]).reshape(-1, 3), A.upload(data["src_pcd"]).reshape(-1, 3)
+    src_corr, tgt_corr = A.upload(data["src_corr_pts"]).reshape(-1, 3), A.upload(data["tgt_corr_pts"]).reshape(-1, 3)
+    index = A.upload(torch.as_tensor(data["metric_index_list"]).reshape(-1), torch.int64)
+    ends = lambda t: A.cumulative([t.shape[0]], "cuda")
+    r = nfmr_batch(ends(raw), raw, deformed, ends(src_corr), src_corr, tgt_corr, ends(index), index,
+                   A.upload(data["rot"]).reshape(1, 3, 3), A.upload(data["trans"]).reshape(1, 3), recall_thr=recall_thr)
     return r["nfmr"][0].cpu()
 
 
@@ -142,8 +97,8 @@ def blend_anchor_motion(query_loc, reference_loc, reference_flow, knn=3, search_
     if knn != 3:
         raise NotImplementedError("blend_anchor_motion: only knn = 3 (the reference's setting)")
     as_numpy = not torch.is_tensor(query_loc)
-    f32, i32 = torch.float32, torch.int32
-    q, ref, flow = (_cuda(x, f32).reshape(-1, 3) for x in (query_loc, reference_loc, reference_flow))
+    i32 = torch.int32
+    q, ref, flow = (A.upload(x).reshape(-1, 3) for x in (query_loc, reference_loc, reference_flow))
     if ref.shape != flow.shape:
         raise L.RoitrError("reference_loc and reference_flow must have the same shape")
     if ref.shape[0] < 3:
@@ -152,11 +107,10 @@ def blend_anchor_motion(query_loc, reference_loc, reference_flow, knn=3, search_
     out = torch.empty_like(q)
     mask = torch.empty((q.shape[0],), dtype=i32, device=dev)
     status = torch.empty((1,), dtype=i32, device=dev)
-    rs = torch.tensor([0, ref.shape[0]], dtype=i32, device=dev)
-    qs = torch.tensor([0, q.shape[0]], dtype=i32, device=dev)
-    L.check(_sig().roitr_blend_anchor_motion(1, int(ref.shape[0]), rs.data_ptr(), ref.data_ptr(), flow.data_ptr(), int(q.shape[0]),
-                                             qs.data_ptr(), q.data_ptr(), float(search_radius), 0, out.data_ptr(), mask.data_ptr(),
-                                             status.data_ptr(), L.stream_ptr().value), "blend_anchor_motion")
+    rs, qs = A.cumulative([ref.shape[0]], dev), A.cumulative([q.shape[0]], dev)
+    L.check(L.lib().roitr_blend_anchor_motion(1, int(ref.shape[0]), rs.data_ptr(), ref.data_ptr(), flow.data_ptr(), int(q.shape[0]),
+                                              qs.data_ptr(), q.data_ptr(), float(search_radius), 0, out.data_ptr(), mask.data_ptr(),
+                                              status.data_ptr(), L.stream_ptr().value), "blend_anchor_motion")
     mask = mask.bool()
     return (out.cpu().numpy(), mask.cpu().numpy()) if as_numpy else (out, mask)
 
@@ -167,20 +121,15 @@ def nfmr_handle(handle, metric_index_list, **kw):
     out_tgt_pts, valid in the strided and the compacted patch layout alike (as Evaluator.evaluate_batch and register_handle read
     them); the clouds (src_raw_pcd, src_pcd) and the poses come from handle["pairs"].  metric_index_list: one index tensor per pair."""
     pairs, out, B = handle["pairs"], handle["out"], handle["B"]
-    if not handle["have_gt"]:
-        raise L.RoitrError("nfmr_handle needs ground-truth transforms (rot / trans) in the pairs")
+    rot, trans = handle_poses(handle, "nfmr_handle")
     if len(metric_index_list) != B:
         raise L.RoitrError(f"nfmr_handle: {len(metric_index_list)} metric index lists for {B} pairs")
     dev = out["pair_starts"].device
-    f32, i32 = torch.float32, torch.int32
-    def offsets(ns):
-        return torch.tensor(np.concatenate([[0], np.cumsum(ns)]).astype(np.int32), device=dev)
+    f32 = torch.float32
     raw = torch.cat([p["src_raw_pcd"].to(f32) for p in pairs], 0)
     deformed = torch.cat([p["src_pcd"].to(f32) for p in pairs], 0)
     index = torch.cat([torch.as_tensor(m).reshape(-1).to(device=dev, dtype=torch.int64) for m in metric_index_list], 0)
-    rot = torch.stack([p["rot"].reshape(3, 3).to(f32) for p in pairs])
-    trans = torch.stack([p["trans"].reshape(3).to(f32) for p in pairs])
     rows = int(handle["starts"][-1]) if "starts" in handle else int(out["out_src_pts"].shape[0])   # the buffers are sized for the worst case
-    return nfmr_batch(offsets([int(p["src_raw_pcd"].shape[0]) for p in pairs]), raw, deformed, out["pair_starts"],
-                      out["out_src_pts"][:rows], out["out_tgt_pts"][:rows], offsets([int(torch.as_tensor(m).numel()) for m in metric_index_list]),
+    return nfmr_batch(A.cumulative(handle["n_all"][:B], dev), raw, deformed, out["pair_starts"], out["out_src_pts"][:rows],
+                      out["out_tgt_pts"][:rows], A.cumulative([int(torch.as_tensor(m).numel()) for m in metric_index_list], dev),
                       index, rot, trans, **kw)

@@ -12,29 +12,17 @@ d2 < radius^2, strictly, with radius taken as fp32.  Open3D's KD-tree may decide
 unpinned.  No CPU fallback.
 """
 import collections
-import ctypes
 
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib as L
+from .riga import handle_layout, handle_poses
 
 STATUS_NONFINITE, STATUS_EMPTY, STATUS_OVERFLOW = 1, 2, 4
 
 PairGroundTruth = collections.namedtuple("PairGroundTruth", "overlap_src overlap_tgt n_src_hit n_tgt_hit info count nn_idx nn_dist2 status")
-
-
-def _sig():
-    lib = L.lib()
-    if getattr(lib, "_pg_sig", False):
-        return lib
-    P, I = ctypes.c_void_p, ctypes.c_int
-    lib.roitr_pairgt_workspace_bytes.restype = ctypes.c_size_t
-    lib.roitr_pairgt_workspace_bytes.argtypes = [I, I, I, ctypes.c_longlong]
-    lib.roitr_pairgt_stats.argtypes = [I, I, I, P, P, P, P, P, P, ctypes.c_float, I, P, P, P, P, P, P, P, P, P]
-    lib.roitr_pairgt_correspondences.argtypes = [I, I, I, P, P, P, P, P, P, ctypes.c_float, I, ctypes.c_longlong, P, P, P, P, P, P]
-    lib._pg_sig = True
-    return lib
 
 
 def _check_offsets(name, offset, rows):
@@ -48,12 +36,9 @@ def _check_offsets(name, offset, rows):
 
 
 def _inputs(src, src_offset, tgt, tgt_offset, rot, trans):
-    for t in (src, tgt):
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise L.RoitrError("roitr_amd.pairgt needs ROCm device tensors (no CPU fallback)")
+    src, tgt = A.dev(src, torch.float32, "pairgt").reshape(-1, 3), A.dev(tgt, torch.float32, "pairgt").reshape(-1, 3)
     dev = src.device
-    src = src.to(torch.float32).reshape(-1, 3).contiguous()
-    tgt = tgt.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    tgt = tgt.to(dev)
     _check_offsets("src_offset", src_offset, int(src.shape[0]))
     _check_offsets("tgt_offset", tgt_offset, int(tgt.shape[0]))
     so = torch.as_tensor(src_offset).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
@@ -68,10 +53,6 @@ def _inputs(src, src_offset, tgt, tgt_offset, rot, trans):
     return src, so, tgt, to, rot, trans, B, dev
 
 
-def _ws(lib, B, n, m, capacity, dev):
-    return torch.empty((max(int(lib.roitr_pairgt_workspace_bytes(B, n, m, capacity)), 1),), dtype=torch.uint8, device=dev)
-
-
 def _stats(lib, src, so, tgt, to, rot, trans, radius, inverse, want_info, B, dev):
     n, m = int(src.shape[0]), int(tgt.shape[0])
     count = torch.empty((n,), dtype=torch.int32, device=dev)
@@ -81,7 +62,7 @@ def _stats(lib, src, so, tgt, to, rot, trans, radius, inverse, want_info, B, dev
     overlap = torch.empty((B,), dtype=torch.float64, device=dev)
     info = torch.empty((B, 6, 6), dtype=torch.float64, device=dev) if want_info else None
     status = torch.empty((B,), dtype=torch.int32, device=dev)
-    ws = _ws(lib, B, n, m, 0, dev)
+    ws = A.workspace(lib.roitr_pairgt_workspace_bytes(B, n, m, 0), dev)
     L.check(lib.roitr_pairgt_stats(B, n, m, src.data_ptr(), so.data_ptr(), tgt.data_ptr(), to.data_ptr(), rot.data_ptr(), trans.data_ptr(),
                                    float(radius), int(inverse), count.data_ptr(), nn_idx.data_ptr(), nn_d2.data_ptr(), n_hit.data_ptr(),
                                    overlap.data_ptr(), None if info is None else info.data_ptr(), status.data_ptr(), ws.data_ptr(),
@@ -105,7 +86,7 @@ def pair_ground_truth(src, src_offset, tgt, tgt_offset, rot, trans, radius, both
       status (B) int32: bit 1 a non-finite coordinate or transform, bit 2 an empty cloud: such a pair has no correspondences and
         nan ratios (both sides' bits are merged)."""
     src, so, tgt, to, rot, trans, B, dev = _inputs(src, src_offset, tgt, tgt_offset, rot, trans)
-    lib = _sig()
+    lib = L.lib()
     count, nn_idx, nn_d2, n_hit, overlap, info, status = _stats(lib, src, so, tgt, to, rot, trans, radius, 0, True, B, dev)
     ov_t = hit_t = None
     if both_sides:
@@ -117,13 +98,13 @@ def pair_ground_truth(src, src_offset, tgt, tgt_offset, rot, trans, radius, both
 def correspondences_once(src, so, tgt, to, rot, trans, radius, K, capacity, B, dev):
     """One roitr_pairgt_correspondences call with a candidate buffer of `capacity` entries on prepared inputs: (corr (capacity,2),
     corr_offset (B), rows, needed, status) with rows / needed read back from the device (the one host read)."""
-    lib = _sig()
+    lib = L.lib()
     n, m = int(src.shape[0]), int(tgt.shape[0])
     corr = torch.empty((capacity, 2), dtype=torch.int32, device=dev)
     corr_offset = torch.empty((B,), dtype=torch.int32, device=dev)
     total = torch.empty((2,), dtype=torch.int64, device=dev)
     status = torch.empty((B,), dtype=torch.int32, device=dev)
-    ws = _ws(lib, B, n, m, capacity, dev)
+    ws = A.workspace(lib.roitr_pairgt_workspace_bytes(B, n, m, capacity), dev)
     L.check(lib.roitr_pairgt_correspondences(B, n, m, src.data_ptr(), so.data_ptr(), tgt.data_ptr(), to.data_ptr(), rot.data_ptr(),
                                              trans.data_ptr(), float(radius), 0 if K is None else int(K), capacity, corr.data_ptr(),
                                              corr_offset.data_ptr(), total.data_ptr(), status.data_ptr(), ws.data_ptr(),
@@ -156,11 +137,8 @@ def radius_correspondences(src, src_offset, tgt, tgt_offset, rot, trans, radius,
 def get_correspondences(src_pcd, tgt_pcd, trans, search_voxel_size, K=None):
     """lib/utils.py:72-96 with (N,3) arrays or tensors in place of Open3D clouds and `trans` the 4x4 source-to-target transform:
     the (?, 2) int64 tensor of (source index, target index) with the target within search_voxel_size of the moved source point."""
-    def dev32(x):
-        t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-        if torch.is_tensor(x) and not x.is_cuda:
-            raise L.RoitrError("roitr_amd.pairgt needs ROCm device tensors (no CPU fallback)")
-        return t.to(device="cuda", dtype=torch.float32).reshape(-1, 3).contiguous()
+    def dev32(x):   # numpy arrays are uploaded, host tensors refused
+        return (A.dev(x, torch.float32, "get_correspondences") if torch.is_tensor(x) else A.upload(x)).reshape(-1, 3)
     src, tgt = dev32(src_pcd), dev32(tgt_pcd)
     T = torch.as_tensor(np.asarray(trans.detach().cpu() if torch.is_tensor(trans) else trans, dtype=np.float64).reshape(4, 4))
     off = lambda t: torch.tensor([t.shape[0]], dtype=torch.int32, device=src.device)
@@ -172,16 +150,11 @@ def get_correspondences(src_pcd, tgt_pcd, trans, search_voxel_size, K=None):
 def handle_clouds(handle):
     """(src, src_offset, tgt, tgt_offset, rot, trans) of a RIGA_v2.launch_batch() handle: the clouds the model was fed and the
     ground-truth transforms of its pairs."""
-    if not handle["have_gt"]:
-        raise L.RoitrError("pairgt_handle needs ground-truth transforms (rot / trans) in the pairs")
-    B, sizes = handle["B"], handle["n_all"]
-    pts = handle["keep"][1]
-    o = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    dev = pts.device
-    src, tgt = pts[:int(o[B])], pts[int(o[B]):int(o[2 * B])]
-    src_off = torch.tensor(o[1:B + 1].astype(np.int32), device=dev)
-    tgt_off = torch.tensor((o[B + 1:2 * B + 1] - o[B]).astype(np.int32), device=dev)
-    return src, src_off, tgt, tgt_off, handle["keep"][4].reshape(B, 3, 3), handle["keep"][5].reshape(B, 3)
+    rot, trans = handle_poses(handle, "pairgt_handle")
+    pts, src_starts, tgt_starts = handle_layout(handle, "point")
+    B = handle["B"]
+    n_src = sum(handle["n_all"][:B])
+    return pts[:n_src], src_starts[1:], pts[n_src:], tgt_starts[1:] - n_src, rot.reshape(B, 3, 3), trans.reshape(B, 3)
 
 
 def pairgt_handle(handle, radius, both_sides=True):

@@ -14,6 +14,7 @@ import ctypes
 
 import torch
 
+from . import _args as A
 from . import _lib as L
 from .pointops import GRID_MIN_POINTS
 
@@ -28,9 +29,7 @@ def estimate_normals(xyz, offset, knn=33, view_point=(0.0, 0.0, 0.0), use_grid=N
 
     view_point=None keeps the unoriented PCA direction (Open3D's sign is arbitrary); otherwise the result equals
     normal_redirect(points, open3d_normals, view_point)."""
-    if not xyz.is_cuda:
-        raise L.RoitrError("roitr_amd.prep needs ROCm device tensors (no CPU fallback)")
-    xyz = xyz.contiguous().float()
+    xyz = A.dev(xyz, torch.float32, "estimate_normals")
     offset = offset.to(torch.int32).contiguous()
     n, b = int(xyz.shape[0]), int(offset.shape[0])
     out = torch.empty((n, 3), dtype=torch.float32, device=xyz.device)
@@ -39,7 +38,6 @@ def estimate_normals(xyz, offset, knn=33, view_point=(0.0, 0.0, 0.0), use_grid=N
     if use_grid is None:
         use_grid = n > GRID_MIN_POINTS * b
     lib = L.lib()
-    lib.roitr_normals_workspace_bytes.restype = ctypes.c_size_t
     ws = torch.empty(lib.roitr_normals_workspace_bytes(b, n, int(knn)), dtype=torch.uint8, device=xyz.device)
     vp = _vp(view_point) if view_point is not None else None
     L.check(lib.roitr_estimate_normals(b, n, L.ptr(xyz), L.ptr(offset), int(knn), 1 if use_grid else 0, vp, L.ptr(out), L.ptr(ws),
@@ -49,9 +47,7 @@ def estimate_normals(xyz, offset, knn=33, view_point=(0.0, 0.0, 0.0), use_grid=N
 
 def normal_redirect(points, normals, view_point):
     """dataset/common.py:312-320: make the normals point towards the view point."""
-    if not points.is_cuda:
-        raise L.RoitrError("roitr_amd.prep needs ROCm device tensors (no CPU fallback)")
-    points, normals = points.contiguous().float(), normals.contiguous().float()
+    points, normals = A.dev(points, torch.float32, "normal_redirect"), normals.contiguous().float()
     out = torch.empty_like(normals)
     L.check(L.lib().roitr_normal_redirect(int(points.shape[0]), L.ptr(points), L.ptr(normals), _vp(view_point), L.ptr(out), L.stream_ptr()),
             "normal_redirect")
@@ -74,9 +70,7 @@ def voxel_down_sample(xyz, offset, voxel_size, attr=None, strict=True):
       a voxel index above 65535, bit 2 = a non-finite coordinate; such a cloud yields no voxels and inverse = -1.
     strict: raise RoitrError naming the first cloud with a status bit.  One host read (the total, to slice the capacity buffers; the
     status words travel with it)."""
-    if not xyz.is_cuda:
-        raise L.RoitrError("roitr_amd.prep needs ROCm device tensors (no CPU fallback)")
-    xyz = xyz.contiguous().float()
+    xyz = A.dev(xyz, torch.float32, "voxel_down_sample")
     offset = offset.to(device=xyz.device, dtype=torch.int32).contiguous()
     n, b = int(xyz.shape[0]), int(offset.shape[0])
     c = 0
@@ -91,7 +85,6 @@ def voxel_down_sample(xyz, offset, voxel_size, attr=None, strict=True):
     tail = torch.empty((2 * b,), dtype=torch.int32, device=dev)   # new_offset, status: one host read for both
     new_offset, status = tail[:b], tail[b:]
     lib = L.lib()
-    lib.roitr_voxel_workspace_bytes.restype = ctypes.c_size_t
     ws = torch.empty(lib.roitr_voxel_workspace_bytes(b, n, c), dtype=torch.uint8, device=dev)
     L.check(lib.roitr_voxel_downsample(b, n, L.ptr(xyz), L.ptr(offset), ctypes.c_double(float(voxel_size)), c, L.ptr(attr), L.ptr(out_xyz),
                                        L.ptr(new_offset), L.ptr(counts), L.ptr(inverse), L.ptr(out_attr), L.ptr(status), L.ptr(ws),
@@ -114,9 +107,7 @@ def random_subsample(offset, limit, seed=0, cloud_keys=None):
     idx: the kept GLOBAL rows (int32), ascending -- the reference's np.random.permutation(n)[:points_lim] keeps permutation order and
     its stream cannot be reproduced on a device; the distribution of the kept set is the same.  cloud_keys (b ints): k per cloud
     (default: the cloud's position); the selection depends on (seed, k, cloud size, limit) only, not on the rest of the call."""
-    if not offset.is_cuda:
-        raise L.RoitrError("roitr_amd.prep needs ROCm device tensors (no CPU fallback)")
-    offset = offset.to(torch.int32).contiguous()
+    offset = A.dev(offset, torch.int32, "random_subsample")
     dev = offset.device
     b = int(offset.shape[0])
     keys = None
@@ -129,7 +120,6 @@ def random_subsample(offset, limit, seed=0, cloud_keys=None):
     idx = torch.empty((n,), dtype=torch.int32, device=dev)
     new_offset = torch.empty((b,), dtype=torch.int32, device=dev)
     lib = L.lib()
-    lib.roitr_subsample_workspace_bytes.restype = ctypes.c_size_t
     ws = torch.empty(lib.roitr_subsample_workspace_bytes(b, n), dtype=torch.uint8, device=dev)
     L.check(lib.roitr_random_subsample(b, n, L.ptr(offset), int(limit), ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), L.ptr(keys),
                                        L.ptr(idx), L.ptr(new_offset), L.ptr(ws), L.stream_ptr()), "random_subsample")

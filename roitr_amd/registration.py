@@ -10,33 +10,15 @@ Differences from the reference, by design: the iteration count is fixed (50 000,
 function of (seed, pair key, iteration), so a pair's pose does not depend on the batch it travels in; weighted sampling of fewer
 positive-confidence rows than n_points takes all of them (numpy's choice raises there).  Parity with Open3D itself is unpinned.
 """
-import ctypes
 import math
 
 import numpy as np
 import torch
 
+from . import _args as A
 from . import _lib as L
 
 SAMPLE_MODES = {"all": 0, "topk": 1, "weighted": 2}
-
-
-def _sig():
-    lib = L.lib()
-    if getattr(lib, "_rg_sig", False):
-        return lib
-    lib.roitr_registration_workspace_bytes.restype = ctypes.c_size_t
-    lib.roitr_registration_workspace_bytes.argtypes = [ctypes.c_int] * 4
-    lib.roitr_ransac_correspondences.argtypes = (
-        [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-         ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64,
-         ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_void_p] * 7)
-    lib.roitr_ransac_samples.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_void_p, ctypes.c_void_p]
-    lib.roitr_weighted_procrustes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                              ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
-    lib._rg_sig = True
-    return lib
 
 
 def _keys(pair_keys, B, dev):
@@ -48,10 +30,6 @@ def _keys(pair_keys, B, dev):
             raise L.RoitrError(f"pair_keys: {k.numel()} keys for {B} pairs")
     k = k & 0xFFFFFFFF
     return torch.where(k >= 2 ** 31, k - 2 ** 32, k).to(torch.int32).to(dev)   # the uint32 bit pattern
-
-
-def _f32(t, dev):
-    return torch.as_tensor(t).to(device=dev, dtype=torch.float32).contiguous()
 
 
 @torch.no_grad()
@@ -70,16 +48,16 @@ def ransac_batch(starts, src_pts, tgt_pts, scores=None, *, n_points=1000, sample
     dev = src_pts.device if src_pts.is_cuda else torch.device("cuda")
     starts = torch.as_tensor(starts).to(device=dev, dtype=torch.int32).contiguous()
     B = int(starts.shape[0]) - 1
-    src = _f32(src_pts, dev).reshape(-1, 3)
-    tgt = _f32(tgt_pts, dev).reshape(-1, 3)
+    src = A.upload(src_pts, device=dev).reshape(-1, 3)
+    tgt = A.upload(tgt_pts, device=dev).reshape(-1, 3)
     if src.shape != tgt.shape:
         raise ValueError("src_pts and tgt_pts must have the same shape")
-    w = None if scores is None else _f32(scores, dev).reshape(-1)
+    w = None if scores is None else A.upload(scores, device=dev).reshape(-1)
     rows = int(src.shape[0])
     if w is not None and int(w.shape[0]) != rows:
         raise ValueError("scores must have one entry per row")
     keys = _keys(pair_keys, max(B, 0), dev)
-    lib = _sig()
+    lib = L.lib()
     Bc = max(B, 0)
     out = dict(T=torch.empty((Bc, 4, 4), dtype=torch.float32, device=dev),
                inliers=torch.empty((Bc,), dtype=torch.int32, device=dev),
@@ -88,7 +66,7 @@ def ransac_batch(starts, src_pts, tgt_pts, scores=None, *, n_points=1000, sample
                n_used=torch.empty((Bc,), dtype=torch.int32, device=dev),
                selected=torch.full((rows,), -1, dtype=torch.int32, device=dev))
     nbytes = int(lib.roitr_registration_workspace_bytes(Bc, rows, max(int(iterations), 1), int(chunks))) if Bc > 0 else 0
-    ws = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+    ws = A.workspace(nbytes, dev)
     L.check(lib.roitr_ransac_correspondences(
         B, L.ptr(starts).value, rows, src.data_ptr(), tgt.data_ptr(), None if w is None else w.data_ptr(), keys.data_ptr(),
         SAMPLE_MODES[sample], int(n_points), int(ransac_n), float(distance_threshold), float(edge_similarity), int(iterations),
@@ -107,8 +85,8 @@ def ransac_samples(n, pair_keys=None, seed=0, it0=0, count=1):
     B = int(n.shape[0])
     keys = _keys(pair_keys, B, dev)
     out = torch.empty((B, int(count), 3), dtype=torch.int32, device=dev)
-    L.check(_sig().roitr_ransac_samples(B, n.data_ptr(), keys.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF, int(it0), int(count),
-                                        out.data_ptr(), L.stream_ptr().value), "ransac_samples")
+    L.check(L.lib().roitr_ransac_samples(B, n.data_ptr(), keys.data_ptr(), int(seed) & 0xFFFFFFFFFFFFFFFF, int(it0), int(count),
+                                         out.data_ptr(), L.stream_ptr().value), "ransac_samples")
     return out
 
 
@@ -135,8 +113,7 @@ def ransac_pose_estimation_correspondences(src_pcd, tgt_pcd, correspondences, mu
     corr = corr.reshape(-1, 2)
     s, t = src[corr[:, 0]], tgt[corr[:, 1]]
     dev = torch.device("cuda")
-    starts = torch.tensor([0, s.shape[0]], dtype=torch.int32, device=dev)
-    r = ransac_batch(starts, torch.from_numpy(s).to(dev), torch.from_numpy(t).to(dev), None, sample="all",
+    r = ransac_batch(A.cumulative([s.shape[0]], dev), torch.from_numpy(s).to(dev), torch.from_numpy(t).to(dev), None, sample="all",
                      distance_threshold=distance_threshold, ransac_n=ransac_n, iterations=iterations, seed=seed)
     return r["T"][0].cpu().numpy().astype(np.float64)
 
@@ -155,16 +132,12 @@ def ransac_pose_estimation(src_pcd, tgt_pcd, src_feat, tgt_feat, mutual=False, d
     mutual branch does, where Open3D takes the L2 nearest neighbour in feature space -- the same list for equal-norm descriptors
     (the model's are unit-normalised), not otherwise (descmatch.match_batch(metric="sqdist", mode="row") gives the L2 list)."""
     from . import descmatch
-    dev = torch.device("cuda")
-    def dev32(x):
-        t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-        return t.to(device=dev, dtype=torch.float32).contiguous()
-    src, tgt = dev32(src_pcd).reshape(-1, 3), dev32(tgt_pcd).reshape(-1, 3)
-    sf, tf = dev32(src_feat), dev32(tgt_feat)
+    src, tgt = A.upload(src_pcd).reshape(-1, 3), A.upload(tgt_pcd).reshape(-1, 3)
+    sf, tf = A.upload(src_feat), A.upload(tgt_feat)
     if sf.shape[0] != src.shape[0] or tf.shape[0] != tgt.shape[0]:
         raise L.RoitrError("ransac_pose_estimation: one descriptor per point is needed")
-    ends = lambda n: torch.tensor([0, n], dtype=torch.int32, device=dev)
-    m = descmatch.match_batch(ends(sf.shape[0]), sf, ends(tf.shape[0]), tf, metric="dot", mode="mutual" if mutual else "row")
+    m = descmatch.match_batch(A.cumulative([sf.shape[0]], "cuda"), sf, A.cumulative([tf.shape[0]], "cuda"), tf, metric="dot",
+                              mode="mutual" if mutual else "row")
     corr = m["corr"].long()
     r = ransac_batch(m["corr_starts"], src[corr[:, 0]], tgt[corr[:, 1]], None, sample="all", distance_threshold=distance_threshold,
                      ransac_n=ransac_n, iterations=iterations, seed=seed)
@@ -180,11 +153,11 @@ def weighted_procrustes(src_points, tgt_points, weights=None, weight_thresh=0., 
     w = None if weights is None else (weights.unsqueeze(0) if squeeze else weights)
     dev = src.device if src.is_cuda else torch.device("cuda")
     B, N = int(src.shape[0]), int(src.shape[1])
-    src, tgt = _f32(src, dev), _f32(tgt, dev)
-    w = None if w is None else _f32(w, dev)
+    src, tgt = A.upload(src, device=dev), A.upload(tgt, device=dev)
+    w = None if w is None else A.upload(w, device=dev)
     T = torch.empty((B, 4, 4), dtype=torch.float32, device=dev)
-    L.check(_sig().roitr_weighted_procrustes(B, N, src.data_ptr(), tgt.data_ptr(), None if w is None else w.data_ptr(),
-                                             float(weight_thresh), float(eps), T.data_ptr(), L.stream_ptr().value), "weighted_procrustes")
+    L.check(L.lib().roitr_weighted_procrustes(B, N, src.data_ptr(), tgt.data_ptr(), None if w is None else w.data_ptr(),
+                                              float(weight_thresh), float(eps), T.data_ptr(), L.stream_ptr().value), "weighted_procrustes")
     if return_transform:
         return T.squeeze(0) if squeeze else T
     R, t = T[:, :3, :3].contiguous(), T[:, :3, 3].contiguous()

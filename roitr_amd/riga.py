@@ -17,6 +17,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import _args as A
 from . import _lib as L
 
 
@@ -649,6 +650,36 @@ class RIGA_v2(nn.Module):
         pair = dict(src_pcd=src_pcd, tgt_pcd=tgt_pcd, src_feats=src_feats, tgt_feats=tgt_feats, src_normals=src_normals,
                     tgt_normals=tgt_normals, rot=rot, trans=trans, src_raw_pcd=src_raw_pcd)
         return self.forward_batch([pair])[0]
+
+
+# ---- what the evaluation operators read of a launch_batch() handle.  `keep` is read at call time: finish_batch replaces it when it
+# repeats an overfull call, while the sizes (n_all, n4) the cached starts are built from are those of the pairs and stay.
+def handle_poses(handle, who):
+    """rot (B,3,3) / trans (B,3) fp32 device tensors of a handle's pairs, as the engine was given them."""
+    if not handle["have_gt"]:
+        raise L.RoitrError(f"{who} needs ground-truth transforms (rot / trans) in the pairs")
+    return handle["keep"][4], handle["keep"][5]
+
+
+def handle_starts(handle, which):
+    """(src_starts, tgt_starts) of a handle's "point" rows (point_feats, the clouds the model was fed) or "node" rows (node_feats,
+    node_xyz), which hold src_0 .. src_{B-1}, tgt_0 .. tgt_{B-1}: source pair b owns rows [src_starts[b], src_starts[b + 1]), its target
+    [tgt_starts[b], tgt_starts[b + 1]); both (B + 1) int32 on the device, uploaded once per handle."""
+    if which not in ("point", "node"):
+        raise L.RoitrError(f"which must be 'point' or 'node', got {which!r}")
+    B = handle["B"]
+    if which + "_starts" not in handle:
+        handle[which + "_starts"] = A.cumulative(handle["n_all" if which == "point" else "n4"], handle["out"]["n_corr"].device)
+    o = handle[which + "_starts"]
+    return o[:B + 1], o[B:]
+
+
+def handle_layout(handle, which):
+    """(rows, src_starts, tgt_starts): handle_starts and the coordinates of those rows, the clouds the model was fed (src_pcd then
+    tgt_pcd) for "point", node_xyz for "node"."""
+    src_starts, tgt_starts = handle_starts(handle, which)
+    rows = handle["keep"][1] if which == "point" else handle["out"]["node_xyz"]
+    return rows[:sum(handle["n_all" if which == "point" else "n4"])], src_starts, tgt_starts
 
 
 def create_model(config):

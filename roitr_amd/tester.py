@@ -14,6 +14,7 @@ import os
 
 import torch
 
+from . import _args as A
 from .shard import assemble_block, gather_result_records, pairs_for_rank, slots_per_rank
 
 
@@ -21,6 +22,11 @@ DESC_INLIER_THRESHOLD = 0.1   # registration/benchmark_utils.py:80 get_inlier_ra
 DESC_FMR_THRESHOLD = 0.05   # registration/evaluate_registration_c2f.py:109: a pair counts when its inlier ratio exceeds it
 RECALL_RMSE = 0.2            # registration/benchmark.py:217 evaluate_registration: a pair is registered when p <= 0.2 ** 2
 OVERLAP_BINS = (("overlap_ge_0.3", 0.3, float("inf")), ("overlap_0.1_0.3", 0.1, 0.3), ("overlap_lt_0.1", float("-inf"), 0.1))
+
+
+def _offsets(clouds, device):
+    """The reference's `offset` of a list of clouds: their cumulative ends, int32 on the device."""
+    return A.cumulative([c.shape[0] for c in clouds], device)[1:]
 
 
 def load_pretrain(model, path):
@@ -93,6 +99,14 @@ class Tester:
         self.metrics = None
         self.records = None   # rank 0 after test(): shard.GatheredRecords {pair id: match scores}
 
+    def _all_ranks(self, per_pair):
+        """A per-pair dict (or None: not collected) merged over all ranks; every rank takes part."""
+        if per_pair is None or self.world == 1:
+            return per_pair
+        parts = [None] * self.world
+        torch.distributed.all_gather_object(parts, per_pair)
+        return {k: v for part in parts for k, v in part.items()}
+
     def _to_device(self, item, device):
         out = {}
         for k, v in item.items():
@@ -109,18 +123,14 @@ class Tester:
         renumbered, under the cap (the reference leaves it pointing into the uncapped cloud)."""
         from .prep import random_subsample, voxel_down_sample
         k = len(items)
-
-        def offsets(clouds):
-            return torch.tensor([c.shape[0] for c in clouds]).cumsum(0).to(device=device, dtype=torch.int32)
-
         raw = [it["raw_src_pcd"].float() for it in items]
         deformed = [it["src_points"].float() for it in items]
         tgt = [it["tgt_points"].float() for it in items]
         metric = [it["metric_index"].to(device).long() if torch.is_tensor(it.get("metric_index")) else None for it in items]
         if self.voxel_size is not None:
-            off_in = offsets(raw)
+            off_in = _offsets(raw, device)
             rs = voxel_down_sample(torch.cat(raw), off_in, self.voxel_size, attr=torch.cat(deformed))
-            rt = voxel_down_sample(torch.cat(tgt), offsets(tgt), self.voxel_size)
+            rt = voxel_down_sample(torch.cat(tgt), _offsets(tgt, device), self.voxel_size)
             lo_in, lo_s, lo_t = [0] + off_in.tolist(), [0] + rs.offset.tolist(), [0] + rt.offset.tolist()
             for j in range(k):
                 if metric[j] is not None:
@@ -129,7 +139,7 @@ class Tester:
             deformed = [rs.attr[lo_s[j]:lo_s[j + 1]] for j in range(k)]
             tgt = [rt.points[lo_t[j]:lo_t[j + 1]] for j in range(k)]
         if self.points_lim is not None:
-            off = offsets(raw + tgt)
+            off = _offsets(raw + tgt, device)
             idx, new_off = random_subsample(off, self.points_lim, self.subsample_seed, [2 * i for i in ids] + [2 * i + 1 for i in ids])
             idx, lo, cut = idx.long(), [0] + off.tolist(), [0] + new_off.tolist()
             for j in range(2 * k):
@@ -185,7 +195,7 @@ class Tester:
             if self.estimate_normals:   # one batched call for all clouds of this forward
                 from .prep import estimate_normals
                 clouds = [it["raw_src_pcd"] for it in items] + [it["tgt_points"] for it in items]
-                off = torch.tensor([c.shape[0] for c in clouds], device=device).cumsum(0).to(torch.int32)
+                off = _offsets(clouds, device)
                 nrm = estimate_normals(torch.cat(clouds).float(), off, 33, self.view_point)
                 lo = [0] + off.tolist()
                 for k, it in enumerate(items):
@@ -270,21 +280,8 @@ class Tester:
         per_pair = self.model.record_scores_per_pair()
         self.records = gather_result_records(assemble_block(blocks, slots_per_rank(n, self.world), per_pair, device),
                                              slots_per_rank(n, self.world), per_pair)
-        desc_all = self.descriptor
-        if self.descriptor is not None and self.world > 1:   # every rank takes part: IR / PIR below cover all ranks, so must desc_*
-            parts = [None] * self.world
-            torch.distributed.all_gather_object(parts, self.descriptor)
-            desc_all = {k: v for part in parts for k, v in part.items()}
-        losses_all = self.losses
-        if self.losses is not None and self.world > 1:
-            parts = [None] * self.world
-            torch.distributed.all_gather_object(parts, self.losses)
-            losses_all = {k: v for part in parts for k, v in part.items()}
-        recall_all = self.recall
-        if self.recall is not None and self.world > 1:
-            parts = [None] * self.world
-            torch.distributed.all_gather_object(parts, self.recall)
-            recall_all = {k: v for part in parts for k, v in part.items()}
+        # every rank takes part: IR / PIR below cover all ranks, so must these
+        desc_all, losses_all, recall_all = self._all_ranks(self.descriptor), self._all_ranks(self.losses), self._all_ranks(self.recall)
         if self.records is None:     # ranks other than 0
             return None
         if self.records.truncated:

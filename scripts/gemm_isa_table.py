@@ -1,9 +1,10 @@
-"""Generated-code table of the GEMM family, for A/B reading of a refactor: compiles gemm.hip, gemm_bf16.hip and gemm_x3.hip of two
-source trees to gfx950 assembly (device side only, the flags of roitr_amd/build.py) and prints, per kernel instantiation, registers,
-LDS, scratch, instruction counts by class and whether the K loop (the backward-branch loop with the most MFMAs) is the same
-instruction sequence up to register renaming.  No GPU needed.
+"""Generated-code table of a set of kernel sources, for A/B reading of a refactor: compiles the named files of csrc/ (default: the GEMM
+family, gemm.hip, gemm_bf16.hip and gemm_x3.hip) of two source trees to gfx950 assembly (device side only, the flags of
+roitr_amd/build.py) and prints, per kernel instantiation, registers, LDS, scratch, instruction counts by class and whether the K loop
+(the backward-branch loop with the most MFMAs; empty for a kernel without MFMAs) is the same instruction sequence up to register
+renaming.  No GPU needed.
 
-    python scripts/gemm_isa_table.py PARENT_TREE BRANCH_TREE > profiles/<name>_isa.txt
+    python scripts/gemm_isa_table.py PARENT_TREE BRANCH_TREE [FILE.hip ...] > profiles/<name>_isa.txt
 """
 import os
 import re
@@ -71,15 +72,15 @@ def kernels(text):
 
 
 def main():
-    parent, branch = sys.argv[1], sys.argv[2]
+    parent, branch, files = sys.argv[1], sys.argv[2], tuple(sys.argv[3:]) or FILES
     cols = ["vgpr", "agpr", "sgpr", "lds", "scratch"] + [c for c, _ in CLASSES] + ["insts"]
-    must = ("vgpr", "agpr", "sgpr", "lds", "scratch", "mfma", "gload", "barrier")
-    print("GEMM family, gfx950 device code of the parent and of this tree (hipcc -S --cuda-device-only, the flags of roitr_amd/build.py).")
+    must = cols
+    print("%s: gfx950 device code of the parent and of this tree (hipcc -S --cuda-device-only, the flags of roitr_amd/build.py)." % ", ".join(files))
     print("Per kernel: parent -> branch where a figure differs.  kloop: the backward-branch loop with the most MFMAs, compared as an")
-    print("instruction sequence with register numbers erased.  `required` = registers, LDS, scratch, MFMA / global-load / barrier counts.\n")
+    print("instruction sequence with register numbers erased.  `required` = registers, LDS, scratch and every instruction count.\n")
     verdict = True
     with tempfile.TemporaryDirectory() as tmp:
-        for f in FILES:
+        for f in files:
             os.makedirs(os.path.join(tmp, "p"), exist_ok=True)
             os.makedirs(os.path.join(tmp, "b"), exist_ok=True)
             kp, kb = kernels(assembly(parent, f, os.path.join(tmp, "p"))), kernels(assembly(branch, f, os.path.join(tmp, "b")))

@@ -179,12 +179,11 @@ def test_selection_modes_and_capacity():
         assert np.array_equal(cut.cpu().numpy(), corr[:need - 1])
     # nothing beyond the capacity is written: the raw entry point on a guarded buffer
     from roitr_amd import _lib as L
-    from roitr_amd.descmatch import _sig
     guard = torch.full((need + 8, 2), -7, dtype=torch.int32, device="cuda")
     st = torch.empty((4,), dtype=torch.int32, device="cuda")
     n_out = torch.empty((1,), dtype=torch.int32, device="cuda")
-    L.check(_sig().roitr_desc_match_select(3, so.data_ptr(), to.data_ptr(), r["row_idx"].data_ptr(), r["col_idx"].data_ptr(), 2,
-                                           st.data_ptr(), guard.data_ptr(), need - 1, n_out.data_ptr(), L.stream_ptr().value), "select")
+    L.check(L.lib().roitr_desc_match_select(3, so.data_ptr(), to.data_ptr(), r["row_idx"].data_ptr(), r["col_idx"].data_ptr(), 2,
+                                            st.data_ptr(), guard.data_ptr(), need - 1, n_out.data_ptr(), L.stream_ptr().value), "select")
     g = guard.cpu().numpy()
     assert int(n_out.item()) == need and np.array_equal(g[:need - 1], corr[:need - 1]) and (g[need - 1:] == -7).all()
 
@@ -262,8 +261,8 @@ def test_ransac_pose_estimation_recovers_a_planted_pose():
 
 def test_refusals():
     from roitr_amd import _lib as L
-    from roitr_amd.descmatch import _sig, match_batch, select
-    lib = _sig()
+    from roitr_amd.descmatch import match_batch, select
+    lib = L.lib()
     UNSUPPORTED, ARG = 3, 1   # csrc/common.h ROITR_ERR_UNSUPPORTED / ROITR_ERR_ARG
     i32, f32 = torch.int32, torch.float32
     off = torch.tensor([0, 8], dtype=i32, device="cuda")

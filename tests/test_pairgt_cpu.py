@@ -153,8 +153,8 @@ def test_host_offsets_are_checked(offset):
 def test_host_side_errors_launch_nothing():
     """radius, K, B and null pointers are checked before anything touches a device: these calls return the argument status here."""
     import ctypes
-    from roitr_amd import pairgt
-    lib = pairgt._sig()
+    from roitr_amd import _lib
+    lib = _lib.lib()
     one = ctypes.c_void_p(256)   # never dereferenced
     stats = lambda b, r, status=one: lib.roitr_pairgt_stats(b, 4, 4, one, one, one, one, one, one, r, 0, None, None, None, one, one, None,
                                                             status, one, None)

@@ -348,7 +348,7 @@ def test_outputs_written_only_for_live_pairs():
     ints = [torch.full((B + 2,), -7, dtype=torch.int32, device="cuda") for _ in range(4)]
     sel = torch.full((rows + 5,), -7, dtype=torch.int32, device="cuda")
     keys = torch.arange(B, dtype=torch.int32, device="cuda")
-    lib = G._sig()
+    lib = L.lib()
     nb = int(lib.roitr_registration_workspace_bytes(B, rows, 2000, 0))
     ws = torch.empty((nb,), dtype=torch.uint8, device="cuda")
     L.check(lib.roitr_ransac_correspondences(B, st.data_ptr(), rows, src.data_ptr(), tgt.data_ptr(), None, keys.data_ptr(), 2, 100, 3,
