@@ -99,7 +99,7 @@ int roitr_add_vectors(int n, const float* a, const float* b, float* out, roitr_s
  * dist2 = SQUARED distances as produced by the kNN call. */
 int roitr_interp3_add(int n, int C, const float* feat, const int* idx, const float* dist2, const float* base, float* out,
                       roitr_stream_t stream);
-/* per-cloud feature mean (model/model.py:101-109) */
+/* per-cloud feature mean (model/model.py:101-109); offset (b) cumulative cloud ends, no cloud empty; compensated fp32 sum over the rows */
 int roitr_segment_mean(int b, int C, const float* x, const int* offset, float* out, roitr_stream_t stream);
 /* SinusoidalPositionalEmbedding (positional_encoding.py:38-62): out (rows, C) */
 int roitr_sinusoid(long rows, int C, const float* vals, const float* div_term, float* out, roitr_stream_t stream);

@@ -18,7 +18,8 @@ class RoitrError(RuntimeError):
 
 # The entry points of the evaluation and preparation modules (registration, nonrigid, descmatch, loss, pairgt, prep, evaluate): their
 # restype / argtypes are read from the prototypes of include/*.h at load, so a call cannot disagree with the header about a type.
-# (The calls of the timed path -- ops, pointops, riga -- convert their arguments themselves.)
+# (The calls of the timed path -- ops, pointops, riga -- convert their arguments themselves.)  The last two lines: the row-wise layers and
+# the positional fold behind the operator wrappers of ops.py, whose prototypes mix `long rows`, `int n` and a by-value `float eps`.
 BOUND = ("roitr_registration_workspace_bytes roitr_ransac_correspondences roitr_ransac_samples roitr_weighted_procrustes "
          "roitr_nfmr_workspace_bytes roitr_nfmr_batch roitr_blend_anchor_motion "
          "roitr_desc_match_workspace_bytes roitr_desc_match_batch roitr_desc_match_select "
@@ -26,7 +27,9 @@ BOUND = ("roitr_registration_workspace_bytes roitr_ransac_correspondences roitr_
          "roitr_pairgt_workspace_bytes roitr_pairgt_stats roitr_pairgt_correspondences "
          "roitr_normals_workspace_bytes roitr_estimate_normals roitr_normal_redirect "
          "roitr_voxel_workspace_bytes roitr_voxel_downsample roitr_subsample_workspace_bytes roitr_random_subsample "
-         "roitr_inlier_counts roitr_coarse_hits").split()
+         "roitr_inlier_counts roitr_coarse_hits "
+         "roitr_build_pfold roitr_add_layernorm roitr_l2_normalize roitr_segment_mean roitr_interp3_add "
+         "roitr_gather_rows roitr_compose_idx roitr_transpose roitr_add_vectors").split()
 _CTYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t, "long": ctypes.c_long,
            "long long": ctypes.c_longlong, "unsigned long long": ctypes.c_uint64, "unsigned int": ctypes.c_uint,
            "unsigned": ctypes.c_uint, "roitr_stream_t": ctypes.c_void_p, "void": None}

@@ -441,14 +441,24 @@ extern "C" int roitr_local_attention(const RoitrLocalAttn* a, hipStream_t stream
     if (a->M <= 0) return ROITR_OK;
     const int hv = a->H / 64;
     // heads = the 4 DPP rows of a wave; float4 row accesses need 16-byte aligned rows
-    if (a->heads != 4 || a->H % 64 || (a->K != 8 && a->K != 16) || (hv != 1 && hv != 2 && hv != 4 && hv != 8)) return ROITR_ERR_UNSUPPORTED;
+    if (a->heads != 4 || a->H % 64 || (a->K != 8 && a->K != 16) || (hv != 1 && hv != 2 && hv != 4 && hv != 8)) {
+        roitr_set_error("local_attention: heads must be 4, K 8 or 16, H 64, 128, 256 or 512", __FILE__, __LINE__);
+        return ROITR_ERR_UNSUPPORTED;
+    }
     const bool half = a->bf16 != 0;
-    if (half && a->bf16 != 3) return ROITR_ERR_UNSUPPORTED;   // bf16 rows in AND out, or fp32 both
-    if (!half && hv > 1 && ((a->ldq | a->ldk | a->ldv | a->ldo) % (hv > 4 ? 4 : hv) || ((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out) % 16))
+    if (half && a->bf16 != 3) {   // bf16 rows in AND out, or fp32 both
+        roitr_set_error("local_attention: bf16 must be 0 (fp32 rows) or 3 (q / k / v and output rows stored in bf16)", __FILE__, __LINE__);
         return ROITR_ERR_UNSUPPORTED;
+    }
+    if (!half && hv > 1 && ((a->ldq | a->ldk | a->ldv | a->ldo) % (hv > 4 ? 4 : hv) || ((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out) % 16)) {
+        roitr_set_error("local_attention: fp32 rows of H > 64 need ldq / ldk / ldv / ldo multiples of min(H / 64, 4) floats and 16-byte aligned q / k / v / out", __FILE__, __LINE__);
+        return ROITR_ERR_UNSUPPORTED;
+    }
     // bf16 rows: a lane reads HV bf16 = 2 HV bytes in pieces of at most 8 -> rows and bases aligned to min(2 HV, 8) bytes
-    if (half && (((a->ldq | a->ldk | a->ldv | a->ldo) * 2) % (hv >= 4 ? 8 : 2 * hv) || ((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out) % 8))
+    if (half && (((a->ldq | a->ldk | a->ldv | a->ldo) * 2) % (hv >= 4 ? 8 : 2 * hv) || ((uintptr_t)a->q | (uintptr_t)a->k | (uintptr_t)a->v | (uintptr_t)a->out) % 8)) {
+        roitr_set_error("local_attention: bf16 rows need ldq / ldk / ldv / ldo multiples of min(H / 64, 4) elements and 8-byte aligned q / k / v / out", __FILE__, __LINE__);
         return ROITR_ERR_UNSUPPORTED;
+    }
     // algorithmic bytes: q row + K gathered k and v rows + ppf + idx in, one row out
     roitr_prof_begin(ROITR_PROF_LOCAL_ATTN, (double)a->M * ((a->H + 20.0) * 4 + a->K * (2.0 * a->H * 4 + 20.0) + a->H * 4.0), stream);
 #define LA_LAUNCH(KK, HH, NN)                                                                                             \

@@ -136,9 +136,23 @@ __global__ __launch_bounds__(256) void segment_mean_kernel(int C, const float* _
 {
     const int b = blockIdx.x;
     const int s = b == 0 ? 0 : offset[b - 1], e = offset[b];
+    // compensated (Kahan) sum: a plain running fp32 sum of n rows is only good to (n - 1) 2^-24 sum |x| -- measured 1.04 x the
+    // 2^-23 sum |x| the mean is held to (tests/test_rowwise_gpu.py) at 255 rows already, and a cloud has as many rows as it has nodes
     for (int c = threadIdx.x; c < C; c += 256) {
-        float acc = 0.f;
-        for (int r = s; r < e; ++r) acc += x[(size_t)r * C + c];
+        float acc = 0.f, lost = 0.f;
+        auto add = [&](float v) {
+            const float y = v - lost;
+            const float t = acc + y;
+            lost = (t - acc) - y;
+            acc = t;
+        };
+        const float* xc = x + c;
+        int r = s;
+        for (; r + 4 <= e; r += 4) {   // four loads in flight; the rows still enter the sum one after the other
+            const float v0 = xc[(size_t)r * C], v1 = xc[(size_t)(r + 1) * C], v2 = xc[(size_t)(r + 2) * C], v3 = xc[(size_t)(r + 3) * C];
+            add(v0); add(v1); add(v2); add(v3);
+        }
+        for (; r < e; ++r) add(xc[(size_t)r * C]);
         out[(size_t)b * C + c] = acc / (float)(e - s);
     }
 }

@@ -392,6 +392,155 @@ def local_attention_fold(x, q, qt, group_idx, ppf, wpe, wvpe, bvpe, node_order=N
     return xbar, vpart
 
 
+class _LocalAttn(ctypes.Structure):
+    _fields_ = [("M", ctypes.c_int), ("K", ctypes.c_int), ("H", ctypes.c_int), ("heads", ctypes.c_int),
+                ("q", ctypes.c_void_p), ("ldq", ctypes.c_int), ("k", ctypes.c_void_p), ("ldk", ctypes.c_int),
+                ("v", ctypes.c_void_p), ("ldv", ctypes.c_int), ("group_idx", ctypes.c_void_p), ("ppf", ctypes.c_void_p),
+                ("wvpe", ctypes.c_void_p), ("bvpe", ctypes.c_void_p), ("scale", ctypes.c_float),
+                ("out", ctypes.c_void_p), ("ldo", ctypes.c_int), ("node_order", ctypes.c_void_p), ("bf16", ctypes.c_int),
+                ("wpe", ctypes.c_void_p), ("bpe", ctypes.c_void_p)]
+
+
+def _attn_rows(t, what, dtype):
+    """Row stride of a 2-D device operand of `dtype` whose rows are contiguous (a column block of a wider buffer is fine)."""
+    if t.dim() != 2 or t.stride(1) != 1 or t.dtype != dtype:
+        raise L.RoitrError(f"local_attention: {what} must be a 2-D {dtype} tensor with contiguous rows")
+    return int(t.stride(0))
+
+
+def local_attention(q, k, v, group_idx, ppf, wvpe, bvpe, wpe=None, bpe=None, ldq=None, ldk=None, ldv=None, ldo=None, bf16=False,
+                    node_order=None, out=None, heads=4, scale=None):
+    """The generic local PPF attention (csrc/local_attn.hip local_attn_kernel / local_attn_quad_kernel; include/roitr_engine.h
+    RoitrLocalAttn; attention.py:152-200 with the positional branch folded).  q (M, >= H) rows of the nodes, k / v (N_in, >= H) rows of the
+    input cloud, group_idx (M, K) int32 rows of k / v, K in {8, 16}, ppf (M, K, 4), wvpe (H, 4), bvpe (H).  wpe (H, 4) / bpe (H) given: the
+    kernel forms the positional score coefficients itself; None: the q rows carry them as 5 x heads extra columns behind the H channels
+    ([Wpe_h^T q_h (4), q_h . bpe_h] per head).  ldq / ldk / ldv / ldo: row strides in elements (default: the tensors' own), so q | k | v may
+    be column blocks of one buffer.  bf16=True: q / k / v are torch.bfloat16 rows and so is the output (RoitrLocalAttn::bf16 = 3).
+    node_order: optional (M, 4) float32 whose last column holds the node index bits.  out: optional preallocated (>= M, >= H) tensor with
+    contiguous rows; only its first H columns of the M node rows are written.  Returns out (M, H)."""
+    dt = torch.bfloat16 if bf16 else torch.float32
+    f = lambda t: None if t is None else t.contiguous().float()
+    sq, sk, sv = _attn_rows(q, "q", dt), _attn_rows(k, "k", dt), _attn_rows(v, "v", dt)
+    group_idx, ppf, wvpe, bvpe, wpe, bpe, no = _i32c(group_idx), f(ppf), f(wvpe), f(bvpe), f(wpe), f(bpe), f(node_order)
+    M, K, H = int(group_idx.shape[0]), int(group_idx.shape[1]), int(wvpe.shape[0])
+    if (wpe is None) != (bpe is None):
+        raise L.RoitrError("local_attention: wpe and bpe are given together or not at all")
+    if int(q.shape[0]) < M or int(q.shape[1]) < (H if wpe is not None else H + 5 * heads) or int(k.shape[1]) < H or int(v.shape[1]) < H:
+        raise L.RoitrError("local_attention: q (M, >= H [+ 5 * heads]), k / v (N_in, >= H)")
+    if out is None:
+        out = torch.empty((M, H), dtype=dt, device=q.device)
+    so = _attn_rows(out, "out", dt)
+    if int(out.shape[0]) < M or int(out.shape[1]) < H:
+        raise L.RoitrError("local_attention: out (>= M, >= H)")
+    a = _LocalAttn()
+    a.M, a.K, a.H, a.heads = M, K, H, int(heads)
+    a.q, a.ldq, a.k, a.ldk, a.v, a.ldv = L.ptr(q), int(sq if ldq is None else ldq), L.ptr(k), int(sk if ldk is None else ldk), L.ptr(v), int(sv if ldv is None else ldv)
+    a.group_idx, a.ppf, a.wvpe, a.bvpe = L.ptr(group_idx), L.ptr(ppf), L.ptr(wvpe), L.ptr(bvpe)
+    a.scale = 1.0 / float(H // heads) ** 0.5 if scale is None else float(scale)
+    a.out, a.ldo, a.node_order = L.ptr(out), int(so if ldo is None else ldo), L.ptr(no)
+    a.bf16 = 3 if bf16 is True else int(bf16)
+    a.wpe, a.bpe = L.ptr(wpe), L.ptr(bpe)
+    L.check(L.lib().roitr_local_attention(ctypes.byref(a), L.stream_ptr()), "local_attention")
+    return out
+
+
+def build_pfold(wpe, bpe, heads=4):
+    """roitr_build_pfold (csrc/local_attn.hip): Pfold (5 * heads, H) with row 5 h + j = Wpe[:, j] (j < 4) / bpe (j = 4) on the channels of
+    head h and zero elsewhere, so that q @ Pfold.T are the extra q columns of RoitrLocalAttn."""
+    wpe, bpe = wpe.contiguous().float(), bpe.contiguous().float()
+    H = int(wpe.shape[0])
+    out = torch.empty((5 * int(heads), H), dtype=torch.float32, device=wpe.device)
+    L.check(L.lib().roitr_build_pfold(H, int(heads), L.ptr(wpe), L.ptr(bpe), L.ptr(out), L.stream_ptr()), "build_pfold")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
+# Row-wise layers (csrc/nn_ops.hip; "row-wise layers" of include/roitr_engine.h)
+# ------------------------------------------------------------------------------------------------
+def _c(t, dt=torch.float32):
+    return None if t is None else t.contiguous().to(dt)
+
+
+def add_layernorm(x, gamma, beta, res=None, res_idx=None, post=None, relu=False, eps=1e-5):
+    """roitr_add_layernorm: [relu](LayerNorm(x + res[res_idx]) * gamma + beta + post) for x (M, C), C <= 1024; res (R, C) with res_idx
+    (M,) int32 rows of it, or (M, C) without; post (M, C).  attention.py:319, model/model.py:138-140."""
+    x, gm, bt, rs, ri, po = _c(x), _c(gamma), _c(beta), _c(res), _c(res_idx, torch.int32), _c(post)
+    M, C = int(x.shape[0]), int(x.shape[1])
+    out = torch.empty_like(x)
+    L.check(L.lib().roitr_add_layernorm(M, C, L.ptr(x), L.ptr(rs), L.ptr(ri), L.ptr(gm), L.ptr(bt), L.ptr(po), int(relu), float(eps),
+                                        L.ptr(out), L.stream_ptr()), "add_layernorm")
+    return out
+
+
+def l2_normalize(x):
+    """roitr_l2_normalize: F.normalize(x, p=2, dim=1) of x (M, C), C <= 1024 (model/RIGA_v2.py:64-65)."""
+    x = _c(x)
+    out = torch.empty_like(x)
+    L.check(L.lib().roitr_l2_normalize(int(x.shape[0]), int(x.shape[1]), L.ptr(x), L.ptr(out), L.stream_ptr()), "l2_normalize")
+    return out
+
+
+def segment_mean(x, offset):
+    """roitr_segment_mean: the mean row of every cloud of x (T, C); offset (b,) int32 cumulative cloud ends, no cloud empty
+    (model/model.py:101-109).  Returns (b, C)."""
+    x, off = _c(x), _c(offset, torch.int32)
+    b, C = int(off.shape[0]), int(x.shape[1])
+    out = torch.empty((b, C), dtype=torch.float32, device=x.device)
+    L.check(L.lib().roitr_segment_mean(b, C, L.ptr(x), L.ptr(off), L.ptr(out), L.stream_ptr()), "segment_mean")
+    return out
+
+
+def interp3_add(feat, idx, dist2, base=None):
+    """roitr_interp3_add: base + the three-nearest-neighbour inverse-distance interpolation of the rows of feat (R, C); idx (n, 3) int32
+    rows of feat, dist2 (n, 3) SQUARED distances, base (n, C) or None (functions/pointops.py:168-182 + model/model.py:116)."""
+    feat, idx, dist2, base = _c(feat), _c(idx, torch.int32), _c(dist2), _c(base)
+    n, C = int(idx.shape[0]), int(feat.shape[1])
+    out = torch.empty((n, C), dtype=torch.float32, device=feat.device)
+    L.check(L.lib().roitr_interp3_add(n, C, L.ptr(feat), L.ptr(idx), L.ptr(dist2), L.ptr(base), L.ptr(out), L.stream_ptr()), "interp3_add")
+    return out
+
+
+def gather_rows(x, idx, limit=0):
+    """roitr_gather_rows: out[r] = x[idx[r]] for x (R, C), idx (rows,) int32; a negative index gives a zero row, and so does an index
+    >= limit when limit > 0 (limit <= 0: every non-negative index must be a row of x)."""
+    x, idx = _c(x), _c(idx, torch.int32)
+    rows, C = int(idx.shape[0]), int(x.shape[1])
+    out = torch.empty((rows, C), dtype=torch.float32, device=x.device)
+    L.check(L.lib().roitr_gather_rows(rows, C, L.ptr(x), L.ptr(idx), int(limit), L.ptr(out), L.stream_ptr()), "gather_rows")
+    return out
+
+
+def compose_idx(outer, inner):
+    """roitr_compose_idx: outer[inner] for int32 index vectors."""
+    outer, inner = _c(outer, torch.int32), _c(inner, torch.int32)
+    out = torch.empty_like(inner)
+    L.check(L.lib().roitr_compose_idx(int(inner.shape[0]), L.ptr(outer), L.ptr(inner), L.ptr(out), L.stream_ptr()), "compose_idx")
+    return out
+
+
+def transpose(x, out=None):
+    """roitr_transpose: x (rows, cols) float32 -> (cols, rows).  x and a preallocated out may be column blocks of wider buffers (contiguous
+    rows; their row strides are the ld_in / ld_out of the call): only the (cols, rows) block of out is written."""
+    rows, cols = int(x.shape[0]), int(x.shape[1])
+    if out is None:
+        out = torch.empty((cols, rows), dtype=torch.float32, device=x.device)
+    for t, shape in ((x, (rows, cols)), (out, (cols, rows))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or t.stride(1) != 1 or t.stride(0) < shape[1]:
+            raise L.RoitrError("transpose: float32 (rows, cols) -> (cols, rows) with contiguous rows")
+    L.check(L.lib().roitr_transpose(rows, cols, L.ptr(x), int(x.stride(0)), L.ptr(out), int(out.stride(0)), L.stream_ptr()), "transpose")
+    return out
+
+
+def add_vectors(a, b):
+    """roitr_add_vectors: a + b over n floats (the bias of a folded layer)."""
+    a, b = _c(a), _c(b)
+    if a.shape != b.shape:
+        raise L.RoitrError("add_vectors: two vectors of one length")
+    out = torch.empty_like(a)
+    L.check(L.lib().roitr_add_vectors(int(a.numel()), L.ptr(a), L.ptr(b), L.ptr(out), L.stream_ptr()), "add_vectors")
+    return out
+
+
 class _LocalTd(ctypes.Structure):
     _fields_ = [("M", ctypes.c_int), ("in_dim", ctypes.c_int), ("H", ctypes.c_int),
                 ("x", ctypes.c_void_p), ("node_idx", ctypes.c_void_p), ("group_idx", ctypes.c_void_p), ("ppf", ctypes.c_void_p),
@@ -480,16 +629,20 @@ class _LocalFirst(ctypes.Structure):
                 ("scale", ctypes.c_float), ("eps", ctypes.c_float), ("out", ctypes.c_void_p)]
 
 
-def local_first(x, group_idx, ppf, w, node_order=None):
+def local_first(x, group_idx, ppf, w, node_order=None, out=None):
     """The first local transformer of the network in its rank-1 form (csrc/local_block.hip local_first_kernel;
     include/roitr_engine.h RoitrLocalFirst).  x (M,) the scalar input feature, group_idx (M, K) int32, K in {8, 16}, ppf (M, K, 4);
-    w: dict of head_consts (64), G (64, 32), zero_bias (64), norm_w, norm_b, wout (64, 64), bout.  Returns (M, 64)."""
+    w: dict of head_consts (64), G (64, 32), zero_bias (64), norm_w, norm_b, wout (64, 64), bout.  Returns (M, 64); a preallocated
+    contiguous float32 `out` (>= M, 64) is written in its first M rows only."""
     f = lambda t: t.contiguous().float()
     x, ppf = f(x), f(ppf)
     group_idx = _i32c(group_idx)
     w = {k: f(v) for k, v in w.items()}
     M, K = int(x.shape[0]), int(group_idx.shape[1])
-    out = torch.empty((M, 64), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((M, 64), dtype=torch.float32, device=x.device)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 2 or out.shape[1] != 64 or out.shape[0] < M:
+        raise L.RoitrError("local_first: out must be a contiguous float32 (>= M, 64) tensor")
     a = _LocalFirst()
     a.M, a.K = M, K
     a.x, a.group_idx, a.ppf = L.ptr(x), L.ptr(group_idx), L.ptr(ppf)

@@ -88,7 +88,8 @@ def _header_struct(name):
 def test_ctypes_mirrors_match_the_header():
     """The ctypes structures of roitr_amd/ops.py, field by field (name, type, order, hence offsets) against include/roitr_engine.h."""
     from roitr_amd import ops
-    for mirror, name in ((ops._NodeCorr, "RoitrNodeCorr"), (ops._OT, "RoitrOT"), (ops._Fine, "RoitrFine"), (ops._Coarse, "RoitrCoarse")):
+    for mirror, name in ((ops._NodeCorr, "RoitrNodeCorr"), (ops._OT, "RoitrOT"), (ops._Fine, "RoitrFine"), (ops._Coarse, "RoitrCoarse"),
+                         (ops._LocalAttn, "RoitrLocalAttn")):
         want = _header_struct(name)
         got = [(f[0], f[1]) for f in mirror._fields_]
         assert got == want, (name, [(a, b) for a, b in zip(got, want) if a != b], len(got), len(want))
@@ -110,7 +111,7 @@ def header_parameter_counts():
 def test_bound_signatures_follow_the_headers():
     from roitr_amd import _lib
     lib, counts = _lib.lib(), header_parameter_counts()
-    assert len(_lib.BOUND) == len(set(_lib.BOUND)) == 26
+    assert len(_lib.BOUND) == len(set(_lib.BOUND)) == 35
     for name in _lib.BOUND:
         fn = getattr(lib, name)
         assert len(fn.argtypes) == counts[name], name
