@@ -584,6 +584,49 @@ int roitr_weighted_procrustes(int batch, int n, const float* src_pts, const floa
                               float eps, float* transforms, roitr_stream_t stream);
 
 
+/* ------------------------------------------------------------------ RANSAC-free registration
+ * GeoTransformer's local-to-global registration (LGR) on the patches of the coarse-to-fine matcher: one pose hypothesis per patch,
+ * verification over all correspondences, iterative reweighted refits.  No random stream.  Pair b owns rows [starts[b], starts[b+1])
+ * of src_pts / tgt_pts (fp32 (N,3)), scores (fp32 (N); NULL = all 1) and row_patch (int32 (N)), the layout
+ * RoitrForwardIO::pair_starts / out_src_pts / out_tgt_pts / out_scores / out_patch has in the strided and in the compacted patch
+ * layout alike: only equality of neighbouring row_patch entries is read.  total_rows >= starts[pairs]; starts are clamped into
+ * [0, total_rows] before anything is read through them.
+ * Parameters: radius (acceptance radius, finite, > 0), min_rows (rows a patch needs to form a hypothesis, >= 3: GeoTransformer's
+ *   correspondence_threshold), steps (number of global solves, >= 1: GeoTransformer's num_refinement_steps, 5 there).
+ * Runs: row r of pair b starts a run when r == starts[b] or row_patch[r] != row_patch[r-1].  A run of at least min_rows rows is a
+ *   hypothesis; hypotheses are numbered in row order.
+ * Solve(rows, w): roitr_weighted_procrustes with weight_thresh 0 and eps 1e-5: centroids cs, ct = sum w p / (sum w + eps),
+ *   H = sum w (s - cs)(t - ct)^T, all sums in float64 on the fp32 inputs, the rotation from rg_solve_rigid (registration_math.h),
+ *   T rounded to fp32.  Residual: rg_dist2 (fp32, fixed FMA order); a row is an inlier when d^2 < radius^2, strictly.
+ * Local stage: T_h = Solve(the rows of run h, their scores).  Verification: count_h = the rows of the pair that are inliers under
+ *   T_h; the winner has the largest count, ties go to the lower hypothesis number.
+ * Global stage: w0 = score x [inlier under T_winner], T1 = Solve(all rows, w0); for k = 1 .. steps - 1: wk = score x [inlier under
+ *   Tk], T(k+1) = Solve(all rows, wk).  A pair without a hypothesis starts from T0 = Solve(all rows, score) instead of T_winner
+ *   (GeoTransformer's degenerate branch) and goes on in the same way.  A solve whose weights sum to 0 keeps the previous transform,
+ *   sets ROITR_LGR_EMPTY_REFIT and ends the loop.
+ * Outputs per pair: transforms (B,4,4) row-major; inliers (count under the final transform); best_hypothesis (-1: none);
+ *   best_first_row (first row of the winning run, local to the pair; -1: none); hypotheses (their number); local_inliers
+ *   (count_winner; the count under T0 in the degenerate branch); status (bits below; a pair without rows: identity, NO_ROWS alone).
+ * Optional outputs (NULL allowed), each of capacity total_rows / min_rows hypotheses: hyp_first_row, hyp_transforms (12 floats
+ *   each: [R | t] row-major 3x4) and hyp_counts; hyp_starts (pairs + 1): pair b's hypotheses are entries [hyp_starts[b],
+ *   hyp_starts[b] + hypotheses[b]) with hyp_starts[b] = starts[b] / min_rows (a pair of n rows has at most n / min_rows hypotheses,
+ *   so the ranges of different pairs never meet and are found without a scan over the pairs; entries between them are not written).
+ * Determinism: a pair's results are bitwise independent of the batch it travels in, of where its rows sit in the arrays, of the
+ *   absolute values in row_patch and of a repeat of the call: every float64 sum is a strided per-lane sum over the row index local
+ *   to the run (16 lanes) or to the pair (256 lanes) followed by a fixed butterfly; the only atomics add integer counts.
+ * The workspace (device, caller-owned) holds at least roitr_lgr_workspace_bytes(pairs, total_rows) bytes (host-only, monotone).
+ * Refusals (ROITR_ERR_ARG, nothing is launched or written): null pointers, a radius not finite and positive, min_rows < 3,
+ *   steps < 1, total_rows < 0, more than 65535 pairs, a short workspace. */
+#define ROITR_LGR_NO_ROWS 1
+#define ROITR_LGR_NO_LOCAL 2
+#define ROITR_LGR_EMPTY_REFIT 4
+size_t roitr_lgr_workspace_bytes(int pairs, int total_rows);
+int roitr_lgr_batch(int pairs, const int* starts, int total_rows, const float* src_pts, const float* tgt_pts, const float* scores,
+                    const int* row_patch, float radius, int min_rows, int steps, void* workspace, size_t workspace_bytes,
+                    float* transforms, int* inliers, int* best_hypothesis, int* best_first_row, int* hypotheses, int* local_inliers,
+                    int* status, int* hyp_starts, int* hyp_first_row, float* hyp_transforms, int* hyp_counts, roitr_stream_t stream);
+
+
 /* ------------------------------------------------------------------ 4DMatch non-rigid evaluation
  * registration/evaluate_fdmatch.py:50-115: NFMR (non-rigid feature matching recall) of every pair of a batch.  Pair b owns points
  * [src_offsets[b], src_offsets[b+1]) of src_raw (the undeformed source) and src_deformed (what the model was fed), both (total_src,

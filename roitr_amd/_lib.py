@@ -77,10 +77,21 @@ def lib():
         for name in ("roitr_engine_create",):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = ctypes.c_void_p
-        protos = header_prototypes()
-        for name in BOUND:
-            getattr(_lib, name).restype, getattr(_lib, name).argtypes = protos[name]
+        _assign(_lib, BOUND)
     return _lib
+
+
+def _assign(handle, names):
+    protos = header_prototypes()
+    for name in names:
+        getattr(handle, name).restype, getattr(handle, name).argtypes = protos[name]
+
+
+def bind(names):
+    """restype / argtypes from the header for a module's own entry points (those not listed in BOUND); returns the library."""
+    handle = lib()
+    _assign(handle, names)
+    return handle
 
 
 def check(status, what=""):

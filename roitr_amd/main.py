@@ -27,7 +27,8 @@ def main():
     ap.add_argument("--evaluate", action="store_true", help="report mean PIR / IR (lib/loss.py Evaluator) computed on the device")
     ap.add_argument("--estimate-normals", action="store_true", help="recompute the normals on the GPU (open3d knn=33 + normal_redirect)")
     ap.add_argument("--register", action="store_true",
-                    help="estimate every pair's pose on the GPU (correspondence RANSAC, registration.py) and save it as est_transform")
+                    help="estimate every pair's pose on the GPU (--estimator: correspondence RANSAC, registration.py, or local-to-global "
+                         "registration, lgr.py) and save it as est_transform")
     ap.add_argument("--nonrigid", action="store_true",
                     help="synthetic 4DMatch-shaped pairs with a real deformation and metric points (synthetic.make_nonrigid_pair); "
                          "with --evaluate on a 4DMatch config the mean NFMR is reported (nonrigid.py)")
@@ -53,6 +54,11 @@ def main():
                          "record at index 0; implies --recall")
     ap.add_argument("--ransac-iterations", type=int, default=50000)
     ap.add_argument("--ransac-points", type=int, default=1000, help="correspondences drawn per pair (probability ~ confidence)")
+    ap.add_argument("--estimator", choices=("ransac", "lgr"), default="ransac",
+                    help="pose estimator of --register: correspondence RANSAC, or RANSAC-free local-to-global registration on the "
+                         "matcher's patches (deterministic, no random stream)")
+    ap.add_argument("--lgr-radius", type=float, default=0.1, help="acceptance radius of the lgr estimator (metres)")
+    ap.add_argument("--lgr-steps", type=int, default=5, help="global reweighted solves of the lgr estimator")
     args = ap.parse_args()
     args.recall = args.recall or args.write_gt is not None
     args.register = args.register or args.recall
@@ -82,7 +88,8 @@ def main():
                     estimate_normals=args.estimate_normals, register=args.register,
                     ransac=dict(iterations=args.ransac_iterations, n_points=args.ransac_points), descriptor_eval=args.descriptor_eval, validate=args.validate,
                     voxel_size=args.voxel_size, points_lim=args.points_lim, subsample_seed=args.subsample_seed,
-                    recall=args.recall, overlap_radius=args.overlap_radius)
+                    recall=args.recall, overlap_radius=args.overlap_radius, estimator=args.estimator,
+                    lgr=dict(radius=args.lgr_radius, steps=args.lgr_steps))
     counts = tester.test()
     if rank == 0 and tester.validation:
         v = tester.validation
@@ -93,7 +100,7 @@ def main():
     if args.descriptor_eval and args.evaluate:
         _print_descriptor(tester.descriptor or {}, world)
     if args.register and args.evaluate:
-        _print_registration(tester.registration, world)
+        _print_registration(tester.registration, world, args.estimator)
     if args.recall and rank == 0 and tester.metrics:
         m = tester.metrics
         print(f"[roitr_amd] registration recall (RMSE <= 0.2 m, overlap radius {args.overlap_radius:g} m) {m['RR']:.4f} over {m['RR_pairs']} "
@@ -119,7 +126,7 @@ def main():
         torch.distributed.destroy_process_group()
 
 
-def _print_registration(reg, world):
+def _print_registration(reg, world, estimator="ransac"):
     """Mean / median RRE and RTE and the share of pairs within 15 deg / 0.3 m, over every rank's pairs (rank 0 prints)."""
     import numpy as np
     rows = [(k,) + v for k, v in sorted(reg.items())]
@@ -132,7 +139,7 @@ def _print_registration(reg, world):
     rre = np.array([r[1] for r in rows])
     rte = np.array([r[2] for r in rows])
     ok = float(np.mean((rre < 15.0) & (rte < 0.3)))
-    print(f"[roitr_amd] registration over {len(rows)} pairs: RRE mean {rre.mean():.3f} deg, median {np.median(rre):.3f} deg; "
+    print(f"[roitr_amd] registration ({estimator}) over {len(rows)} pairs: RRE mean {rre.mean():.3f} deg, median {np.median(rre):.3f} deg; "
           f"RTE mean {rte.mean():.4f} m, median {np.median(rte):.4f} m")
     print(f"[roitr_amd] pairs with RRE < 15 deg and RTE < 0.3 m: {ok:.4f} (a pose-error success rate, not the 3DMatch-protocol "
           "registration recall, which needs the benchmark's gt.info)")

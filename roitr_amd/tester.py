@@ -41,13 +41,17 @@ def load_pretrain(model, path):
 class Tester:
     def __init__(self, config, model, dataset, snapshot_dir="snapshot", pairs_per_forward=8, rank=0, world=1, evaluate=False,
                  estimate_normals=False, view_point=(0.0, 0.0, 0.0), register=False, ransac=None, nonrigid=None, descriptor_eval=False,
-                 validate=False, voxel_size=None, points_lim=None, subsample_seed=0, recall=False, overlap_radius=0.0375):
+                 validate=False, voxel_size=None, points_lim=None, subsample_seed=0, recall=False, overlap_radius=0.0375,
+                 estimator="ransac", lgr=None):
         """evaluate: also compute PIR / IR per pair on the device (lib/loss.py:169-213 Evaluator) and return their means.
         estimate_normals: ignore the dataset's normals and recompute them on the GPU from the points the way the
         reference's dataset code does (open3d estimate_normals(knn=33) + normal_redirect, dataset/tdmatch.py:120-127).
         register: also estimate every pair's pose on the device (registration.register_handle, keyed on the GLOBAL pair id, so the
         poses do not depend on sharding or pairs_per_forward; `ransac` holds its keyword arguments) and save it as `est_transform`
         in the pair's file.  With evaluate as well, `registration` maps this rank's pair ids to (RRE degrees, RTE metres, inliers).
+        estimator: "ransac" (the default, as above) or "lgr": the pose comes from lgr.lgr_handle (local-to-global registration on the
+        matcher's patches: no random stream, so no keys; `lgr` holds its keyword arguments); everything downstream of the pose
+        (est_transform, RRE / RTE, the inlier column, the recall rows) is the same code.
         With evaluate on the 4DMatch / 4DLoMatch benchmark and items that carry `metric_index`, the NFMR of every pair is computed
         on the device (nonrigid.nfmr_handle; `nonrigid` holds its keyword arguments) and `self.nonrigid` maps this rank's pair ids
         to (NFMR, number of metric points); it stays None otherwise.
@@ -86,7 +90,10 @@ class Tester:
         self.evaluate, self.estimate_normals, self.view_point = evaluate or validate, estimate_normals, view_point
         register = register or recall
         self.evaluate = self.evaluate or recall
+        if estimator not in ("ransac", "lgr"):
+            raise ValueError("estimator must be 'ransac' or 'lgr'")
         self.register, self.ransac = register, dict(ransac or {})
+        self.estimator, self.lgr = estimator, dict(lgr or {})
         self.registration = {} if register and self.evaluate else None
         self.recall = {} if recall else None
         self.gt = {} if recall else None
@@ -246,7 +253,11 @@ class Tester:
                 est = None
                 if self.register:
                     from .registration import pose_errors, register_handle
-                    reg = register_handle(handle, pair_keys=ids, **self.ransac)
+                    if self.estimator == "lgr":
+                        from .lgr import lgr_handle
+                        reg = lgr_handle(handle, **self.lgr)
+                    else:
+                        reg = register_handle(handle, pair_keys=ids, **self.ransac)
                     est = reg["T"].cpu()
                     if self.registration is not None:
                         rre, rte = pose_errors(est, torch.stack([p["rot"].reshape(3, 3) for p in pairs]),
