@@ -169,6 +169,50 @@ int roitr_pairgt_correspondences(int b, int n, int m, const float* src, const in
                                  const float* rot, const float* trans, float radius, int k, long long capacity, int* corr,
                                  int* corr_offset, long long* total, int* status, void* ws, roitr_stream_t stream);
 
+/* ------------------------------------------------------------------ ICP pose refinement: point-to-point and point-to-plane
+ * Open3D's RegistrationICP restated on the dense clouds; parity with the original is unpinned.
+ * Inputs.  B ragged pairs in the layout of roitr_pairgt_stats: src (n,3) / tgt (m,3) fp32, cumulative int32 src_offset / tgt_offset (B)
+ *   under the same precondition; tgt_normals (m,3) fp32 or NULL; init_T (B,4,4) fp32 row-major, source to target, only the top three rows
+ *   are read; max_dist fp32, finite, > 0; iterations >= 0; rel_fitness, rel_rmse double >= 0 (Open3D's defaults: 1e-6, 1e-6, 30 iterations).
+ * Mode.  tgt_normals == NULL: point-to-point; otherwise point-to-plane.
+ * State.  Each pair has a state T_s, 12 fp32 values, T_0 = init_T.
+ * Evaluation E(T_s): the decision of roitr_pairgt_stats with R, t taken from T_s, in float64 on the fp32 inputs, every product and sum
+ *   rounded on its own: p' = ((R[c][0] px + R[c][1] py) + R[c][2] pz) + t[c], d2 as in pairgt.  The match of source point i is the target
+ *   point of least (d2, j) with d2 < (double)max_dist^2, strictly.  n_corr = matched points, fitness = n_corr / n_src (float64),
+ *   rmse = sqrt(sum d2 / n_corr), 0 when n_corr = 0.
+ * Loop.  For s = 0, 1, ...:  1. evaluate E(T_s);  2. if s > 0 and |fitness_s - fitness_{s-1}| < rel_fitness and |rmse_s - rmse_{s-1}| <
+ *   rel_rmse, stop with bit CONVERGED;  3. if s == iterations, stop;  4. otherwise compute the update -- if it cannot be computed, stop
+ *   with the bits given below;  5. go on with T_{s+1}.  The outputs belong to the last evaluated state: at most iterations + 1 evaluations.
+ * Update.  All sums over the matched points, in float64.
+ *   Point-to-point: T_{s+1} = Solve(original source points -> matched target points), weights 1: the rigid solve of the registration
+ *     operators on centroids and centred cross-covariance, T rounded to fp32.  n_corr < 3: bit TOO_FEW, stop.
+ *   Point-to-plane: r_i = (p'_i - q_i) . n_i, J_i = [p'_i x n_i, n_i]; (sum J J^T) x = -sum J r by a float64 Cholesky (L D L^T);
+ *     dT from x = (a, b, g, tx, ty, tz) as Open3D's TransformVector6dToMatrix4d, R = Rz(g) Ry(b) Rx(a), t = (tx, ty, tz);
+ *     T_{s+1} = fp32(dT T_s), the product in float64.  n_corr < 6: bit TOO_FEW, stop.  A non-positive or non-finite pivot: bit SINGULAR,
+ *     T_s is kept, stop.
+ * Status bits.  NONFINITE (a non-finite coordinate, normal or init_T entry), EMPTY (an empty cloud), TOO_FEW, SINGULAR, CONVERGED.  A
+ *   NONFINITE or EMPTY pair returns init_T, fitness NaN, rmse NaN, n_corr 0, steps 0; the other pairs of the call are unaffected.
+ * Outputs (optional unless noted).  T (B,4,4) fp32, last row 0 0 0 1 (required); fitness (B), rmse (B) double; n_corr (B), steps (B) int:
+ *   the s at which the pair stopped; status (B) (required); nn_idx (n) int: the match of every source point under the final state,
+ *   pair-local, -1 for none; trace_T (iterations + 1, B, 12) fp32 and trace_stat (iterations + 1, B, 2) double (fitness, rmse): one row
+ *   per evaluation, rows after a pair's stop repeat its last row.
+ * Host-side errors (nothing is launched): max_dist not finite or not positive, negative iterations or tolerances, B outside 1..65536,
+ *   null required pointers.
+ * Determinism.  The match is an exact decision.  Every float64 sum of a pair is taken in a fixed order that depends on the pair's own
+ *   point indices only (thread t of 256 sums points t, t + 256, ..., then the fixed binary tree of the pairgt reduction); no
+ *   floating-point atomics: a pair's results are bitwise the same alone, anywhere in a batch, and on repeats.
+ * ws: roitr_icp_workspace_bytes(B, n, m, iterations).  No host synchronisation, no host read; 2 launches per evaluation. */
+#define ROITR_ICP_NONFINITE 1
+#define ROITR_ICP_EMPTY 2
+#define ROITR_ICP_TOO_FEW 4
+#define ROITR_ICP_SINGULAR 8
+#define ROITR_ICP_CONVERGED 16
+size_t roitr_icp_workspace_bytes(int b, int n, int m, int iterations);
+int    roitr_icp_batch(int b, int n, int m, const float* src, const int* src_offset, const float* tgt, const int* tgt_offset,
+                       const float* tgt_normals, const float* init_T, float max_dist, int iterations, double rel_fitness,
+                       double rel_rmse, float* T, double* fitness, double* rmse, int* n_corr, int* steps, int* status,
+                       int* nn_idx, float* trace_T, double* trace_stat, void* ws, roitr_stream_t stream);
+
 int roitr_grouping_forward(int m, int nsample, int c, const float* input, const int* idx, float* output, roitr_stream_t stream);
 int roitr_grouping_backward(int m, int nsample, int c, const float* grad_output, const int* idx, float* grad_input, roitr_stream_t stream);
 int roitr_interpolation_forward(int n, int c, int k, const float* input, const int* idx, const float* weight, float* output, roitr_stream_t stream);

@@ -35,11 +35,9 @@ typedef long long i64;
 // and the float64 rule is written with these three.
 #pragma clang fp contract(off)
 
-namespace {
+#include "ball_walk.h"   // pg_mul / pg_add / pg_sub, cell_of_axis, ball_cells
 
-__device__ __forceinline__ double pg_mul(double a, double b) { return a * b; }
-__device__ __forceinline__ double pg_add(double a, double b) { return a + b; }
-__device__ __forceinline__ double pg_sub(double a, double b) { return a - b; }
+namespace {
 
 struct PgWs {
     void* knn;        // grid workspace of the searched clouds
@@ -115,30 +113,6 @@ __device__ __forceinline__ void move_point(const float* __restrict__ R, const fl
         for (int c = 0; c < 3; ++c)
             o[c] = pg_add(pg_add(pg_mul((double)R[c], dx), pg_mul((double)R[3 + c], dy)), pg_mul((double)R[6 + c], dz));
     }
-}
-
-// Cells [lo, hi] of one axis that can hold a searched point q (fp32) with a within-radius distance to the query coordinate x.
-//   * Accepted means d2 < r^2 with d2 >= fl((x - q)^2) (1 - 2^-52) (the two other squares are >= 0 and a sum rounds by 2^-53 twice),
-//     and fl((x - q)^2) >= (x - q)^2 (1 - 2^-52) (one rounded difference, one rounded square): |x - q| < r (1 + 2^-51).
-//   * wlo = fl(x - rb), whi = fl(x + rb) are off by at most 2^-53 (|x| + rb) each.  With rb = r (1 + 1e-9) + 1e-15 |x| (itself good to
-//     three roundings of 2^-53) the slack 1e-9 r + 1e-15 |x| exceeds 2^-51 r + 2^-53 (|x| + rb) + 3 * 2^-53 rb by orders of
-//     magnitude, so wlo <= x - |x - q| <= q <= whi for every accepted q.
-//   * __double2float_rd / _ru round OUTWARDS, so flo <= q <= fhi in fp32.  The grid's cell of a coordinate,
-//     min(max((int)floorf((v - o) * inv_h), 0), dim - 1), is a composition of non-decreasing fp32 functions of v (a rounded difference
-//     with a constant, a rounded product with a positive constant, floor, clamp), and the expression below is the same one in the same
-//     precision (the clamp is done in float first, so nothing far outside overflows an int): cell(flo) <= cell(q) <= cell(fhi).
-// Hence no margin in cell units is needed and the range can never exclude a pair the float64 test accepts.
-__device__ __forceinline__ int cell_of_axis(float v, float o, float inv_h, int dim)
-{
-    return (int)fminf(fmaxf(floorf((v - o) * inv_h), 0.f), (float)(dim - 1));
-}
-__device__ __forceinline__ void ball_cells(double x, double r, float o, float inv_h, int dim, int& lo, int& hi, float& fhi)
-{
-    const double rb = r * (1.0 + 1e-9) + 1e-15 * fabs(x);
-    const float flo = __double2float_rd(x - rb);
-    fhi = __double2float_ru(x + rb);
-    lo = cell_of_axis(flo, o, inv_h, dim);
-    hi = cell_of_axis(fhi, o, inv_h, dim);
 }
 
 // One lane per query.  FILL = false: count, nearest (d2, j) with ties to the lower j.  FILL = true: the candidates of the run, in walk

@@ -59,9 +59,15 @@ def main():
                          "matcher's patches (deterministic, no random stream)")
     ap.add_argument("--lgr-radius", type=float, default=0.1, help="acceptance radius of the lgr estimator (metres)")
     ap.add_argument("--lgr-steps", type=int, default=5, help="global reweighted solves of the lgr estimator")
+    ap.add_argument("--refine", choices=("none", "point", "plane"), default="none",
+                    help="refine the estimated pose by ICP on the dense clouds (icp.py): point-to-point, or point-to-plane on the target "
+                         "normals; implies --register")
+    ap.add_argument("--icp-distance", type=float, default=0.05, help="maximum correspondence distance of the refinement (metres)")
+    ap.add_argument("--icp-iterations", type=int, default=30)
     args = ap.parse_args()
+    args.refine = None if args.refine == "none" else args.refine
     args.recall = args.recall or args.write_gt is not None
-    args.register = args.register or args.recall
+    args.register = args.register or args.recall or args.refine is not None
     args.evaluate = args.evaluate or args.validate or args.recall
     config = Config(load_config(args.config))
     rank, world = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1))
@@ -89,7 +95,8 @@ def main():
                     ransac=dict(iterations=args.ransac_iterations, n_points=args.ransac_points), descriptor_eval=args.descriptor_eval, validate=args.validate,
                     voxel_size=args.voxel_size, points_lim=args.points_lim, subsample_seed=args.subsample_seed,
                     recall=args.recall, overlap_radius=args.overlap_radius, estimator=args.estimator,
-                    lgr=dict(radius=args.lgr_radius, steps=args.lgr_steps))
+                    lgr=dict(radius=args.lgr_radius, steps=args.lgr_steps), refine=args.refine,
+                    icp=dict(max_dist=args.icp_distance, iterations=args.icp_iterations))
     counts = tester.test()
     if rank == 0 and tester.validation:
         v = tester.validation
@@ -101,6 +108,8 @@ def main():
         _print_descriptor(tester.descriptor or {}, world)
     if args.register and args.evaluate:
         _print_registration(tester.registration, world, args.estimator)
+    if args.refine is not None:
+        _print_refinement(tester.refinement, tester.refinement_status, world, args.refine)
     if args.recall and rank == 0 and tester.metrics:
         m = tester.metrics
         print(f"[roitr_amd] registration recall (RMSE <= 0.2 m, overlap radius {args.overlap_radius:g} m) {m['RR']:.4f} over {m['RR_pairs']} "
@@ -143,6 +152,26 @@ def _print_registration(reg, world, estimator="ransac"):
           f"RTE mean {rte.mean():.4f} m, median {np.median(rte):.4f} m")
     print(f"[roitr_amd] pairs with RRE < 15 deg and RTE < 0.3 m: {ok:.4f} (a pose-error success rate, not the 3DMatch-protocol "
           "registration recall, which needs the benchmark's gt.info)")
+
+
+def _print_refinement(refinement, status, world, mode):
+    """Mean / median RRE and RTE before and after the ICP refinement, mean steps and pairs per status bit (rank 0 prints)."""
+    import numpy as np
+    from . import icp
+    rows = [v + (status[k],) for k, v in sorted(refinement.items())]
+    if world > 1:
+        allrows = [None] * world
+        torch.distributed.all_gather_object(allrows, rows)
+        rows = [r for part in allrows for r in part]
+    if int(os.environ.get("RANK", 0)) != 0 or not rows:
+        return
+    a = np.array([r[:7] for r in rows], dtype=np.float64)
+    bits = ", ".join(f"{name} {sum(1 for r in rows if r[7] & bit)}" for name, bit in
+                     (("converged", icp.CONVERGED), ("too few", icp.TOO_FEW), ("singular", icp.SINGULAR), ("empty", icp.EMPTY),
+                      ("non-finite", icp.NONFINITE)))
+    print(f"[roitr_amd] ICP refinement (point-to-{mode}) over {len(rows)} pairs: RRE mean {a[:, 0].mean():.3f} -> {a[:, 2].mean():.3f} deg, "
+          f"median {np.median(a[:, 0]):.3f} -> {np.median(a[:, 2]):.3f} deg; RTE mean {a[:, 1].mean():.4f} -> {a[:, 3].mean():.4f} m, median "
+          f"{np.median(a[:, 1]):.4f} -> {np.median(a[:, 3]):.4f} m; mean steps {a[:, 6].mean():.1f}; pairs: {bits}")
 
 
 def _print_descriptor(desc, world):

@@ -682,6 +682,11 @@ def handle_layout(handle, which):
     return rows[:sum(handle["n_all" if which == "point" else "n4"])], src_starts, tgt_starts
 
 
+def handle_normals(handle):
+    """The normals the model was fed for the "point" rows of handle_layout (src_normals then tgt_normals), (rows, 3) fp32."""
+    return handle["keep"][2][:sum(handle["n_all"])]
+
+
 def create_model(config):
     """model/RIGA_v2.py:178."""
     return RIGA_v2(config)

@@ -42,7 +42,7 @@ class Tester:
     def __init__(self, config, model, dataset, snapshot_dir="snapshot", pairs_per_forward=8, rank=0, world=1, evaluate=False,
                  estimate_normals=False, view_point=(0.0, 0.0, 0.0), register=False, ransac=None, nonrigid=None, descriptor_eval=False,
                  validate=False, voxel_size=None, points_lim=None, subsample_seed=0, recall=False, overlap_radius=0.0375,
-                 estimator="ransac", lgr=None):
+                 estimator="ransac", lgr=None, refine=None, icp=None):
         """evaluate: also compute PIR / IR per pair on the device (lib/loss.py:169-213 Evaluator) and return their means.
         estimate_normals: ignore the dataset's normals and recompute them on the GPU from the points the way the
         reference's dataset code does (open3d estimate_normals(knn=33) + normal_redirect, dataset/tdmatch.py:120-127).
@@ -80,7 +80,12 @@ class Tester:
         overlap bin of overlap_src (RR_overlap_ge_0.3: the 3DMatch range, RR_overlap_0.1_0.3: 3DLoMatch, RR_overlap_lt_0.1, each
         with its _pairs count; nan for an empty bin) and pairs_without_overlap, the pairs left out.  Every pair's file additionally
         holds gt_overlap (2, float64: source side, target side) and gt_info (6,6 float64); `self.gt` keeps (T_gt, info,
-        overlap_src, T_est) per pair id for write_gt.  With recall off, files, records and metrics are what they are without it."""
+        overlap_src, T_est) per pair id for write_gt.  With recall off, files, records and metrics are what they are without it.
+        refine: None, "point" or "plane": after the estimator's pose, ICP on the clouds the model saw (icp.icp_handle from reg["T"],
+        point-to-point or point-to-plane on the target normals; `icp` holds its keyword arguments); implies register.  The refined
+        transform takes the place of the estimated one everywhere downstream (est_transform, `registration`, the recall rows), and
+        `self.refinement` maps this rank's pair ids to (rre_before, rte_before, rre_after, rte_after, fitness, rmse, steps),
+        `self.refinement_status` to the pair's ICP status word.  With refine=None nothing of it is imported or run."""
         self.config, self.model, self.dataset = config, model, dataset
         self.snapshot_dir = snapshot_dir
         self.pairs_per_forward = pairs_per_forward
@@ -88,12 +93,17 @@ class Tester:
         self.voxel_size, self.points_lim, self.subsample_seed = voxel_size, points_lim, subsample_seed
         estimate_normals = estimate_normals or voxel_size is not None or points_lim is not None
         self.evaluate, self.estimate_normals, self.view_point = evaluate or validate, estimate_normals, view_point
-        register = register or recall
+        if refine not in (None, "point", "plane"):
+            raise ValueError("refine must be None, 'point' or 'plane'")
+        register = register or recall or refine is not None
         self.evaluate = self.evaluate or recall
         if estimator not in ("ransac", "lgr"):
             raise ValueError("estimator must be 'ransac' or 'lgr'")
         self.register, self.ransac = register, dict(ransac or {})
         self.estimator, self.lgr = estimator, dict(lgr or {})
+        self.refine, self.icp = refine, dict(icp or {})
+        self.refinement = {} if refine is not None else None
+        self.refinement_status = {} if refine is not None else None
         self.registration = {} if register and self.evaluate else None
         self.recall = {} if recall else None
         self.gt = {} if recall else None
@@ -259,9 +269,19 @@ class Tester:
                     else:
                         reg = register_handle(handle, pair_keys=ids, **self.ransac)
                     est = reg["T"].cpu()
+                    if self.refine is not None or self.registration is not None:
+                        gt_pose = (torch.stack([p["rot"].reshape(3, 3) for p in pairs]), torch.stack([p["trans"].reshape(3) for p in pairs]))
+                    if self.refine is not None:
+                        from .icp import icp_handle
+                        ref = icp_handle(handle, reg["T"], plane=self.refine == "plane", **self.icp)
+                        before, est = pose_errors(est, *gt_pose), ref["T"].cpu()
+                        after = pose_errors(est, *gt_pose)
+                        cols = [x.cpu().tolist() for x in (*before, *after, ref["fitness"], ref["rmse"], ref["steps"], ref["status"])]
+                        for k, idx in enumerate(ids):
+                            self.refinement[idx] = tuple(float(c[k]) for c in cols[:6]) + (int(cols[6][k]),)
+                            self.refinement_status[idx] = int(cols[7][k])
                     if self.registration is not None:
-                        rre, rte = pose_errors(est, torch.stack([p["rot"].reshape(3, 3) for p in pairs]),
-                                               torch.stack([p["trans"].reshape(3) for p in pairs]))
+                        rre, rte = pose_errors(est, *gt_pose)
                         inl = reg["inliers"].cpu().tolist()
                         for k, idx in enumerate(ids):
                             self.registration[idx] = (float(rre[k]), float(rte[k]), int(inl[k]))
