@@ -627,6 +627,57 @@ int roitr_lgr_batch(int pairs, const int* starts, int total_rows, const float* s
                     int* status, int* hyp_starts, int* hyp_first_row, float* hyp_transforms, int* hyp_counts, roitr_stream_t stream);
 
 
+/* ------------------------------------------------------------------ spatial-compatibility registration
+ * Pose hypotheses from the second-order spatial compatibility of the correspondences themselves, the idea of SC2-PCR (Chen et al.,
+ * CVPR 2022), for sets without patch structure: no random stream, no row_patch.  PARITY WITH SC2-PCR IS NOT CLAIMED: the operator is
+ * defined here.  Simplifications against the paper: seeds by degree instead of a leading eigenvector plus non-maximum suppression;
+ * one consensus stage instead of two; hard (0 / 1) compatibility only.
+ * Inputs as roitr_lgr_batch without row_patch: pair b owns rows [starts[b], starts[b+1]) (clamped into [0, total_rows]) of src_pts /
+ * tgt_pts (fp32 (N,3)) and scores (fp32 (N); NULL = all 1).  Inputs must be finite; they are not checked.
+ * Parameters: compat_dist (finite, > 0), radius (finite, > 0), max_rows (3 ... 8192), max_seeds (1 ... 1024), k (consensus size,
+ *   3 ... 64), steps (>= 1).
+ * 1. Selection.  A pair of n rows has m = min(n, max_rows) selected rows.  n <= max_rows: all rows in row order.  Otherwise: the
+ *   max_rows rows of largest (score, -row) -- the key is float_image(score) of csrc/common.h, a lower row wins among equal scores;
+ *   with NULL scores the first max_rows rows -- listed in ascending row order, and status bit TRUNCATED is set.  Selected row
+ *   a in [0, m) is row sel[a] of the pair; p_a, q_a are its source and target point.
+ * 2. Graph.  For a != b: d_ab = | rg_len(p_a, p_b) - rg_len(q_a, q_b) |, rg_len in float64 on the fp32 inputs (registration_math.h);
+ *   C_ab = d_ab < (double)compat_dist, strictly; C_aa = 0; deg_a = sum_b C_ab.
+ * 3. Seeds.  S = min(max_seeds, m) seeds: the S selected rows of largest (deg, -a).  A seed's rank is its position in that order.
+ * 4. Consensus set of seed s.  c_b = C_sb * sum_x C_sx C_bx (the common compatible neighbours).  Members: the seed plus the at most
+ *   k - 1 indices b with c_b > 0 of largest (c_b, -b).  Fewer than 3 members: the hypothesis is invalid, its count is -1.  Weights:
+ *   w_b = (float)c_b and w_s = (float)max_b c_b, integers <= 8190; scores take no part.  T_rank = Solve(members in ascending a, w),
+ *   the Solve of roitr_lgr_batch above: float64 moments, eps 1e-5, rg_solve_rigid, T rounded to fp32.
+ * 5. Verification and global stage: those of roitr_lgr_batch, over ALL n rows of the pair (not only the selected ones).  Residual
+ *   rg_dist2, inlier when d^2 < radius^2 strictly; the winner is the valid hypothesis with the largest count, ties go to the lower
+ *   rank; then `steps` reweighted solves with score x [inlier].  A pair without a valid hypothesis starts from Solve(all rows, score)
+ *   and sets NO_HYPOTHESIS; a solve whose weights sum to 0 keeps the transform, sets EMPTY_REFIT and ends the loop; a pair without
+ *   rows gets the identity and NO_ROWS alone.
+ * Outputs per pair: transforms (B,4,4); inliers; best_rank (-1: none); best_seed_row (row local to the pair, -1: none); seeds (S);
+ *   hypotheses (the valid ones); local_inliers (the winner's count; the count under the first solve without a hypothesis); status.
+ * Optional outputs (NULL allowed): degree (total_rows) int32, deg of the selected rows of every pair and -1 for its unselected rows
+ *   (rows outside every pair are not written); seed_rows (pairs x max_seeds) local rows in rank order, -1 padded; seed_members
+ *   (pairs x max_seeds x k) local rows ascending, -1 padded (an invalid hypothesis lists the one or two rows it has); hyp_transforms (pairs x
+ *   max_seeds x 12), zeros for an invalid hypothesis and for ranks >= S; hyp_counts (pairs x max_seeds), -1 for those.
+ * Slots: pair b's begin at b x max_seeds; there is no scan over the pairs and no host read.
+ * Determinism: as roitr_lgr_batch.  Every decision of stages 1 - 4 is an integer or an exact float64 comparison, every float64 sum
+ *   runs in an order fixed by the pair's own local indices, the only atomics add integers: a pair's results are bitwise independent
+ *   of its batch, its slot, its row offset, of max_rows / max_seeds capacity that changes no decision, and of repeats.
+ * The workspace (device, caller-owned) holds at least roitr_compat_workspace_bytes() bytes (host-only, monotone; 0 for arguments the
+ *   batch call refuses).  It holds C bit-packed: pairs x max_rows x ceil(max_rows / 64) 64-bit words.
+ * Refusals (ROITR_ERR_ARG, nothing is launched or written): null pointers, parameters out of the ranges above, total_rows < 0,
+ *   more than 65535 pairs, a short workspace. */
+#define ROITR_COMPAT_NO_ROWS 1
+#define ROITR_COMPAT_NO_HYPOTHESIS 2
+#define ROITR_COMPAT_EMPTY_REFIT 4
+#define ROITR_COMPAT_TRUNCATED 8
+size_t roitr_compat_workspace_bytes(int pairs, int total_rows, int max_rows, int max_seeds, int k);
+int roitr_compat_batch(int pairs, const int* starts, int total_rows, const float* src_pts, const float* tgt_pts, const float* scores,
+                       float compat_dist, float radius, int max_rows, int max_seeds, int k, int steps, void* workspace,
+                       size_t workspace_bytes, float* transforms, int* inliers, int* best_rank, int* best_seed_row, int* seeds,
+                       int* hypotheses, int* local_inliers, int* status, int* degree, int* seed_rows, int* seed_members,
+                       float* hyp_transforms, int* hyp_counts, roitr_stream_t stream);
+
+
 /* ------------------------------------------------------------------ 4DMatch non-rigid evaluation
  * registration/evaluate_fdmatch.py:50-115: NFMR (non-rigid feature matching recall) of every pair of a batch.  Pair b owns points
  * [src_offsets[b], src_offsets[b+1]) of src_raw (the undeformed source) and src_deformed (what the model was fed), both (total_src,

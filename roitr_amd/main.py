@@ -13,7 +13,8 @@ from .riga import create_model
 from .tester import SyntheticPairs, Tester, load_pretrain
 
 
-def main():
+def parser():
+    """The command line of `python -m roitr_amd.main`."""
     ap = argparse.ArgumentParser()
     ap.add_argument("config")
     ap.add_argument("--pretrain", default=None)
@@ -27,8 +28,8 @@ def main():
     ap.add_argument("--evaluate", action="store_true", help="report mean PIR / IR (lib/loss.py Evaluator) computed on the device")
     ap.add_argument("--estimate-normals", action="store_true", help="recompute the normals on the GPU (open3d knn=33 + normal_redirect)")
     ap.add_argument("--register", action="store_true",
-                    help="estimate every pair's pose on the GPU (--estimator: correspondence RANSAC, registration.py, or local-to-global "
-                         "registration, lgr.py) and save it as est_transform")
+                    help="estimate every pair's pose on the GPU (--estimator: correspondence RANSAC, registration.py, local-to-global "
+                         "registration, lgr.py, or spatial-compatibility registration, compat.py) and save it as est_transform")
     ap.add_argument("--nonrigid", action="store_true",
                     help="synthetic 4DMatch-shaped pairs with a real deformation and metric points (synthetic.make_nonrigid_pair); "
                          "with --evaluate on a 4DMatch config the mean NFMR is reported (nonrigid.py)")
@@ -54,17 +55,26 @@ def main():
                          "record at index 0; implies --recall")
     ap.add_argument("--ransac-iterations", type=int, default=50000)
     ap.add_argument("--ransac-points", type=int, default=1000, help="correspondences drawn per pair (probability ~ confidence)")
-    ap.add_argument("--estimator", choices=("ransac", "lgr"), default="ransac",
-                    help="pose estimator of --register: correspondence RANSAC, or RANSAC-free local-to-global registration on the "
-                         "matcher's patches (deterministic, no random stream)")
+    ap.add_argument("--estimator", choices=("ransac", "lgr", "compat"), default="ransac",
+                    help="pose estimator of --register: correspondence RANSAC, RANSAC-free local-to-global registration on the "
+                         "matcher's patches, or spatial-compatibility registration on the correspondences alone (both deterministic, "
+                         "no random stream)")
     ap.add_argument("--lgr-radius", type=float, default=0.1, help="acceptance radius of the lgr estimator (metres)")
     ap.add_argument("--lgr-steps", type=int, default=5, help="global reweighted solves of the lgr estimator")
+    ap.add_argument("--compat-dist", type=float, default=0.1,
+                    help="compat estimator: two correspondences are compatible when their point distances differ by less (metres)")
+    ap.add_argument("--compat-seeds", type=int, default=64, help="compat estimator: hypotheses per pair (seeds by degree)")
+    ap.add_argument("--compat-k", type=int, default=20, help="compat estimator: rows of a seed's consensus set")
     ap.add_argument("--refine", choices=("none", "point", "plane"), default="none",
                     help="refine the estimated pose by ICP on the dense clouds (icp.py): point-to-point, or point-to-plane on the target "
                          "normals; implies --register")
     ap.add_argument("--icp-distance", type=float, default=0.05, help="maximum correspondence distance of the refinement (metres)")
     ap.add_argument("--icp-iterations", type=int, default=30)
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = parser().parse_args()
     args.refine = None if args.refine == "none" else args.refine
     args.recall = args.recall or args.write_gt is not None
     args.register = args.register or args.recall or args.refine is not None
@@ -95,7 +105,8 @@ def main():
                     ransac=dict(iterations=args.ransac_iterations, n_points=args.ransac_points), descriptor_eval=args.descriptor_eval, validate=args.validate,
                     voxel_size=args.voxel_size, points_lim=args.points_lim, subsample_seed=args.subsample_seed,
                     recall=args.recall, overlap_radius=args.overlap_radius, estimator=args.estimator,
-                    lgr=dict(radius=args.lgr_radius, steps=args.lgr_steps), refine=args.refine,
+                    lgr=dict(radius=args.lgr_radius, steps=args.lgr_steps),
+                    compat=dict(compat_dist=args.compat_dist, max_seeds=args.compat_seeds, k=args.compat_k), refine=args.refine,
                     icp=dict(max_dist=args.icp_distance, iterations=args.icp_iterations))
     counts = tester.test()
     if rank == 0 and tester.validation:

@@ -145,6 +145,25 @@ def ransac_pose_estimation(src_pcd, tgt_pcd, src_feat, tgt_feat, mutual=False, d
 
 
 @torch.no_grad()
+def compat_pose_estimation(src_pcd, tgt_pcd, src_feat, tgt_feat, mutual=False, **kw):
+    """The descriptor-matching twin of ransac_pose_estimation without RANSAC: the same matches (descmatch under the dot product,
+    mutual or every source point with its best target), then compat.compat_batch on the matched point pairs with the match scores as
+    confidences (they order the rows when there are more than max_rows; the estimator itself is deterministic and takes no seed).
+    kw: compat_batch's keyword arguments.  Returns the 4x4 float64 numpy transformation."""
+    from . import descmatch
+    from .compat import compat_batch
+    src, tgt = A.upload(src_pcd).reshape(-1, 3), A.upload(tgt_pcd).reshape(-1, 3)
+    sf, tf = A.upload(src_feat), A.upload(tgt_feat)
+    if sf.shape[0] != src.shape[0] or tf.shape[0] != tgt.shape[0]:
+        raise L.RoitrError("compat_pose_estimation: one descriptor per point is needed")
+    m = descmatch.match_batch(A.cumulative([sf.shape[0]], "cuda"), sf, A.cumulative([tf.shape[0]], "cuda"), tf, metric="dot",
+                              mode="mutual" if mutual else "row")
+    corr = m["corr"].long()
+    r = compat_batch(m["corr_starts"], src[corr[:, 0]], tgt[corr[:, 1]], m["row_val"][corr[:, 0]], **kw)
+    return r["T"][0].cpu().numpy().astype(np.float64)
+
+
+@torch.no_grad()
 def weighted_procrustes(src_points, tgt_points, weights=None, weight_thresh=0., eps=1e-5, return_transform=False):
     """lib/utils.py:159-212 on the GPU (same signature and squeeze rule): (B, N, 3) or (N, 3) -> R, t or the 4x4 transform."""
     squeeze = src_points.ndim == 2

@@ -42,7 +42,7 @@ class Tester:
     def __init__(self, config, model, dataset, snapshot_dir="snapshot", pairs_per_forward=8, rank=0, world=1, evaluate=False,
                  estimate_normals=False, view_point=(0.0, 0.0, 0.0), register=False, ransac=None, nonrigid=None, descriptor_eval=False,
                  validate=False, voxel_size=None, points_lim=None, subsample_seed=0, recall=False, overlap_radius=0.0375,
-                 estimator="ransac", lgr=None, refine=None, icp=None):
+                 estimator="ransac", lgr=None, refine=None, icp=None, compat=None):
         """evaluate: also compute PIR / IR per pair on the device (lib/loss.py:169-213 Evaluator) and return their means.
         estimate_normals: ignore the dataset's normals and recompute them on the GPU from the points the way the
         reference's dataset code does (open3d estimate_normals(knn=33) + normal_redirect, dataset/tdmatch.py:120-127).
@@ -50,7 +50,9 @@ class Tester:
         poses do not depend on sharding or pairs_per_forward; `ransac` holds its keyword arguments) and save it as `est_transform`
         in the pair's file.  With evaluate as well, `registration` maps this rank's pair ids to (RRE degrees, RTE metres, inliers).
         estimator: "ransac" (the default, as above) or "lgr": the pose comes from lgr.lgr_handle (local-to-global registration on the
-        matcher's patches: no random stream, so no keys; `lgr` holds its keyword arguments); everything downstream of the pose
+        matcher's patches: no random stream, so no keys; `lgr` holds its keyword arguments) or "compat": the pose comes from
+        compat.compat_handle (spatial-compatibility registration: no random stream and no patch structure either; `compat` holds its
+        keyword arguments); everything downstream of the pose
         (est_transform, RRE / RTE, the inlier column, the recall rows) is the same code.
         With evaluate on the 4DMatch / 4DLoMatch benchmark and items that carry `metric_index`, the NFMR of every pair is computed
         on the device (nonrigid.nfmr_handle; `nonrigid` holds its keyword arguments) and `self.nonrigid` maps this rank's pair ids
@@ -97,10 +99,10 @@ class Tester:
             raise ValueError("refine must be None, 'point' or 'plane'")
         register = register or recall or refine is not None
         self.evaluate = self.evaluate or recall
-        if estimator not in ("ransac", "lgr"):
-            raise ValueError("estimator must be 'ransac' or 'lgr'")
+        if estimator not in ("ransac", "lgr", "compat"):
+            raise ValueError("estimator must be 'ransac', 'lgr' or 'compat'")
         self.register, self.ransac = register, dict(ransac or {})
-        self.estimator, self.lgr = estimator, dict(lgr or {})
+        self.estimator, self.lgr, self.compat = estimator, dict(lgr or {}), dict(compat or {})
         self.refine, self.icp = refine, dict(icp or {})
         self.refinement = {} if refine is not None else None
         self.refinement_status = {} if refine is not None else None
@@ -266,6 +268,9 @@ class Tester:
                     if self.estimator == "lgr":
                         from .lgr import lgr_handle
                         reg = lgr_handle(handle, **self.lgr)
+                    elif self.estimator == "compat":
+                        from .compat import compat_handle
+                        reg = compat_handle(handle, **self.compat)
                     else:
                         reg = register_handle(handle, pair_keys=ids, **self.ransac)
                     est = reg["T"].cpu()
