@@ -105,6 +105,43 @@ int roitr_estimate_normals(int b, int n, const float* xyz, const int* offset, in
 int roitr_normal_redirect(int n, const float* xyz, const float* normals_in, const float* view_point, float* normals_out,
                           roitr_stream_t stream);
 
+/* ------------------------------------------------------------------ FPFH descriptors: the learning-free baseline
+ * Open3D's compute_fpfh_feature(pcd, KDTreeSearchParamHybrid(radius, max_nn)) restated; parity with the original is unpinned.  b clouds
+ * in the `offset` layout of the normals: xyz (n,3), normals (n,3) fp32, offset (b) cumulative int32 with offset[b-1] == n (PRECONDITION,
+ * as for roitr_pairgt_stats: the offsets are device memory and are not checked); empty clouds are legal.  All arithmetic is float64 on
+ * the fp32 inputs, every product, sum and quotient rounded on its own (no FMA); a dot product is (a0 b0 + a1 b1) + a2 b2, a cross
+ * product's component a1 b2 - a2 b1.
+ * Neighbours K(i) of point i of cloud c: row i of this library's exact kNN of the cloud against itself with nsample = max_nn
+ *   (roitr_knn_build_grid_ex + roitr_knnquery_ex: ascending distance, the lower index first among equal ones).  Slots k >= size(c) are
+ *   padding and ignored; entries j == i are dropped; of the rest at most the first max_nn - 1 stay; of those, j is kept iff
+ *   d2 = (dx dx + dy dy) + dz dz < radius radius, dp = p_j - p_i = (dx, dy, dz) (strict).  m_i = |K(i)|, in row order.
+ * Pair feature of (i, j): d = sqrt(d2).  d == 0: f = (0, 0, 0).  Otherwise a1 = n_i . dp / d, a2 = n_j . dp / d; if |a1| < |a2|:
+ *   (n1, n2, dp) = (n_j, n_i, -dp) and f2 = -a2, else (n1, n2) = (n_i, n_j) and f2 = a1.  v = dp x n1; |v| == 0: f = (0, 0, 0).  Otherwise
+ *   v /= |v|, w = n1 x v, f1 = v . n2, f0 = atan2(w . n2, n1 . n2).  Normals are used as given, not normalised.
+ * Bins: h0 = clamp(floor(11 (f0 + pi) / (2 pi)), 0, 10), h1 = clamp(floor(11 (f1 + 1) / 2), 0, 10), h2 likewise from f2 (a NaN goes to
+ *   bin 0); counts_i[h0], counts_i[11 + h1], counts_i[22 + h2] each get +1 per neighbour: integers <= 99.
+ * SPFH_i[b] = counts_i[b] (100 / m_i), all zero when m_i == 0.
+ * FPFH: for j in K(i) in row order with d2 > 0: val[b] = SPFH_j[b] / d2, F_i[b] += val[b], and S_i[g] += val[b] for the 11 bins b of group
+ *   g = b div 11 in ascending b.  Then F_i[b] = (S_i[g] != 0 ? F_i[b] 100 / S_i[g] : F_i[b]) + SPFH_i[b], rounded once to fp32 into
+ *   fpfh[i out_stride + b]; columns 33 .. out_stride - 1 are written as 0.
+ * Outputs: fpfh (n, out_stride) fp32; spfh_counts (n, 33) int32 and nbr_count (n) int32 = m_i, optional (NULL); status (b): bit 1 = the
+ *   cloud holds a non-finite coordinate or normal; all of that cloud's rows (fpfh, spfh_counts, nbr_count) are 0 then and the other
+ *   clouds of the call are unaffected.  Nothing is read out of bounds whatever the values are.
+ * Host-side errors (ROITR_ERR_ARG, nothing is launched): max_nn outside [2, 100] (the kNN's limit), out_stride < 33, radius not finite
+ *   or not positive, b or n negative, b > 65535, b == 0 with n > 0, null required pointers, workspace_bytes below
+ *   roitr_fpfh_workspace_bytes(b, n, max_nn).  n == 0 or an empty cloud is not an error.
+ * Determinism: counts are integers and every float64 sum is taken in row order by one wave; no floating-point atomics.  A cloud's
+ *   outputs are bitwise the same alone, anywhere in a batch and on repeats, with or without the optional outputs, for any out_stride.
+ * No host synchronisation, no host read.  The workspace holds the kNN rows: n max_nn 4 bytes dominate. */
+size_t roitr_fpfh_workspace_bytes(int b, int n, int max_nn);
+int roitr_fpfh_batch(int b, int n, const float* xyz, const float* normals, const int* offset,
+                     double radius, int max_nn, int out_stride,
+                     float* fpfh,          /* (n, out_stride) */
+                     int* spfh_counts,     /* optional (n, 33) */
+                     int* nbr_count,       /* optional (n)     */
+                     int* status,          /* (b) */
+                     void* workspace, size_t workspace_bytes, roitr_stream_t stream);
+
 /* ------------------------------------------------------------------ raw scans: voxel grid + point cap
  * Open3D's voxel_down_sample restated (parity with the original is unpinned, as for the normals).  Per cloud, in float64 on the fp32
  * inputs: vmb = min_bound - voxel_size / 2, ijk = floor((p - vmb) / voxel_size); one output point per occupied voxel = the sum of its

@@ -70,6 +70,11 @@ def parser():
                          "normals; implies --register")
     ap.add_argument("--icp-distance", type=float, default=0.05, help="maximum correspondence distance of the refinement (metres)")
     ap.add_argument("--icp-iterations", type=int, default=30)
+    ap.add_argument("--fpfh-baseline", action="store_true",
+                    help="with --evaluate and --register: also run the learning-free baseline on the same pairs (fpfh.py): FPFH "
+                         "descriptors, mutual matches under the squared distance, the pose from --estimator (ransac or compat)")
+    ap.add_argument("--fpfh-radius", type=float, default=0.125, help="FPFH neighbourhood radius (metres)")
+    ap.add_argument("--fpfh-max-nn", type=int, default=100, help="FPFH neighbourhood size: the point and at most N - 1 neighbours (2 .. 100)")
     return ap
 
 
@@ -107,7 +112,8 @@ def main():
                     recall=args.recall, overlap_radius=args.overlap_radius, estimator=args.estimator,
                     lgr=dict(radius=args.lgr_radius, steps=args.lgr_steps),
                     compat=dict(compat_dist=args.compat_dist, max_seeds=args.compat_seeds, k=args.compat_k), refine=args.refine,
-                    icp=dict(max_dist=args.icp_distance, iterations=args.icp_iterations))
+                    icp=dict(max_dist=args.icp_distance, iterations=args.icp_iterations),
+                    fpfh_baseline=dict(radius=args.fpfh_radius, max_nn=args.fpfh_max_nn) if args.fpfh_baseline else None)
     counts = tester.test()
     if rank == 0 and tester.validation:
         v = tester.validation
@@ -119,6 +125,11 @@ def main():
         _print_descriptor(tester.descriptor or {}, world)
     if args.register and args.evaluate:
         _print_registration(tester.registration, world, args.estimator)
+    if args.fpfh_baseline and rank == 0 and tester.metrics and "fpfh_ir" in tester.metrics:
+        m = tester.metrics
+        print(f"[roitr_amd] FPFH baseline ({args.estimator}, radius {args.fpfh_radius:g} m, max_nn {args.fpfh_max_nn}) over {m['fpfh_pairs']} "
+              f"pairs: IR {m['fpfh_ir']:.4f}, RRE mean {m['fpfh_rre']:.3f} deg, RTE mean {m['fpfh_rte']:.4f} m, pairs with RRE < 15 deg "
+              f"and RTE < 0.3 m: {m['fpfh_success']:.4f}")
     if args.refine is not None:
         _print_refinement(tester.refinement, tester.refinement_status, world, args.refine)
     if args.recall and rank == 0 and tester.metrics:

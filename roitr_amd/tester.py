@@ -42,7 +42,7 @@ class Tester:
     def __init__(self, config, model, dataset, snapshot_dir="snapshot", pairs_per_forward=8, rank=0, world=1, evaluate=False,
                  estimate_normals=False, view_point=(0.0, 0.0, 0.0), register=False, ransac=None, nonrigid=None, descriptor_eval=False,
                  validate=False, voxel_size=None, points_lim=None, subsample_seed=0, recall=False, overlap_radius=0.0375,
-                 estimator="ransac", lgr=None, refine=None, icp=None, compat=None):
+                 estimator="ransac", lgr=None, refine=None, icp=None, compat=None, fpfh_baseline=None):
         """evaluate: also compute PIR / IR per pair on the device (lib/loss.py:169-213 Evaluator) and return their means.
         estimate_normals: ignore the dataset's normals and recompute them on the GPU from the points the way the
         reference's dataset code does (open3d estimate_normals(knn=33) + normal_redirect, dataset/tdmatch.py:120-127).
@@ -87,7 +87,15 @@ class Tester:
         point-to-point or point-to-plane on the target normals; `icp` holds its keyword arguments); implies register.  The refined
         transform takes the place of the estimated one everywhere downstream (est_transform, `registration`, the recall rows), and
         `self.refinement` maps this rank's pair ids to (rre_before, rte_before, rre_after, rte_after, fitness, rmse, steps),
-        `self.refinement_status` to the pair's ICP status word.  With refine=None nothing of it is imported or run."""
+        `self.refinement_status` to the pair's ICP status word.  With refine=None nothing of it is imported or run.
+        fpfh_baseline: None, or a dict (radius, max_nn, mutual; defaults 0.125, 100, True) that switches on the learning-free baseline
+        (fpfh.fpfh_handle) with evaluate and register: FPFH descriptors of the clouds and normals the model was fed, matched under
+        the squared distance, their pose from the selected estimator with its keyword arguments ("ransac", keyed on the global pair
+        id like the model's, or "compat"; "lgr" needs the matcher's patches and is refused with a ValueError).  `self.fpfh` maps this
+        rank's pair ids to (inlier ratio of the matches at get_inlier_ratio's 0.1 m, nan without matches; RRE degrees; RTE metres;
+        number of matches) and on rank 0 `metrics` gains fpfh_ir (mean over the pairs that have matches), fpfh_rre, fpfh_rte (means)
+        and fpfh_success (share of pairs with RRE < 15 degrees and RTE < 0.3 m), over the pairs of ALL ranks.  Files, records and
+        every other metric are what they are without it."""
         self.config, self.model, self.dataset = config, model, dataset
         self.snapshot_dir = snapshot_dir
         self.pairs_per_forward = pairs_per_forward
@@ -104,6 +112,10 @@ class Tester:
         self.register, self.ransac = register, dict(ransac or {})
         self.estimator, self.lgr, self.compat = estimator, dict(lgr or {}), dict(compat or {})
         self.refine, self.icp = refine, dict(icp or {})
+        if fpfh_baseline is not None and estimator == "lgr":
+            raise ValueError("the FPFH baseline has no patches: it runs with estimator 'ransac' or 'compat', not 'lgr'")
+        self.fpfh_baseline = None if fpfh_baseline is None else dict(fpfh_baseline)
+        self.fpfh = {} if fpfh_baseline is not None and register and self.evaluate else None
         self.refinement = {} if refine is not None else None
         self.refinement_status = {} if refine is not None else None
         self.registration = {} if register and self.evaluate else None
@@ -290,6 +302,18 @@ class Tester:
                         inl = reg["inliers"].cpu().tolist()
                         for k, idx in enumerate(ids):
                             self.registration[idx] = (float(rre[k]), float(rte[k]), int(inl[k]))
+                if self.fpfh is not None:
+                    from .fpfh import fpfh_handle
+                    from .registration import pose_errors
+                    kw = dict(self.fpfh_baseline)
+                    mode = "mutual" if kw.pop("mutual", True) else "row"
+                    base = fpfh_handle(handle, mode=mode, estimator=self.estimator, pair_keys=ids,
+                                       estimator_kw=self.compat if self.estimator == "compat" else self.ransac,
+                                       inlier_distance_threshold=DESC_INLIER_THRESHOLD, **kw)
+                    rre, rte = pose_errors(base["reg"]["T"].cpu(), torch.stack([p["rot"].reshape(3, 3) for p in pairs]),
+                                           torch.stack([p["trans"].reshape(3) for p in pairs]))
+                    for k, (idx, ir, cnt) in enumerate(zip(ids, base["ir"].cpu().tolist(), base["n_matches"].cpu().tolist())):
+                        self.fpfh[idx] = (float(ir), float(rre[k]), float(rte[k]), int(cnt))
                 gt_rows = None
                 if self.recall is not None:
                     gt_rows = self._recall_rows(handle, ids, pairs, est)
@@ -318,6 +342,7 @@ class Tester:
                                              slots_per_rank(n, self.world), per_pair)
         # every rank takes part: IR / PIR below cover all ranks, so must these
         desc_all, losses_all, recall_all = self._all_ranks(self.descriptor), self._all_ranks(self.losses), self._all_ranks(self.recall)
+        fpfh_all = self._all_ranks(self.fpfh)
         if self.records is None:     # ranks other than 0
             return None
         if self.records.truncated:
@@ -342,6 +367,8 @@ class Tester:
                                     desc_FMR=sum(1 for x in wo if x > DESC_FMR_THRESHOLD) / max(len(wo), 1))
             if recall_all is not None:
                 self.metrics.update(recall_metrics(recall_all))
+            if fpfh_all is not None:
+                self.metrics.update(fpfh_metrics(fpfh_all))
             if losses_all is not None:
                 self.validation = {"PIR": self.metrics["PIR"], "IR": self.metrics["IR"], "pairs": len(losses_all),
                                    "skipped": {"PIR": self.metrics["pairs_without_coarse"], "IR": 0}}
@@ -350,6 +377,16 @@ class Tester:
                     self.validation[key] = sum(vals) / len(vals) if vals else float("nan")
                     self.validation["skipped"][key] = len(losses_all) - len(vals)
         return counts
+
+
+def fpfh_metrics(rows):
+    """{pair id: (ir, rre, rte, matches)} -> the baseline's report: fpfh_ir over the pairs that have matches, mean fpfh_rre / fpfh_rte,
+    fpfh_success = share of pairs with RRE < 15 degrees and RTE < 0.3 m (main.py's pose-error success rate)."""
+    v = [rows[k] for k in sorted(rows)]
+    ir = [r[0] for r in v if r[0] == r[0]]
+    mean = lambda x: sum(x) / len(x) if x else float("nan")
+    return {"fpfh_ir": mean(ir), "fpfh_rre": mean([r[1] for r in v]), "fpfh_rte": mean([r[2] for r in v]),
+            "fpfh_success": mean([1.0 if r[1] < 15.0 and r[2] < 0.3 else 0.0 for r in v]), "fpfh_pairs": len(v)}
 
 
 def recall_error(T_gt, T_est, info):
