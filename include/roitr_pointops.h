@@ -250,6 +250,47 @@ int    roitr_icp_batch(int b, int n, int m, const float* src, const int* src_off
                        double rel_rmse, float* T, double* fitness, double* rmse, int* n_corr, int* steps, int* status,
                        int* nn_idx, float* trace_T, double* trace_stat, void* ws, roitr_stream_t stream);
 
+/* ------------------------------------------------------------------ Generalized ICP: plane-to-plane refinement from normals
+ * Open3D's RegistrationGeneralizedICP restated on the dense clouds with the covariances fixed by the normals; parity with the original
+ * is unpinned.  Deviation stated: Open3D tests convergence on the RMSE of its whitened residuals; this operator tests it on the
+ * Euclidean (fitness, rmse) of roitr_icp_batch.  Caller-supplied covariances, robust kernels and point weights are not part of it.
+ * Inputs.  As roitr_icp_batch, except: src_normals (n,3) and tgt_normals (m,3) fp32 are both required; epsilon double in [1e-6, 1]
+ *   (Open3D's default: 1e-3).
+ * Normals.  nh = n / sqrt((nx nx + ny ny) + nz nz), in float64 on the fp32 values, every component divided by the root.  A squared
+ *   length of exactly 0 gives nh = 0: an isotropic point, C = I.  The covariance of a point is C = I - (1 - epsilon) nh nh^T:
+ *   eigenvalues (epsilon, 1, 1), the normal the epsilon-axis.  A non-finite normal on either side: bit NONFINITE for its pair.
+ * State, Evaluation E(T_s), Loop.  Exactly roitr_icp_batch's: the same float64 move, the match the target point of least (d2, j) with
+ *   d2 < (double)max_dist^2, n_corr, fitness and the Euclidean rmse, the same convergence rule on (fitness, rmse), at most
+ *   iterations + 1 evaluations, the outputs belong to the last evaluated state.
+ * Update.  All sums over the matched points, in float64, every product and sum rounded on its own.  Per matched pair (p, q):
+ *   p' the moved point, d = p' - q;  a = R nh_s with R from T_s, a[r] = (R[r][0] u0 + R[r][1] u1) + R[r][2] u2;  b = nh_t;
+ *   c = 1 - epsilon (computed once, on the host);
+ *   M = 2I - c (a a^T + b b^T), symmetric, upper triangle: m_xy = [x == y ? 2 : 0] - c * (a_x a_y + b_x b_y);
+ *   W = M^-1 by cofactors: C00 = m11 m22 - m12 m12, C01 = m12 m02 - m01 m22, C02 = m01 m12 - m11 m02, C11 = m00 m22 - m02 m02,
+ *     C12 = m01 m02 - m00 m12, C22 = m00 m11 - m01 m01, det = (m00 C00 + m01 C01) + m02 C02, w_xy = C_xy / det;
+ *   J = [ -[p']x | I ] (3 x 6), x = (alpha, beta, gamma, tx, ty, tz);
+ *   e = W d, e_x = (w_x0 d0 + w_x1 d1) + w_x2 d2;  K = W (-[p']x), row x of K = p' x (row x of W);  G = [p']x K, column y of G =
+ *     p' x (column y of K), every cross product component a difference of two products;
+ *   A = sum J^T W J = sum [ G  K^T ; K  W ] (upper triangle, 21 sums);  g = sum J^T W d = sum (p' x e, e) (6 sums);
+ *   A x = -g by the float64 L D L^T of the point-to-plane mode; dT from x as there (TransformVector6dToMatrix4d);
+ *   T_{s+1} = fp32(dT T_s), the product in float64.  n_corr < 6: bit TOO_FEW, stop.  A non-positive or non-finite pivot: bit SINGULAR,
+ *   T_s is kept, stop.
+ * Status bits.  The ROITR_ICP_* values, with their meaning there.
+ * Outputs.  As roitr_icp_batch, and objective (B) double (optional) = sum d^T W d / n_corr of the last evaluated state, d^T W d =
+ *   (d0 e0 + d1 e1) + d2 e2, 0 when n_corr = 0, NaN for a NONFINITE or EMPTY pair: the quantity the step minimises.  trace_stat is
+ *   (iterations + 1, B, 3) double: fitness, rmse, objective.
+ * Host-side errors (nothing is launched): epsilon outside [1e-6, 1] or not finite, either normals pointer null, and roitr_icp_batch's.
+ * Determinism.  As roitr_icp_batch: the match is an exact decision; every float64 sum of a pair is taken in the order of the ICP update
+ *   (thread t of 256 sums points t, t + 256, ..., then the same binary tree); no floating-point atomics: a pair's results are bitwise
+ *   the same alone, anywhere in a ragged batch, and on repeats.
+ * ws: roitr_gicp_workspace_bytes(B, n, m, iterations).  No host synchronisation, no host read; 2 launches per evaluation. */
+size_t roitr_gicp_workspace_bytes(int b, int n, int m, int iterations);
+int    roitr_gicp_batch(int b, int n, int m, const float* src, const int* src_offset, const float* tgt, const int* tgt_offset,
+                        const float* src_normals, const float* tgt_normals, const float* init_T, float max_dist, double epsilon,
+                        int iterations, double rel_fitness, double rel_rmse, float* T, double* fitness, double* rmse,
+                        double* objective, int* n_corr, int* steps, int* status, int* nn_idx, float* trace_T, double* trace_stat,
+                        void* ws, roitr_stream_t stream);
+
 int roitr_grouping_forward(int m, int nsample, int c, const float* input, const int* idx, float* output, roitr_stream_t stream);
 int roitr_grouping_backward(int m, int nsample, int c, const float* grad_output, const int* idx, float* grad_input, roitr_stream_t stream);
 int roitr_interpolation_forward(int n, int c, int k, const float* input, const int* idx, const float* weight, float* output, roitr_stream_t stream);

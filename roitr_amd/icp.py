@@ -5,7 +5,8 @@ clouds.  Open3D's registration_icp restated (include/roitr_pointops.h states the
 original is unpinned): per pair, nearest target point within max_dist of every moved source point (an exact float64 decision),
 fitness / rmse, the relative convergence test, then a rigid solve (point-to-point) or a Gauss-Newton step on the point-to-plane
 residuals.  The whole loop of a batch runs on the device: two launches per evaluation, no host read, the state rounded to fp32
-between steps.  Robust kernels, point weights, colored / generalized ICP and a multi-scale schedule are out of scope.  No CPU fallback.
+between steps.  Robust kernels, point weights, colored ICP and a multi-scale schedule are out of scope (generalized ICP: gicp.py).
+No CPU fallback.
 """
 import numpy as np
 import torch

@@ -65,11 +65,13 @@ def parser():
                     help="compat estimator: two correspondences are compatible when their point distances differ by less (metres)")
     ap.add_argument("--compat-seeds", type=int, default=64, help="compat estimator: hypotheses per pair (seeds by degree)")
     ap.add_argument("--compat-k", type=int, default=20, help="compat estimator: rows of a seed's consensus set")
-    ap.add_argument("--refine", choices=("none", "point", "plane"), default="none",
+    ap.add_argument("--refine", choices=("none", "point", "plane", "gicp"), default="none",
                     help="refine the estimated pose by ICP on the dense clouds (icp.py): point-to-point, or point-to-plane on the target "
-                         "normals; implies --register")
+                         "normals; gicp: generalized ICP, plane-to-plane on the normals of both clouds (gicp.py); implies --register")
     ap.add_argument("--icp-distance", type=float, default=0.05, help="maximum correspondence distance of the refinement (metres)")
     ap.add_argument("--icp-iterations", type=int, default=30)
+    ap.add_argument("--gicp-epsilon", type=float, default=1e-3,
+                    help="--refine gicp: the covariance eigenvalue along a point's normal, in [1e-6, 1] (1: isotropic points)")
     ap.add_argument("--fpfh-baseline", action="store_true",
                     help="with --evaluate and --register: also run the learning-free baseline on the same pairs (fpfh.py): FPFH "
                          "descriptors, mutual matches under the squared distance, the pose from --estimator (ransac or compat)")
@@ -112,7 +114,8 @@ def main():
                     recall=args.recall, overlap_radius=args.overlap_radius, estimator=args.estimator,
                     lgr=dict(radius=args.lgr_radius, steps=args.lgr_steps),
                     compat=dict(compat_dist=args.compat_dist, max_seeds=args.compat_seeds, k=args.compat_k), refine=args.refine,
-                    icp=dict(max_dist=args.icp_distance, iterations=args.icp_iterations),
+                    icp=dict(max_dist=args.icp_distance, iterations=args.icp_iterations,
+                             **(dict(epsilon=args.gicp_epsilon) if args.refine == "gicp" else {})),
                     fpfh_baseline=dict(radius=args.fpfh_radius, max_nn=args.fpfh_max_nn) if args.fpfh_baseline else None)
     counts = tester.test()
     if rank == 0 and tester.validation:
@@ -191,7 +194,8 @@ def _print_refinement(refinement, status, world, mode):
     bits = ", ".join(f"{name} {sum(1 for r in rows if r[7] & bit)}" for name, bit in
                      (("converged", icp.CONVERGED), ("too few", icp.TOO_FEW), ("singular", icp.SINGULAR), ("empty", icp.EMPTY),
                       ("non-finite", icp.NONFINITE)))
-    print(f"[roitr_amd] ICP refinement (point-to-{mode}) over {len(rows)} pairs: RRE mean {a[:, 0].mean():.3f} -> {a[:, 2].mean():.3f} deg, "
+    label = "generalized, plane-to-plane" if mode == "gicp" else f"point-to-{mode}"
+    print(f"[roitr_amd] ICP refinement ({label}) over {len(rows)} pairs: RRE mean {a[:, 0].mean():.3f} -> {a[:, 2].mean():.3f} deg, "
           f"median {np.median(a[:, 0]):.3f} -> {np.median(a[:, 2]):.3f} deg; RTE mean {a[:, 1].mean():.4f} -> {a[:, 3].mean():.4f} m, median "
           f"{np.median(a[:, 1]):.4f} -> {np.median(a[:, 3]):.4f} m; mean steps {a[:, 6].mean():.1f}; pairs: {bits}")
 

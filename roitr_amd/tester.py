@@ -88,6 +88,8 @@ class Tester:
         transform takes the place of the estimated one everywhere downstream (est_transform, `registration`, the recall rows), and
         `self.refinement` maps this rank's pair ids to (rre_before, rte_before, rre_after, rte_after, fitness, rmse, steps),
         `self.refinement_status` to the pair's ICP status word.  With refine=None nothing of it is imported or run.
+        refine="gicp": the same with generalized ICP (gicp.gicp_handle: plane-to-plane on the normals of both clouds); `icp` then also
+        carries `epsilon`.  The rows of `self.refinement` / `self.refinement_status` are the same; gicp.py is imported in this mode only.
         fpfh_baseline: None, or a dict (radius, max_nn, mutual; defaults 0.125, 100, True) that switches on the learning-free baseline
         (fpfh.fpfh_handle) with evaluate and register: FPFH descriptors of the clouds and normals the model was fed, matched under
         the squared distance, their pose from the selected estimator with its keyword arguments ("ransac", keyed on the global pair
@@ -103,8 +105,8 @@ class Tester:
         self.voxel_size, self.points_lim, self.subsample_seed = voxel_size, points_lim, subsample_seed
         estimate_normals = estimate_normals or voxel_size is not None or points_lim is not None
         self.evaluate, self.estimate_normals, self.view_point = evaluate or validate, estimate_normals, view_point
-        if refine not in (None, "point", "plane"):
-            raise ValueError("refine must be None, 'point' or 'plane'")
+        if refine not in (None, "point", "plane", "gicp"):
+            raise ValueError("refine must be None, 'point', 'plane' or 'gicp'")
         register = register or recall or refine is not None
         self.evaluate = self.evaluate or recall
         if estimator not in ("ransac", "lgr", "compat"):
@@ -289,8 +291,12 @@ class Tester:
                     if self.refine is not None or self.registration is not None:
                         gt_pose = (torch.stack([p["rot"].reshape(3, 3) for p in pairs]), torch.stack([p["trans"].reshape(3) for p in pairs]))
                     if self.refine is not None:
-                        from .icp import icp_handle
-                        ref = icp_handle(handle, reg["T"], plane=self.refine == "plane", **self.icp)
+                        if self.refine == "gicp":
+                            from .gicp import gicp_handle
+                            ref = gicp_handle(handle, reg["T"], **self.icp)
+                        else:
+                            from .icp import icp_handle
+                            ref = icp_handle(handle, reg["T"], plane=self.refine == "plane", **self.icp)
                         before, est = pose_errors(est, *gt_pose), ref["T"].cpu()
                         after = pose_errors(est, *gt_pose)
                         cols = [x.cpu().tolist() for x in (*before, *after, ref["fitness"], ref["rmse"], ref["steps"], ref["status"])]
