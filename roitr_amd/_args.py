@@ -48,6 +48,24 @@ def upload(x, dtype=torch.float32, device="cuda"):
     return t.to(device=device, dtype=dtype).contiguous()
 
 
+def correspondences(starts, src_pts, tgt_pts, scores, per_row="scores"):
+    """The row arrays of the hypothesis estimators (lgr, compat), tensors or arrays on either side, as device tensors on src_pts's
+    device: (device, starts int32, B, src (rows,3), tgt (rows,3), rows, w (rows) or None).  per_row: what the error about a
+    scores length names."""
+    src_pts = src_pts if torch.is_tensor(src_pts) else torch.as_tensor(src_pts)
+    device = src_pts.device if src_pts.is_cuda else torch.device("cuda")
+    starts = torch.as_tensor(starts).to(device=device, dtype=torch.int32).contiguous()
+    src = upload(src_pts, device=device).reshape(-1, 3)
+    tgt = upload(tgt_pts, device=device).reshape(-1, 3)
+    if src.shape != tgt.shape:
+        raise ValueError("src_pts and tgt_pts must have the same shape")
+    rows = int(src.shape[0])
+    w = None if scores is None else upload(scores, device=device).reshape(-1)
+    if w is not None and int(w.shape[0]) != rows:
+        raise ValueError(f"{per_row} must have one entry per row")
+    return device, starts, max(int(starts.shape[0]) - 1, 0), src, tgt, rows, w
+
+
 def cumulative(sizes, device):
     """starts (len(sizes) + 1) int32 on the device of host-known row counts: [0, n0, n0 + n1, ...]; (n,) gives one pair's [0, n]."""
     return torch.tensor(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32), device=device)

@@ -39,18 +39,7 @@ def compat_batch(starts, src_pts, tgt_pts, scores, *, compat_dist=0.1, radius=0.
     winning seed's row, local to the pair), seeds, hypotheses (valid ones), local_inliers (the winner's count) and status (bits
     NO_ROWS, NO_HYPOTHESIS, EMPTY_REFIT, TRUNCATED).  return_stages adds degree (rows; -1: not selected), seed_rows (B, max_seeds),
     seed_members (B, max_seeds, k), hyp_T (B, max_seeds, 3, 4) and hyp_counts (B, max_seeds), by rank, -1 / 0 padded."""
-    src_pts = src_pts if torch.is_tensor(src_pts) else torch.as_tensor(src_pts)
-    dev = src_pts.device if src_pts.is_cuda else torch.device("cuda")
-    starts = torch.as_tensor(starts).to(device=dev, dtype=torch.int32).contiguous()
-    B = max(int(starts.shape[0]) - 1, 0)
-    src = A.upload(src_pts, device=dev).reshape(-1, 3)
-    tgt = A.upload(tgt_pts, device=dev).reshape(-1, 3)
-    if src.shape != tgt.shape:
-        raise ValueError("src_pts and tgt_pts must have the same shape")
-    rows = int(src.shape[0])
-    w = None if scores is None else A.upload(scores, device=dev).reshape(-1)
-    if w is not None and int(w.shape[0]) != rows:
-        raise ValueError("scores must have one entry per row")
+    dev, starts, B, src, tgt, rows, w = A.correspondences(starts, src_pts, tgt_pts, scores)
     if max_rows is None:
         max_rows = max(3, min(MAX_ROWS_DEFAULT, rows))
     max_rows, max_seeds, k = int(max_rows), int(max_seeds), int(k)

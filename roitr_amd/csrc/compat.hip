@@ -18,8 +18,10 @@
 //                            the order of the unique key c_b << 13 | 8191 - b (the (k-1)-th largest c by bisection, ties at it in
 //                            index order by a quota), compacts the members in ascending order, 16 lanes
 //                            per hypothesis sum the float64 moments and one lane per hypothesis runs the Jacobi solve;
-//   compat_verify_kernel     as lgr_verify_kernel: one block per 512 rows of the concatenated array, one hypothesis per lane;
-//   compat_global_kernel     as lgr_global_kernel: arg-max of the counts, `steps` reweighted solves, the final count.
+//   compat_verify_kernel     verify_tile of procrustes_block.h, the body lgr_verify_kernel has too: one block per 512 rows of the
+//                            concatenated array, one hypothesis per lane; here a slot with the count -1 (invalid) is skipped;
+//   compat_global_kernel     arg-max of the counts among the valid hypotheses, then global_refit of procrustes_block.h, as
+//                            lgr_global_kernel: `steps` reweighted solves, the final count.
 // Every decision up to the member sets is an integer or one float64 comparison per (a, b); the float64 sums run over the member
 // index (16 lanes) or the pair's local row index (256 lanes) with fixed butterflies; the only atomics add integer counts.
 #include "common.h"
@@ -69,14 +71,6 @@ CpWorkspace carve(void* ws, int pairs, int max_rows, int max_seeds)
     w.moments = c.take<double>(15 * P * S);
     w.bytes = c.bytes;
     return w;
-}
-
-// sum over the 64 lanes of a wave, in every lane
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ selection
@@ -394,43 +388,8 @@ __global__ __launch_bounds__(LG_THREADS) void compat_verify_kernel(int pairs, co
                                                                    const float* __restrict__ src, const float* __restrict__ tgt,
                                                                    int max_seeds, CpWorkspace ws, float thr2)
 {
-    __shared__ float4 ts[LG_ROWS], tt[LG_ROWS];
-    const int row0 = blockIdx.x * LG_ROWS, m = min(LG_ROWS, total_rows - row0);
-    if (row0 >= starts[pairs]) return;   // capacity rows behind the last pair
-    for (int j = threadIdx.x; j < m; j += LG_THREADS) {
-        const size_t r = (size_t)(row0 + j);
-        ts[j] = make_float4(src[3 * r], src[3 * r + 1], src[3 * r + 2], 0.f);
-        tt[j] = make_float4(tgt[3 * r], tgt[3 * r + 1], tgt[3 * r + 2], 0.f);
-    }
-    __syncthreads();
-    // the last pair that starts at or before row0 (pair 0 if none does), then every pair that starts inside the block's rows
-    int lo = 0, hi = pairs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (starts[mid] <= row0) lo = mid; else hi = mid - 1;
-    }
-    for (int p = lo; p < pairs; ++p) {
-        const int2 rg = starts_range(starts, p, total_rows);
-        if (rg.x >= row0 + m) break;
-        const int j0 = max(rg.x, row0) - row0, j1 = min(rg.y, row0 + m) - row0;
-        if (j1 <= j0) continue;
-        const int H = min(max_seeds, ws.m[p]);
-        const size_t hb = (size_t)p * max_seeds;
-        for (int h = threadIdx.x; h < H; h += LG_THREADS) {
-            if (ws.hyp_count[hb + h] < 0) continue;   // invalid: stays -1 (a valid count only grows from 0)
-            float T[12];
-            const float* Th = ws.hyp_T + 12 * (hb + h);
-#pragma unroll
-            for (int i = 0; i < 12; ++i) T[i] = Th[i];
-            int cnt = 0;
-#pragma unroll 4
-            for (int j = j0; j < j1; ++j) {
-                const float4 a = ts[j], q = tt[j];
-                cnt += rg_dist2(T, a.x, a.y, a.z, q.x, q.y, q.z) < thr2;
-            }
-            if (cnt) atomicAdd(ws.hyp_count + hb + h, cnt);
-        }
-    }
+    auto slots = [&](int p, int) { return HypSlots<size_t>{min(max_seeds, ws.m[p]), (size_t)p * max_seeds}; };
+    verify_tile<true>(pairs, starts, total_rows, src, tgt, slots, ws.hyp_T, ws.hyp_count, thr2);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ global stage
@@ -462,10 +421,7 @@ __global__ __launch_bounds__(LG_THREADS) void compat_global_kernel(const int* __
         const unsigned long long kq = ((unsigned long long)(unsigned)(c + 1) << 32) | (unsigned)(0x7fffffff - h);
         key = kq > key ? kq : key;
     }
-    key = wave_max_u64(key);
-    if ((tid & 63) == 0) redk[tid >> 6] = key;
-    __syncthreads();
-    key = max(max(redk[0], redk[1]), max(redk[2], redk[3]));
+    key = block_winner(key, redk);
     valid = block_sum_i(valid, red4);
     const int best = valid > 0 ? 0x7fffffff - (int)(unsigned)(key & 0xffffffffu) : -1;
     for (int h = tid; h < max_seeds; h += LG_THREADS) {   // every slot of the pair: ranks without a seed read -1 / 0
@@ -477,80 +433,12 @@ __global__ __launch_bounds__(LG_THREADS) void compat_global_kernel(const int* __
     }
 
     float T[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    int st = 0, local = 0, final_count = 0;
-    auto count_under = [&](const float (&Tc)[12]) {
-        int c = 0;
-        for (int j = tid; j < n; j += LG_THREADS) {
-            const size_t r = (size_t)(s + j);
-            c += rg_dist2(Tc, src[3 * r], src[3 * r + 1], src[3 * r + 2], tgt[3 * r], tgt[3 * r + 1], tgt[3 * r + 2]) < thr2;
-        }
-        return block_sum_i(c, red4);
-    };
-    // one solve over all rows of the pair, weights score x [inlier under Tc] (gate) or the score alone; false: the weights sum to 0
-    auto solve = [&](const float (&Tc)[12], bool gate, float (&Tn)[12]) {
-        auto row = [&](int j, float (&p)[3], float (&q)[3], float& w) {
-            const size_t r = (size_t)(s + j);
-            p[0] = src[3 * r]; p[1] = src[3 * r + 1]; p[2] = src[3 * r + 2];
-            q[0] = tgt[3 * r]; q[1] = tgt[3 * r + 1]; q[2] = tgt[3 * r + 2];
-            const bool in = !gate || rg_dist2(Tc, p[0], p[1], p[2], q[0], q[1], q[2]) < thr2;
-            w = in ? (scores ? scores[r] : 1.0f) : 0.f;
-        };
-        double a[7], cs[3], ct[3], Hm[9];
-        moments_first(n, tid, LG_THREADS, row, a);
-        block_sum_d<7>(a, red);
-        if (a[0] == 0.0) return false;
-        centroids(a, cs, ct);
-        moments_second(n, tid, LG_THREADS, row, cs, ct, Hm);
-        block_sum_d<9>(Hm, red);
-        if (tid < 64) {   // every lane holds the same moments: one wave solves
-            rg_solve_rigid(Hm, cs, ct, Tn);
-            if (tid == 0)
-#pragma unroll
-                for (int i = 0; i < 12; ++i) Ts[i] = Tn[i];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 12; ++i) Tn[i] = Ts[i];
-        return true;
-    };
-    if (n == 0) {
-        st = ROITR_COMPAT_NO_ROWS;
-    } else {
-        if (n > max_rows) st |= ROITR_COMPAT_TRUNCATED;
-        bool alive = true;
-        if (best >= 0) {
-#pragma unroll
-            for (int i = 0; i < 12; ++i) T[i] = ws.hyp_T[12 * (hb + best) + i];
-            local = ws.hyp_count[hb + best];
-        } else {   // no valid hypothesis: start from all rows under their scores
-            st |= ROITR_COMPAT_NO_HYPOTHESIS;
-            float Tn[12];
-            alive = solve(T, false, Tn);
-            if (alive) {
-#pragma unroll
-                for (int i = 0; i < 12; ++i) T[i] = Tn[i];
-                local = count_under(T);
-            }
-        }
-        for (int it = 0; it < steps && alive; ++it) {
-            const float Tc[12] = {T[0], T[1], T[2], T[3], T[4], T[5], T[6], T[7], T[8], T[9], T[10], T[11]};
-            float Tn[12];
-            alive = solve(Tc, true, Tn);
-            if (alive) {
-#pragma unroll
-                for (int i = 0; i < 12; ++i) T[i] = Tn[i];
-            }
-        }
-        if (!alive) st |= ROITR_COMPAT_EMPTY_REFIT;
-        final_count = count_under(T);
-    }
-    if (tid < 16) {
-        const int r = tid >> 2, c = tid & 3;
-        float v = r == 3 ? (c == 3 ? 1.f : 0.f) : 0.f;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) v = (r < 3 && i == 4 * r + c) ? T[i] : v;
-        T_out[16 * (size_t)b + tid] = v;
-    }
+    int local, final_count;
+    const bool won = best >= 0;
+    int st = global_refit(s, n, src, tgt, scores, steps, thr2, won ? ws.hyp_T + 12 * (hb + best) : nullptr,
+                          won ? ws.hyp_count + hb + best : nullptr, T, local, final_count, red, red4, Ts);
+    if (n > max_rows) st |= ROITR_COMPAT_TRUNCATED;
+    write_T44(T_out + 16 * (size_t)b, T);
     if (tid == 0) {
         inliers[b] = final_count;
         best_rank[b] = best;

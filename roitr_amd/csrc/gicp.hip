@@ -2,7 +2,8 @@
 // B ragged pairs per call.  The operator is defined in include/roitr_pointops.h above roitr_gicp_batch; this file follows that text.
 //
 // The covariance of a point is fixed by its unit normal, C = I - (1 - eps) n n^T, so nothing is estimated here: the call is
-// roitr_icp_batch's (icp_common.h: status pass, grid, start, exact match) with another update step.  Per evaluation, two launches:
+// roitr_icp_batch's (icp_common.h: icp_run with its checks, status pass, grid, start, exact match and loop; icp_stats, icp_stop_early and
+// icp_commit around the solve) with another update step.  Per evaluation, two launches:
 //   icp_match_kernel     the match of icp.hip, unchanged.
 //   gicp_update_kernel   one workgroup per pair: per matched point, in registers, the unit normals, the rotated source normal, the
 //                        symmetric M = 2I - (1 - eps)(a a^T + b b^T), its inverse W by cofactors, W J through the structure of
@@ -119,22 +120,15 @@ __global__ __launch_bounds__(ICP_THREADS) void gicp_update_kernel(int b, int s, 
         a[27] = pg_add(a[27], e[0]); a[28] = pg_add(a[28], e[1]); a[29] = pg_add(a[29], e[2]);
     }
     ICP_REDUCE_TREE(a, red, NV, wave, lane)
-    // every lane of wave 0 holds the same sums and takes the same decisions; lane 0 writes
-    const double cn = a[0];   // a count below 2^53: exact
-    const int nc = (int)cn;
-    const double fitness = cn / (double)ns, rmse = nc > 0 ? sqrt(a[1] / cn) : 0.0, obj = nc > 0 ? a[2] / cn : 0.0;
-    bool stop = false;
+    // every lane of wave 0 holds the same sums and takes the same decisions; lane 0 writes (icp_common.h)
+    const IcpStats st = icp_stats(a, ns);
+    const double obj = st.nc > 0 ? a[2] / st.cn : 0.0;
     int bits = 0;
     float Tn[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) Tn[k] = T[k];
-    if (s > 0 && fabs(fitness - prev[2 * (size_t)pr]) < rel_fitness && fabs(rmse - prev[2 * (size_t)pr + 1]) < rel_rmse) {
-        stop = true; bits = ROITR_ICP_CONVERGED;
-    } else if (s == iterations) {
-        stop = true;
-    } else if (nc < 6) {
-        stop = true; bits = ROITR_ICP_TOO_FEW;
-    } else {
+    bool stop = icp_stop_early(s, iterations, st, prev + 2 * (size_t)pr, rel_fitness, rel_rmse, 6, bits);
+    if (!stop) {
         double rhs[6], x[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) rhs[k] = -a[24 + k];
@@ -144,39 +138,7 @@ __global__ __launch_bounds__(ICP_THREADS) void gicp_update_kernel(int b, int s, 
             stop = true; bits = ROITR_ICP_SINGULAR;
         }
     }
-    const size_t row = (size_t)s * b + pr;
-    if (lane == 0) {   // constant indices only: a lane-indexed T[] would live in scratch
-        if (o.trace_T)
-#pragma unroll
-            for (int k = 0; k < 12; ++k) o.trace_T[row * 12 + k] = T[k];
-        if (o.trace_stat) { o.trace_stat[row * 3] = fitness; o.trace_stat[row * 3 + 1] = rmse; o.trace_stat[row * 3 + 2] = obj; }
-    }
-    if (!stop) {
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 12; ++k) state[(size_t)pr * 12 + k] = Tn[k];
-            prev[2 * (size_t)pr] = fitness; prev[2 * (size_t)pr + 1] = rmse;
-        }
-        return;
-    }
-    // the stop: the rest of the trace repeats this row
-    for (int e = lane; e < iterations - s; e += 64) {
-        const size_t rr = (size_t)(s + 1 + e) * b + pr;
-        if (o.trace_T)
-#pragma unroll
-            for (int k = 0; k < 12; ++k) o.trace_T[rr * 12 + k] = T[k];
-        if (o.trace_stat) { o.trace_stat[rr * 3] = fitness; o.trace_stat[rr * 3 + 1] = rmse; o.trace_stat[rr * 3 + 2] = obj; }
-    }
-    if (lane == 0) {
-        active[pr] = 0;
-        if (o.T) write_T16(o.T + 16 * (size_t)pr, T);
-        if (o.fitness) o.fitness[pr] = fitness;
-        if (o.rmse) o.rmse[pr] = rmse;
-        if (objective) objective[pr] = obj;
-        if (o.n_corr) o.n_corr[pr] = nc;
-        if (o.steps) o.steps[pr] = s;
-        o.status[pr] |= bits;
-    }
+    icp_commit<3>(b, pr, s, iterations, lane, T, Tn, stop, bits, st, obj, state, active, prev, o, objective);
 }
 
 }  // namespace
@@ -193,42 +155,22 @@ extern "C" int roitr_gicp_batch(int b, int n, int m, const float* src, const int
                                 double* objective, int* n_corr, int* steps, int* status, int* nn_idx, float* trace_T,
                                 double* trace_stat, void* ws, hipStream_t stream)
 {
-    if (!(max_dist > 0.f) || !std::isfinite(max_dist)) return refuse(ROITR_ERR_ARG, "gicp_batch: max_dist must be finite and positive");
     if (!(epsilon >= 1e-6 && epsilon <= 1.0)) return refuse(ROITR_ERR_ARG, "gicp_batch: epsilon must lie in [1e-6, 1]");
-    if (iterations < 0 || !(rel_fitness >= 0.0) || !(rel_rmse >= 0.0))
-        return refuse(ROITR_ERR_ARG, "gicp_batch: iterations, rel_fitness and rel_rmse must not be negative");
-    if (b <= 0 || b > ICP_MAX_PAIRS) return refuse(ROITR_ERR_ARG, "gicp_batch: 1 <= B <= 65536 pairs");
-    if (n < 0 || m < 0 || n > 0x7fffffff - ICP_THREADS || m > 0x7fffffff - ICP_THREADS)
-        return refuse(ROITR_ERR_ARG, "gicp_batch: point counts out of range");
-    if (!src_offset || !tgt_offset || !init_T || !T || !status || !ws || (n > 0 && !src) || (m > 0 && !tgt))
-        return refuse(ROITR_ERR_ARG, "gicp_batch: null pointer");
     if (!src_normals || !tgt_normals) return refuse(ROITR_ERR_ARG, "gicp_batch: null normals pointer (both clouds need normals)");
-    const IcpWs w = carve(ws, b, n, m, iterations);
-    int* match = nn_idx ? nn_idx : w.match;   // stopped pairs are not matched again: the buffer ends up holding every pair's final matches
     const IcpOut o{T, fitness, rmse, n_corr, steps, status, trace_T, trace_stat};
-    ROITR_HIP(hipMemsetAsync(status, 0, (size_t)b * 4, stream));
-    if (n > 0) ROITR_HIP(hipMemsetAsync(match, 0xff, (size_t)n * 4, stream));
-    const int most = n > m ? (n > b ? n : b) : (m > b ? m : b);
-    gicp_prepare_kernel<<<div_up(most, ICP_THREADS), ICP_THREADS, 0, stream>>>(b, n, m, src, src_offset, tgt, tgt_offset, src_normals,
-                                                                           tgt_normals, init_T, w.clean, status);
-    ROITR_LAUNCH_CHECK();
-    const RoitrGridView gv = roitr_knn_grid_view(b, m, 0, w.knn);
-    if (m > 0) {
-        const int rc = roitr_knn_build_grid_ex(b, m, 0, w.clean, tgt_offset, w.knn, 0.f, stream);
-        if (rc != ROITR_OK) return rc;
-    }
-    // all-ones bytes are a NaN: what the objective of a pair that never runs (NONFINITE, EMPTY) stays; every other pair writes its own
-    if (objective) ROITR_HIP(hipMemsetAsync(objective, 0xff, (size_t)b * 8, stream));
-    icp_start_kernel<3><<<div_up(b, ICP_THREADS), ICP_THREADS, 0, stream>>>(b, iterations, init_T, w.state, w.active, w.prev, o);
-    ROITR_LAUNCH_CHECK();
+    auto prepare = [&](const IcpWs& w, int most) {
+        // all-ones bytes are a NaN: what the objective of a pair that never runs (NONFINITE, EMPTY) stays; every other pair writes its
+        // own.  Set here, behind the driver's checks: a refused call leaves the outputs untouched.
+        if (objective) ROITR_HIP(hipMemsetAsync(objective, 0xff, (size_t)b * 8, stream));
+        gicp_prepare_kernel<<<div_up(most, ICP_THREADS), ICP_THREADS, 0, stream>>>(b, n, m, src, src_offset, tgt, tgt_offset, src_normals,
+                                                                               tgt_normals, init_T, w.clean, status);
+        return ROITR_OK;
+    };
     const double c = 1.0 - epsilon;
-    // n == 0 or m == 0: every pair carries EMPTY, nothing is active and no lane reads the (unbuilt) grid
-    for (int s = 0; s <= iterations && n > 0 && m > 0; ++s) {
-        icp_match_kernel<<<div_up(n, ICP_THREADS), ICP_THREADS, 0, stream>>>(b, n, src, src_offset, tgt, tgt_offset, w.state, w.active,
-                                                                            (double)max_dist, gv.grids, gv.cell_start, gv.sorted, match, w.d2);
+    auto update = [&](const IcpWs& w, const int* match, int s) {
         gicp_update_kernel<<<b, ICP_THREADS, 0, stream>>>(b, s, iterations, rel_fitness, rel_rmse, c, src, src_offset, tgt, tgt_offset,
                                                          src_normals, tgt_normals, match, w.d2, w.state, w.active, w.prev, o, objective);
-        ROITR_LAUNCH_CHECK();
-    }
-    return ROITR_OK;
+    };
+    return icp_run<3>("gicp_batch", b, n, m, src, src_offset, tgt, tgt_offset, init_T, max_dist, iterations, rel_fitness, rel_rmse, o,
+                      nn_idx, ws, stream, prepare, update);
 }

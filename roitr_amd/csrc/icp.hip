@@ -14,7 +14,9 @@
 //                       pairgt_reduce_kernel: t + 128, t + 64 through LDS, t + 32 .. t + 1 inside wave 0), then wave 0 tests
 //                       convergence, solves, and writes the next state, the trace row and -- at a stop -- the outputs.
 // Lanes and workgroups of a stopped pair leave at once: the launch count depends on `iterations` alone, nothing is read back.
-// Everything but the update kernel lives in icp_common.h, which gicp.hip shares.
+// What is left here is the mode's own part: the per-point sums and the solve of icp_update_kernel, and the two launches handed to icp_run.
+// The host sequence (icp_run), the match kernel, the tree and what wave 0 does around the solve (icp_stats, icp_stop_early, icp_commit)
+// live in icp_common.h, which gicp.hip shares.
 #include "common.h"
 #include "knn_grid.h"
 #include "registration_math.h"
@@ -87,31 +89,23 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_update_kernel(int b, int s, i
         }
     }
     ICP_REDUCE_TREE(a, red, NV, wave, lane)
-    // every lane of wave 0 holds the same sums and takes the same decisions; lane 0 writes
-    const double cn = a[0];   // a count below 2^53: exact
-    const int nc = (int)cn;
-    const double fitness = cn / (double)ns, rmse = nc > 0 ? sqrt(a[1] / cn) : 0.0;
-    bool stop = false;
+    // every lane of wave 0 holds the same sums and takes the same decisions; lane 0 writes (icp_common.h)
+    const IcpStats st = icp_stats(a, ns);
     int bits = 0;
     float Tn[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) Tn[k] = T[k];
-    if (s > 0 && fabs(fitness - prev[2 * (size_t)pr]) < rel_fitness && fabs(rmse - prev[2 * (size_t)pr + 1]) < rel_rmse) {
-        stop = true; bits = ROITR_ICP_CONVERGED;
-    } else if (s == iterations) {
-        stop = true;
-    } else if (nc < (PLANE ? 6 : 3)) {
-        stop = true; bits = ROITR_ICP_TOO_FEW;
-    } else if (!PLANE) {
+    bool stop = icp_stop_early(s, iterations, st, prev + 2 * (size_t)pr, rel_fitness, rel_rmse, PLANE ? 6 : 3, bits);
+    if (!stop && !PLANE) {
         double cs_[3], ct_[3], H[9];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) { cs_[c] = a[2 + c] / cn; ct_[c] = a[5 + c] / cn; }
+        for (int c = 0; c < 3; ++c) { cs_[c] = a[2 + c] / st.cn; ct_[c] = a[5 + c] / st.cn; }
 #pragma unroll
         for (int x = 0; x < 3; ++x)
 #pragma unroll
             for (int y = 0; y < 3; ++y) H[3 * x + y] = a[8 + 3 * x + y] - a[2 + x] * ct_[y];   // sum (p - cs)(q - ct)^T
         rg_solve_rigid(H, cs_, ct_, Tn);
-    } else {
+    } else if (!stop) {
         double rhs[6], x[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) rhs[k] = -a[23 + k];
@@ -121,38 +115,7 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_update_kernel(int b, int s, i
             stop = true; bits = ROITR_ICP_SINGULAR;
         }
     }
-    const size_t row = (size_t)s * b + pr;
-    if (lane == 0) {   // constant indices only: a lane-indexed T[] would live in scratch
-        if (o.trace_T)
-#pragma unroll
-            for (int k = 0; k < 12; ++k) o.trace_T[row * 12 + k] = T[k];
-        if (o.trace_stat) { o.trace_stat[row * 2] = fitness; o.trace_stat[row * 2 + 1] = rmse; }
-    }
-    if (!stop) {
-        if (lane == 0) {
-#pragma unroll
-            for (int k = 0; k < 12; ++k) state[(size_t)pr * 12 + k] = Tn[k];
-            prev[2 * (size_t)pr] = fitness; prev[2 * (size_t)pr + 1] = rmse;
-        }
-        return;
-    }
-    // the stop: the rest of the trace repeats this row
-    for (int e = lane; e < iterations - s; e += 64) {
-        const size_t rr = (size_t)(s + 1 + e) * b + pr;
-        if (o.trace_T)
-#pragma unroll
-            for (int k = 0; k < 12; ++k) o.trace_T[rr * 12 + k] = T[k];
-        if (o.trace_stat) { o.trace_stat[rr * 2] = fitness; o.trace_stat[rr * 2 + 1] = rmse; }
-    }
-    if (lane == 0) {
-        active[pr] = 0;
-        if (o.T) write_T16(o.T + 16 * (size_t)pr, T);
-        if (o.fitness) o.fitness[pr] = fitness;
-        if (o.rmse) o.rmse[pr] = rmse;
-        if (o.n_corr) o.n_corr[pr] = nc;
-        if (o.steps) o.steps[pr] = s;
-        o.status[pr] |= bits;
-    }
+    icp_commit<2>(b, pr, s, iterations, lane, T, Tn, stop, bits, st, 0.0, state, active, prev, o, nullptr);
 }
 
 }  // namespace
@@ -168,41 +131,20 @@ extern "C" int roitr_icp_batch(int b, int n, int m, const float* src, const int*
                                double rel_rmse, float* T, double* fitness, double* rmse, int* n_corr, int* steps, int* status,
                                int* nn_idx, float* trace_T, double* trace_stat, void* ws, hipStream_t stream)
 {
-    if (!(max_dist > 0.f) || !std::isfinite(max_dist)) return refuse(ROITR_ERR_ARG, "icp_batch: max_dist must be finite and positive");
-    if (iterations < 0 || !(rel_fitness >= 0.0) || !(rel_rmse >= 0.0))
-        return refuse(ROITR_ERR_ARG, "icp_batch: iterations, rel_fitness and rel_rmse must not be negative");
-    if (b <= 0 || b > ICP_MAX_PAIRS) return refuse(ROITR_ERR_ARG, "icp_batch: 1 <= B <= 65536 pairs");
-    if (n < 0 || m < 0 || n > 0x7fffffff - ICP_THREADS || m > 0x7fffffff - ICP_THREADS)
-        return refuse(ROITR_ERR_ARG, "icp_batch: point counts out of range");
-    if (!src_offset || !tgt_offset || !init_T || !T || !status || !ws || (n > 0 && !src) || (m > 0 && !tgt))
-        return refuse(ROITR_ERR_ARG, "icp_batch: null pointer");
-    const IcpWs w = carve(ws, b, n, m, iterations);
-    int* match = nn_idx ? nn_idx : w.match;   // stopped pairs are not matched again: the buffer ends up holding every pair's final matches
     const IcpOut o{T, fitness, rmse, n_corr, steps, status, trace_T, trace_stat};
-    ROITR_HIP(hipMemsetAsync(status, 0, (size_t)b * 4, stream));
-    if (n > 0) ROITR_HIP(hipMemsetAsync(match, 0xff, (size_t)n * 4, stream));
-    const int most = n > m ? (n > b ? n : b) : (m > b ? m : b);
-    icp_prepare_kernel<<<div_up(most, ICP_THREADS), ICP_THREADS, 0, stream>>>(b, n, m, src, src_offset, tgt, tgt_offset, tgt_normals, init_T,
-                                                                          w.clean, status);
-    ROITR_LAUNCH_CHECK();
-    const RoitrGridView gv = roitr_knn_grid_view(b, m, 0, w.knn);
-    if (m > 0) {
-        const int rc = roitr_knn_build_grid_ex(b, m, 0, w.clean, tgt_offset, w.knn, 0.f, stream);
-        if (rc != ROITR_OK) return rc;
-    }
-    icp_start_kernel<2><<<div_up(b, ICP_THREADS), ICP_THREADS, 0, stream>>>(b, iterations, init_T, w.state, w.active, w.prev, o);
-    ROITR_LAUNCH_CHECK();
-    // n == 0 or m == 0: every pair carries EMPTY, nothing is active and no lane reads the (unbuilt) grid
-    for (int s = 0; s <= iterations && n > 0 && m > 0; ++s) {
-        icp_match_kernel<<<div_up(n, ICP_THREADS), ICP_THREADS, 0, stream>>>(b, n, src, src_offset, tgt, tgt_offset, w.state, w.active,
-                                                                            (double)max_dist, gv.grids, gv.cell_start, gv.sorted, match, w.d2);
+    auto prepare = [&](const IcpWs& w, int most) {
+        icp_prepare_kernel<<<div_up(most, ICP_THREADS), ICP_THREADS, 0, stream>>>(b, n, m, src, src_offset, tgt, tgt_offset, tgt_normals,
+                                                                              init_T, w.clean, status);
+        return ROITR_OK;
+    };
+    auto update = [&](const IcpWs& w, const int* match, int s) {
         if (tgt_normals)
             icp_update_kernel<true><<<b, ICP_THREADS, 0, stream>>>(b, s, iterations, rel_fitness, rel_rmse, src, src_offset, tgt, tgt_offset,
                                                                    tgt_normals, match, w.d2, w.state, w.active, w.prev, o);
         else
             icp_update_kernel<false><<<b, ICP_THREADS, 0, stream>>>(b, s, iterations, rel_fitness, rel_rmse, src, src_offset, tgt, tgt_offset,
                                                                     nullptr, match, w.d2, w.state, w.active, w.prev, o);
-        ROITR_LAUNCH_CHECK();
-    }
-    return ROITR_OK;
+    };
+    return icp_run<2>("icp_batch", b, n, m, src, src_offset, tgt, tgt_offset, init_T, max_dist, iterations, rel_fitness, rel_rmse, o, nn_idx,
+                      ws, stream, prepare, update);
 }

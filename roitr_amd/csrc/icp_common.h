@@ -1,7 +1,9 @@
 // What the ICP family shares on the device (icp.hip: point-to-point / point-to-plane, gicp.hip: plane-to-plane): the workspace, the
 // status pass, the per-pair start, the float64 move, the exact nearest-neighbour match, the 6x6 L D L^T solve, the composition of a
-// step with the state and the ordered reduction tree.  Carved out of icp.hip unchanged, the way ball_walk.h was carved out of
-// pairgt.hip; every translation unit that includes it gets its own copy of the kernels (anonymous namespace).
+// step with the state, the ordered reduction tree, what wave 0 of an update kernel does around its solve (icp_stats, icp_stop_early,
+// icp_commit) and the host side of a call (icp_run).  Carved out of icp.hip, the way ball_walk.h was carved out of pairgt.hip; every
+// translation unit that includes it gets its own copy of the kernels (anonymous namespace).  The device functions round every product
+// and sum on its own: pg_add / pg_mul / pg_sub, or plain operators under the includer's contract(off).
 // Include it AFTER `#pragma clang fp contract(off)`, like ball_walk.h: the operator's rule is "every product and sum rounded on its own";
 // and include common.h, knn_grid.h and workspace.h BEFORE that pragma, as icp.hip always has, so that their inline fp32 code keeps
 // the contraction it is compiled with everywhere else (the includes below are then no-ops).
@@ -11,6 +13,7 @@
 #include "roitr_pointops.h"
 #include "workspace.h"
 #include <cmath>
+#include <cstdio>
 
 #define ICP_THREADS 256
 #define ICP_MAX_PAIRS 65536
@@ -304,5 +307,112 @@ __device__ __forceinline__ void compose_step(const double (&x)[6], const float (
         _Pragma("unroll") for (int w = 32; w > 0; w >>= 1) v = pg_add(v, __shfl_down(v, w, 64)); \
         a[k] = __shfl(v, 0, 64);                                                                 \
     }
+
+// What wave 0 of an update kernel does after the tree, every lane holding the same sums and taking the same decisions: icp_stats,
+// icp_stop_early, the mode's own solve (Tn, or SINGULAR and a stop), icp_commit.
+struct IcpStats { double cn; int nc; double fitness, rmse; };
+
+// a[0]: the match count (below 2^53: exact), a[1]: sum d2; ns: the pair's source points
+__device__ __forceinline__ IcpStats icp_stats(const double* a, int ns)
+{
+    IcpStats st;
+    st.cn = a[0];
+    st.nc = (int)st.cn;
+    st.fitness = st.cn / (double)ns;
+    st.rmse = st.nc > 0 ? sqrt(a[1] / st.cn) : 0.0;
+    return st;
+}
+
+// The stops that come before a solve, in their order: converged against the pair's prev (fitness, rmse), the last evaluation, fewer than
+// min_corr matches.  true: the pair stops at this evaluation with `bits`.
+__device__ __forceinline__ bool icp_stop_early(int s, int iterations, const IcpStats& st, const double* prev, double rel_fitness,
+                                               double rel_rmse, int min_corr, int& bits)
+{
+    if (s > 0 && fabs(st.fitness - prev[0]) < rel_fitness && fabs(st.rmse - prev[1]) < rel_rmse) { bits = ROITR_ICP_CONVERGED; return true; }
+    if (s == iterations) return true;
+    if (st.nc < min_corr) { bits = ROITR_ICP_TOO_FEW; return true; }
+    return false;
+}
+
+// The trace row of evaluation s, then either the next state Tn and the pair's prev, or -- at a stop -- the rest of the trace (it repeats
+// this row), the active word, the outputs and the status bits.  NSTAT 3: `third` is the last trace_stat column and goes to objective[pr].
+template <int NSTAT>
+__device__ __forceinline__ void icp_commit(int b, int pr, int s, int iterations, int lane, const float (&T)[12], const float (&Tn)[12],
+                                           bool stop, int bits, const IcpStats& st, double third, float* __restrict__ state,
+                                           int* __restrict__ active, double* __restrict__ prev, const IcpOut& o,
+                                           double* __restrict__ objective)
+{
+    auto trace = [&](size_t row) {   // constant indices only: a lane-indexed T[] would live in scratch
+        if (o.trace_T)
+#pragma unroll
+            for (int k = 0; k < 12; ++k) o.trace_T[row * 12 + k] = T[k];
+        if (o.trace_stat) {
+            o.trace_stat[row * NSTAT] = st.fitness; o.trace_stat[row * NSTAT + 1] = st.rmse;
+            if (NSTAT == 3) o.trace_stat[row * NSTAT + 2] = third;
+        }
+    };
+    if (lane == 0) trace((size_t)s * b + pr);
+    if (!stop) {
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) state[(size_t)pr * 12 + k] = Tn[k];
+            prev[2 * (size_t)pr] = st.fitness; prev[2 * (size_t)pr + 1] = st.rmse;
+        }
+        return;
+    }
+    for (int e = lane; e < iterations - s; e += 64) trace((size_t)(s + 1 + e) * b + pr);
+    if (lane == 0) {
+        active[pr] = 0;
+        if (o.T) write_T16(o.T + 16 * (size_t)pr, T);
+        if (o.fitness) o.fitness[pr] = st.fitness;
+        if (o.rmse) o.rmse[pr] = st.rmse;
+        if (NSTAT == 3 && objective) objective[pr] = third;
+        if (o.n_corr) o.n_corr[pr] = st.nc;
+        if (o.steps) o.steps[pr] = s;
+        o.status[pr] |= bits;
+    }
+}
+
+// The host side of a call: the argument checks (error texts begin with `who`), the two memsets, prepare(w, most) -- the mode's status
+// pass over `most` threads --, the target grid, the start and the evaluation loop of icp_match_kernel and update(w, match, s).  NSTAT:
+// the columns of trace_stat.
+template <int NSTAT, class Prepare, class Update>
+int icp_run(const char* who, int b, int n, int m, const float* src, const int* src_offset, const float* tgt, const int* tgt_offset,
+            const float* init_T, float max_dist, int iterations, double rel_fitness, double rel_rmse, const IcpOut& o, int* nn_idx, void* ws,
+            hipStream_t stream, Prepare prepare, Update update)
+{
+    auto bad = [&](const char* what) {
+        char text[160];
+        snprintf(text, sizeof(text), "%s: %s", who, what);
+        return refuse(ROITR_ERR_ARG, text);
+    };
+    if (!(max_dist > 0.f) || !std::isfinite(max_dist)) return bad("max_dist must be finite and positive");
+    if (iterations < 0 || !(rel_fitness >= 0.0) || !(rel_rmse >= 0.0)) return bad("iterations, rel_fitness and rel_rmse must not be negative");
+    if (b <= 0 || b > ICP_MAX_PAIRS) return bad("1 <= B <= 65536 pairs");
+    if (n < 0 || m < 0 || n > 0x7fffffff - ICP_THREADS || m > 0x7fffffff - ICP_THREADS) return bad("point counts out of range");
+    if (!src_offset || !tgt_offset || !init_T || !o.T || !o.status || !ws || (n > 0 && !src) || (m > 0 && !tgt)) return bad("null pointer");
+    const IcpWs w = carve(ws, b, n, m, iterations);
+    int* match = nn_idx ? nn_idx : w.match;   // stopped pairs are not matched again: the buffer ends up holding every pair's final matches
+    ROITR_HIP(hipMemsetAsync(o.status, 0, (size_t)b * 4, stream));
+    if (n > 0) ROITR_HIP(hipMemsetAsync(match, 0xff, (size_t)n * 4, stream));
+    const int rcp = prepare(w, n > m ? (n > b ? n : b) : (m > b ? m : b));
+    if (rcp != ROITR_OK) return rcp;
+    ROITR_LAUNCH_CHECK();
+    const RoitrGridView gv = roitr_knn_grid_view(b, m, 0, w.knn);
+    if (m > 0) {
+        const int rc = roitr_knn_build_grid_ex(b, m, 0, w.clean, tgt_offset, w.knn, 0.f, stream);
+        if (rc != ROITR_OK) return rc;
+    }
+    icp_start_kernel<NSTAT><<<div_up(b, ICP_THREADS), ICP_THREADS, 0, stream>>>(b, iterations, init_T, w.state, w.active, w.prev, o);
+    ROITR_LAUNCH_CHECK();
+    // n == 0 or m == 0: every pair carries EMPTY, nothing is active and no lane reads the (unbuilt) grid
+    for (int s = 0; s <= iterations && n > 0 && m > 0; ++s) {
+        icp_match_kernel<<<div_up(n, ICP_THREADS), ICP_THREADS, 0, stream>>>(b, n, src, src_offset, tgt, tgt_offset, w.state, w.active,
+                                                                            (double)max_dist, gv.grids, gv.cell_start, gv.sorted, match, w.d2);
+        update(w, match, s);
+        ROITR_LAUNCH_CHECK();
+    }
+    return ROITR_OK;
+}
 
 }  // namespace

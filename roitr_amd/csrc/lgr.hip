@@ -16,6 +16,8 @@
 // (hypothesis chunks x row chunks x pairs) would have to be sized for the worst pair in both dimensions.  Counts are integers, so
 // the chunk borders (global row positions) cannot change a result.  Every float64 sum is a strided per-lane sum over the local
 // row index followed by a fixed butterfly, so it depends on the pair's (the run's) own rows only.
+// The bodies of the last two kernels are verify_tile, block_winner, global_refit and write_T44 of procrustes_block.h, which compat.hip
+// calls too: the kernels here say where a pair's hypothesis slots are, form the winner key and write this operator's outputs.
 #include "common.h"
 #include "procrustes_block.h"
 #include "registration_math.h"
@@ -133,41 +135,8 @@ __global__ __launch_bounds__(LG_THREADS) void lgr_verify_kernel(int pairs, const
                                                                 int min_rows, LgWorkspace ws, const int* __restrict__ hypotheses,
                                                                 float thr2)
 {
-    __shared__ float4 ts[LG_ROWS], tt[LG_ROWS];
-    const int row0 = blockIdx.x * LG_ROWS, m = min(LG_ROWS, total_rows - row0);
-    if (row0 >= starts[pairs]) return;   // capacity rows behind the last pair (the engine's buffers are sized for the worst case)
-    for (int j = threadIdx.x; j < m; j += LG_THREADS) {
-        const size_t r = (size_t)(row0 + j);
-        ts[j] = make_float4(src[3 * r], src[3 * r + 1], src[3 * r + 2], 0.f);
-        tt[j] = make_float4(tgt[3 * r], tgt[3 * r + 1], tgt[3 * r + 2], 0.f);
-    }
-    __syncthreads();
-    // the last pair that starts at or before row0 (pair 0 if none does), then every pair that starts inside the block's rows
-    int lo = 0, hi = pairs - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (starts[mid] <= row0) lo = mid; else hi = mid - 1;
-    }
-    for (int p = lo; p < pairs; ++p) {
-        const int2 rg = starts_range(starts, p, total_rows);
-        if (rg.x >= row0 + m) break;
-        const int j0 = max(rg.x, row0) - row0, j1 = min(rg.y, row0 + m) - row0;
-        if (j1 <= j0) continue;
-        const int H = hypotheses[p], hb = rg.x / min_rows;
-        for (int h = threadIdx.x; h < H; h += LG_THREADS) {
-            float T[12];
-            const float* Th = ws.hyp_T + 12 * (size_t)(hb + h);
-#pragma unroll
-            for (int k = 0; k < 12; ++k) T[k] = Th[k];
-            int cnt = 0;
-#pragma unroll 4
-            for (int j = j0; j < j1; ++j) {
-                const float4 a = ts[j], q = tt[j];
-                cnt += rg_dist2(T, a.x, a.y, a.z, q.x, q.y, q.z) < thr2;
-            }
-            if (cnt) atomicAdd(ws.hyp_count + hb + h, cnt);
-        }
-    }
+    auto slots = [&](int p, int first_row) { return HypSlots<int>{hypotheses[p], first_row / min_rows}; };
+    verify_tile<false>(pairs, starts, total_rows, src, tgt, slots, ws.hyp_T, ws.hyp_count, thr2);
 }
 
 __global__ __launch_bounds__(LG_THREADS) void lgr_global_kernel(const int* __restrict__ starts, int total_rows,
@@ -194,10 +163,7 @@ __global__ __launch_bounds__(LG_THREADS) void lgr_global_kernel(const int* __res
         const unsigned long long k = ((unsigned long long)(unsigned)ws.hyp_count[hb + h] << 32) | (unsigned)(0x7fffffff - h);
         key = k > key ? k : key;
     }
-    key = wave_max_u64(key);
-    if ((tid & 63) == 0) redk[tid >> 6] = key;
-    __syncthreads();
-    key = max(max(redk[0], redk[1]), max(redk[2], redk[3]));
+    key = block_winner(key, redk);
     const int best = H > 0 ? 0x7fffffff - (int)(unsigned)(key & 0xffffffffu) : -1;
     if (hyp_starts) {
         if (tid == 0) hyp_starts[b] = hb;
@@ -211,80 +177,11 @@ __global__ __launch_bounds__(LG_THREADS) void lgr_global_kernel(const int* __res
     }
 
     float T[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    int st = 0, local = 0, final_count = 0;
-    auto count_under = [&](const float (&Tc)[12]) {
-        int c = 0;
-        for (int j = tid; j < n; j += LG_THREADS) {
-            const size_t r = (size_t)(s + j);
-            c += rg_dist2(Tc, src[3 * r], src[3 * r + 1], src[3 * r + 2], tgt[3 * r], tgt[3 * r + 1], tgt[3 * r + 2]) < thr2;
-        }
-        return block_sum_i(c, red4);
-    };
-    // one solve over all rows of the pair, weights score x [inlier under Tc] (gate) or the score alone; false: the weights sum to 0
-    auto solve = [&](const float (&Tc)[12], bool gate, float (&Tn)[12]) {
-        auto row = [&](int j, float (&p)[3], float (&q)[3], float& w) {
-            const size_t r = (size_t)(s + j);
-            p[0] = src[3 * r]; p[1] = src[3 * r + 1]; p[2] = src[3 * r + 2];
-            q[0] = tgt[3 * r]; q[1] = tgt[3 * r + 1]; q[2] = tgt[3 * r + 2];
-            const bool in = !gate || rg_dist2(Tc, p[0], p[1], p[2], q[0], q[1], q[2]) < thr2;
-            w = in ? (scores ? scores[r] : 1.0f) : 0.f;
-        };
-        double a[7], cs[3], ct[3], Hm[9];
-        moments_first(n, tid, LG_THREADS, row, a);
-        block_sum_d<7>(a, red);
-        if (a[0] == 0.0) return false;
-        centroids(a, cs, ct);
-        moments_second(n, tid, LG_THREADS, row, cs, ct, Hm);
-        block_sum_d<9>(Hm, red);
-        // every lane holds the same moments: one wave solves, the others leave the float64 pipe to the block next door
-        if (tid < 64) {
-            rg_solve_rigid(Hm, cs, ct, Tn);
-            if (tid == 0)
-#pragma unroll
-                for (int k = 0; k < 12; ++k) Ts[k] = Tn[k];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 12; ++k) Tn[k] = Ts[k];
-        return true;
-    };
-    if (n == 0) {
-        st = ROITR_LGR_NO_ROWS;
-    } else {
-        bool alive = true;
-        if (best >= 0) {
-#pragma unroll
-            for (int k = 0; k < 12; ++k) T[k] = ws.hyp_T[12 * (size_t)(hb + best) + k];
-            local = ws.hyp_count[hb + best];
-        } else {   // GeoTransformer's degenerate branch: start from all rows under their scores
-            st |= ROITR_LGR_NO_LOCAL;
-            float Tn[12];
-            alive = solve(T, false, Tn);
-            if (alive) {
-#pragma unroll
-                for (int k = 0; k < 12; ++k) T[k] = Tn[k];
-                local = count_under(T);
-            }
-        }
-        for (int k = 0; k < steps && alive; ++k) {
-            const float Tc[12] = {T[0], T[1], T[2], T[3], T[4], T[5], T[6], T[7], T[8], T[9], T[10], T[11]};
-            float Tn[12];
-            alive = solve(Tc, true, Tn);
-            if (alive) {
-#pragma unroll
-                for (int i = 0; i < 12; ++i) T[i] = Tn[i];
-            }
-        }
-        if (!alive) st |= ROITR_LGR_EMPTY_REFIT;
-        final_count = count_under(T);
-    }
-    if (tid < 16) {
-        const int r = tid >> 2, c = tid & 3;
-        float v = r == 3 ? (c == 3 ? 1.f : 0.f) : 0.f;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) v = (r < 3 && k == 4 * r + c) ? T[k] : v;
-        T_out[16 * (size_t)b + tid] = v;
-    }
+    int local, final_count;
+    const bool won = best >= 0;
+    const int st = global_refit(s, n, src, tgt, scores, steps, thr2, won ? ws.hyp_T + 12 * (size_t)(hb + best) : nullptr,
+                                won ? ws.hyp_count + hb + best : nullptr, T, local, final_count, red, red4, Ts);
+    write_T44(T_out + 16 * (size_t)b, T);
     if (tid == 0) {
         inliers[b] = final_count;
         best_hypothesis[b] = best;

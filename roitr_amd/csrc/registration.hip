@@ -229,6 +229,7 @@ __global__ __launch_bounds__(RG_THREADS) void ransac_hyp_kernel(const int* __res
 }
 
 // fixed-tree block sum of NV doubles per thread (every thread gets the totals); red holds RG_THREADS * NV doubles
+// (procrustes_block.h's block_sum_d is a wave butterfly that folds in another order: unifying the two would change result bits)
 template <int NV>
 __device__ __forceinline__ void block_sum_d(double (&v)[NV], double* red)
 {

@@ -12,8 +12,7 @@ import torch
 
 from . import _args as A
 from . import _lib as L
-from .icp import CONVERGED, EMPTY, NONFINITE, SINGULAR, TOO_FEW  # noqa: F401  (the status bits are the ICP operator's)
-from .pairgt import _check_offsets
+from .icp import CONVERGED, EMPTY, NONFINITE, SINGULAR, TOO_FEW, _prepare  # noqa: F401  (the status bits are the ICP operator's)
 
 _bound = None
 
@@ -36,42 +35,16 @@ def gicp_batch(src, src_offset, tgt, tgt_offset, init_T, *, src_normals, tgt_nor
     Returns icp_batch's dict of device tensors (T, fitness, rmse, n_corr, steps, status) plus objective (B) float64, the mean of
     d^T W d over the matches of the last evaluated state.  return_matches adds nn_idx (n) int32; return_trace adds trace_T
     (iterations + 1, B, 3, 4) and trace_stat (iterations + 1, B, 3): fitness, rmse and objective of every evaluation."""
-    src, tgt = A.points(src, "gicp: src"), A.points(tgt, "gicp: tgt")
-    dev = src.device
-    tgt = tgt.to(dev)
-    n, m = int(src.shape[0]), int(tgt.shape[0])
-    _check_offsets("src_offset", src_offset, n)
-    _check_offsets("tgt_offset", tgt_offset, m)
-    so = torch.as_tensor(src_offset).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-    to = torch.as_tensor(tgt_offset).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-    B = int(so.shape[0])
-    if int(to.shape[0]) != B:
-        raise L.RoitrError("gicp: src_offset and tgt_offset must have one entry per pair")
-    T0 = A.dev(init_T, torch.float32, "gicp: init_T").to(dev).reshape(-1, 4, 4)
-    if int(T0.shape[0]) != B:
-        raise L.RoitrError(f"gicp: {B} pairs need init_T (B,4,4)")
     if src_normals is None or tgt_normals is None:
         raise L.RoitrError("gicp: src_normals and tgt_normals are both required")
-    ns = A.points(src_normals, "gicp: src_normals").to(dev)
-    nt = A.points(tgt_normals, "gicp: tgt_normals").to(dev)
-    if int(ns.shape[0]) != n or int(nt.shape[0]) != m:
-        raise L.RoitrError("gicp: the normals must have one row per point of their cloud")
-    iterations = int(iterations)
-    rows = max(iterations, 0) + 1
-    f64 = lambda: torch.empty((B,), dtype=torch.float64, device=dev)
-    i32 = lambda: torch.empty((B,), dtype=torch.int32, device=dev)
-    out = dict(T=torch.empty((B, 4, 4), dtype=torch.float32, device=dev), fitness=f64(), rmse=f64(), objective=f64(), n_corr=i32(),
-               steps=i32(), status=i32())
-    if return_matches:
-        out["nn_idx"] = torch.empty((n,), dtype=torch.int32, device=dev)
-    if return_trace:
-        out["trace_T"] = torch.empty((rows, B, 3, 4), dtype=torch.float32, device=dev)
-        out["trace_stat"] = torch.empty((rows, B, 3), dtype=torch.float64, device=dev)
-    opt = lambda k: out[k].data_ptr() if k in out else None
+    B, n, m, src, so, tgt, to, T0, (ns, nt), iterations, out, opt = _prepare(
+        "gicp", src, src_offset, tgt, tgt_offset, init_T, (src_normals, tgt_normals),
+        "gicp: the normals must have one row per point of their cloud", iterations, return_matches, return_trace, nstat=3,
+        extra=("objective",))
     # an empty tensor has a null data pointer: the entry point wants the normals' pointers non-null even when a side has no points
-    ptr = lambda t: t.data_ptr() if t.numel() else torch.empty((1, 3), dtype=torch.float32, device=dev).data_ptr()
+    ptr = lambda t: t.data_ptr() if t.numel() else torch.empty((1, 3), dtype=torch.float32, device=src.device).data_ptr()
     lib = _lib()
-    ws = A.workspace(lib.roitr_gicp_workspace_bytes(B, n, m, max(iterations, 0)), dev)
+    ws = A.workspace(lib.roitr_gicp_workspace_bytes(B, n, m, max(iterations, 0)), src.device)
     L.check(lib.roitr_gicp_batch(B, n, m, src.data_ptr(), so.data_ptr(), tgt.data_ptr(), to.data_ptr(), ptr(ns), ptr(nt), T0.data_ptr(),
                                  float(max_dist), float(epsilon), iterations, float(rel_fitness), float(rel_rmse), out["T"].data_ptr(),
                                  out["fitness"].data_ptr(), out["rmse"].data_ptr(), out["objective"].data_ptr(),

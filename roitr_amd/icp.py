@@ -28,6 +28,44 @@ def _lib():
     return _bound
 
 
+def _prepare(who, src, src_offset, tgt, tgt_offset, init_T, normals, normals_error, iterations, return_matches, return_trace, nstat=2,
+             extra=()):
+    """Argument preparation and output allocation of icp_batch and gicp.gicp_batch; `who` begins the error texts.  normals:
+    (src_normals, tgt_normals), None for a side the call does not read; a side with another row count than its cloud raises
+    normals_error.  nstat: the columns of trace_stat; extra: names of further (B,) float64 outputs, placed behind rmse.  Returns
+    (B, n, m, src, src_offset, tgt, tgt_offset, init_T, normals, iterations, out, opt): device tensors, the output dict and
+    opt(name), an optional output's pointer or None."""
+    src, tgt = A.points(src, f"{who}: src"), A.points(tgt, f"{who}: tgt")
+    dev = src.device
+    tgt = tgt.to(dev)
+    n, m = int(src.shape[0]), int(tgt.shape[0])
+    _check_offsets("src_offset", src_offset, n)
+    _check_offsets("tgt_offset", tgt_offset, m)
+    so = torch.as_tensor(src_offset).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    to = torch.as_tensor(tgt_offset).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    B = int(so.shape[0])
+    if int(to.shape[0]) != B:
+        raise L.RoitrError(f"{who}: src_offset and tgt_offset must have one entry per pair")
+    T0 = A.dev(init_T, torch.float32, f"{who}: init_T").to(dev).reshape(-1, 4, 4)
+    if int(T0.shape[0]) != B:
+        raise L.RoitrError(f"{who}: {B} pairs need init_T (B,4,4)")
+    normals = [None if t is None else A.points(t, f"{who}: {side}_normals").to(dev) for t, side in zip(normals, ("src", "tgt"))]
+    if any(t is not None and int(t.shape[0]) != count for t, count in zip(normals, (n, m))):
+        raise L.RoitrError(normals_error)
+    iterations = int(iterations)
+    rows = max(iterations, 0) + 1
+    f64 = lambda: torch.empty((B,), dtype=torch.float64, device=dev)
+    i32 = lambda: torch.empty((B,), dtype=torch.int32, device=dev)
+    out = dict(T=torch.empty((B, 4, 4), dtype=torch.float32, device=dev), fitness=f64(), rmse=f64(), **{k: f64() for k in extra},
+               n_corr=i32(), steps=i32(), status=i32())
+    if return_matches:
+        out["nn_idx"] = torch.empty((n,), dtype=torch.int32, device=dev)
+    if return_trace:
+        out["trace_T"] = torch.empty((rows, B, 3, 4), dtype=torch.float32, device=dev)
+        out["trace_stat"] = torch.empty((rows, B, nstat), dtype=torch.float64, device=dev)
+    return B, n, m, src, so, tgt, to, T0, normals, iterations, out, lambda k: out[k].data_ptr() if k in out else None
+
+
 @torch.no_grad()
 def icp_batch(src, src_offset, tgt, tgt_offset, init_T, *, tgt_normals=None, max_dist=0.05, iterations=30, rel_fitness=1e-6,
               rel_rmse=1e-6, return_matches=False, return_trace=False):
@@ -40,38 +78,11 @@ def icp_batch(src, src_offset, tgt, tgt_offset, init_T, *, tgt_normals=None, max
     NONFINITE or EMPTY pair returns init_T and nan).  return_matches adds nn_idx (n) int32, the pair-local match of every source point
     under the final state (-1: none); return_trace adds trace_T (iterations + 1, B, 3, 4) and trace_stat (iterations + 1, B, 2):
     state, fitness and rmse of every evaluation (rows after a pair's stop repeat its last one)."""
-    src, tgt = A.points(src, "icp: src"), A.points(tgt, "icp: tgt")
-    dev = src.device
-    tgt = tgt.to(dev)
-    n, m = int(src.shape[0]), int(tgt.shape[0])
-    _check_offsets("src_offset", src_offset, n)
-    _check_offsets("tgt_offset", tgt_offset, m)
-    so = torch.as_tensor(src_offset).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-    to = torch.as_tensor(tgt_offset).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-    B = int(so.shape[0])
-    if int(to.shape[0]) != B:
-        raise L.RoitrError("icp: src_offset and tgt_offset must have one entry per pair")
-    T0 = A.dev(init_T, torch.float32, "icp: init_T").to(dev).reshape(-1, 4, 4)
-    if int(T0.shape[0]) != B:
-        raise L.RoitrError(f"icp: {B} pairs need init_T (B,4,4)")
-    nrm = None
-    if tgt_normals is not None:
-        nrm = A.points(tgt_normals, "icp: tgt_normals").to(dev)
-        if int(nrm.shape[0]) != m:
-            raise L.RoitrError("icp: tgt_normals must have one row per target point")
-    iterations = int(iterations)
-    rows = max(iterations, 0) + 1
-    out = dict(T=torch.empty((B, 4, 4), dtype=torch.float32, device=dev), fitness=torch.empty((B,), dtype=torch.float64, device=dev),
-               rmse=torch.empty((B,), dtype=torch.float64, device=dev), n_corr=torch.empty((B,), dtype=torch.int32, device=dev),
-               steps=torch.empty((B,), dtype=torch.int32, device=dev), status=torch.empty((B,), dtype=torch.int32, device=dev))
-    if return_matches:
-        out["nn_idx"] = torch.empty((n,), dtype=torch.int32, device=dev)
-    if return_trace:
-        out["trace_T"] = torch.empty((rows, B, 3, 4), dtype=torch.float32, device=dev)
-        out["trace_stat"] = torch.empty((rows, B, 2), dtype=torch.float64, device=dev)
-    opt = lambda k: out[k].data_ptr() if k in out else None
+    B, n, m, src, so, tgt, to, T0, (_, nrm), iterations, out, opt = _prepare(
+        "icp", src, src_offset, tgt, tgt_offset, init_T, (None, tgt_normals), "icp: tgt_normals must have one row per target point",
+        iterations, return_matches, return_trace)
     lib = _lib()
-    ws = A.workspace(lib.roitr_icp_workspace_bytes(B, n, m, max(iterations, 0)), dev)
+    ws = A.workspace(lib.roitr_icp_workspace_bytes(B, n, m, max(iterations, 0)), src.device)
     L.check(lib.roitr_icp_batch(B, n, m, src.data_ptr(), so.data_ptr(), tgt.data_ptr(), to.data_ptr(),
                                 None if nrm is None else nrm.data_ptr(), T0.data_ptr(), float(max_dist), iterations, float(rel_fitness),
                                 float(rel_rmse), out["T"].data_ptr(), out["fitness"].data_ptr(), out["rmse"].data_ptr(),

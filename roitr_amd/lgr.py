@@ -34,18 +34,9 @@ def lgr_batch(starts, src_pts, tgt_pts, scores, row_patch, *, radius=0.1, min_ro
     best_first_row (local first row of the winning patch), hypotheses (patches with at least min_rows rows), local_inliers (the
     winner's count) and status (bits NO_ROWS, NO_LOCAL, EMPTY_REFIT).  return_hypotheses adds hyp_starts (B+1), hyp_first_row,
     hyp_T (.,3,4) and hyp_counts: pair b's hypotheses are entries [hyp_starts[b], hyp_starts[b] + hypotheses[b])."""
-    src_pts = src_pts if torch.is_tensor(src_pts) else torch.as_tensor(src_pts)
-    dev = src_pts.device if src_pts.is_cuda else torch.device("cuda")
-    starts = torch.as_tensor(starts).to(device=dev, dtype=torch.int32).contiguous()
-    B = max(int(starts.shape[0]) - 1, 0)
-    src = A.upload(src_pts, device=dev).reshape(-1, 3)
-    tgt = A.upload(tgt_pts, device=dev).reshape(-1, 3)
-    if src.shape != tgt.shape:
-        raise ValueError("src_pts and tgt_pts must have the same shape")
-    rows = int(src.shape[0])
-    w = None if scores is None else A.upload(scores, device=dev).reshape(-1)
+    dev, starts, B, src, tgt, rows, w = A.correspondences(starts, src_pts, tgt_pts, scores, per_row="scores and row_patch")
     patch = A.upload(row_patch, dtype=torch.int32, device=dev).reshape(-1)
-    if (w is not None and int(w.shape[0]) != rows) or int(patch.shape[0]) != rows:
+    if int(patch.shape[0]) != rows:
         raise ValueError("scores and row_patch must have one entry per row")
     ints = lambda n: torch.empty((n,), dtype=torch.int32, device=dev)
     out = dict(T=torch.empty((B, 4, 4), dtype=torch.float32, device=dev), inliers=ints(B), best_hypothesis=ints(B),

@@ -21,6 +21,7 @@ RAGGED = ["m_65", None, "two_rows", "incompatible", "ratio_10"]   # None: a pair
 FIELDS = ("T", "inliers", "best_rank", "best_seed_row", "seeds", "hypotheses", "local_inliers", "status")
 STAGES = ("degree", "seed_rows", "seed_members", "hyp_T", "hyp_counts")
 EMPTY = (np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32), np.zeros(0, np.float32))
+FRONT_SEED = 41   # make_set(FRONT_SEED, 511, 0.3) is decided and within the cap (checked where it is used)
 
 
 def run(sets, scores="own", **kw):
@@ -130,6 +131,21 @@ def test_slot_offset_and_repeat_do_not_matter(name):
         r = run([U.fixture(front)[0], data])
         assert same(pair_of(r, 1), alone(name)), (name, front)
     assert same(pair_of(run([data]), 0), alone(name))
+
+
+def test_rows_straddle_a_verification_tile_behind_another_pair():
+    """511 rows in front: the next pair's first row is the last of the verification kernel's first 512-row tile, the rest lie in the
+    second, so its counts are added from two blocks; the pair behind it has invalid (-1) hypotheses only, which both blocks skip."""
+    front = U.make_set(FRONT_SEED, 511, 0.3)
+    ref = U.compat_ref(*front[:3])
+    assert U.decided(ref) and U.within_cap(ref)
+    names = ["m_129", "two_rows"]
+    r = run([front] + [U.fixture(n)[0] for n in names])
+    assert r["starts"].tolist() == [0, 511, 640, 642] and int(r["seeds"][2]) == 2 and (r["hyp_counts"][2][:2] == -1).all()
+    check_against_ref(pair_of(r, 0), ref, "front_511")
+    for b, name in enumerate(names, 1):
+        check_against_ref(pair_of(r, b), U.reference(name), name, pose=name != "two_rows")
+        assert same(pair_of(r, b), alone(name)), name
 
 
 @pytest.mark.parametrize("name", ["m_63", "m_129", "lattice"])
