@@ -73,6 +73,9 @@ typedef struct RoitrGemm {
 #define ROITR_BF16_X3 8
 int roitr_gemm(const RoitrGemm* g, roitr_stream_t stream);
 int roitr_gemm_bf16_supported(const RoitrGemm* g);
+/* Diagnostics: block-tile rows of the fp32 LayerNorm launches with N == 256 -- 32 (csrc/gemm_ln256.hip, the default) or 64 (the
+ * 64 x 256 instantiation of the general kernel).  Process-wide; the results are the same bytes. */
+int roitr_gemm_set_ln256_tile(int rows);
 /* fp32 -> bf16 (round to nearest even), n elements; dst 4-byte aligned */
 int roitr_f32_to_bf16(long n, const float* src, unsigned short* dst, roitr_stream_t stream);
 /* shapes / layouts the split kernel takes (RoitrGemm::bf16 == ROITR_BF16_X3) */
@@ -517,6 +520,10 @@ int roitr_engine_graph_count(void* engine);
  * keep them on the caller's stream.  on == 2: on the engine's stream for every call.  on == 0: never -- the same launches, on the same
  * buffers, queued on the caller's stream in front of the decoder.  The results are the same bytes in every mode. */
 int roitr_engine_set_phase_overlap(void* engine, int on);
+/* The 256-wide fp32 Linear + LayerNorm layers (levels 3 - 4, global transformer, dec4 / dec3) run as ONE launch (csrc/gemm_ln256.hip) from
+ * `rows` rows per launch on, as GEMM + roitr_add_layernorm below.  rows == 0: never; rows < 0: the built-in default.  The two forms give
+ * the same bytes; fp32 operand mode only (the bf16 and split modes keep their launches). */
+int roitr_engine_set_ln256_min_rows(void* engine, int rows);
 /* Diagnostics: out5 = {capacity of the main scratch arena in bytes, its largest fill since it was allocated, capacity of the branch arena,
  * its fill in the last call, 1 if the last forward queued its branch on the engine's own stream (0: on the caller's)}. */
 int roitr_engine_scratch_info(void* engine, long* out5);

@@ -101,6 +101,11 @@ struct Arena {
     }
 };
 
+// 256-wide fp32 Linear + LayerNorm as one launch (ln256_fuses): the default row threshold, the longest K it covers, "never"
+constexpr int LN256_MIN_ROWS = 39936;   // level-4 rows of 512 pairs of 5 000 points: the smallest measured size at which one launch won
+constexpr int LN256_MAX_K = 512;
+constexpr int LN256_NEVER = 0x7fffffff;
+
 struct Engine {
     RoitrEngineConfig cfg;
     std::map<std::string, std::pair<const float*, long>> params;
@@ -166,6 +171,7 @@ struct Engine {
     hipStream_t branch = nullptr;    // the global transformer and the coarse front, beside the decoder on the main stream
     int phase_overlap = 1;           // roitr_engine_set_phase_overlap: 0 = the branch's launches are queued on the main stream, in front of the decoder;
                                      // 1 = on the branch stream for calls of at least BRANCH_MIN_NODES superpoints; 2 = on the branch stream always
+    int ln256_min_rows = LN256_MIN_ROWS;   // roitr_engine_set_ln256_min_rows: rows from which a 256-wide fp32 Linear + LayerNorm runs as one launch
     bool branch_forked = false;      // the current forward has issued work on `branch` that `st` has not joined yet
     bool on_branch = false;          // the last forward queued its branch on the branch stream (roitr_engine_scratch_info)
     std::string err;
@@ -279,17 +285,28 @@ int gemm(hipStream_t st, int M, const float* A, const Lin& l, float* C, bool rel
 // nn.Linear followed by (+ residual) LayerNorm (+ post-add) (ReLU): one launch when the layer is 64 wide (the LayerNorm
 // runs in the GEMM epilogue, the (M, 64) intermediate never reaches HBM), the two-launch sequence otherwise.
 // `tmp` (M x l.out) is only touched by the two-launch form.
-// The fused form is bitwise the two-launch result, so the choice could depend on the row count without breaking batch
-// invariance.  Measured and dropped: fusing the 256-wide rows as well (64 x 256 tiles leave the coarse levels with too few, too
-// fat blocks: +1.0 ms per 128-pair forward), also for small M only, to save the 41 add_layernorm launches of a one-pair
-// forward -- 5.84 vs 5.23 ms per pair: a 64 x 256 tile puts four accumulators (4096 MFMA cycles per K-slab) on the critical
-// path of a handful of blocks, which costs more than the launch it saves.  Round 3, at 512 pairs per call (the choice may depend on
-// M: the forms are bitwise twins): fusing the 256-wide rows from M >= 60 000 / 200 000 rows: 93.1 / 92.6 vs 92.5 ms per step.
+// The fused form is bitwise the two-launch result, so the choice may depend on the row count without breaking batch invariance.
+// 64 / 128 columns: always fused.  256 columns (fp32 operand mode only; bf16 and the three-way split keep their paths): fused on the
+// 32 x 256 tile of gemm_ln256.hip from LN256_MIN_ROWS rows, see ln256_fuses() for what was measured.
 // TransitionUp's interpolation addend (RoitrGemm::ip_*): rows of `feat` (l.out floats) mixed by the 3-NN of every output row
 struct Interp3 { const float* feat; const int* idx; const float* dist2; };
 bool ln_fuses(int N, int K, int lda, int ldw)
 {
     return (N == 64 || N == 128) && K % 32 == 0 && lda % 4 == 0 && ldw % 4 == 0;
+}
+// The 256-wide layers (levels 3 - 4, the global transformer, dec4 / dec3).  Measured per shape, events, the forms alternated
+// (scripts/bench_gemm_ln.py, profiles/ln256_shapes.txt), fused 32 x 256 launch against GEMM + add_layernorm, K = 256 / 384 / 512, five
+// epilogues: 319 488 rows 0.75 - 0.94 of the two launches, 79 872 rows 0.77 - 0.95, 39 936 rows 0.82 - 0.96; 19 968 rows 0.98 - 1.25,
+// 9 984 rows 0.99 - 1.17, 624 rows 1.7 - 2.3 (a one-pair call: the two accumulator chains of a handful of blocks are the critical
+// path, the plain GEMM has its 32 x 32 tiles there).  The break-even lies between 19 968 and 39 936 rows for every K; the rule is the
+// smallest measured size that won.  The 64 x 256 instantiation of the general kernel loses to both at 39 936 rows and below and to the
+// 32 x 256 tile everywhere (it reaches 0.83 - 0.98 of two launches at 319 488 / 79 872 rows).  Per 512-pair step: 78.63 -> 77.55 ms.
+// K above LN256_MAX_K was not measured (no such layer).
+bool ln256_fuses(int M, int N, int K, int lda, int ldw, const Lin& l, int bf)
+{
+    const Engine* E = g_engine;
+    if (!E || E->cfg.operand_dtype != 0 || l.wb || bf) return false;
+    return N == 256 && K % 32 == 0 && K <= LN256_MAX_K && lda % 4 == 0 && ldw % 4 == 0 && M >= E->ln256_min_rows;
 }
 // bf: ROITR_BF16_A (A stored bf16; lda in elements) and / or ROITR_BF16_C (out stored bf16: fused form only)
 // A_cat (optional): the second K-half of the operand, [A | A_cat] with A (M, k_cat) dense and A_cat (M, l.in - k_cat) of leading
@@ -302,9 +319,10 @@ int gemm_ln(hipStream_t st, int M, const float* A, const Lin& l, const float* re
     const float* b = l.b;
     const int K = l.in, N = l.out;
     const int lda = A_cat ? k_cat : K, ldw = K;
-    // measured per 128-pair forward: fusing the 64-wide layers -1.55 ms, + the 128-wide ones -0.4 ms, + the 256-wide ones
-    // +1.0 ms (64 x 256 tiles leave the coarse levels with too few, too fat blocks) -> default limit 128
-    if (ln_fuses(N, K, lda, ldw)) {
+    // measured per 128-pair forward: fusing the 64-wide layers -1.55 ms, + the 128-wide ones -0.4 ms
+    // res gathered by res_idx from the buffer the launch writes: another block may have stored the row already (no such call site)
+    const bool gather_in_place = res_idx && res == out;
+    if (ln_fuses(N, K, lda, ldw) || (ln256_fuses(M, N, K, lda, ldw, l, bf) && !gather_in_place)) {
         RoitrGemm g;
         memset(&g, 0, sizeof(g));
         g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.W = w; g.ldw = ldw; g.bias = b; g.alpha = 1.0f; g.C = out; g.ldc = N; g.batch = 1;
@@ -1982,6 +2000,14 @@ extern "C" int roitr_engine_scratch_info(void* h, long* out5)
     Engine& E = *(Engine*)h;
     out5[0] = (long)E.arena.cap; out5[1] = (long)E.arena.peak; out5[2] = (long)E.barena.cap; out5[3] = (long)E.barena.peak;
     out5[4] = E.on_branch ? 1 : 0;
+    return ROITR_OK;
+}
+
+extern "C" int roitr_engine_set_ln256_min_rows(void* h, int rows)
+{
+    Engine& E = *(Engine*)h;
+    const int r = rows < 0 ? LN256_MIN_ROWS : rows == 0 ? LN256_NEVER : rows;
+    if (E.ln256_min_rows != r) { E.ln256_min_rows = r; E.arena_epoch++; }   // another launch sequence: captured forwards are stale
     return ROITR_OK;
 }
 

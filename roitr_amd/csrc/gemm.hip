@@ -584,6 +584,8 @@ struct ShapeTimer {
 
 int roitr_gemm_bf16_launch(const RoitrGemm* g, hipStream_t stream);   // gemm_bf16.hip
 int roitr_gemm_x3_launch(const RoitrGemm* g, hipStream_t stream);     // gemm_x3.hip
+bool roitr_gemm_ln256_takes(const RoitrGemm* g);                      // gemm_ln256.hip: the 32 x 256 LayerNorm tile
+void roitr_gemm_ln256_launch(const RoitrGemm* g, hipStream_t stream);
 
 // What the fp32 launcher below settled on, and what was tried on the way:
 // Measured and dropped (A/B on the forward bench): 64x128 / 128x128 multi-accumulator tiles (19.7 / 22.0 vs 16.9 ms of
@@ -643,7 +645,9 @@ extern "C" int roitr_gemm(const RoitrGemm* g, hipStream_t stream)
     ShapeTimer timer(g, fast, stream);
     const bool a2 = g->A2 != nullptr;
     const bool il = T >= GEMM_IL_MIN_TILES;   // staging loads spread over the MFMA stream (see the kernel): large grids only
-    if (fast && !ln && T < GEMM_SMALL_MAX_TILES) {   // a fraction of a tile per SIMD: 32 x 32 tiles with 4x shorter accumulator chains
+    if (fast && ln && tn == 4 && roitr_gemm_ln256_takes(g)) {   // 256-wide LayerNorm rows: 32 x 256 tiles (what it does not take falls through)
+        roitr_gemm_ln256_launch(g, stream);
+    } else if (fast && !ln && T < GEMM_SMALL_MAX_TILES) {   // a fraction of a tile per SIMD: 32 x 32 tiles with 4x shorter accumulator chains
         const int sx = div_up(g->N, SM), sy = div_up(g->M, SM);
         const int ST = sx * sy * g->batch;
         if (a2) gemm_small_kernel<true><<<xcd_grid(ST), 256, 0, stream>>>(*g, sx, sy, ST);

@@ -297,6 +297,12 @@ class RIGA_v2(nn.Module):
         self._ensure_engine()
         L.check(L.lib().roitr_engine_set_phase_overlap(self._engine, ctypes.c_int(int(on))), "set_phase_overlap")
 
+    def set_ln256_min_rows(self, rows=-1):
+        """Rows per launch from which the 256-wide fp32 Linear + LayerNorm layers run as one launch (csrc/gemm_ln256.hip): 0 never, < 0 the
+        built-in default.  The results are the same bytes either way (for the tests)."""
+        self._ensure_engine()
+        L.check(L.lib().roitr_engine_set_ln256_min_rows(self._engine, ctypes.c_int(int(rows))), "set_ln256_min_rows")
+
     def scratch_info(self):
         """Diagnostics of the engine's scratch: capacities and fills of the main and the branch arena in bytes, and whether the last forward
         queued its branch (global transformer + coarse front) on the engine's branch stream."""
