@@ -2,8 +2,13 @@
 
 There is no CPU fallback anywhere in this package: if the HIP library is missing or fails to load,
 importing an operator raises.  (The CPU restatement lives under oracle/ and is test-only.)
+
+Struct layouts (struct()) and prototypes (BOUND, bind(), binder()) are read from include/*.h by one reader, _headers(); nothing of them
+is typed a second time in Python.  tests/test_abi_cpu.py holds every struct's sizeof / offsetof against the C compiler.  The calls of
+the timed path (riga, pointops) are left undeclared and convert their own arguments.
 """
 import ctypes
+import functools
 import os
 import re
 
@@ -18,8 +23,8 @@ class RoitrError(RuntimeError):
 
 # The entry points of the evaluation and preparation modules (registration, nonrigid, descmatch, loss, pairgt, prep, evaluate): their
 # restype / argtypes are read from the prototypes of include/*.h at load, so a call cannot disagree with the header about a type.
-# (The calls of the timed path -- ops, pointops, riga -- convert their arguments themselves.)  The last two lines: the row-wise layers and
-# the positional fold behind the operator wrappers of ops.py, whose prototypes mix `long rows`, `int n` and a by-value `float eps`.
+# (The calls of the timed path -- pointops, riga -- convert their arguments themselves.)  The last two lines: the row-wise layers and
+# the positional fold behind the operator wrappers of ops.py; ops.py binds the rest of what it calls itself (binder()).
 BOUND = ("roitr_registration_workspace_bytes roitr_ransac_correspondences roitr_ransac_samples roitr_weighted_procrustes "
          "roitr_nfmr_workspace_bytes roitr_nfmr_batch roitr_blend_anchor_motion "
          "roitr_desc_match_workspace_bytes roitr_desc_match_batch roitr_desc_match_select "
@@ -36,7 +41,8 @@ _CTYPES = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_doub
 
 
 def _ctype(decl, named):
-    """ctypes type of a C parameter or return declaration; any pointer is a c_void_p.  named: the last word may be the parameter's name."""
+    """ctypes type of a C parameter, field or return declaration; any pointer is a c_void_p, `x[n]` of a parameter included (struct fields
+    come here without their `[n]`).  named: the last word may be the name."""
     if "*" in decl or "[" in decl:
         return ctypes.c_void_p
     words = [w for w in decl.split() if w != "const"]
@@ -45,18 +51,50 @@ def _ctype(decl, named):
     return _CTYPES[" ".join(words)]   # KeyError: a type this table does not know
 
 
-def header_prototypes():
-    """{function name: (restype, [argtypes])} of every prototype in include/roitr_pointops.h and include/roitr_engine.h."""
-    protos = {}
+def _fields(body):
+    """[(field, ctypes type)] of a struct body: `int M, N, K;`, `const float* A;`, `int geo_is_cross[16];`."""
+    fields = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        first, *more = [item.strip() for item in decl.split(",")]
+        base, first = re.fullmatch(r"(.*?)([\*\s]*\b\w+\s*(?:\[\d+\])?)", first, re.S).groups()   # the type words | the first declarator
+        for item in [first] + more:
+            stars, name, count = re.fullmatch(r"([\*\s]*)(\w+)\s*(?:\[(\d+)\])?", item).groups()
+            ct = _ctype(f"{base} {stars} {name}", True)
+            fields.append((name, ct * int(count) if count else ct))
+    return fields
+
+
+@functools.lru_cache(maxsize=None)
+def _headers():
+    """(structs, prototypes) of include/roitr_pointops.h and include/roitr_engine.h: the one reader of the headers."""
+    structs, protos = {}, {}
     for h in ("roitr_pointops.h", "roitr_engine.h"):
         text = open(os.path.join(os.path.dirname(_HERE), "include", h)).read()
         text = re.sub(r"/\*.*?\*/|//[^\n]*|^\s*#[^\n]*|extern \"C\" \{", "", text, flags=re.S | re.M)
+        for name, body in re.findall(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;", text):
+            structs[name] = _fields(body)
         while re.search(r"\{[^{}]*\}", text):   # struct bodies
             text = re.sub(r"\{[^{}]*\}", "", text)
         for ret, name, params in re.findall(r"([\w\s\*]+?)\b(\w+)\s*\(([^()]*)\)\s*;", text):
             params = [p.strip() for p in params.split(",") if p.strip() not in ("", "void")]
             protos[name] = (_ctype(ret.strip(), False), [_ctype(p, True) for p in params])
-    return protos
+    return structs, protos
+
+
+def header_structs():
+    """{struct name: [(field, ctypes type), ...]} of every `typedef struct X { ... } X;` of the two headers."""
+    return _headers()[0]
+
+
+def header_prototypes():
+    """{function name: (restype, [argtypes])} of every prototype of the two headers."""
+    return _headers()[1]
+
+
+@functools.lru_cache(maxsize=None)
+def struct(name):
+    """The ctypes.Structure of a struct of the headers (needs the header only, not the library)."""
+    return type(name, (ctypes.Structure,), {"_fields_": header_structs()[name]})
 
 
 def lib():
@@ -92,6 +130,11 @@ def bind(names):
     handle = lib()
     _assign(handle, names)
     return handle
+
+
+def binder(names):
+    """A function that returns the library with `names` bound from the header; it binds on its first call (binding parses the headers)."""
+    return functools.lru_cache(maxsize=None)(lambda: bind(names))
 
 
 def check(status, what=""):

@@ -16,15 +16,7 @@ NO_ROWS, NO_HYPOTHESIS, EMPTY_REFIT, TRUNCATED = 1, 2, 4, 8   # status bits (ROI
 MAX_ROWS_DEFAULT = 2048
 
 
-_bound = None
-
-
-def _lib():
-    """The library with this module's two entry points bound from the header (once: binding parses the headers)."""
-    global _bound
-    if _bound is None:
-        _bound = L.bind(("roitr_compat_workspace_bytes", "roitr_compat_batch"))
-    return _bound
+_lib = L.binder(("roitr_compat_workspace_bytes", "roitr_compat_batch"))   # the library with this module's two entry points bound from the header
 
 
 @torch.no_grad()

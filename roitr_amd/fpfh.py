@@ -17,15 +17,7 @@ from .pairgt import _check_offsets
 NONFINITE = 1   # status bit: the cloud holds a non-finite coordinate or normal; its rows are zero
 BINS = 33
 
-_bound = None
-
-
-def _lib():
-    """The library with this module's two entry points bound from the header (once: binding parses the headers)."""
-    global _bound
-    if _bound is None:
-        _bound = L.bind(("roitr_fpfh_workspace_bytes", "roitr_fpfh_batch"))
-    return _bound
+_lib = L.binder(("roitr_fpfh_workspace_bytes", "roitr_fpfh_batch"))   # the library with this module's two entry points bound from the header
 
 
 @torch.no_grad()

@@ -14,15 +14,7 @@ from . import _args as A
 from . import _lib as L
 from .icp import CONVERGED, EMPTY, NONFINITE, SINGULAR, TOO_FEW, _prepare  # noqa: F401  (the status bits are the ICP operator's)
 
-_bound = None
-
-
-def _lib():
-    """The library with this module's two entry points bound from the header (once: binding parses the headers)."""
-    global _bound
-    if _bound is None:
-        _bound = L.bind(("roitr_gicp_workspace_bytes", "roitr_gicp_batch"))
-    return _bound
+_lib = L.binder(("roitr_gicp_workspace_bytes", "roitr_gicp_batch"))   # the library with this module's two entry points bound from the header
 
 
 @torch.no_grad()

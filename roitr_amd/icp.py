@@ -17,15 +17,7 @@ from .pairgt import _check_offsets
 
 NONFINITE, EMPTY, TOO_FEW, SINGULAR, CONVERGED = 1, 2, 4, 8, 16   # status bits (ROITR_ICP_* of include/roitr_pointops.h)
 
-_bound = None
-
-
-def _lib():
-    """The library with this module's two entry points bound from the header (once: binding parses the headers)."""
-    global _bound
-    if _bound is None:
-        _bound = L.bind(("roitr_icp_workspace_bytes", "roitr_icp_batch"))
-    return _bound
+_lib = L.binder(("roitr_icp_workspace_bytes", "roitr_icp_batch"))   # the library with this module's two entry points bound from the header
 
 
 def _prepare(who, src, src_offset, tgt, tgt_offset, init_T, normals, normals_error, iterations, return_matches, return_trace, nstat=2,

@@ -14,15 +14,7 @@ from . import _lib as L
 NO_ROWS, NO_LOCAL, EMPTY_REFIT = 1, 2, 4   # status bits (ROITR_LGR_* of include/roitr_engine.h)
 
 
-_bound = None
-
-
-def _lib():
-    """The library with this module's two entry points bound from the header (once: binding parses the headers)."""
-    global _bound
-    if _bound is None:
-        _bound = L.bind(("roitr_lgr_workspace_bytes", "roitr_lgr_batch"))
-    return _bound
+_lib = L.binder(("roitr_lgr_workspace_bytes", "roitr_lgr_batch"))   # the library with this module's two entry points bound from the header
 
 
 @torch.no_grad()

@@ -2,13 +2,45 @@
 
 Each function cites the reference function it stands for.  ROCm device tensors only.
 """
+import ctypes
+
 import torch
 
 from . import _lib as L
 
+# The library with every entry point this file calls declared from the header (the row-wise layers and roitr_build_pfold are in L.BOUND):
+# a Python int / float is converted to the prototype's `long rows`, `size_t`, by-value `float eps` by ctypes, not by the call site.
+# (roitr_local_block_dbg, the tuning hook of local_block, is exported but in no header: a struct pointer, an int and the stream.)
+_lib = L.binder("""roitr_calc_ppf roitr_point_to_node_partition roitr_coarse_scratch_floats roitr_coarse_matching roitr_adaptive_matching
+    roitr_optimal_transport roitr_fine_matching roitr_split_bf16x3 roitr_gemm roitr_add_layernorm_interp roitr_geo_table_floats
+    roitr_geo_table_build roitr_geo_embed_table roitr_geo_embed_bf16 roitr_split3_bf16 roitr_geo_embed_split roitr_geo_embed
+    roitr_local_attention_fold roitr_local_attention roitr_local_td_supported roitr_local_td roitr_local_block
+    roitr_local_first roitr_local_weights_prepare roitr_local_weights_release roitr_local_weights_count
+    roitr_local_weights_reorder_host roitr_mha roitr_geo_indices roitr_build_padded_clouds roitr_node_occlusion_score
+    roitr_node_correspondences""".split())
+
+# The argument structs of include/roitr_engine.h: fields in header order, everything not set is 0 / NULL.
+_Coarse = L.struct("RoitrCoarse")
+_OT = L.struct("RoitrOT")
+_Fine = L.struct("RoitrFine")
+_Gemm = L.struct("RoitrGemm")
+_LocalAttnFold = L.struct("RoitrLocalAttnFold")
+_LocalAttn = L.struct("RoitrLocalAttn")
+_LocalTd = L.struct("RoitrLocalTd")
+_LocalBlock = L.struct("RoitrLocalBlock")
+_LocalFirst = L.struct("RoitrLocalFirst")
+_Mha = L.struct("RoitrMha")
+_NodeCorr = L.struct("RoitrNodeCorr")
+
+
+def _c(t):
+    """float32 and contiguous, or None"""
+    return None if t is None else t.contiguous().float()
+
 
 def _i32c(t):
-    return t.to(torch.int32).contiguous()
+    """int32 and contiguous, or None"""
+    return None if t is None else t.to(torch.int32).contiguous()
 
 
 def calc_ppf(points, point_normals, ref_points, ref_normals, group_idx):
@@ -19,7 +51,7 @@ def calc_ppf(points, point_normals, ref_points, ref_normals, group_idx):
     m, k = group_idx.shape
     out = torch.empty((m, k, 4), dtype=torch.float32, device=points.device)
     grp = _i32c(group_idx)
-    L.check(L.lib().roitr_calc_ppf(m, k, L.ptr(points.contiguous()), L.ptr(point_normals.contiguous()),
+    L.check(_lib().roitr_calc_ppf(m, k, L.ptr(points.contiguous()), L.ptr(point_normals.contiguous()),
                                    L.ptr(ref_points.contiguous()), L.ptr(ref_normals.contiguous()), L.ptr(grp), L.ptr(out),
                                    L.stream_ptr()), "calc_ppf")
     return out
@@ -35,32 +67,6 @@ def calc_ppf_gpu(points, point_normals, patches, patch_normals):
 # ------------------------------------------------------------------------------------------------
 # Matching-tail operators (single pair / single batch of patches), thin ctypes fronts of the batched kernels.
 # ------------------------------------------------------------------------------------------------
-import ctypes  # noqa: E402
-
-_P = ctypes.c_void_p
-
-
-class _Coarse(ctypes.Structure):
-    _fields_ = [("pairs", ctypes.c_int), ("C", ctypes.c_int), ("num_corr", ctypes.c_int), ("dual_norm", ctypes.c_int),
-                ("max_ref", ctypes.c_int), ("max_src", ctypes.c_int), ("feats", _P), ("node_offset", _P), ("node_masks", _P),
-                ("scratch", _P), ("scratch_stride", ctypes.c_long), ("tgt_corr", _P), ("src_corr", _P), ("corr_scores", _P),
-                ("n_corr", _P), ("xy", _P), ("xy_stride", ctypes.c_long), ("xy_ld", ctypes.c_int), ("lds_cap", ctypes.c_int)]
-
-
-class _OT(ctypes.Structure):
-    _fields_ = [("pairs", ctypes.c_int), ("num_corr", ctypes.c_int), ("limit", ctypes.c_int), ("num_iter", ctypes.c_int),
-                ("n_corr", _P), ("scores", _P), ("row_masks", _P), ("col_masks", _P), ("alpha", _P), ("out", _P),
-                ("pair_off", _P), ("slots", ctypes.c_int)]
-
-
-class _Fine(ctypes.Structure):
-    _fields_ = [("pairs", ctypes.c_int), ("num_corr", ctypes.c_int), ("limit", ctypes.c_int), ("k", ctypes.c_int),
-                ("mutual", ctypes.c_int), ("conf", ctypes.c_float), ("n_corr", _P), ("ot", _P), ("row_masks", _P),
-                ("col_masks", _P), ("row_pts", _P), ("col_pts", _P), ("global_scores", _P), ("flags", _P), ("counts", _P),
-                ("offsets", _P), ("n_out", _P), ("out_row_pts", _P), ("out_col_pts", _P), ("out_scores", _P), ("out_patch", _P), ("out_cap", ctypes.c_long),
-                ("pair_off", _P), ("slots", ctypes.c_int), ("pair_starts", _P)]
-
-
 def point_to_node_partition(points, nodes, point_limit):
     """lib/utils.py:428-471 -> (point_to_node (N,) i64, node_masks (M,) bool, node_knn_indices (M,K) i64, node_knn_masks bool)"""
     dev = points.device
@@ -74,7 +80,7 @@ def point_to_node_partition(points, nodes, point_limit):
     nm = torch.zeros(M, dtype=i32, device=dev)
     kidx = torch.zeros((M, point_limit), dtype=i32, device=dev)
     kmask = torch.zeros((M, point_limit), dtype=i32, device=dev)
-    L.check(L.lib().roitr_point_to_node_partition(1, N, M, L.ptr(points.contiguous()), L.ptr(po), L.ptr(nodes.contiguous()), L.ptr(no),
+    L.check(_lib().roitr_point_to_node_partition(1, N, M, L.ptr(points.contiguous()), L.ptr(po), L.ptr(nodes.contiguous()), L.ptr(no),
                                                   L.ptr(con), int(point_limit), L.ptr(p2n), L.ptr(p2nd), L.ptr(nm), L.ptr(kidx),
                                                   L.ptr(kmask), L.stream_ptr()), "point_to_node_partition")
     return p2n.long(), nm.bool(), kidx.long(), kmask.bool()
@@ -84,10 +90,9 @@ def coarse_matching(ref_feats, src_feats, ref_masks, src_masks, num_corresponden
     """model/modules.py:141-178 CoarseMatching.forward -> (ref_corr_indices, src_corr_indices, corr_scores)"""
     dev = ref_feats.device
     nr, ns = ref_feats.shape[0], src_feats.shape[0]
-    lib = L.lib()
-    lib.roitr_coarse_scratch_floats.restype = ctypes.c_size_t
-    feats = torch.cat([src_feats, ref_feats], 0).contiguous().float()   # cloud order: [src, tgt(=ref)]
-    masks = torch.cat([src_masks, ref_masks], 0).to(torch.int32).contiguous()
+    lib = _lib()
+    feats = _c(torch.cat([src_feats, ref_feats], 0))   # cloud order: [src, tgt(=ref)]
+    masks = _i32c(torch.cat([src_masks, ref_masks], 0))
     off = torch.tensor([ns, ns + nr], dtype=torch.int32, device=dev)
     stride = lib.roitr_coarse_scratch_floats(nr, ns)
     scratch = torch.empty(stride, dtype=torch.float32, device=dev)
@@ -96,8 +101,9 @@ def coarse_matching(ref_feats, src_feats, ref_masks, src_masks, num_corresponden
     sc = torch.zeros(P, dtype=torch.int32, device=dev)
     cs = torch.zeros(P, dtype=torch.float32, device=dev)
     nc = torch.zeros(1, dtype=torch.int32, device=dev)
-    a = _Coarse(1, feats.shape[1], P, int(dual_normalization), nr, ns, L.ptr(feats), L.ptr(off), L.ptr(masks), L.ptr(scratch),
-                stride, L.ptr(tc), L.ptr(sc), L.ptr(cs), L.ptr(nc), L.ptr(None), 0, 0)
+    a = _Coarse(pairs=1, C=feats.shape[1], num_corr=P, dual_norm=int(dual_normalization), max_ref=nr, max_src=ns, feats=L.ptr(feats),
+                node_offset=L.ptr(off), node_masks=L.ptr(masks), scratch=L.ptr(scratch), scratch_stride=stride, tgt_corr=L.ptr(tc),
+                src_corr=L.ptr(sc), corr_scores=L.ptr(cs), n_corr=L.ptr(nc))
     L.check(lib.roitr_coarse_matching(ctypes.byref(a), L.stream_ptr()), "coarse_matching")
     n = int(nc.item())
     return tc[:n].long(), sc[:n].long(), cs[:n]
@@ -110,11 +116,10 @@ def optimal_transport(scores, row_masks, col_masks, alpha, num_iter=100):
     out = torch.zeros((B, M + 1, N + 1), dtype=torch.float32, device=dev)
     nc = torch.tensor([B], dtype=torch.int32, device=dev)
     al = torch.as_tensor(alpha, dtype=torch.float32, device=dev).reshape(1).contiguous()
-    sc = scores.contiguous().float()
-    rm = row_masks.to(torch.int32).contiguous()   # named: temporaries must outlive the launch
-    cm = col_masks.to(torch.int32).contiguous()
-    a = _OT(1, B, M, int(num_iter), L.ptr(nc), L.ptr(sc), L.ptr(rm), L.ptr(cm), L.ptr(al), L.ptr(out))
-    L.check(L.lib().roitr_optimal_transport(ctypes.byref(a), L.stream_ptr()), "optimal_transport")
+    sc, rm, cm = _c(scores), _i32c(row_masks), _i32c(col_masks)   # named: temporaries must outlive the launch
+    a = _OT(pairs=1, num_corr=B, limit=M, num_iter=int(num_iter), n_corr=L.ptr(nc), scores=L.ptr(sc), row_masks=L.ptr(rm),
+            col_masks=L.ptr(cm), alpha=L.ptr(al), out=L.ptr(out))
+    L.check(_lib().roitr_optimal_transport(ctypes.byref(a), L.stream_ptr()), "optimal_transport")
     return out
 
 
@@ -135,28 +140,16 @@ def fine_matching(ref_knn_points, src_knn_points, ref_knn_masks, src_knn_masks, 
     o_r = torch.zeros((cap, 3), dtype=torch.float32, device=dev)
     o_c = torch.zeros((cap, 3), dtype=torch.float32, device=dev)
     o_s = torch.zeros(cap, dtype=torch.float32, device=dev)
-    rm, cm = ref_knn_masks.to(i32).contiguous(), src_knn_masks.to(i32).contiguous()
-    rp, cp = ref_knn_points.contiguous().float(), src_knn_points.contiguous().float()
-    ms = matching_scores.contiguous().float()
-    gs = global_scores.contiguous().float() if global_scores is not None else None
-    a = _Fine(1, B, Lm, int(k), int(mutual), float(confidence_threshold), L.ptr(nc), L.ptr(ms), L.ptr(rm), L.ptr(cm), L.ptr(rp),
-              L.ptr(cp), L.ptr(gs), L.ptr(flags), L.ptr(counts), L.ptr(offs), L.ptr(n_out), L.ptr(o_r), L.ptr(o_c), L.ptr(o_s), L.ptr(None), cap)
-    L.check(L.lib().roitr_fine_matching(ctypes.byref(a), L.stream_ptr()), "fine_matching")
+    rm, cm = _i32c(ref_knn_masks), _i32c(src_knn_masks)
+    rp, cp = _c(ref_knn_points), _c(src_knn_points)
+    ms, gs = _c(matching_scores), _c(global_scores)
+    a = _Fine(pairs=1, num_corr=B, limit=Lm, k=int(k), mutual=int(mutual), conf=float(confidence_threshold), n_corr=L.ptr(nc), ot=L.ptr(ms),
+              row_masks=L.ptr(rm), col_masks=L.ptr(cm), row_pts=L.ptr(rp), col_pts=L.ptr(cp), global_scores=L.ptr(gs), flags=L.ptr(flags),
+              counts=L.ptr(counts), offsets=L.ptr(offs), n_out=L.ptr(n_out), out_row_pts=L.ptr(o_r), out_col_pts=L.ptr(o_c),
+              out_scores=L.ptr(o_s), out_cap=cap)
+    L.check(_lib().roitr_fine_matching(ctypes.byref(a), L.stream_ptr()), "fine_matching")
     n = int(n_out.item())
     return o_r[:n], o_c[:n], o_s[:n]
-
-
-class _Gemm(ctypes.Structure):
-    _fields_ = [("M", ctypes.c_int), ("N", ctypes.c_int), ("K", ctypes.c_int), ("A", _P), ("A2", _P), ("lda", ctypes.c_int),
-                ("a_idx", _P), ("a_limit", ctypes.c_int), ("W", _P), ("ldw", ctypes.c_int), ("w_idx", _P), ("w_limit", ctypes.c_int),
-                ("bias", _P), ("alpha", ctypes.c_float), ("relu", ctypes.c_int), ("C", _P), ("ldc", ctypes.c_int),
-                ("batch", ctypes.c_int), ("sA", ctypes.c_long), ("sW", ctypes.c_long), ("sC", ctypes.c_long),
-                ("sBias", ctypes.c_long), ("sAidx", ctypes.c_long), ("sWidx", ctypes.c_long), ("seg_off", _P),
-                ("seg_a0", ctypes.c_int), ("seg_w0", ctypes.c_int),
-                ("ln_gamma", _P), ("ln_beta", _P), ("ln_res", _P), ("ln_res_idx", _P), ("ln_post", _P),
-                ("ln_relu", ctypes.c_int), ("ln_eps", ctypes.c_float), ("bf16", ctypes.c_int),
-                ("A_cat", _P), ("lda_cat", ctypes.c_int), ("k_cat", ctypes.c_int),
-                ("ip_feat", _P), ("ip_idx", _P), ("ip_dist2", _P), ("a_cat_idx", _P), ("batch_live", _P), ("w_piece", ctypes.c_long)]
 
 
 BF16_W, BF16_A, BF16_C, BF16_X3 = 1, 2, 4, 8   # RoitrGemm::bf16 flags (include/roitr_engine.h)
@@ -164,9 +157,9 @@ BF16_W, BF16_A, BF16_C, BF16_X3 = 1, 2, 4, 8   # RoitrGemm::bf16 flags (include/
 
 def split_bf16x3(weight):
     """roitr_split_bf16x3: (N, K) fp32 -> (3, N, K) bf16 with weight == pieces.float().sum(0) exactly (csrc/gemm_x3.hip)."""
-    w = weight.contiguous().float()
+    w = _c(weight)
     out = torch.empty((3,) + tuple(w.shape), dtype=torch.bfloat16, device=w.device)
-    L.check(L.lib().roitr_split_bf16x3(ctypes.c_long(w.numel()), L.ptr(w), L.ptr(out), ctypes.c_long(w.numel()), L.stream_ptr()), "split_bf16x3")
+    L.check(_lib().roitr_split_bf16x3(w.numel(), L.ptr(w), L.ptr(out), w.numel(), L.stream_ptr()), "split_bf16x3")
     return out
 
 
@@ -174,29 +167,29 @@ def _bf16_flags(bf16, x, weight, out_bf16):
     """bf16 operand mode of the GEMM: the weight is stored bf16, x is rounded while staged unless it already is a bfloat16
     tensor, the output is stored bf16 on request.  Returns (x, weight, flags)."""
     if not bf16:
-        return x.contiguous().float(), weight.contiguous().float(), 0
+        return _c(x), _c(weight), 0
     flags = BF16_W | (BF16_C if out_bf16 else 0)
     w = weight.contiguous().to(torch.bfloat16)
     if x.dtype == torch.bfloat16:
         return x.contiguous(), w, flags | BF16_A
-    return x.contiguous().float(), w, flags
+    return _c(x), w, flags
 
 
 def _k_cat(g, x, x_cat, keep, x_cat_idx=None, addend=None):
     """RoitrGemm::A_cat: the product reads [x | x_cat] along K without the concatenation ever existing (fp32 fast path only).
     x_cat_idx: row gather of x_cat alone (RoitrGemm::a_cat_idx); addend: RoitrGemm::A2, added to the x part."""
     if addend is not None:
-        ad = addend.contiguous().float()
+        ad = _c(addend)
         keep.append(ad)
         g.A2 = L.ptr(ad)
     if x_cat is None:
         return
-    xc = x_cat.contiguous().float()
+    xc = _c(x_cat)
     keep.append(xc)
     g.A_cat, g.lda_cat, g.k_cat = L.ptr(xc), xc.shape[1], x.shape[1]
     g.K = x.shape[1] + xc.shape[1]
     if x_cat_idx is not None:
-        ix = x_cat_idx.contiguous().to(torch.int32)
+        ix = _i32c(x_cat_idx)
         keep.append(ix)
         g.a_cat_idx = L.ptr(ix)
 
@@ -208,25 +201,27 @@ def _x3(g, weight, keep):
     g.W, g.bf16, g.w_piece = L.ptr(w3), BF16_X3, weight.numel()
 
 
+def _gemm(x, weight, bias, out, flags, **fields):
+    """RoitrGemm of out = x @ weight.T + bias in one batch of dense rows, plus `fields`."""
+    (M, K), N = x.shape, weight.shape[0]
+    return _Gemm(M=M, N=N, K=K, A=L.ptr(x), lda=K, W=L.ptr(weight), ldw=weight.shape[1], bias=L.ptr(bias), C=L.ptr(out), ldc=N, batch=1,
+                 bf16=flags, **fields)
+
+
 def linear(x, weight, bias=None, relu=False, alpha=1.0, bf16=False, out_bf16=False, x_cat=None, x_cat_idx=None, addend=None, x3=False):
     """act(alpha * x @ weight.T + bias): the kernel behind every nn.Linear of the path.  Default: the fp32 MFMA GEMM.
     bf16=True: the bf16-operand kernel (csrc/gemm_bf16.hip; weights stored bf16, fp32 accumulate); x may be a bfloat16
     tensor (stored-bf16 activation), out_bf16 stores the result in bf16.  x_cat: a second operand block, the product is
     [x | x_cat] @ weight.T (the K-concatenated A of the folded block transformers)."""
     x, weight, flags = _bf16_flags(bf16, x, weight, out_bf16)
-    M, K = x.shape
-    N = weight.shape[0]
-    out = torch.empty((M, N), dtype=torch.bfloat16 if flags & BF16_C else torch.float32, device=x.device)
-    b = bias.contiguous().float() if bias is not None else None
-    g = _Gemm(M, N, K, L.ptr(x), L.ptr(None), K, L.ptr(None), 0, L.ptr(weight), K, L.ptr(None), 0, L.ptr(b), float(alpha), int(relu),
-              L.ptr(out), N, 1, 0, 0, 0, 0, 0, 0, L.ptr(None), 0, 0)
-    g.bf16 = flags
+    out = torch.empty((x.shape[0], weight.shape[0]), dtype=torch.bfloat16 if flags & BF16_C else torch.float32, device=x.device)
+    b = _c(bias)
+    g = _gemm(x, weight, b, out, flags, alpha=float(alpha), relu=int(relu))
     keep = []
     _k_cat(g, x, x_cat, keep, x_cat_idx, addend)
-    g.ldw = weight.shape[1]
     if x3:   # fp32 in, fp32 out, products on the bf16 matrix cores by the three-way split (csrc/gemm_x3.hip)
         _x3(g, weight, keep)
-    L.check(L.lib().roitr_gemm(ctypes.byref(g), L.stream_ptr()), "gemm")
+    L.check(_lib().roitr_gemm(ctypes.byref(g), L.stream_ptr()), "gemm")
     return out
 
 
@@ -237,34 +232,28 @@ def linear_layernorm(x, weight, bias, gamma, beta, res=None, res_idx=None, post=
     bf16 / out_bf16 as in linear().  interp = (feat (R, N), idx (M, 3) int32, dist2 (M, 3)): TransitionUp's three-nearest-neighbour
     interpolation (pointops.py:168-182) of the rows of `feat`, added after the activation (fp32 kernel only)."""
     x, weight, flags = _bf16_flags(bf16, x, weight, out_bf16)
-    M, K = x.shape
-    N = weight.shape[0]
-    out = torch.empty((M, N), dtype=torch.bfloat16 if flags & BF16_C else torch.float32, device=x.device)
-    c = lambda t, dt=torch.float32: None if t is None else t.contiguous().to(dt)
-    b, gm, bt, rs, ri, po = c(bias), c(gamma), c(beta), c(res), c(res_idx, torch.int32), c(post)
-    g = _Gemm(M, N, K, L.ptr(x), L.ptr(None), K, L.ptr(None), 0, L.ptr(weight), K, L.ptr(None), 0, L.ptr(b), 1.0, 0,
-              L.ptr(out), N, 1, 0, 0, 0, 0, 0, 0, L.ptr(None), 0, 0, L.ptr(gm), L.ptr(bt), L.ptr(rs), L.ptr(ri), L.ptr(po), int(relu), float(eps))
-    g.bf16 = flags
+    out = torch.empty((x.shape[0], weight.shape[0]), dtype=torch.bfloat16 if flags & BF16_C else torch.float32, device=x.device)
+    b, gm, bt, rs, ri, po = _c(bias), _c(gamma), _c(beta), _c(res), _i32c(res_idx), _c(post)
+    g = _gemm(x, weight, b, out, flags, alpha=1.0, ln_relu=int(relu), ln_eps=float(eps))
+    g.ln_gamma, g.ln_beta, g.ln_res, g.ln_res_idx, g.ln_post = L.ptr(gm), L.ptr(bt), L.ptr(rs), L.ptr(ri), L.ptr(po)
     keep = []
     _k_cat(g, x, x_cat, keep, x_cat_idx, addend)
-    g.ldw = weight.shape[1]
     if interp is not None:
-        keep += [c(interp[0]), c(interp[1], torch.int32), c(interp[2])]
+        keep += [_c(interp[0]), _i32c(interp[1]), _c(interp[2])]
         g.ip_feat, g.ip_idx, g.ip_dist2 = L.ptr(keep[-3]), L.ptr(keep[-2]), L.ptr(keep[-1])
     if x3:
         _x3(g, weight, keep)
-    L.check(L.lib().roitr_gemm(ctypes.byref(g), L.stream_ptr()), "gemm+layernorm")
+    L.check(_lib().roitr_gemm(ctypes.byref(g), L.stream_ptr()), "gemm+layernorm")
     return out
 
 
 def add_layernorm_interp(x, gamma, beta, feat, idx, dist2, res=None, res_idx=None, relu=False, eps=1e-5):
     """[relu](LayerNorm(x + res[res_idx]) * gamma + beta) + three-nearest-neighbour interpolation of the rows of `feat`
     (roitr_add_layernorm_interp: the two-launch twin of linear_layernorm(..., interp=...))."""
-    c = lambda t, dt=torch.float32: None if t is None else t.contiguous().to(dt)
-    x, gm, bt, rs, ri, ft, ix, d2 = c(x), c(gamma), c(beta), c(res), c(res_idx, torch.int32), c(feat), c(idx, torch.int32), c(dist2)
+    x, gm, bt, rs, ri, ft, ix, d2 = _c(x), _c(gamma), _c(beta), _c(res), _i32c(res_idx), _c(feat), _i32c(idx), _c(dist2)
     M, C = x.shape
     out = torch.empty_like(x)
-    L.check(L.lib().roitr_add_layernorm_interp(M, C, L.ptr(x), L.ptr(rs), L.ptr(ri), L.ptr(gm), L.ptr(bt), int(relu), ctypes.c_float(eps),
+    L.check(_lib().roitr_add_layernorm_interp(M, C, L.ptr(x), L.ptr(rs), L.ptr(ri), L.ptr(gm), L.ptr(bt), int(relu), float(eps),
                                                L.ptr(ft), L.ptr(ix), L.ptr(d2), L.ptr(out), L.stream_ptr()), "add_layernorm_interp")
     return out
 
@@ -274,11 +263,10 @@ def adaptive_superpoint_matching(src_feats, tgt_feats, src_masks, tgt_masks, min
     indexes the first returned index list).  Returns (src_corr_indices, tgt_corr_indices, corr_scores)."""
     dev = src_feats.device
     na, nb = src_feats.shape[0], tgt_feats.shape[0]
-    lib = L.lib()
-    lib.roitr_coarse_scratch_floats.restype = ctypes.c_size_t
+    lib = _lib()
     xy = linear(src_feats, tgt_feats)                       # (na, nb) feature dot products
-    feats = torch.cat([tgt_feats, src_feats], 0).contiguous().float()      # engine cloud order: [second set, first set]
-    masks = torch.cat([tgt_masks, src_masks], 0).to(torch.int32).contiguous()
+    feats = _c(torch.cat([tgt_feats, src_feats], 0))      # engine cloud order: [second set, first set]
+    masks = _i32c(torch.cat([tgt_masks, src_masks], 0))
     off = torch.tensor([nb, nb + na], dtype=torch.int32, device=dev)
     stride = lib.roitr_coarse_scratch_floats(na, nb)
     scratch = torch.empty(stride, dtype=torch.float32, device=dev)
@@ -287,9 +275,10 @@ def adaptive_superpoint_matching(src_feats, tgt_feats, src_masks, tgt_masks, min
     ib = torch.zeros(cap, dtype=torch.int32, device=dev)
     sc = torch.zeros(cap, dtype=torch.float32, device=dev)
     nc = torch.zeros(1, dtype=torch.int32, device=dev)
-    a = _Coarse(1, feats.shape[1], cap, 0, na, nb, L.ptr(feats), L.ptr(off), L.ptr(masks), L.ptr(scratch), stride, L.ptr(ia), L.ptr(ib),
-                L.ptr(sc), L.ptr(nc), L.ptr(xy), 0, nb)
-    L.check(lib.roitr_adaptive_matching(ctypes.byref(a), int(min_num_correspondences), ctypes.c_float(similarity_threshold),
+    a = _Coarse(pairs=1, C=feats.shape[1], num_corr=cap, max_ref=na, max_src=nb, feats=L.ptr(feats), node_offset=L.ptr(off),
+                node_masks=L.ptr(masks), scratch=L.ptr(scratch), scratch_stride=stride, tgt_corr=L.ptr(ia), src_corr=L.ptr(ib),
+                corr_scores=L.ptr(sc), n_corr=L.ptr(nc), xy=L.ptr(xy), xy_ld=nb)
+    L.check(lib.roitr_adaptive_matching(ctypes.byref(a), int(min_num_correspondences), float(similarity_threshold),
                                         L.stream_ptr()), "adaptive_matching")
     n = int(nc.item())
     return ia[:n].long(), ib[:n].long(), sc[:n]
@@ -302,13 +291,12 @@ def geo_table_build(div_term, w_d, b_d, w_a, b_a, interval=2.0, d_range=48.0, a_
     import math
     C = int(w_d.shape[0])
     nd, na = int(math.ceil(d_range / interval)), int(math.floor(a_range / interval)) + 1
-    lib = L.lib()
-    h = lambda t: t.detach().float().cpu().contiguous()
-    div_h, wd_h, bd_h, wa_h, ba_h = map(h, (div_term, w_d, b_d, w_a, b_a))
+    lib = _lib()
+    div_h, wd_h, bd_h, wa_h, ba_h = (_c(t.detach().cpu()) for t in (div_term, w_d, b_d, w_a, b_a))
     table = torch.empty(int(lib.roitr_geo_table_floats(C, nd, na)), dtype=torch.float32)
     fit = (ctypes.c_double * 6)()
     hp = L.host_ptr
-    L.check(lib.roitr_geo_table_build(C, hp(div_h), hp(wd_h), hp(bd_h), hp(wa_h), hp(ba_h), L.c_float(interval), nd, na,
+    L.check(lib.roitr_geo_table_build(C, hp(div_h), hp(wd_h), hp(bd_h), hp(wa_h), hp(ba_h), float(interval), nd, na,
                                       hp(table), fit), "geo_table_build")
     return table.to(w_d.device), nd, na, list(fit)
 
@@ -317,10 +305,9 @@ def geo_embed_table(d_idx, a_idx, table, interval, n_int_d, n_int_a, div_term, w
     """The embedding of geo_embed() evaluated from the function table; values outside the table are evaluated directly."""
     rows, k = int(a_idx.shape[0]), int(a_idx.shape[1])
     C = int(w_d.shape[0])
-    f = lambda t: t.contiguous().float()
-    d_idx, a_idx, table, div_term, w_d, b_d, w_a, b_a = map(f, (d_idx, a_idx, table, div_term, w_d, b_d, w_a, b_a))
+    d_idx, a_idx, table, div_term, w_d, b_d, w_a, b_a = map(_c, (d_idx, a_idx, table, div_term, w_d, b_d, w_a, b_a))
     out = torch.empty((rows, C), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=d_idx.device)
-    L.check(L.lib().roitr_geo_embed_table(ctypes.c_long(rows), C, k, L.ptr(d_idx), L.ptr(a_idx), L.ptr(table), L.c_float(interval),
+    L.check(_lib().roitr_geo_embed_table(rows, C, k, L.ptr(d_idx), L.ptr(a_idx), L.ptr(table), float(interval),
                                           int(n_int_d), int(n_int_a), L.ptr(div_term), L.ptr(w_d), L.ptr(b_d), L.ptr(w_a), L.ptr(b_a),
                                           L.ptr(out), 1 if out_bf16 else 0, L.stream_ptr()), "geo_embed_table")
     return out
@@ -332,34 +319,25 @@ def geo_embed(d_idx, a_idx, div_term, w_d, b_d, w_a, b_a, split=False, bf16=Fals
     operands (weights stored bf16, the sinusoid rounded to bf16, fp32 accumulate) -- the engine's bf16 operand mode."""
     rows, k = int(a_idx.shape[0]), int(a_idx.shape[1])
     C = int(w_d.shape[0])
-    f = lambda t: t.contiguous().float()
-    d_idx, a_idx, div_term, w_d, b_d, w_a, b_a = map(f, (d_idx, a_idx, div_term, w_d, b_d, w_a, b_a))
+    d_idx, a_idx, div_term, w_d, b_d, w_a, b_a = map(_c, (d_idx, a_idx, div_term, w_d, b_d, w_a, b_a))
     out = torch.empty((rows, C), dtype=torch.float32, device=d_idx.device)
-    lib = L.lib()
+    lib = _lib()
     if bf16:
         wdh, wah = w_d.to(torch.bfloat16).contiguous(), w_a.to(torch.bfloat16).contiguous()
-        L.check(lib.roitr_geo_embed_bf16(ctypes.c_long(rows), C, k, L.ptr(d_idx), L.ptr(a_idx), L.ptr(div_term), L.ptr(wdh), L.ptr(b_d),
+        L.check(lib.roitr_geo_embed_bf16(rows, C, k, L.ptr(d_idx), L.ptr(a_idx), L.ptr(div_term), L.ptr(wdh), L.ptr(b_d),
                                          L.ptr(wah), L.ptr(b_a), L.ptr(out), L.stream_ptr()), "geo_embed_bf16")
         return out
     if split:
         wd3 = torch.empty((3, C, C), dtype=torch.int16, device=out.device)
         wa3 = torch.empty((3, C, C), dtype=torch.int16, device=out.device)
-        L.check(lib.roitr_split3_bf16(ctypes.c_long(C * C), L.ptr(w_d), L.ptr(wd3), L.stream_ptr()), "split3")
-        L.check(lib.roitr_split3_bf16(ctypes.c_long(C * C), L.ptr(w_a), L.ptr(wa3), L.stream_ptr()), "split3")
-        L.check(lib.roitr_geo_embed_split(ctypes.c_long(rows), C, k, L.ptr(d_idx), L.ptr(a_idx), L.ptr(div_term), L.ptr(wd3), L.ptr(b_d),
+        L.check(lib.roitr_split3_bf16(C * C, L.ptr(w_d), L.ptr(wd3), L.stream_ptr()), "split3")
+        L.check(lib.roitr_split3_bf16(C * C, L.ptr(w_a), L.ptr(wa3), L.stream_ptr()), "split3")
+        L.check(lib.roitr_geo_embed_split(rows, C, k, L.ptr(d_idx), L.ptr(a_idx), L.ptr(div_term), L.ptr(wd3), L.ptr(b_d),
                                           L.ptr(wa3), L.ptr(b_a), L.ptr(out), L.stream_ptr()), "geo_embed_split")
     else:
-        L.check(lib.roitr_geo_embed(ctypes.c_long(rows), C, k, L.ptr(d_idx), L.ptr(a_idx), L.ptr(div_term), L.ptr(w_d), L.ptr(b_d),
+        L.check(lib.roitr_geo_embed(rows, C, k, L.ptr(d_idx), L.ptr(a_idx), L.ptr(div_term), L.ptr(w_d), L.ptr(b_d),
                                     L.ptr(w_a), L.ptr(b_a), L.ptr(out), L.stream_ptr()), "geo_embed")
     return out
-
-
-class _LocalAttnFold(ctypes.Structure):
-    _fields_ = [("M", ctypes.c_int), ("in_dim", ctypes.c_int), ("H", ctypes.c_int),
-                ("x", ctypes.c_void_p), ("ldx", ctypes.c_int), ("q", ctypes.c_void_p), ("ldq", ctypes.c_int),
-                ("qt", ctypes.c_void_p), ("group_idx", ctypes.c_void_p), ("ppf", ctypes.c_void_p),
-                ("wpe", ctypes.c_void_p), ("wvpe", ctypes.c_void_p), ("bvpe", ctypes.c_void_p), ("scale", ctypes.c_float),
-                ("xbar", ctypes.c_void_p), ("vpart", ctypes.c_void_p), ("node_order", ctypes.c_void_p), ("ldqt", ctypes.c_int)]
 
 
 def local_attention_fold(x, q, qt, group_idx, ppf, wpe, wvpe, bvpe, node_order=None, packed=False):
@@ -369,8 +347,7 @@ def local_attention_fold(x, q, qt, group_idx, ppf, wpe, wvpe, bvpe, node_order=N
     Returns (xbar (M, 4, I) = sum_j a_hj x_j, vpart (M, H) = Wvpe_h pbar_h + bvpe_h): the attention output of the unfolded form is
     vpart + [Wv'_h xbar_h + bv'_h]_h.  packed=True: q and qt are handed over as the two column blocks of ONE (M, H + 4 I) buffer (row
     stride H + 4 I for both: RoitrLocalAttnFold.ldq / ldqt), the way the engine's single q | q~ GEMM leaves them."""
-    f = lambda t: t.contiguous().float()
-    x, q, qt, ppf, wpe, wvpe, bvpe = f(x), f(q), f(qt), f(ppf), f(wpe), f(wvpe), f(bvpe)
+    x, q, qt, ppf, wpe, wvpe, bvpe = _c(x), _c(q), _c(qt), _c(ppf), _c(wpe), _c(wvpe), _c(bvpe)
     both = torch.cat([q, qt.reshape(q.shape[0], -1)], 1).contiguous() if packed else None
     group_idx = _i32c(group_idx)
     M, H, I = int(q.shape[0]), int(q.shape[1]), int(x.shape[1])
@@ -386,19 +363,10 @@ def local_attention_fold(x, q, qt, group_idx, ppf, wpe, wvpe, bvpe, node_order=N
         a.qt = ctypes.c_void_p(both.data_ptr() + 4 * H)
     a.group_idx, a.ppf, a.wpe, a.wvpe, a.bvpe = L.ptr(group_idx), L.ptr(ppf), L.ptr(wpe), L.ptr(wvpe), L.ptr(bvpe)
     a.scale, a.xbar, a.vpart = 1.0 / float(H // 4) ** 0.5, L.ptr(xbar), L.ptr(vpart)
-    no = f(node_order) if node_order is not None else None
+    no = _c(node_order)
     a.node_order = L.ptr(no)
-    L.check(L.lib().roitr_local_attention_fold(ctypes.byref(a), L.stream_ptr()), "local_attention_fold")
+    L.check(_lib().roitr_local_attention_fold(ctypes.byref(a), L.stream_ptr()), "local_attention_fold")
     return xbar, vpart
-
-
-class _LocalAttn(ctypes.Structure):
-    _fields_ = [("M", ctypes.c_int), ("K", ctypes.c_int), ("H", ctypes.c_int), ("heads", ctypes.c_int),
-                ("q", ctypes.c_void_p), ("ldq", ctypes.c_int), ("k", ctypes.c_void_p), ("ldk", ctypes.c_int),
-                ("v", ctypes.c_void_p), ("ldv", ctypes.c_int), ("group_idx", ctypes.c_void_p), ("ppf", ctypes.c_void_p),
-                ("wvpe", ctypes.c_void_p), ("bvpe", ctypes.c_void_p), ("scale", ctypes.c_float),
-                ("out", ctypes.c_void_p), ("ldo", ctypes.c_int), ("node_order", ctypes.c_void_p), ("bf16", ctypes.c_int),
-                ("wpe", ctypes.c_void_p), ("bpe", ctypes.c_void_p)]
 
 
 def _attn_rows(t, what, dtype):
@@ -419,9 +387,8 @@ def local_attention(q, k, v, group_idx, ppf, wvpe, bvpe, wpe=None, bpe=None, ldq
     node_order: optional (M, 4) float32 whose last column holds the node index bits.  out: optional preallocated (>= M, >= H) tensor with
     contiguous rows; only its first H columns of the M node rows are written.  Returns out (M, H)."""
     dt = torch.bfloat16 if bf16 else torch.float32
-    f = lambda t: None if t is None else t.contiguous().float()
     sq, sk, sv = _attn_rows(q, "q", dt), _attn_rows(k, "k", dt), _attn_rows(v, "v", dt)
-    group_idx, ppf, wvpe, bvpe, wpe, bpe, no = _i32c(group_idx), f(ppf), f(wvpe), f(bvpe), f(wpe), f(bpe), f(node_order)
+    group_idx, ppf, wvpe, bvpe, wpe, bpe, no = _i32c(group_idx), _c(ppf), _c(wvpe), _c(bvpe), _c(wpe), _c(bpe), _c(node_order)
     M, K, H = int(group_idx.shape[0]), int(group_idx.shape[1]), int(wvpe.shape[0])
     if (wpe is None) != (bpe is None):
         raise L.RoitrError("local_attention: wpe and bpe are given together or not at all")
@@ -440,34 +407,30 @@ def local_attention(q, k, v, group_idx, ppf, wvpe, bvpe, wpe=None, bpe=None, ldq
     a.out, a.ldo, a.node_order = L.ptr(out), int(so if ldo is None else ldo), L.ptr(no)
     a.bf16 = 3 if bf16 is True else int(bf16)
     a.wpe, a.bpe = L.ptr(wpe), L.ptr(bpe)
-    L.check(L.lib().roitr_local_attention(ctypes.byref(a), L.stream_ptr()), "local_attention")
+    L.check(_lib().roitr_local_attention(ctypes.byref(a), L.stream_ptr()), "local_attention")
     return out
 
 
 def build_pfold(wpe, bpe, heads=4):
     """roitr_build_pfold (csrc/local_attn.hip): Pfold (5 * heads, H) with row 5 h + j = Wpe[:, j] (j < 4) / bpe (j = 4) on the channels of
     head h and zero elsewhere, so that q @ Pfold.T are the extra q columns of RoitrLocalAttn."""
-    wpe, bpe = wpe.contiguous().float(), bpe.contiguous().float()
+    wpe, bpe = _c(wpe), _c(bpe)
     H = int(wpe.shape[0])
     out = torch.empty((5 * int(heads), H), dtype=torch.float32, device=wpe.device)
-    L.check(L.lib().roitr_build_pfold(H, int(heads), L.ptr(wpe), L.ptr(bpe), L.ptr(out), L.stream_ptr()), "build_pfold")
+    L.check(_lib().roitr_build_pfold(H, int(heads), L.ptr(wpe), L.ptr(bpe), L.ptr(out), L.stream_ptr()), "build_pfold")
     return out
 
 
 # ------------------------------------------------------------------------------------------------
 # Row-wise layers (csrc/nn_ops.hip; "row-wise layers" of include/roitr_engine.h)
 # ------------------------------------------------------------------------------------------------
-def _c(t, dt=torch.float32):
-    return None if t is None else t.contiguous().to(dt)
-
-
 def add_layernorm(x, gamma, beta, res=None, res_idx=None, post=None, relu=False, eps=1e-5):
     """roitr_add_layernorm: [relu](LayerNorm(x + res[res_idx]) * gamma + beta + post) for x (M, C), C <= 1024; res (R, C) with res_idx
     (M,) int32 rows of it, or (M, C) without; post (M, C).  attention.py:319, model/model.py:138-140."""
-    x, gm, bt, rs, ri, po = _c(x), _c(gamma), _c(beta), _c(res), _c(res_idx, torch.int32), _c(post)
+    x, gm, bt, rs, ri, po = _c(x), _c(gamma), _c(beta), _c(res), _i32c(res_idx), _c(post)
     M, C = int(x.shape[0]), int(x.shape[1])
     out = torch.empty_like(x)
-    L.check(L.lib().roitr_add_layernorm(M, C, L.ptr(x), L.ptr(rs), L.ptr(ri), L.ptr(gm), L.ptr(bt), L.ptr(po), int(relu), float(eps),
+    L.check(_lib().roitr_add_layernorm(M, C, L.ptr(x), L.ptr(rs), L.ptr(ri), L.ptr(gm), L.ptr(bt), L.ptr(po), int(relu), float(eps),
                                         L.ptr(out), L.stream_ptr()), "add_layernorm")
     return out
 
@@ -476,45 +439,45 @@ def l2_normalize(x):
     """roitr_l2_normalize: F.normalize(x, p=2, dim=1) of x (M, C), C <= 1024 (model/RIGA_v2.py:64-65)."""
     x = _c(x)
     out = torch.empty_like(x)
-    L.check(L.lib().roitr_l2_normalize(int(x.shape[0]), int(x.shape[1]), L.ptr(x), L.ptr(out), L.stream_ptr()), "l2_normalize")
+    L.check(_lib().roitr_l2_normalize(int(x.shape[0]), int(x.shape[1]), L.ptr(x), L.ptr(out), L.stream_ptr()), "l2_normalize")
     return out
 
 
 def segment_mean(x, offset):
     """roitr_segment_mean: the mean row of every cloud of x (T, C); offset (b,) int32 cumulative cloud ends, no cloud empty
     (model/model.py:101-109).  Returns (b, C)."""
-    x, off = _c(x), _c(offset, torch.int32)
+    x, off = _c(x), _i32c(offset)
     b, C = int(off.shape[0]), int(x.shape[1])
     out = torch.empty((b, C), dtype=torch.float32, device=x.device)
-    L.check(L.lib().roitr_segment_mean(b, C, L.ptr(x), L.ptr(off), L.ptr(out), L.stream_ptr()), "segment_mean")
+    L.check(_lib().roitr_segment_mean(b, C, L.ptr(x), L.ptr(off), L.ptr(out), L.stream_ptr()), "segment_mean")
     return out
 
 
 def interp3_add(feat, idx, dist2, base=None):
     """roitr_interp3_add: base + the three-nearest-neighbour inverse-distance interpolation of the rows of feat (R, C); idx (n, 3) int32
     rows of feat, dist2 (n, 3) SQUARED distances, base (n, C) or None (functions/pointops.py:168-182 + model/model.py:116)."""
-    feat, idx, dist2, base = _c(feat), _c(idx, torch.int32), _c(dist2), _c(base)
+    feat, idx, dist2, base = _c(feat), _i32c(idx), _c(dist2), _c(base)
     n, C = int(idx.shape[0]), int(feat.shape[1])
     out = torch.empty((n, C), dtype=torch.float32, device=feat.device)
-    L.check(L.lib().roitr_interp3_add(n, C, L.ptr(feat), L.ptr(idx), L.ptr(dist2), L.ptr(base), L.ptr(out), L.stream_ptr()), "interp3_add")
+    L.check(_lib().roitr_interp3_add(n, C, L.ptr(feat), L.ptr(idx), L.ptr(dist2), L.ptr(base), L.ptr(out), L.stream_ptr()), "interp3_add")
     return out
 
 
 def gather_rows(x, idx, limit=0):
     """roitr_gather_rows: out[r] = x[idx[r]] for x (R, C), idx (rows,) int32; a negative index gives a zero row, and so does an index
     >= limit when limit > 0 (limit <= 0: every non-negative index must be a row of x)."""
-    x, idx = _c(x), _c(idx, torch.int32)
+    x, idx = _c(x), _i32c(idx)
     rows, C = int(idx.shape[0]), int(x.shape[1])
     out = torch.empty((rows, C), dtype=torch.float32, device=x.device)
-    L.check(L.lib().roitr_gather_rows(rows, C, L.ptr(x), L.ptr(idx), int(limit), L.ptr(out), L.stream_ptr()), "gather_rows")
+    L.check(_lib().roitr_gather_rows(rows, C, L.ptr(x), L.ptr(idx), int(limit), L.ptr(out), L.stream_ptr()), "gather_rows")
     return out
 
 
 def compose_idx(outer, inner):
     """roitr_compose_idx: outer[inner] for int32 index vectors."""
-    outer, inner = _c(outer, torch.int32), _c(inner, torch.int32)
+    outer, inner = _i32c(outer), _i32c(inner)
     out = torch.empty_like(inner)
-    L.check(L.lib().roitr_compose_idx(int(inner.shape[0]), L.ptr(outer), L.ptr(inner), L.ptr(out), L.stream_ptr()), "compose_idx")
+    L.check(_lib().roitr_compose_idx(int(inner.shape[0]), L.ptr(outer), L.ptr(inner), L.ptr(out), L.stream_ptr()), "compose_idx")
     return out
 
 
@@ -527,7 +490,7 @@ def transpose(x, out=None):
     for t, shape in ((x, (rows, cols)), (out, (cols, rows))):
         if t.dtype != torch.float32 or tuple(t.shape) != shape or t.stride(1) != 1 or t.stride(0) < shape[1]:
             raise L.RoitrError("transpose: float32 (rows, cols) -> (cols, rows) with contiguous rows")
-    L.check(L.lib().roitr_transpose(rows, cols, L.ptr(x), int(x.stride(0)), L.ptr(out), int(out.stride(0)), L.stream_ptr()), "transpose")
+    L.check(_lib().roitr_transpose(rows, cols, L.ptr(x), int(x.stride(0)), L.ptr(out), int(out.stride(0)), L.stream_ptr()), "transpose")
     return out
 
 
@@ -537,17 +500,8 @@ def add_vectors(a, b):
     if a.shape != b.shape:
         raise L.RoitrError("add_vectors: two vectors of one length")
     out = torch.empty_like(a)
-    L.check(L.lib().roitr_add_vectors(int(a.numel()), L.ptr(a), L.ptr(b), L.ptr(out), L.stream_ptr()), "add_vectors")
+    L.check(_lib().roitr_add_vectors(int(a.numel()), L.ptr(a), L.ptr(b), L.ptr(out), L.stream_ptr()), "add_vectors")
     return out
-
-
-class _LocalTd(ctypes.Structure):
-    _fields_ = [("M", ctypes.c_int), ("in_dim", ctypes.c_int), ("H", ctypes.c_int),
-                ("x", ctypes.c_void_p), ("node_idx", ctypes.c_void_p), ("group_idx", ctypes.c_void_p), ("ppf", ctypes.c_void_p),
-                ("node_order", ctypes.c_void_p), ("wqqt", ctypes.c_void_p), ("bqqt", ctypes.c_void_p), ("wv", ctypes.c_void_p),
-                ("bv", ctypes.c_void_p), ("wpe", ctypes.c_void_p), ("wvpe", ctypes.c_void_p), ("bvpe", ctypes.c_void_p),
-                ("wcat", ctypes.c_void_p), ("bcat", ctypes.c_void_p), ("norm_w", ctypes.c_void_p), ("norm_b", ctypes.c_void_p),
-                ("wout", ctypes.c_void_p), ("bout", ctypes.c_void_p), ("scale", ctypes.c_float), ("eps", ctypes.c_float), ("out", ctypes.c_void_p)]
 
 
 def local_td(x, node_idx, group_idx, ppf, w, node_order=None):
@@ -555,35 +509,23 @@ def local_td(x, node_idx, group_idx, ppf, w, node_order=None):
     include/roitr_engine.h RoitrLocalTd).  x (N_in, 64) input rows, node_idx (M,) int32 row of x of every node, group_idx (M, 16) int32
     rows of x, ppf (M, 16, 4); w: dict of the folded weights wqqt (384, 64), bqqt (384), wv (128, 64), bv (128), wpe / wvpe (128, 4),
     bvpe (128), wcat (128, 192), bcat, norm_w, norm_b, wout (128, 128), bout.  Returns (M, 128)."""
-    f = lambda t: t.contiguous().float()
-    x, ppf = f(x), f(ppf)
+    x, ppf = _c(x), _c(ppf)
     node_idx, group_idx = _i32c(node_idx), _i32c(group_idx)
-    w = {k: f(v) for k, v in w.items()}
+    w = {k: _c(v) for k, v in w.items()}
     M, I, H = int(node_idx.shape[0]), int(x.shape[1]), int(w["wout"].shape[0])
-    if int(group_idx.shape[1]) != 16 or not L.lib().roitr_local_td_supported(I, H, 16):
+    if int(group_idx.shape[1]) != 16 or not _lib().roitr_local_td_supported(I, H, 16):
         raise L.RoitrError("local_td: in_dim 64, H 128, 16 neighbours per node")
     out = torch.empty((M, H), dtype=torch.float32, device=x.device)
     a = _LocalTd()
     a.M, a.in_dim, a.H = M, I, H
     a.x, a.node_idx, a.group_idx, a.ppf = L.ptr(x), L.ptr(node_idx), L.ptr(group_idx), L.ptr(ppf)
-    no = f(node_order) if node_order is not None else None
+    no = _c(node_order)
     a.node_order = L.ptr(no)
     for k in ("wqqt", "bqqt", "wv", "bv", "wpe", "wvpe", "bvpe", "wcat", "bcat", "norm_w", "norm_b", "wout", "bout"):
         setattr(a, k, L.ptr(w[k]))
     a.scale, a.eps, a.out = 1.0 / float(H // 4) ** 0.5, 1e-5, L.ptr(out)
-    L.check(L.lib().roitr_local_td(ctypes.byref(a), L.stream_ptr()), "local_td")
+    L.check(_lib().roitr_local_td(ctypes.byref(a), L.stream_ptr()), "local_td")
     return out
-
-
-class _LocalBlock(ctypes.Structure):
-    _fields_ = [("M", ctypes.c_int), ("K", ctypes.c_int), ("H", ctypes.c_int),
-                ("x", ctypes.c_void_p), ("kv", ctypes.c_void_p), ("group_idx", ctypes.c_void_p), ("ppf", ctypes.c_void_p),
-                ("node_order", ctypes.c_void_p), ("wq", ctypes.c_void_p), ("bq", ctypes.c_void_p),
-                ("wpe", ctypes.c_void_p), ("bpe", ctypes.c_void_p), ("wvpe", ctypes.c_void_p), ("bvpe", ctypes.c_void_p),
-                ("wcat", ctypes.c_void_p), ("bcat", ctypes.c_void_p), ("norm_w", ctypes.c_void_p), ("norm_b", ctypes.c_void_p),
-                ("wout", ctypes.c_void_p), ("bout", ctypes.c_void_p), ("bn2_w", ctypes.c_void_p), ("bn2_b", ctypes.c_void_p),
-                ("scale", ctypes.c_float), ("eps", ctypes.c_float), ("out", ctypes.c_void_p), ("kv_bf16", ctypes.c_int),
-                ("wq_h", ctypes.c_void_p), ("wcat_h", ctypes.c_void_p), ("wout_h", ctypes.c_void_p)]
 
 
 def local_block(x, kv, group_idx, ppf, w, node_order=None, variant=None, bf16_weights=False):
@@ -596,16 +538,15 @@ def local_block(x, kv, group_idx, ppf, w, node_order=None, variant=None, bf16_we
     the three on-chip GEMMs take bf16 matrix operands (RoitrLocalBlock::wq_h / wcat_h / wout_h; the copies are made here)."""
     M, H = int(x.shape[0]), int(x.shape[1])
     K = int(group_idx.shape[1])
-    f = lambda t: t.contiguous().float()
     kv_h = kv.dtype == torch.bfloat16
-    x, kv, ppf = f(x), (kv.contiguous() if kv_h else f(kv)), f(ppf)
+    x, kv, ppf = _c(x), (kv.contiguous() if kv_h else _c(kv)), _c(ppf)
     group_idx = _i32c(group_idx)
-    keep = {k: f(v) for k, v in w.items()}
+    keep = {k: _c(v) for k, v in w.items()}
     out = torch.empty((M, H), dtype=torch.float32, device=x.device)
     a = _LocalBlock()
     a.M, a.K, a.H = M, K, H
     a.x, a.kv, a.group_idx, a.ppf = L.ptr(x), L.ptr(kv), L.ptr(group_idx), L.ptr(ppf)
-    no = f(node_order) if node_order is not None else None
+    no = _c(node_order)
     a.node_order = L.ptr(no)
     for k in ("wq", "bq", "wpe", "bpe", "wvpe", "bvpe", "wcat", "bcat", "norm_w", "norm_b", "wout", "bout", "bn2_w", "bn2_b"):
         setattr(a, k, L.ptr(keep[k]))
@@ -615,18 +556,10 @@ def local_block(x, kv, group_idx, ppf, w, node_order=None, variant=None, bf16_we
         keep_h = {k: keep[k].to(torch.bfloat16).contiguous() for k in ("wq", "wcat", "wout")}
         a.wq_h, a.wcat_h, a.wout_h = L.ptr(keep_h["wq"]), L.ptr(keep_h["wcat"]), L.ptr(keep_h["wout"])
     if variant is None:
-        L.check(L.lib().roitr_local_block(ctypes.byref(a), L.stream_ptr()), "local_block")
+        L.check(_lib().roitr_local_block(ctypes.byref(a), L.stream_ptr()), "local_block")
     else:
-        L.check(L.lib().roitr_local_block_dbg(ctypes.byref(a), int(variant), L.stream_ptr()), "local_block_dbg")
+        L.check(_lib().roitr_local_block_dbg(ctypes.byref(a), int(variant), L.stream_ptr()), "local_block_dbg")
     return out
-
-
-class _LocalFirst(ctypes.Structure):
-    _fields_ = [("M", ctypes.c_int), ("K", ctypes.c_int),
-                ("x", ctypes.c_void_p), ("group_idx", ctypes.c_void_p), ("ppf", ctypes.c_void_p), ("node_order", ctypes.c_void_p),
-                ("head_consts", ctypes.c_void_p), ("G", ctypes.c_void_p), ("zero_bias", ctypes.c_void_p),
-                ("norm_w", ctypes.c_void_p), ("norm_b", ctypes.c_void_p), ("wout", ctypes.c_void_p), ("bout", ctypes.c_void_p),
-                ("scale", ctypes.c_float), ("eps", ctypes.c_float), ("out", ctypes.c_void_p)]
 
 
 def local_first(x, group_idx, ppf, w, node_order=None, out=None):
@@ -634,10 +567,9 @@ def local_first(x, group_idx, ppf, w, node_order=None, out=None):
     include/roitr_engine.h RoitrLocalFirst).  x (M,) the scalar input feature, group_idx (M, K) int32, K in {8, 16}, ppf (M, K, 4);
     w: dict of head_consts (64), G (64, 32), zero_bias (64), norm_w, norm_b, wout (64, 64), bout.  Returns (M, 64); a preallocated
     contiguous float32 `out` (>= M, 64) is written in its first M rows only."""
-    f = lambda t: t.contiguous().float()
-    x, ppf = f(x), f(ppf)
+    x, ppf = _c(x), _c(ppf)
     group_idx = _i32c(group_idx)
-    w = {k: f(v) for k, v in w.items()}
+    w = {k: _c(v) for k, v in w.items()}
     M, K = int(x.shape[0]), int(group_idx.shape[1])
     if out is None:
         out = torch.empty((M, 64), dtype=torch.float32, device=x.device)
@@ -646,12 +578,12 @@ def local_first(x, group_idx, ppf, w, node_order=None, out=None):
     a = _LocalFirst()
     a.M, a.K = M, K
     a.x, a.group_idx, a.ppf = L.ptr(x), L.ptr(group_idx), L.ptr(ppf)
-    no = f(node_order) if node_order is not None else None
+    no = _c(node_order)
     a.node_order = L.ptr(no)
     for k in ("head_consts", "G", "zero_bias", "norm_w", "norm_b", "wout", "bout"):
         setattr(a, k, L.ptr(w[k]))
     a.scale, a.eps, a.out = 0.25, 1e-5, L.ptr(out)
-    L.check(L.lib().roitr_local_first(ctypes.byref(a), L.stream_ptr()), "local_first")
+    L.check(_lib().roitr_local_first(ctypes.byref(a), L.stream_ptr()), "local_first")
     return out
 
 
@@ -666,39 +598,30 @@ def local_weights_prepare(w):
     slice of one), kept by the library under w's address until local_weights_release(w).  local_block / local_td / local_first take
     the fragment path when all of their weights are prepared (include/roitr_engine.h); the caller keeps `w` alive and unchanged."""
     rows, k, ldw = _weight_view(w)
-    L.check(L.lib().roitr_local_weights_prepare(L.ptr(w), rows, k, ldw, L.stream_ptr()), "local_weights_prepare")
+    L.check(_lib().roitr_local_weights_prepare(L.ptr(w), rows, k, ldw, L.stream_ptr()), "local_weights_prepare")
 
 
 def local_weights_release(w):
     """roitr_local_weights_release: frees every copy kept under w's address (none: a no-op)."""
-    L.check(L.lib().roitr_local_weights_release(L.ptr(w)), "local_weights_release")
+    L.check(_lib().roitr_local_weights_release(L.ptr(w)), "local_weights_release")
 
 
 def local_weights_count():
     """roitr_local_weights_count: the number of fragment-ordered copies the library holds."""
-    return int(L.lib().roitr_local_weights_count())
+    return int(_lib().roitr_local_weights_count())
 
 
 def local_weights_reorder_host(w):
     """roitr_local_weights_reorder_host: the fragment order of a HOST weight (rows, k) (rows may be strided), as a flat host tensor."""
     rows, k, ldw = _weight_view(w)
     dst = torch.empty(rows * k, dtype=torch.float32)
-    L.check(L.lib().roitr_local_weights_reorder_host(L.host_ptr(w), rows, k, ldw, L.host_ptr(dst)), "local_weights_reorder_host")
+    L.check(_lib().roitr_local_weights_reorder_host(L.host_ptr(w), rows, k, ldw, L.host_ptr(dst)), "local_weights_reorder_host")
     return dst
 
 
 # ------------------------------------------------------------------------------------------------
 # Global geometric transformer (csrc/geo_attn.hip)
 # ------------------------------------------------------------------------------------------------
-class _Mha(ctypes.Structure):
-    _fields_ = [("q_row0", ctypes.c_int), ("q_rows", ctypes.c_int), ("C", ctypes.c_int), ("heads", ctypes.c_int),
-                ("q", _P), ("ldq", ctypes.c_int), ("k", _P), ("ldk", ctypes.c_int), ("v", _P), ("ldv", ctypes.c_int),
-                ("offset", _P), ("cloud_of_row", _P), ("partner", _P),
-                ("E", _P), ("eoff", _P), ("qt", _P), ("bp", _P),
-                ("scale", ctypes.c_float), ("nk_max", ctypes.c_int), ("out", _P), ("ldo", ctypes.c_int), ("ebar", _P),
-                ("e_bf16", ctypes.c_int)]
-
-
 def _rows(t, what):
     """Row stride of a 2-D float32 device operand whose rows are contiguous (a column slice of a wider buffer is fine)."""
     if t.dim() != 2 or t.stride(1) != 1 or t.dtype != torch.float32:
@@ -740,7 +663,7 @@ def multi_head_attention(q, k, v, offset, cloud_of_row, nk_max, heads=4, partner
             raise L.RoitrError("multi_head_attention: ebar (T, heads, C) contiguous")
         a.E, a.eoff, a.qt, a.bp, a.ebar = L.ptr(E), L.ptr(eoff), L.ptr(qt), L.ptr(bp), L.ptr(ebar)
         a.e_bf16 = int(E.dtype == torch.bfloat16)
-    L.check(L.lib().roitr_mha(ctypes.byref(a), L.stream_ptr()), "mha")
+    L.check(_lib().roitr_mha(ctypes.byref(a), L.stream_ptr()), "mha")
     return out, ebar
 
 
@@ -756,11 +679,11 @@ def geo_indices(points, sizes, sigma_d=0.2, sigma_a=15.0, angle_k=3):
     offset = ends.to(torch.int32).to(dev)
     cloud_of_row = torch.repeat_interleave(torch.arange(len(sizes), dtype=torch.int32), torch.tensor(sizes)).to(dev)
     etot = int(blocks.sum())
-    pts = points.contiguous().float()
+    pts = _c(points)
     d_idx = torch.empty((etot,), dtype=torch.float32, device=dev)
     a_idx = torch.empty((etot, angle_k), dtype=torch.float32, device=dev)
-    L.check(L.lib().roitr_geo_indices(int(ends[-1]), L.ptr(pts), L.ptr(offset), L.ptr(cloud_of_row), L.ptr(eoff), L.c_float(sigma_d),
-                                      L.c_float(sigma_a), int(angle_k), max(sizes), L.ptr(d_idx), L.ptr(a_idx), L.stream_ptr()),
+    L.check(_lib().roitr_geo_indices(int(ends[-1]), L.ptr(pts), L.ptr(offset), L.ptr(cloud_of_row), L.ptr(eoff), float(sigma_d),
+                                      float(sigma_a), int(angle_k), max(sizes), L.ptr(d_idx), L.ptr(a_idx), L.stream_ptr()),
             "geo_indices")
     return d_idx, a_idx
 
@@ -768,24 +691,17 @@ def geo_indices(points, sizes, sigma_d=0.2, sigma_a=15.0, angle_k=3):
 # ------------------------------------------------------------------------------------------------
 # Ground-truth side outputs (csrc/gt.hip), batched over pairs; clouds laid out [src_0..src_{B-1}, tgt_0..tgt_{B-1}].
 # ------------------------------------------------------------------------------------------------
-class _NodeCorr(ctypes.Structure):
-    _fields_ = [("pairs", ctypes.c_int), ("limit", ctypes.c_int), ("max_nodes", ctypes.c_int), ("pos_radius", ctypes.c_float),
-                ("nodes", _P), ("node_offset", _P), ("node_masks", _P), ("points", _P), ("pt_offset", _P), ("knn_idx", _P),
-                ("knn_mask", _P), ("rot", _P), ("trans", _P), ("overlap", _P), ("mat_stride", ctypes.c_long), ("out_idx", _P),
-                ("out_overlap", _P), ("out_count", _P), ("n_nodes", ctypes.c_int), ("nodes_t", _P), ("radius", _P)]
-
-
 def build_padded_clouds(points, pt_offset, rot, trans):
     """roitr_build_padded_clouds (lib/utils.py:505-506 + RIGA_v2.py:86-87): points (n,3) of the 2*pairs clouds, pt_offset (2*pairs,)
     cumulative, rot (pairs,3,3), trans (pairs,3) -> (padded (n + 2*pairs, 3), offsets (3*pairs,) i32)."""
     dev = points.device
     pairs = pt_offset.shape[0] // 2
     n = points.shape[0]
-    pts, off = points.contiguous().float(), _i32c(pt_offset)
-    r, t = rot.contiguous().float(), trans.contiguous().float()
+    pts, off = _c(points), _i32c(pt_offset)
+    r, t = _c(rot), _c(trans)
     out = torch.empty((n + 2 * pairs, 3), dtype=torch.float32, device=dev)
     out_off = torch.empty(3 * pairs, dtype=torch.int32, device=dev)
-    L.check(L.lib().roitr_build_padded_clouds(pairs, n, L.ptr(pts), L.ptr(off), L.ptr(r), L.ptr(t), L.ptr(out), L.ptr(out_off),
+    L.check(_lib().roitr_build_padded_clouds(pairs, n, L.ptr(pts), L.ptr(off), L.ptr(r), L.ptr(t), L.ptr(out), L.ptr(out_off),
                                               L.stream_ptr()), "build_padded_clouds")
     return out, out_off
 
@@ -797,10 +713,10 @@ def node_occlusion_score(cloud_of_node, pt_offset, knn_idx, knn_mask, node_masks
     n_nodes, limit = knn_idx.shape
     con, off = _i32c(cloud_of_node), _i32c(pt_offset)
     ki, km, nm = _i32c(knn_idx), _i32c(knn_mask), _i32c(node_masks)
-    d2 = d2_padded.contiguous().float()
+    d2 = _c(d2_padded)
     out = torch.empty(n_nodes, dtype=torch.float32, device=dev)
-    L.check(L.lib().roitr_node_occlusion_score(n_nodes, limit, L.ptr(con), L.ptr(off), L.ptr(ki), L.ptr(km), L.ptr(nm), L.ptr(d2),
-                                               L.c_float(overlap_thres), L.ptr(out), L.stream_ptr()), "node_occlusion_score")
+    L.check(_lib().roitr_node_occlusion_score(n_nodes, limit, L.ptr(con), L.ptr(off), L.ptr(ki), L.ptr(km), L.ptr(nm), L.ptr(d2),
+                                               float(overlap_thres), L.ptr(out), L.stream_ptr()), "node_occlusion_score")
     return out
 
 
@@ -818,17 +734,18 @@ def node_correspondences(nodes, node_offset, node_masks, points, pt_offset, knn_
         max_nodes = max(b - a for a, b in zip(ends[:-1], ends[1:]))
     max_nodes = int(max_nodes)
     mat_stride = max_nodes * max_nodes if mat_stride is None else int(mat_stride)
-    nd, pts = nodes.contiguous().float(), points.contiguous().float()
+    nd, pts = _c(nodes), _c(points)
     nm, ki, km = _i32c(node_masks), _i32c(knn_idx), _i32c(knn_mask)
-    r, t = rot.contiguous().float(), trans.contiguous().float()
+    r, t = _c(rot), _c(trans)
     overlap = torch.empty((pairs, mat_stride), dtype=torch.float32, device=dev)
     out_idx = torch.zeros((pairs, mat_stride, 2), dtype=torch.int32, device=dev)
     out_ov = torch.zeros((pairs, mat_stride), dtype=torch.float32, device=dev)
     out_cnt = torch.zeros(pairs, dtype=torch.int32, device=dev)
     nodes_t = torch.empty((n_nodes, 3), dtype=torch.float32, device=dev)
     radius = torch.empty(n_nodes, dtype=torch.float32, device=dev)
-    a = _NodeCorr(pairs, limit, max_nodes, float(pos_radius), L.ptr(nd), L.ptr(noff), L.ptr(nm), L.ptr(pts), L.ptr(poff), L.ptr(ki),
-                  L.ptr(km), L.ptr(r), L.ptr(t), L.ptr(overlap), mat_stride, L.ptr(out_idx), L.ptr(out_ov), L.ptr(out_cnt), n_nodes,
-                  L.ptr(nodes_t), L.ptr(radius))
-    L.check(L.lib().roitr_node_correspondences(ctypes.byref(a), L.stream_ptr()), "node_correspondences")
+    a = _NodeCorr(pairs=pairs, limit=limit, max_nodes=max_nodes, pos_radius=float(pos_radius), nodes=L.ptr(nd), node_offset=L.ptr(noff),
+                  node_masks=L.ptr(nm), points=L.ptr(pts), pt_offset=L.ptr(poff), knn_idx=L.ptr(ki), knn_mask=L.ptr(km), rot=L.ptr(r),
+                  trans=L.ptr(t), overlap=L.ptr(overlap), mat_stride=mat_stride, out_idx=L.ptr(out_idx), out_overlap=L.ptr(out_ov),
+                  out_count=L.ptr(out_cnt), n_nodes=n_nodes, nodes_t=L.ptr(nodes_t), radius=L.ptr(radius))
+    L.check(_lib().roitr_node_correspondences(ctypes.byref(a), L.stream_ptr()), "node_correspondences")
     return out_idx, out_ov, out_cnt

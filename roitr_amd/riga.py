@@ -125,26 +125,8 @@ def _attach(root, key, tensor, kind):
         mod.register_buffer(parts[-1], tensor)
 
 
-class _CConfig(ctypes.Structure):
-    _fields_ = [("factor", ctypes.c_int), ("num_corr", ctypes.c_int), ("point_limit", ctypes.c_int),
-                ("fine_topk", ctypes.c_int), ("fine_mutual", ctypes.c_int), ("fine_use_global_score", ctypes.c_int),
-                ("fine_conf", ctypes.c_float), ("n_geo_layers", ctypes.c_int), ("geo_is_cross", ctypes.c_int * 16),
-                ("matching_radius", ctypes.c_float), ("adaptive_coarse", ctypes.c_int), ("occlusion_radius", ctypes.c_float),
-                ("operand_dtype", ctypes.c_int)]
-
-
-_P = ctypes.c_void_p
-
-
-class _CForwardIO(ctypes.Structure):
-    _fields_ = [("pairs", ctypes.c_int), ("n_points", ctypes.POINTER(ctypes.c_int)),
-                ("points_geom", _P), ("normals", _P), ("feats", _P), ("points_out", _P), ("rot", _P), ("trans", _P),
-                ("node_xyz", _P), ("node_feats", _P), ("point_feats", _P), ("node_masks", _P), ("node_knn_idx", _P),
-                ("node_knn_mask", _P), ("tgt_corr", _P), ("src_corr", _P), ("corr_scores", _P), ("n_corr", _P),
-                ("tgt_knn_pts", _P), ("src_knn_pts", _P), ("tgt_knn_masks", _P), ("src_knn_masks", _P),
-                ("matching_scores", _P), ("out_tgt_pts", _P), ("out_src_pts", _P), ("out_scores", _P), ("out_patch", _P),
-                ("fine_offsets", _P), ("n_out", _P), ("gt_node_occ", _P), ("gt_corr_idx", _P), ("gt_corr_overlaps", _P),
-                ("gt_corr_count", _P), ("inputs_ready", _P), ("patch_offsets", _P), ("pair_starts", _P), ("patch_slots", ctypes.c_int)]
+_CConfig = L.struct("RoitrEngineConfig")
+_CForwardIO = L.struct("RoitrForwardIO")
 
 
 def _cfg_get(config, key, default=None):
@@ -483,7 +465,7 @@ class RIGA_v2(nn.Module):
         io = _CForwardIO()
         io.pairs = B
         arr = (ctypes.c_int * (2 * B))(*n_all)
-        io.n_points = ctypes.cast(arr, ctypes.POINTER(ctypes.c_int))
+        io.n_points = ctypes.cast(arr, ctypes.c_void_p)
         io.points_geom, io.normals, io.feats, io.points_out = L.ptr(geom), L.ptr(nrm), L.ptr(feats), L.ptr(pout)
         io.rot, io.trans = L.ptr(rot), L.ptr(trans)
         io.inputs_ready = ready.cuda_event if ready is not None else None
@@ -527,7 +509,7 @@ class RIGA_v2(nn.Module):
                         meta_host=torch.empty((n_meta,), dtype=i32, pin_memory=True), arr=(ctypes.c_int * (2 * B))(*n_all))
             io = _CForwardIO()
             io.pairs = B
-            io.n_points = ctypes.cast(slot["arr"], ctypes.POINTER(ctypes.c_int))
+            io.n_points = ctypes.cast(slot["arr"], ctypes.c_void_p)
             io.points_geom, io.normals, io.feats, io.points_out = L.ptr(slot["geom"]), L.ptr(slot["nrm"]), L.ptr(slot["feats"]), L.ptr(slot["pout"])
             io.rot, io.trans = L.ptr(slot["rot"]), L.ptr(slot["trans"])
             io.patch_slots = slots if self.factor != 1 else 0

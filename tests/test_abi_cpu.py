@@ -1,5 +1,6 @@
-"""CPU: the C-ABI library loads and exports every symbol the headers declare (no compute calls); the signatures roitr_amd/_lib.py
-reads from include/*.h for the evaluation and preparation entry points; the host-only *_workspace_bytes() values."""
+"""CPU: the C-ABI library loads and exports every symbol the headers declare (no compute calls); the struct classes roitr_amd/_lib.py
+makes from include/*.h against the C compiler's layout of the same headers; the signatures it reads from them for the evaluation and
+preparation entry points and for everything roitr_amd/ops.py calls; the host-only *_workspace_bytes() values."""
 import ctypes
 import os
 import re
@@ -61,38 +62,91 @@ def test_product_never_imports_the_oracle():
                 assert "liboracle" not in text and "pointops_cpu" not in text and "roitr_ref" not in text, f
 
 
-def _header_struct(name):
-    """[(field, ctypes type)] of `typedef struct <name> { ... }` in include/roitr_engine.h (scalars int / long / float / size_t and
-    pointers only)."""
-    import re
-    text = open(os.path.join(ROOT, "include", "roitr_engine.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), text, re.S).group(1)
-    scalars = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        m = re.match(r"(?:const\s+)?(?:unsigned\s+)?([A-Za-z_][A-Za-z0-9_]*)\s*(.*)$", decl, re.S)
-        base, rest = m.group(1), m.group(2)
-        for item in rest.split(","):
-            item = item.strip()
-            if item.startswith("*"):
-                fields.append((item.lstrip("* ").strip(), ctypes.c_void_p))
-            else:
-                fields.append((item, scalars[base]))
-    return fields
+MIRRORS = {"ops": dict(_Gemm="RoitrGemm", _LocalAttn="RoitrLocalAttn", _LocalAttnFold="RoitrLocalAttnFold", _LocalBlock="RoitrLocalBlock",
+                      _LocalTd="RoitrLocalTd", _LocalFirst="RoitrLocalFirst", _Mha="RoitrMha", _Coarse="RoitrCoarse", _OT="RoitrOT",
+                      _Fine="RoitrFine", _NodeCorr="RoitrNodeCorr"),
+           "riga": dict(_CConfig="RoitrEngineConfig", _CForwardIO="RoitrForwardIO")}
 
 
-def test_ctypes_mirrors_match_the_header():
-    """The ctypes structures of roitr_amd/ops.py, field by field (name, type, order, hence offsets) against include/roitr_engine.h."""
+def test_struct_layouts_match_the_compiler(tmp_path):
+    """sizeof and every offsetof of all 14 structs of include/*.h, as the C compiler lays them out from the headers themselves, against
+    the ctypes classes roitr_amd/_lib.py makes from its own reading of the headers (the classes ops.py, riga.py and the tests use)."""
+    import importlib
+    import subprocess
+    from roitr_amd import _lib as L
+    from roitr_amd.build import HIPCC
+    structs = L.header_structs()
+    assert len(structs) == 14 and sum(len(f) for f in structs.values()) == 321   # ABI 4: a field the reader drops can hide in padding
+    for module, names in MIRRORS.items():
+        for attr, name in names.items():
+            assert getattr(importlib.import_module("roitr_amd." + module), attr) is L.struct(name), (module, attr)
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "roitr_pointops.h"', '#include "roitr_engine.h"', 'int main(void) {']
+    for name, fields in structs.items():
+        lines.append(f'printf("{name} %zu\\n", sizeof({name}));')
+        lines += [f'printf("{name}.{f} %zu\\n", offsetof({name}, {f}));' for f, _ in fields]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines + ["return 0; }", ""]))
+    subprocess.run([HIPCC, "-x", "c", str(src), "-I", os.path.join(ROOT, "include"), "-o", str(exe)], check=True)   # no compiler: an error
+    want = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    got = {}
+    for name, fields in structs.items():
+        got[name] = str(ctypes.sizeof(L.struct(name)))
+        got.update({f"{name}.{f}": str(getattr(L.struct(name), f).offset) for f, _ in fields})
+    assert len(want) == 14 + 321 and got == want, sorted(set(got.items()) ^ set(want.items()))
+
+
+def test_struct_reader_against_hand_written_fields():
+    from roitr_amd import _lib as L
+    structs = L.header_structs()
+    assert structs["RoitrOT"] == [("pairs", I), ("num_corr", I), ("limit", I), ("num_iter", I), ("n_corr", P), ("scores", P),
+                                  ("row_masks", P), ("col_masks", P), ("alpha", P), ("out", P), ("pair_off", P), ("slots", I)]
+    cfg = structs["RoitrEngineConfig"]
+    assert [(n, t) for n, t in cfg if n != "geo_is_cross"] == [
+        ("factor", I), ("num_corr", I), ("point_limit", I), ("fine_topk", I), ("fine_mutual", I), ("fine_use_global_score", I),
+        ("fine_conf", F), ("n_geo_layers", I), ("matching_radius", F), ("adaptive_coarse", I), ("occlusion_radius", F),
+        ("operand_dtype", I)]
+    name, arr = cfg[8]
+    assert name == "geo_is_cross" and arr._type_ is I and arr._length_ == 16 and len(cfg) == 13
+    # the other forms a field takes: size_t, long, double, `unsigned char*`; a type the table does not know is an error, not a gap
+    assert L._fields("size_t n; long a, b; double d; unsigned char* flags; const long* eoff") == [
+        ("n", SZ), ("a", ctypes.c_long), ("b", ctypes.c_long), ("d", D), ("flags", P), ("eoff", P)]
+    with pytest.raises(KeyError):
+        L._fields("int a; short b")
+    # every struct a prototype takes has been read
+    text = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("roitr_pointops.h", "roitr_engine.h"))
+    taken = set(re.findall(r"const\s+(Roitr\w+)\s*\*", text))
+    assert len(taken) >= 13 and taken <= set(structs), taken - set(structs)
+
+
+def test_ops_entry_points_are_bound_from_the_headers():
+    """Every entry point roitr_amd/ops.py calls has its restype / argtypes from the header: no call site converts by hand."""
     from roitr_amd import ops
-    for mirror, name in ((ops._NodeCorr, "RoitrNodeCorr"), (ops._OT, "RoitrOT"), (ops._Fine, "RoitrFine"), (ops._Coarse, "RoitrCoarse"),
-                         (ops._LocalAttn, "RoitrLocalAttn")):
-        want = _header_struct(name)
-        got = [(f[0], f[1]) for f in mirror._fields_]
-        assert got == want, (name, [(a, b) for a, b in zip(got, want) if a != b], len(got), len(want))
+    source = open(os.path.join(ROOT, "roitr_amd", "ops.py")).read()
+    called = set(re.findall(r"\.(roitr_\w+)\(", source))
+    assert len(called) >= 40 and "roitr_gemm" in called and "roitr_add_layernorm" in called
+    lib, counts = ops._lib(), header_parameter_counts()
+    headers = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("roitr_pointops.h", "roitr_engine.h"))
+    sized = set(re.findall(r"^size_t\s+(\w+)\s*\(", headers, re.M))
+    assert {"roitr_coarse_scratch_floats", "roitr_geo_table_floats"} <= sized & called
+    assert called - set(counts) == {"roitr_local_block_dbg"}   # the tuning hook no header declares: (struct pointer, int, stream)
+    for name in called & set(counts):
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == counts[name], name
+        assert fn.restype is (SZ if name in sized else I), name
+    for word in ("ctypes.c_long(", "c_float(", ".restype =", "ctypes.Structure"):
+        assert word not in source, word
+
+
+def test_structs_and_ops_import_without_the_library(monkeypatch, tmp_path):
+    import importlib
+    from roitr_amd import _lib as L, ops
+    monkeypatch.setattr(L, "LIB_PATH", str(tmp_path / "missing.so"))
+    monkeypatch.setattr(L, "_lib", None)
+    assert ctypes.sizeof(L.struct.__wrapped__("RoitrGemm")) == ctypes.sizeof(L.struct("RoitrGemm")) > 0
+    ops = importlib.reload(ops)
+    assert ops._Gemm is L.struct("RoitrGemm")
+    with pytest.raises(L.RoitrError):     # nothing above asked for the library: asking does
+        ops._lib()
 
 
 I, F, D, P, SZ = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_void_p, ctypes.c_size_t

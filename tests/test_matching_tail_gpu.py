@@ -518,14 +518,6 @@ def test_fine_matching_compacted_layout(n_corr, slots):
 
 
 # ------------------------------------------------------------------------------------------------ patch gather
-class _Patch(ctypes.Structure):
-    _P = ctypes.c_void_p
-    _fields_ = [("pairs", ctypes.c_int), ("num_corr", ctypes.c_int), ("limit", ctypes.c_int), ("n_corr", _P), ("tgt_corr", _P),
-                ("src_corr", _P), ("node_offset", _P), ("pt_offset", _P), ("knn_idx", _P), ("knn_mask", _P), ("points", _P),
-                ("tgt_rows", _P), ("src_rows", _P), ("tgt_masks", _P), ("src_masks", _P), ("tgt_pts", _P), ("src_pts", _P),
-                ("pair_off", _P), ("slots", ctypes.c_int)]
-
-
 @pytest.mark.parametrize("compacted", [False, True])
 def test_patch_gather_layouts(compacted):
     """Two pairs of different sizes: per slot and knn position the global row (-1 for the pad index n_c), the mask and the point,
@@ -564,7 +556,7 @@ def test_patch_gather_layouts(compacted):
     outs = [torch.full((tot,), -7, dtype=torch.int32, device="cuda") for _ in range(4)]
     opts = [torch.full((tot, 3), float("nan"), device="cuda") for _ in range(2)]
     keep = [i32(n_corr), i32(tc), i32(sc), i32(nd_end), i32(pt_end), i32(knn), i32(kmask), dev(pts)]
-    a = _Patch(pairs, num_corr, lim, *[L.ptr(t) for t in keep], *[L.ptr(t) for t in outs], *[L.ptr(t) for t in opts], L.ptr(po),
+    a = L.struct("RoitrPatch")(pairs, num_corr, lim, *[L.ptr(t) for t in keep], *[L.ptr(t) for t in outs], *[L.ptr(t) for t in opts], L.ptr(po),
                slots if compacted else 0)
     L.check(L.lib().roitr_patch_gather(ctypes.byref(a), L.stream_ptr()), "patch_gather")
     torch.cuda.synchronize()
