@@ -685,6 +685,71 @@ int roitr_compat_batch(int pairs, const int* starts, int total_rows, const float
                        float* hyp_transforms, int* hyp_counts, roitr_stream_t stream);
 
 
+/* ------------------------------------------------------------------ fast global registration
+ * A pose from ONE robust objective over all correspondences of a pair, no hypotheses: the Geman-McClure cost of Fast Global
+ * Registration (Zhou, Park and Koltun, ECCV 2016; Open3D's FastGlobalRegistration), minimised by Gauss-Newton steps on a 6-vector
+ * while the scale mu is lowered (graduated non-convexity).  PARITY WITH OPEN3D IS NOT CLAIMED: the operator is defined here.  Open3D
+ * normalises both clouds by a global scale, draws its tuples from rand() and compares `par` with the unsquared distance; this
+ * operator works in metres, draws from the project's counter-based stream and compares squared with squared.
+ * Inputs as roitr_compat_batch: pair b owns rows [starts[b], starts[b+1]) (clamped into [0, total_rows]) of src_pts / tgt_pts (fp32
+ * (N,3)) and scores (fp32 (N); NULL = all 1); pair_keys (uint32 per pair) and seed feed the triple stream and are read only when
+ * tuples > 0 (pair_keys may be NULL otherwise).  Inputs must be finite; they are not checked.
+ * Parameters: max_dist (the final scale in metres, finite, > 0), division_factor (double, > 1, finite; Open3D: 1.4), iterations
+ *   (1 ... 1024 Gauss-Newton steps), mu_every (>= 1 iterations between two decreases of mu; Open3D: 4), tuples (0 ... 2^28 triples
+ *   DRAWN per pair, 0: no tuple test; the bound is the stream's iteration field), tuple_scale (float in (0, 1); Open3D: 0.95), radius
+ *   (finite, > 0; only for the reported inlier count).
+ * Per pair of n rows, p_c / q_c the source / target point of local row c:
+ * 1. Multiplicity.  m_c = 1 for every row when tuples == 0 or n < 3.  Otherwise, for it in [0, tuples): the triple is what
+ *   roitr_ransac_samples reports for (n, pair_keys[b], seed, it); an invalid iteration is skipped.  It is accepted when each of its
+ *   three edges (a, b), with ls = rg_len(p_a, p_b), lt = rg_len(q_a, q_b) (float64 on the fp32 inputs, registration_math.h) and
+ *   s = (double)tuple_scale, has ls * s < lt && lt * s < ls, strictly.  An accepted triple adds 1 to m of each of its rows (Open3D
+ *   appends an accepted tuple's correspondences with repeats).  No triple accepted: every m_c = 1 and status NO_TUPLES.
+ * 2. Weights.  w_c = (double)score_c * m_c.  Rows with w_c > 0 are USED.  Fewer than 3 used rows: the identity, status TOO_FEW, no
+ *   loop (mu and objective 0).  No rows at all: the identity and NO_ROWS alone.
+ * 3. Centring and start scale, float64.  cs, ct = the plain means of the used rows' source and target points; p~ = p - cs,
+ *   q~ = q - ct; D2 = the largest of |p~|^2, |q~|^2 over the used rows; md2 = (double)max_dist^2; mu_0 = max(D2, md2).  The state
+ *   (R, t), float64, starts at (I, 0) in the centred frame: at the translation that aligns the centroids.
+ * 4. Iteration k = 0 ... iterations - 1 over the used rows: y = R p~ + t, r = y - q~, e = r . r, l = mu / (e + mu), omega = w l^2,
+ *   J = [-[y]x | I] (3 x 6, rotation part first); A = sum omega J^T J, g = sum omega J^T r, objective_k = sum w mu e / (e + mu),
+ *   sum_omega_k = sum omega; x = ldl_solve6(A, -g) (csrc/gauss_newton6.h).  A non-positive or non-finite pivot sets SINGULAR, keeps the
+ *   state and ends the loop.  Otherwise (R, t) <- dT(x) (R, t) in float64, dT = [Rz(x2) Ry(x1) Rx(x0) | x3 x4 x5] (compose_step_d,
+ *   Open3D's TransformVector6dToMatrix4d), and then, if (k + 1) % mu_every == 0 and mu > md2: mu = max(mu / division_factor, md2).
+ *   Every product and sum is rounded on its own (no contraction).
+ * 5. Outputs per pair: transforms (B,4,4) fp32 = [R | ct + t - R cs], rounded once at the end; inliers: rows of the WHOLE pair with
+ *   rg_dist2 < radius^2 (fp32, strictly) under that fp32 transform, as roitr_lgr_batch verifies; n_used; tuples_accepted; steps (the
+ *   updates applied); mu and objective (double: the last scale, the objective of the last evaluated iteration); status (bits below).
+ *   Optional (NULL allowed): multiplicity (total_rows) int32, m_c as it was used (1 under the fallback; rows outside every pair are
+ *   not written); trace (pairs x iterations x 16) double, row k = the 12 values of the centred state [R | t] (rows of 4) BEFORE step
+ *   k, mu_k, objective_k, sum_omega_k, 1.0; rows that were not run are zero.
+ * 6. Determinism: as roitr_compat_batch.  Every float64 sum is a strided per-lane sum over the pair's local row index (256 lanes)
+ *   followed by a fixed butterfly; the maximum D2 does not depend on an order; the only atomics add integers.  A pair's results are
+ *   bitwise independent of its batch, its slot, its row offset and of repeats, and depend on pair_keys[b] and seed only through the
+ *   triples.
+ * Two kernel launches and two memsets for a whole batch, whatever `iterations` is; no host read.
+ * The workspace (device, caller-owned) holds at least roitr_fgr_workspace_bytes() bytes (host-only, monotone; 0 for arguments the
+ *   batch call refuses).
+ * Refusals (ROITR_ERR_ARG, nothing is launched or written): null pointers, pair_keys NULL with tuples > 0, parameters out of the
+ *   ranges above, total_rows < 0, more than 65535 pairs, a short workspace.
+ * roitr_fgr_batch_staged is the same call with the number of rows a pair may have to be staged in LDS (0 ... 1536; roitr_fgr_batch
+ *   passes 1536): longer pairs are swept from global memory in the same order, so the results are bitwise the same for every value.
+ *   It exists so that a test can hold the two paths against each other on the same rows. */
+#define ROITR_FGR_NO_ROWS 1
+#define ROITR_FGR_TOO_FEW 2
+#define ROITR_FGR_SINGULAR 4
+#define ROITR_FGR_NO_TUPLES 8
+size_t roitr_fgr_workspace_bytes(int pairs, int total_rows);
+int roitr_fgr_batch(int pairs, const int* starts, int total_rows, const float* src_pts, const float* tgt_pts, const float* scores,
+                    const unsigned int* pair_keys, unsigned long long seed, float max_dist, double division_factor, int iterations,
+                    int mu_every, int tuples, float tuple_scale, float radius, void* workspace, size_t workspace_bytes,
+                    float* transforms, int* inliers, int* n_used, int* tuples_accepted, int* steps, double* mu, double* objective,
+                    int* status, int* multiplicity, double* trace, roitr_stream_t stream);
+int roitr_fgr_batch_staged(int pairs, const int* starts, int total_rows, const float* src_pts, const float* tgt_pts, const float* scores,
+                           const unsigned int* pair_keys, unsigned long long seed, float max_dist, double division_factor,
+                           int iterations, int mu_every, int tuples, float tuple_scale, float radius, int lds_rows, void* workspace,
+                           size_t workspace_bytes, float* transforms, int* inliers, int* n_used, int* tuples_accepted, int* steps,
+                           double* mu, double* objective, int* status, int* multiplicity, double* trace, roitr_stream_t stream);
+
+
 /* ------------------------------------------------------------------ 4DMatch non-rigid evaluation
  * registration/evaluate_fdmatch.py:50-115: NFMR (non-rigid feature matching recall) of every pair of a batch.  Pair b owns points
  * [src_offsets[b], src_offsets[b+1]) of src_raw (the undeformed source) and src_deformed (what the model was fed), both (total_src,

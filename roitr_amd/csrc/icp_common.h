@@ -20,6 +20,7 @@
 #define ICP_SKIP (ROITR_ICP_NONFINITE | ROITR_ICP_EMPTY)
 
 #include "ball_walk.h"
+#include "gauss_newton6.h"
 
 namespace {
 
@@ -227,64 +228,8 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_match_kernel(int b, int n, co
     out_d2[i] = best;
 }
 
-// x of (L D L^T) x = b for the symmetric 6x6 A (upper triangle, row-major, 21 values); false on a non-positive or non-finite pivot
-__device__ __forceinline__ bool ldl_solve6(const double* A21, const double (&rhs)[6], double (&x)[6])
-{
-    double A[6][6], L[6][6], d[6];
-    int at = 0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-        for (int j = i; j < 6; ++j) { A[i][j] = A21[at]; A[j][i] = A21[at]; ++at; }
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double v = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) v -= L[j][k] * L[j][k] * d[k];
-        ok = ok && v > 0.0 && isfinite(v);
-        d[j] = v;
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double w = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) w -= L[i][k] * L[j][k] * d[k];
-            L[i][j] = w / v;
-        }
-    }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = rhs[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
-        y[i] = v;
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = y[i] / d[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) v -= L[k][i] * x[k];
-        x[i] = v;
-    }
-    return ok;
-}
-
-// T_next = fp32(dT T) with dT = [Rz(g) Ry(b) Rx(a) | t] of x = (a, b, g, tx, ty, tz): Open3D's TransformVector6dToMatrix4d
-__device__ __forceinline__ void compose_step(const double (&x)[6], const float (&T)[12], float (&Tn)[12])
-{
-    const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
-    const double R[9] = {cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa,
-                         sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa,
-                         -sb, cb * sa, cb * ca};
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const double v = R[3 * r] * (double)T[c] + R[3 * r + 1] * (double)T[4 + c] + R[3 * r + 2] * (double)T[8 + c];
-            Tn[4 * r + c] = (float)(c == 3 ? v + x[3 + r] : v);
-        }
-}
+// ldl_solve6 (the 6x6 L D L^T solve) and compose_step (the composition of a step with the state) live in gauss_newton6.h, which
+// fgr.hip includes too.
 
 // The tree of pairgt_reduce_kernel over the NV per-thread sums a[NV] of a workgroup of 256, with red the kernel's __shared__ double
 // [2][NV][64]: t += t + 128, t += t + 64 (LDS), then t += t + 32 .. t + 1 inside wave 0, every lane of which ends up holding the

@@ -91,13 +91,16 @@ def _matched(m, rows):
 
 
 def _estimate(m, matched, estimator, kw, pair_keys=None):
-    """Poses from the matches: compat_batch with 1 / (1 + squared distance) as confidences, or ransac_batch over all of them.  A
+    """Poses from the matches: compat_batch or fgr_batch with 1 / (1 + squared distance) as confidences, or ransac_batch over all of them.  A
     smaller distance is a better match, but the negated distance cannot serve: compat's refits weigh every inlier row by its
     confidence (include/roitr_engine.h), and negative weights mirror the cross-covariance -- an exact copy came back rotated by 180
     degrees.  1 / (1 + d) orders the rows like -d and lies in (0, 1]."""
-    if estimator not in ("compat", "ransac"):
-        raise ValueError("the FPFH baseline runs with estimator 'compat' or 'ransac' (lgr needs the matcher's patches)")
+    if estimator not in ("compat", "ransac", "fgr"):
+        raise ValueError("the FPFH baseline runs with estimator 'compat', 'ransac' or 'fgr' (lgr needs the matcher's patches)")
     si, s, t = matched
+    if estimator == "fgr":   # the same confidences as compat: the objective weighs every row by its score
+        from .fgr import fgr_batch
+        return fgr_batch(m["corr_starts"], s, t, 1.0 / (1.0 + m["row_val"][si]), **dict(dict(pair_keys=pair_keys), **kw))
     if estimator == "compat":
         from .compat import compat_batch
         return compat_batch(m["corr_starts"], s, t, 1.0 / (1.0 + m["row_val"][si]), **kw)
@@ -108,7 +111,7 @@ def _estimate(m, matched, estimator, kw, pair_keys=None):
 @torch.no_grad()
 def fpfh_pose_estimation(src_pcd, tgt_pcd, src_normals, tgt_normals, *, radius=0.125, max_nn=100, mutual=True, estimator="compat", **kw):
     """One pair, from points and normals to a pose without a learned descriptor: FPFH, matches under the squared distance (mutual, or
-    every source point with its nearest target), then compat.compat_batch with 1 / (1 + distance) as confidences or
+    every source point with its nearest target), then compat.compat_batch or fgr.fgr_batch with 1 / (1 + distance) as confidences, or
     registration.ransac_batch over all matches.  kw: the estimator's keyword arguments (compat's own `radius` keeps its default: the
     name is taken by the FPFH radius here).  Returns the 4x4 float64 numpy transform."""
     src, tgt = A.upload(src_pcd).reshape(-1, 3), A.upload(tgt_pcd).reshape(-1, 3)
@@ -122,8 +125,8 @@ def fpfh_pose_estimation(src_pcd, tgt_pcd, src_normals, tgt_normals, *, radius=0
 def fpfh_handle(handle, radius=0.125, max_nn=100, mode="mutual", estimator=None, estimator_kw=None, pair_keys=None,
                 inlier_distance_threshold=None):
     """The baseline on the clouds and normals an engine call already holds (RIGA_v2.launch_batch() handle, after finish_batch): one
-    compute_fpfh over all 2B clouds, one match_batch.  Returns fpfh_match_batch's dict; with estimator ("compat" / "ransac",
-    estimator_kw its keyword arguments, pair_keys the keys of RANSAC's random stream) also reg, the estimator's result dict
+    compute_fpfh over all 2B clouds, one match_batch.  Returns fpfh_match_batch's dict; with estimator ("compat" / "ransac" / "fgr",
+    estimator_kw its keyword arguments, pair_keys the keys of RANSAC's random stream and of fgr's tuple test) also reg, the estimator's result dict
     (T (B,4,4), inliers, ...); with inlier_distance_threshold (needs ground-truth transforms in the pairs) also ir (B,) the share of
     the matches within it under the ground truth (nan: no matches) and n_matches (B,) int32."""
     from . import descmatch

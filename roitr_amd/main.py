@@ -29,7 +29,8 @@ def parser():
     ap.add_argument("--estimate-normals", action="store_true", help="recompute the normals on the GPU (open3d knn=33 + normal_redirect)")
     ap.add_argument("--register", action="store_true",
                     help="estimate every pair's pose on the GPU (--estimator: correspondence RANSAC, registration.py, local-to-global "
-                         "registration, lgr.py, or spatial-compatibility registration, compat.py) and save it as est_transform")
+                         "registration, lgr.py, spatial-compatibility registration, compat.py, or fast global registration, fgr.py) and save "
+                         "it as est_transform")
     ap.add_argument("--nonrigid", action="store_true",
                     help="synthetic 4DMatch-shaped pairs with a real deformation and metric points (synthetic.make_nonrigid_pair); "
                          "with --evaluate on a 4DMatch config the mean NFMR is reported (nonrigid.py)")
@@ -55,16 +56,20 @@ def parser():
                          "record at index 0; implies --recall")
     ap.add_argument("--ransac-iterations", type=int, default=50000)
     ap.add_argument("--ransac-points", type=int, default=1000, help="correspondences drawn per pair (probability ~ confidence)")
-    ap.add_argument("--estimator", choices=("ransac", "lgr", "compat"), default="ransac",
+    ap.add_argument("--estimator", choices=("ransac", "lgr", "compat", "fgr"), default="ransac",
                     help="pose estimator of --register: correspondence RANSAC, RANSAC-free local-to-global registration on the "
-                         "matcher's patches, or spatial-compatibility registration on the correspondences alone (both deterministic, "
-                         "no random stream)")
+                         "matcher's patches, spatial-compatibility registration on the correspondences alone (both deterministic, "
+                         "no random stream), or fast global registration: one robust objective, no hypotheses")
     ap.add_argument("--lgr-radius", type=float, default=0.1, help="acceptance radius of the lgr estimator (metres)")
     ap.add_argument("--lgr-steps", type=int, default=5, help="global reweighted solves of the lgr estimator")
     ap.add_argument("--compat-dist", type=float, default=0.1,
                     help="compat estimator: two correspondences are compatible when their point distances differ by less (metres)")
     ap.add_argument("--compat-seeds", type=int, default=64, help="compat estimator: hypotheses per pair (seeds by degree)")
     ap.add_argument("--compat-k", type=int, default=20, help="compat estimator: rows of a seed's consensus set")
+    ap.add_argument("--fgr-max-dist", type=float, default=0.1, help="fgr estimator: the final scale of the robust cost (metres)")
+    ap.add_argument("--fgr-iterations", type=int, default=128, help="fgr estimator: Gauss-Newton steps (1 .. 1024)")
+    ap.add_argument("--fgr-tuples", type=int, default=0,
+                    help="fgr estimator: triples drawn per pair for the tuple test (0: none), keyed on the global pair id")
     ap.add_argument("--refine", choices=("none", "point", "plane", "gicp"), default="none",
                     help="refine the estimated pose by ICP on the dense clouds (icp.py): point-to-point, or point-to-plane on the target "
                          "normals; gicp: generalized ICP, plane-to-plane on the normals of both clouds (gicp.py); implies --register")
@@ -74,7 +79,7 @@ def parser():
                     help="--refine gicp: the covariance eigenvalue along a point's normal, in [1e-6, 1] (1: isotropic points)")
     ap.add_argument("--fpfh-baseline", action="store_true",
                     help="with --evaluate and --register: also run the learning-free baseline on the same pairs (fpfh.py): FPFH "
-                         "descriptors, mutual matches under the squared distance, the pose from --estimator (ransac or compat)")
+                         "descriptors, mutual matches under the squared distance, the pose from --estimator (ransac, compat or fgr)")
     ap.add_argument("--fpfh-radius", type=float, default=0.125, help="FPFH neighbourhood radius (metres)")
     ap.add_argument("--fpfh-max-nn", type=int, default=100, help="FPFH neighbourhood size: the point and at most N - 1 neighbours (2 .. 100)")
     return ap
@@ -108,6 +113,7 @@ def main():
                     subsample_seed=args.subsample_seed, recall=args.recall, overlap_radius=args.overlap_radius, estimator=args.estimator,
                     lgr=dict(radius=args.lgr_radius, steps=args.lgr_steps), refine=None if args.refine == "none" else args.refine,
                     compat=dict(compat_dist=args.compat_dist, max_seeds=args.compat_seeds, k=args.compat_k),
+                    fgr=dict(max_dist=args.fgr_max_dist, iterations=args.fgr_iterations, tuples=args.fgr_tuples),
                     icp=dict(max_dist=args.icp_distance, iterations=args.icp_iterations, **(dict(epsilon=args.gicp_epsilon) if args.refine == "gicp" else {})),
                     fpfh_baseline=dict(radius=args.fpfh_radius, max_nn=args.fpfh_max_nn) if args.fpfh_baseline else None, gt_dir=args.write_gt)
     counts = tester.test()

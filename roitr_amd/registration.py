@@ -118,6 +118,20 @@ def ransac_pose_estimation_correspondences(src_pcd, tgt_pcd, correspondences, mu
     return r["T"][0].cpu().numpy().astype(np.float64)
 
 
+def _feature_matches(who, src_pcd, tgt_pcd, src_feat, tgt_feat, mutual):
+    """What the *_pose_estimation entries put in front of their estimator: the descriptor matches under the dot product (mutual, or every
+    source point with its best target) as (starts of the one pair, matched source points, matched target points, match scores)."""
+    from . import descmatch
+    src, tgt = A.upload(src_pcd).reshape(-1, 3), A.upload(tgt_pcd).reshape(-1, 3)
+    sf, tf = A.upload(src_feat), A.upload(tgt_feat)
+    if sf.shape[0] != src.shape[0] or tf.shape[0] != tgt.shape[0]:
+        raise L.RoitrError(f"{who}: one descriptor per point is needed")
+    m = descmatch.match_batch(A.cumulative([sf.shape[0]], "cuda"), sf, A.cumulative([tf.shape[0]], "cuda"), tf, metric="dot",
+                              mode="mutual" if mutual else "row")
+    corr = m["corr"].long()
+    return m["corr_starts"], src[corr[:, 0]], tgt[corr[:, 1]], m["row_val"][corr[:, 0]]
+
+
 @torch.no_grad()
 def ransac_pose_estimation(src_pcd, tgt_pcd, src_feat, tgt_feat, mutual=False, distance_threshold=0.05, ransac_n=3, *,
                            iterations=50000, seed=0):
@@ -131,16 +145,9 @@ def ransac_pose_estimation(src_pcd, tgt_pcd, src_feat, tgt_feat, mutual=False, d
     edge-length (0.9) and the distance checker; a fixed number of iterations; mutual=False matches under the dot product, as the
     mutual branch does, where Open3D takes the L2 nearest neighbour in feature space -- the same list for equal-norm descriptors
     (the model's are unit-normalised), not otherwise (descmatch.match_batch(metric="sqdist", mode="row") gives the L2 list)."""
-    from . import descmatch
-    src, tgt = A.upload(src_pcd).reshape(-1, 3), A.upload(tgt_pcd).reshape(-1, 3)
-    sf, tf = A.upload(src_feat), A.upload(tgt_feat)
-    if sf.shape[0] != src.shape[0] or tf.shape[0] != tgt.shape[0]:
-        raise L.RoitrError("ransac_pose_estimation: one descriptor per point is needed")
-    m = descmatch.match_batch(A.cumulative([sf.shape[0]], "cuda"), sf, A.cumulative([tf.shape[0]], "cuda"), tf, metric="dot",
-                              mode="mutual" if mutual else "row")
-    corr = m["corr"].long()
-    r = ransac_batch(m["corr_starts"], src[corr[:, 0]], tgt[corr[:, 1]], None, sample="all", distance_threshold=distance_threshold,
-                     ransac_n=ransac_n, iterations=iterations, seed=seed)
+    starts, s, t, _ = _feature_matches("ransac_pose_estimation", src_pcd, tgt_pcd, src_feat, tgt_feat, mutual)
+    r = ransac_batch(starts, s, t, None, sample="all", distance_threshold=distance_threshold, ransac_n=ransac_n, iterations=iterations,
+                     seed=seed)
     return r["T"][0].cpu().numpy().astype(np.float64)
 
 
@@ -150,16 +157,19 @@ def compat_pose_estimation(src_pcd, tgt_pcd, src_feat, tgt_feat, mutual=False, *
     mutual or every source point with its best target), then compat.compat_batch on the matched point pairs with the match scores as
     confidences (they order the rows when there are more than max_rows; the estimator itself is deterministic and takes no seed).
     kw: compat_batch's keyword arguments.  Returns the 4x4 float64 numpy transformation."""
-    from . import descmatch
     from .compat import compat_batch
-    src, tgt = A.upload(src_pcd).reshape(-1, 3), A.upload(tgt_pcd).reshape(-1, 3)
-    sf, tf = A.upload(src_feat), A.upload(tgt_feat)
-    if sf.shape[0] != src.shape[0] or tf.shape[0] != tgt.shape[0]:
-        raise L.RoitrError("compat_pose_estimation: one descriptor per point is needed")
-    m = descmatch.match_batch(A.cumulative([sf.shape[0]], "cuda"), sf, A.cumulative([tf.shape[0]], "cuda"), tf, metric="dot",
-                              mode="mutual" if mutual else "row")
-    corr = m["corr"].long()
-    r = compat_batch(m["corr_starts"], src[corr[:, 0]], tgt[corr[:, 1]], m["row_val"][corr[:, 0]], **kw)
+    r = compat_batch(*_feature_matches("compat_pose_estimation", src_pcd, tgt_pcd, src_feat, tgt_feat, mutual), **kw)
+    return r["T"][0].cpu().numpy().astype(np.float64)
+
+
+@torch.no_grad()
+def fgr_pose_estimation(src_pcd, tgt_pcd, src_feats, tgt_feats, mutual=True, **kw):
+    """Open3D's registration_fgr_based_on_feature_matching in this project's terms: the matches of compat_pose_estimation (descmatch
+    under the dot product, mutual or every source point with its best target), then fgr.fgr_batch on the matched point pairs with the
+    match scores as confidences.  kw: fgr_batch's keyword arguments (tuples > 0 switches the tuple test on).  Parity with Open3D is
+    not claimed (include/roitr_engine.h above roitr_fgr_batch).  Returns the 4x4 float64 numpy transformation."""
+    from .fgr import fgr_batch
+    r = fgr_batch(*_feature_matches("fgr_pose_estimation", src_pcd, tgt_pcd, src_feats, tgt_feats, mutual), **kw)
     return r["T"][0].cpu().numpy().astype(np.float64)
 
 

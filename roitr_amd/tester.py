@@ -169,8 +169,9 @@ class Descriptor(Stage):
 class Pose(Stage):
     """register: every pair's pose is estimated on the device and saved as `est_transform` in its file.  estimator: "ransac" (registration.
     register_handle, keyed on the GLOBAL pair id, so the poses do not depend on sharding or pairs_per_forward), "lgr" (lgr.lgr_handle: local-
-    to-global registration on the matcher's patches: no random stream, so no keys) or "compat" (compat.compat_handle: spatial-compatibility
-    registration: no random stream and no patch structure either); `ransac` / `lgr` / `compat` hold their keyword arguments, everything
+    to-global registration on the matcher's patches: no random stream, so no keys), "compat" (compat.compat_handle: spatial-compatibility
+    registration: no random stream and no patch structure either) or "fgr" (fgr.fgr_handle: fast global registration, one robust objective
+    and no hypotheses; its optional tuple test is keyed on the GLOBAL pair id like RANSAC); `ransac` / `lgr` / `compat` / `fgr` hold their keyword arguments, everything
     downstream of the pose is the same code.  refine (implies register): None, or ICP from reg["T"] on the clouds the model saw: "point" /
     "plane" (icp.icp_handle: point-to-point, or point-to-plane on the target normals) or "gicp" (gicp.gicp_handle: generalized, plane-to-
     plane on the normals of both clouds; each module is imported in its own mode only); `icp` holds the keyword arguments, `epsilon` among
@@ -180,12 +181,13 @@ class Pose(Stage):
     refinement row + (status,) or None)."""
     name = "pose"
 
-    def __init__(self, estimator, ransac, lgr, compat, refine, icp, errors):
+    def __init__(self, estimator, ransac, lgr, compat, refine, icp, errors, fgr=None):
         if refine not in (None, "point", "plane", "gicp"):
             raise ValueError("refine must be None, 'point', 'plane' or 'gicp'")
-        if estimator not in ("ransac", "lgr", "compat"):
-            raise ValueError("estimator must be 'ransac', 'lgr' or 'compat'")
-        super().__init__(estimator=estimator, kw={"ransac": ransac, "lgr": lgr, "compat": compat}[estimator], refine=refine, icp=icp, errors=errors)
+        if estimator not in ("ransac", "lgr", "compat", "fgr"):
+            raise ValueError("estimator must be 'ransac', 'lgr', 'compat' or 'fgr'")
+        super().__init__(estimator=estimator, kw={"ransac": ransac, "lgr": lgr, "compat": compat, "fgr": dict(fgr or {})}[estimator],
+                         refine=refine, icp=icp, errors=errors)
 
     def run(self, fw):
         from .registration import pose_errors, register_handle
@@ -195,6 +197,9 @@ class Pose(Stage):
         elif self.estimator == "compat":
             from .compat import compat_handle
             fw.reg = compat_handle(fw.handle, **self.kw)
+        elif self.estimator == "fgr":
+            from .fgr import fgr_handle
+            fw.reg = fgr_handle(fw.handle, pair_keys=fw.ids, **self.kw)
         else:
             fw.reg = register_handle(fw.handle, pair_keys=fw.ids, **self.kw)
         fw.est = fw.reg["T"].cpu()
@@ -251,7 +256,7 @@ class Fpfh(Stage):
     """fpfh_baseline: None, or a dict (radius, max_nn, mutual; defaults 0.125, 100, True) that switches on the learning-free baseline
     (fpfh.fpfh_handle) with evaluate and register: FPFH descriptors of the clouds and normals the model was fed, matched under the
     squared distance, their pose from the Pose stage's estimator with its keyword arguments ("ransac", keyed on the global pair id like
-    the model's, or "compat"; "lgr" needs the matcher's patches and is refused with a ValueError).  `Tester.fpfh` maps this rank's pair
+    the model's, "compat" or "fgr"; "lgr" needs the matcher's patches and is refused with a ValueError).  `Tester.fpfh` maps this rank's pair
     ids to (inlier ratio of the matches at get_inlier_ratio's 0.1 m, nan without matches; RRE degrees; RTE metres; number of matches)
     and on rank 0 `metrics` gains fpfh_ir (mean over the pairs that have matches), fpfh_rre, fpfh_rte (means) and fpfh_success (share
     of pairs with RRE < 15 degrees and RTE < 0.3 m), over the pairs of ALL ranks."""
@@ -259,7 +264,7 @@ class Fpfh(Stage):
 
     def __init__(self, options, pose):
         if options is not None and pose.estimator == "lgr":
-            raise ValueError("the FPFH baseline has no patches: it runs with estimator 'ransac' or 'compat', not 'lgr'")
+            raise ValueError("the FPFH baseline has no patches: it runs with estimator 'ransac', 'compat' or 'fgr', not 'lgr'")
         super().__init__(options=options, pose=pose)
 
     def run(self, fw):
@@ -330,7 +335,7 @@ class Tester:
     def __init__(self, config, model, dataset, snapshot_dir="snapshot", pairs_per_forward=8, rank=0, world=1, evaluate=False,
                  estimate_normals=False, view_point=(0.0, 0.0, 0.0), register=False, ransac=None, nonrigid=None, descriptor_eval=False,
                  validate=False, voxel_size=None, points_lim=None, subsample_seed=0, recall=False, overlap_radius=0.0375,
-                 estimator="ransac", lgr=None, refine=None, icp=None, compat=None, fpfh_baseline=None, gt_dir=None):
+                 estimator="ransac", lgr=None, refine=None, icp=None, compat=None, fpfh_baseline=None, gt_dir=None, fgr=None):
         """evaluate: also compute PIR / IR per pair on the device (lib/loss.py:169-213 Evaluator) and return their means.
         estimate_normals: ignore the dataset's normals and recompute them on the GPU from the points the way the
         reference's dataset code does (open3d estimate_normals(knn=33) + normal_redirect, dataset/tdmatch.py:120-127).
@@ -338,7 +343,7 @@ class Tester:
         prep.random_subsample; see _prepare).  With either one set the normals are always re-estimated on the new points (the dataset's
         normals no longer belong to them) and the features are rebuilt as ones.
         The other options are described with their stage: nonrigid (Nonrigid), validate (Losses), descriptor_eval (Descriptor), register /
-        ransac / estimator / lgr / compat / refine / icp (Pose), fpfh_baseline (Fpfh), recall / overlap_radius / gt_dir (Recall).  `stages`
+        ransac / estimator / lgr / compat / fgr / refine / icp (Pose), fpfh_baseline (Fpfh), recall / overlap_radius / gt_dir (Recall).  `stages`
         holds the stages that are on, in running order; a stage that is off leaves None.  Rank 0, after test(): `report`, the printed lines."""
         self.config, self.model, self.dataset, self.snapshot_dir, self.pairs_per_forward = config, model, dataset, snapshot_dir, pairs_per_forward
         self.benchmark = config["benchmark"] if isinstance(config, dict) else config.benchmark
@@ -349,7 +354,8 @@ class Tester:
         self.register = register or recall or refine is not None
         self.estimator, self.refine, self.fpfh_baseline = estimator, refine, None if fpfh_baseline is None else dict(fpfh_baseline)
         self.ransac, self.lgr, self.compat, self.icp = dict(ransac or {}), dict(lgr or {}), dict(compat or {}), dict(icp or {})
-        pose = Pose(estimator, self.ransac, self.lgr, self.compat, refine, self.icp, errors=self.evaluate)
+        self.fgr = dict(fgr or {})
+        pose = Pose(estimator, self.ransac, self.lgr, self.compat, refine, self.icp, errors=self.evaluate, fgr=self.fgr)
         radius = float(config.get("eval_acceptance_radius", 0.1) if isinstance(config, dict) else getattr(config, "eval_acceptance_radius", 0.1))
         every = ((Nonrigid(kw=dict(nonrigid or {}), radius=radius), self.evaluate and self.benchmark in NONRIGID_BENCHMARKS),
                  (Losses(config=config), validate), (Descriptor(), descriptor_eval and self.evaluate), (pose, self.register),
