@@ -168,6 +168,60 @@ size_t roitr_subsample_workspace_bytes(int b, int n);
 int roitr_random_subsample(int b, int n, const int* offset, int limit, unsigned long long seed, const int* cloud_keys, int* idx,
                            int* new_offset, void* ws, roitr_stream_t stream);
 
+/* ------------------------------------------------------------------ outlier removal: statistical and radius filters
+ * Open3D's remove_statistical_outlier(nb_neighbors, std_ratio) and remove_radius_outlier(nb_points, radius) restated; parity with the
+ * original is unpinned (Open3D is not part of the build), this text is the definition.  b clouds in the `offset` layout of the normals:
+ * xyz (n,3) fp32, offset (b) cumulative int32 with offset[b-1] == n (PRECONDITION, as for roitr_fpfh_batch: the offsets are device
+ * memory and are not checked); empty clouds are legal.  All arithmetic is float64 on the fp32 inputs, every product, sum, quotient and
+ * square root rounded on its own (no FMA); dp = p_j - p_i = (dx, dy, dz) is taken in float64, d2 = (dx dx + dy dy) + dz dz.
+ * Statistical filter (nb_neighbors in [2, 100], std_ratio finite).
+ *   Neighbours of point i of cloud c: row i of this library's exact kNN of the cloud against itself with nsample = nb_neighbors
+ *     (roitr_knn_build_grid_ex + roitr_knnquery_ex: ascending distance, the lower index first among equal ones).  Point i itself counts
+ *     wherever it stands in the row (with more than nb_neighbors copies of a point, not at all); slots k >= size(c) are padding and
+ *     ignored: v_i = min(nb_neighbors, size(c)) slots are valid.
+ *   mean_i = (the sum over the valid slots, in ROW order from +0, of sqrt(d2)) / v_i.
+ *   Per cloud, V = size(c):  S1 = sum_i (mean_i > 0 ? mean_i : 0);  cloud_mean = S1 / V;
+ *     S2 = sum_i (mean_i > 0 ? (mean_i - cloud_mean)^2 : 0);  std = sqrt(S2 / (V - 1));  thr = cloud_mean + std_ratio std.
+ *     Points with mean_i == 0 (a point with at least nb_neighbors copies of itself) count in V but not in the sums: Open3D's quirk, kept.
+ *   Order of a per-cloud sum (fixed): the cloud's points in input order are cut into segments of 256; a segment is summed one term
+ *     after the other in input order from +0; the cloud's sum is the sum of its segment sums, one after the other in segment order
+ *     from +0.
+ *   Point i is kept iff mean_i > 0 && mean_i < thr, both strict.  A cloud of one point gives std = sqrt(0 / 0): a NaN threshold and
+ *     nothing kept.  A cloud whose means are all equal and whose sums come out exact (a lattice with nb_neighbors = 2: every mean is half
+ *     the step) has std == 0, thr == cloud_mean, and keeps nothing either.
+ *   stats of an empty cloud are written as 0, 0, 0 (the formulas would give NaN, -0, NaN).
+ * Radius filter (radius finite and positive, nb_points >= 0).
+ *   count_i = the number of points j of the same cloud, i included, with d2 < radius radius (strict; the product rounded once).
+ *   Point i is kept iff count_i > nb_points.
+ * Outputs of both: keep (n) unsigned char 0 / 1;  index (capacity n): the kept GLOBAL rows, ascending, new_offset[b-1] of them, nothing
+ *   is written behind those;  new_offset (b) cumulative kept counts;  status (b): bit 1 = the cloud holds a non-finite coordinate -- it
+ *   keeps nothing and its optional rows are 0; the other clouds of the call are unaffected (the grid and the kNN run on a copy with
+ *   such coordinates zeroed).  Optional (NULL): mean_dist (n) float64 and stats (b,3) float64 = cloud_mean, std, thr for the
+ *   statistical filter; count (n) int32 for the radius filter -- without it a query stops walking at nb_points + 1, keep is the same.
+ * Host-side errors (ROITR_ERR_ARG, nothing is launched): a parameter outside the ranges above, b or n negative, b > 65535, b == 0 with
+ *   n > 0, null required pointers, workspace_bytes below roitr_outlier_workspace_bytes(b, n, nb_neighbors) (nb_neighbors == 0 there:
+ *   the radius filter).  n == 0 or an empty cloud is not an error.
+ * Determinism: mean_i is summed by one lane in row order, the per-cloud sums in the order above, the counts are integers; no
+ *   floating-point atomics.  A cloud's outputs are bitwise the same alone, in any slot of any batch, on repeats, and with or without the
+ *   optional outputs.  No host synchronisation, no host read.  The workspace holds the kNN rows: n nb_neighbors 4 bytes dominate. */
+#define ROITR_OUTLIER_NONFINITE 1
+size_t roitr_outlier_workspace_bytes(int b, int n, int nb_neighbors);
+int roitr_remove_statistical_outlier(int b, int n, const float* xyz, const int* offset, int nb_neighbors, double std_ratio,
+                                     unsigned char* keep,   /* (n) */
+                                     int* index,            /* capacity n */
+                                     int* new_offset,       /* (b) */
+                                     int* status,           /* (b) */
+                                     double* mean_dist,     /* optional (n) */
+                                     double* stats,         /* optional (b, 3) */
+                                     void* workspace, size_t workspace_bytes, roitr_stream_t stream);
+int roitr_remove_radius_outlier(int b, int n, const float* xyz, const int* offset, double radius, int nb_points,
+                                unsigned char* keep,        /* (n) */
+                                int* index,                 /* capacity n */
+                                int* new_offset,            /* (b) */
+                                int* status,                /* (b) */
+                                int* count,                 /* optional (n) */
+                                void* workspace, size_t workspace_bytes, roitr_stream_t stream);
+
 /* kNN(1) distances for a radius test (lib/utils.py:509-521 get_node_occlusion_score): exact when < cap2, otherwise any
  * value >= cap2.  Same workspace / grid rules as roitr_knnquery_ex. */
 int roitr_knn_within(int b, int n, int m, const float* xyz, const float* new_xyz, const int* offset, const int* new_offset,

@@ -45,6 +45,14 @@ def parser():
                          "normals are then re-estimated on the new points")
     ap.add_argument("--points-lim", type=int, default=None,
                     help="cap every cloud at N points, uniform without replacement, on the GPU (the reference's points_lim / max_points)")
+    ap.add_argument("--remove-outliers", choices=("statistical", "radius"), default=None,
+                    help="remove flying pixels and isolated points on the GPU after the voxel grid and before the cap (prep.py): the "
+                         "statistical filter (mean distance to --outlier-nn neighbours against the cloud's mean + --outlier-std sigma) or "
+                         "the radius filter (more than --outlier-points points within --outlier-radius); the normals are then re-estimated")
+    ap.add_argument("--outlier-nn", type=int, default=20, help="statistical filter: neighbours per point, the point included (2 .. 100)")
+    ap.add_argument("--outlier-std", type=float, default=2.0, help="statistical filter: the threshold in standard deviations")
+    ap.add_argument("--outlier-points", type=int, default=16, help="radius filter: a point stays with more than N points within the radius")
+    ap.add_argument("--outlier-radius", type=float, default=0.05, help="radius filter: the radius (metres)")
     ap.add_argument("--subsample-seed", type=int, default=0, help="seed of the cap's counter-based stream")
     ap.add_argument("--recall", action="store_true",
                     help="the 3DMatch-protocol registration recall on the run's own pairs: overlap ratios and gt.info matrices computed "
@@ -85,6 +93,15 @@ def parser():
     return ap
 
 
+def outlier_options(args):
+    """The Tester's `outlier` argument of the parsed command line (None: off)."""
+    if args.remove_outliers == "statistical":
+        return dict(method="statistical", nb_neighbors=args.outlier_nn, std_ratio=args.outlier_std)
+    if args.remove_outliers == "radius":
+        return dict(method="radius", nb_points=args.outlier_points, radius=args.outlier_radius)
+    return None
+
+
 def main():
     args = parser().parse_args()
     config = Config(load_config(args.config))
@@ -115,7 +132,8 @@ def main():
                     compat=dict(compat_dist=args.compat_dist, max_seeds=args.compat_seeds, k=args.compat_k),
                     fgr=dict(max_dist=args.fgr_max_dist, iterations=args.fgr_iterations, tuples=args.fgr_tuples),
                     icp=dict(max_dist=args.icp_distance, iterations=args.icp_iterations, **(dict(epsilon=args.gicp_epsilon) if args.refine == "gicp" else {})),
-                    fpfh_baseline=dict(radius=args.fpfh_radius, max_nn=args.fpfh_max_nn) if args.fpfh_baseline else None, gt_dir=args.write_gt)
+                    fpfh_baseline=dict(radius=args.fpfh_radius, max_nn=args.fpfh_max_nn) if args.fpfh_baseline else None, gt_dir=args.write_gt,
+                    outlier=outlier_options(args))
     counts = tester.test()
     if rank == 0:
         print(*tester.report, f"[roitr_amd] wrote {args.synthetic} result files under {args.snapshot_dir}/{config.benchmark}; "

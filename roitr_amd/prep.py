@@ -99,6 +99,109 @@ def voxel_down_sample(xyz, offset, voxel_size, attr=None, strict=True):
     return VoxelResult(out_xyz[:m], new_offset, out_attr[:m] if out_attr is not None else None, inverse, counts[:m], status)
 
 
+OutlierResult = collections.namedtuple("OutlierResult", "points offset attr index keep status mean_dist stats counts")
+OUTLIER_STATUS_NONFINITE = 1
+_outlier = L.binder(("roitr_outlier_workspace_bytes", "roitr_remove_statistical_outlier", "roitr_remove_radius_outlier"))
+
+
+def _outlier_groups(lib, sizes, k, max_bytes):
+    """Consecutive groups [g0, g1) of clouds whose workspace stays under max_bytes; a single larger cloud goes alone."""
+    groups, g0, rows = [], 0, 0
+    for c, s in enumerate(sizes):
+        if c > g0 and int(lib.roitr_outlier_workspace_bytes(c + 1 - g0, rows + s, k)) > max_bytes:
+            groups.append((g0, c))
+            g0, rows = c, 0
+        rows += s
+    return groups + [(g0, len(sizes))]
+
+
+def _outlier_run(what, xyz, offset, attr, k, max_bytes, call, optional):
+    """The part the two filters share: the buffers, the groups, the calls, ONE host read (new_offset and status of every group), the
+    slices.  optional: (mean_dist, stats, counts) as the caller allocated them, or None.
+    call(lib, b, n, xyz, offset, keep, index, new_offset, status, rows (lo, hi), clouds (g0, g1), ws, nbytes) -> status code, for one group."""
+    xyz = A.points(xyz, what)
+    dev = xyz.device
+    offset = offset.to(device=dev, dtype=torch.int32).contiguous()
+    n, b = int(xyz.shape[0]), int(offset.shape[0])
+    if attr is not None:
+        attr = attr.to(dev)
+        if int(attr.shape[0]) != n:
+            raise L.RoitrError(f"{what}: attr must have one row per point")
+    lib = _outlier()
+    keep = torch.zeros((n,), dtype=torch.uint8, device=dev)
+    index = torch.empty((n,), dtype=torch.int32, device=dev)
+    tail = torch.zeros((2 * b,), dtype=torch.int32, device=dev)   # new_offset, status: one host read for both
+    new_offset, status = tail[:b], tail[b:]
+    groups, bounds = [(0, b)], [0, n]
+    if b > 1 and int(lib.roitr_outlier_workspace_bytes(b, n, k)) > max_bytes:
+        ends = [0] + offset.cpu().tolist()   # only a call that has to be split reads the offsets first
+        groups = _outlier_groups(lib, [ends[c + 1] - ends[c] for c in range(b)], k, max_bytes)
+        bounds = ends
+    for g0, g1 in groups:
+        lo, hi = (0, n) if len(groups) == 1 else (bounds[g0], bounds[g1])
+        if g1 == g0:
+            continue
+        off = offset[g0:g1] if lo == 0 else (offset[g0:g1] - lo).contiguous()
+        nbytes = int(lib.roitr_outlier_workspace_bytes(g1 - g0, hi - lo, k))
+        ws = A.workspace(nbytes, dev)
+        L.check(call(lib, g1 - g0, hi - lo, xyz[lo:hi], off, keep[lo:hi], index[lo:hi], new_offset[g0:g1], status[g0:g1], (lo, hi), (g0, g1),
+                     ws, nbytes), what)
+    host = tail.cpu()
+    if len(groups) > 1:   # group-local rows and counts -> the call's
+        parts, offs, total = [], [], 0
+        for g0, g1 in groups:
+            m = int(host[g1 - 1]) if g1 > g0 else 0
+            parts.append(index[bounds[g0]:bounds[g0] + m] + bounds[g0])
+            offs.append(new_offset[g0:g1] + total)
+            total += m
+        index, new_offset = torch.cat(parts), torch.cat(offs)
+    else:
+        index = index[:int(host[b - 1]) if b else 0]
+    rows = index.long()
+    return OutlierResult(xyz[rows], new_offset, attr[rows] if attr is not None else None, index, keep.bool(), status, *optional)
+
+
+def remove_statistical_outlier(xyz, offset, nb_neighbors=20, std_ratio=2.0, attr=None, return_stats=False, max_workspace_bytes=1 << 30):
+    """Open3D's remove_statistical_outlier restated (include/roitr_pointops.h above roitr_remove_statistical_outlier is the definition;
+    parity with the original is unpinned): xyz (n,3) fp32 device tensor of b concatenated clouds, offset (b) cumulative int32.
+
+    mean_i = the mean distance of point i to the nb_neighbors entries of its kNN row (itself included); a point is kept iff
+    0 < mean_i < cloud_mean + std_ratio * std over its own cloud.  Returns OutlierResult: points (m,3), offset (b) cumulative int32,
+    attr (m,c) the kept rows of `attr` or None, index (m) int32 the kept global rows, ascending, keep (n) bool, status (b) int32 (bit 1 =
+    a non-finite coordinate: the cloud keeps nothing), and with return_stats mean_dist (n) float64 and stats (b,3) float64 = cloud_mean,
+    std, thr (None otherwise; counts is the radius filter's).
+    The clouds are processed in consecutive groups whose workspace (n * nb_neighbors * 4 bytes of kNN rows dominate) stays under
+    max_workspace_bytes; a single larger cloud goes alone.  The results do not depend on the split.  One host read (the totals; a call
+    that has to be split reads the offsets first)."""
+    k, ratio = int(nb_neighbors), float(std_ratio)
+    n, b = int(xyz.shape[0]), int(offset.shape[0])
+    mean = stats = None
+    if return_stats and torch.is_tensor(xyz) and xyz.is_cuda:
+        mean = torch.zeros((n,), dtype=torch.float64, device=xyz.device)
+        stats = torch.zeros((b, 3), dtype=torch.float64, device=xyz.device)
+
+    def call(lib, gb, gn, gx, goff, keep, index, new_offset, status, rows, clouds, ws, nbytes):
+        return lib.roitr_remove_statistical_outlier(gb, gn, L.ptr(gx), L.ptr(goff), k, ratio, L.ptr(keep), L.ptr(index), L.ptr(new_offset),
+                                                    L.ptr(status), L.ptr(mean[rows[0]:rows[1]] if mean is not None else None),
+                                                    L.ptr(stats[clouds[0]:clouds[1]] if stats is not None else None), L.ptr(ws), nbytes,
+                                                    L.stream_ptr())
+    return _outlier_run("remove_statistical_outlier", xyz, offset, attr, k, int(max_workspace_bytes), call, (mean, stats, None))
+
+
+def remove_radius_outlier(xyz, offset, nb_points=16, radius=0.05, attr=None, return_counts=False):
+    """Open3D's remove_radius_outlier restated (defined in include/roitr_pointops.h): a point is kept iff more than nb_points points of
+    its own cloud, itself included, lie strictly within `radius` of it (float64 on the fp32 coordinates).  Arguments and result as
+    remove_statistical_outlier; return_counts adds counts (n) int32, the points within the radius (without it a query stops counting
+    at nb_points + 1).  One host read."""
+    n = int(xyz.shape[0])
+    counts = torch.zeros((n,), dtype=torch.int32, device=xyz.device) if return_counts and torch.is_tensor(xyz) and xyz.is_cuda else None
+
+    def call(lib, gb, gn, gx, goff, keep, index, new_offset, status, rows, clouds, ws, nbytes):
+        return lib.roitr_remove_radius_outlier(gb, gn, L.ptr(gx), L.ptr(goff), float(radius), int(nb_points), L.ptr(keep), L.ptr(index),
+                                               L.ptr(new_offset), L.ptr(status), L.ptr(counts), L.ptr(ws), nbytes, L.stream_ptr())
+    return _outlier_run("remove_radius_outlier", xyz, offset, attr, 0, 1 << 62, call, (None, None, counts))
+
+
 def random_subsample(offset, limit, seed=0, cloud_keys=None):
     """The point cap: offset (b) cumulative int32 device tensor -> (idx, new_offset).
 

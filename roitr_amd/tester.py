@@ -335,20 +335,30 @@ class Tester:
     def __init__(self, config, model, dataset, snapshot_dir="snapshot", pairs_per_forward=8, rank=0, world=1, evaluate=False,
                  estimate_normals=False, view_point=(0.0, 0.0, 0.0), register=False, ransac=None, nonrigid=None, descriptor_eval=False,
                  validate=False, voxel_size=None, points_lim=None, subsample_seed=0, recall=False, overlap_radius=0.0375,
-                 estimator="ransac", lgr=None, refine=None, icp=None, compat=None, fpfh_baseline=None, gt_dir=None, fgr=None):
+                 estimator="ransac", lgr=None, refine=None, icp=None, compat=None, fpfh_baseline=None, gt_dir=None, fgr=None,
+                 outlier=None):
         """evaluate: also compute PIR / IR per pair on the device (lib/loss.py:169-213 Evaluator) and return their means.
         estimate_normals: ignore the dataset's normals and recompute them on the GPU from the points the way the
         reference's dataset code does (open3d estimate_normals(knn=33) + normal_redirect, dataset/tdmatch.py:120-127).
         voxel_size / points_lim / subsample_seed: raw scans in front of the model, on the device (prep.voxel_down_sample,
         prep.random_subsample; see _prepare).  With either one set the normals are always re-estimated on the new points (the dataset's
         normals no longer belong to them) and the features are rebuilt as ones.
+        outlier: dict(method="statistical", nb_neighbors=20, std_ratio=2.0) or dict(method="radius", nb_points=16, radius=0.05): remove
+        flying pixels and isolated points on the device after the voxel grid and before the cap (prep.remove_statistical_outlier /
+        remove_radius_outlier; see _prepare); re-estimates the normals like the two options above.  Rank 0, after test(): the report
+        starts with one line on the removed share per side.
         The other options are described with their stage: nonrigid (Nonrigid), validate (Losses), descriptor_eval (Descriptor), register /
         ransac / estimator / lgr / compat / fgr / refine / icp (Pose), fpfh_baseline (Fpfh), recall / overlap_radius / gt_dir (Recall).  `stages`
         holds the stages that are on, in running order; a stage that is off leaves None.  Rank 0, after test(): `report`, the printed lines."""
         self.config, self.model, self.dataset, self.snapshot_dir, self.pairs_per_forward = config, model, dataset, snapshot_dir, pairs_per_forward
         self.benchmark = config["benchmark"] if isinstance(config, dict) else config.benchmark
         self.rank, self.world, self.voxel_size, self.points_lim, self.subsample_seed = rank, world, voxel_size, points_lim, subsample_seed
-        self.estimate_normals, self.view_point = estimate_normals or voxel_size is not None or points_lim is not None, view_point
+        self.outlier = None if outlier is None else dict(outlier)
+        if self.outlier is not None and self.outlier.get("method") not in ("statistical", "radius"):
+            raise ValueError(f"outlier: method must be 'statistical' or 'radius', got {self.outlier.get('method')!r}")
+        self.outlier_rows = {}   # GLOBAL pair id -> (source points in, kept, target points in, kept)
+        self.estimate_normals = estimate_normals or voxel_size is not None or points_lim is not None or outlier is not None
+        self.view_point = view_point
         recall = recall or gt_dir is not None
         self.evaluate = evaluate or validate or recall
         self.register = register or recall or refine is not None
@@ -370,10 +380,12 @@ class Tester:
         """The reference's preparation of a raw scan, for all clouds of one forward: the voxel grid its 3DMatch files went through
         beforehand (one batched call for the source clouds, on `raw_src_pcd` with `src_points` as the attribute -- the identity for
         rigid items, the deformed cloud of 4DMatch as the per-voxel mean of the deformed points -- and one for the targets), then the
+        outlier filter (one batched call for the sources, on `raw_src_pcd` with `src_points` carried along as the attribute, so a
+        deformed cloud keeps the same rows, and one for the targets), then the
         `points_lim` cap of dataset/tdmatch.py:72-78 / dataset/fdmatch.py:49-56 (one batched call; cloud keys 2 * GLOBAL pair id and
         2 * id + 1, so the kept rows do not depend on sharding or pairs_per_forward; kept rows stay in input order where the reference
         keeps permutation order).  `metric_index` becomes unique(inverse[metric_index]) under the grid and the kept ones of its rows,
-        renumbered, under the cap (the reference leaves it pointing into the uncapped cloud)."""
+        renumbered, under the outlier filter and the cap (the reference leaves it pointing into the uncapped cloud)."""
         from .prep import random_subsample, voxel_down_sample
         k = len(items)
         raw = [it["raw_src_pcd"].float() for it in items]
@@ -388,6 +400,22 @@ class Tester:
             for j in range(k):
                 if metric[j] is not None:
                     metric[j] = torch.unique(rs.inverse[metric[j] + lo_in[j]].long()) - lo_s[j]
+            raw = [rs.points[lo_s[j]:lo_s[j + 1]] for j in range(k)]
+            deformed = [rs.attr[lo_s[j]:lo_s[j + 1]] for j in range(k)]
+            tgt = [rt.points[lo_t[j]:lo_t[j + 1]] for j in range(k)]
+        if self.outlier is not None:
+            from . import prep
+            kw = {key: v for key, v in self.outlier.items() if key != "method"}
+            run = prep.remove_statistical_outlier if self.outlier["method"] == "statistical" else prep.remove_radius_outlier
+            off_s, off_t = _offsets(raw, device), _offsets(tgt, device)
+            rs = run(torch.cat(raw), off_s, attr=torch.cat(deformed), **kw)
+            rt = run(torch.cat(tgt), off_t, **kw)
+            lo_in, lo_s, lo_t = [0] + off_s.tolist(), [0] + rs.offset.tolist(), [0] + rt.offset.tolist()
+            for j in range(k):
+                self.outlier_rows[ids[j]] = (raw[j].shape[0], lo_s[j + 1] - lo_s[j], tgt[j].shape[0], lo_t[j + 1] - lo_t[j])
+                if metric[j] is not None:   # the kept ones of its rows, renumbered, as under the cap
+                    pos = torch.cumsum(rs.keep[lo_in[j]:lo_in[j + 1]].long(), 0) - 1
+                    metric[j] = pos[metric[j]][rs.keep[lo_in[j]:lo_in[j + 1]][metric[j]]]
             raw = [rs.points[lo_s[j]:lo_s[j + 1]] for j in range(k)]
             deformed = [rs.attr[lo_s[j]:lo_s[j + 1]] for j in range(k)]
             tgt = [rt.points[lo_t[j]:lo_t[j + 1]] for j in range(k)]
@@ -416,7 +444,7 @@ class Tester:
     def _load(self, ids, device):
         """The Forward of these pairs, launched: items on the device, prepared, with normals, and the engine call enqueued."""
         items = [{k: v.to(device) if torch.is_tensor(v) else v for k, v in self.dataset[i].items()} for i in ids]
-        if self.voxel_size is not None or self.points_lim is not None:
+        if self.voxel_size is not None or self.points_lim is not None or self.outlier is not None:
             self._prepare(ids, items, device)
         if self.estimate_normals:   # one batched call for all clouds of this forward
             from .prep import estimate_normals
@@ -478,7 +506,10 @@ class Tester:
         per_pair = self.model.record_scores_per_pair()
         self.records = gather_result_records(assemble_block(blocks, slots_per_rank(n, self.world), per_pair, device),
                                              slots_per_rank(n, self.world), per_pair)
-        merged = merge_rows({stage.name: stage.rows for stage in self.stages}, self.world)
+        local = {stage.name: stage.rows for stage in self.stages}
+        if self.outlier is not None:
+            local["outlier"] = self.outlier_rows
+        merged = merge_rows(local, self.world)
         if self.records is None:     # ranks other than 0
             return None
         if self.records.truncated:
@@ -503,7 +534,17 @@ class Tester:
             lines.update(stage.lines(merged[stage.name], getattr(self, stage.publishes)))
             stage.finish(merged[stage.name])
         self.report = [line for slot in REPORT_ORDER for line in lines.get(slot, ())]
+        if self.outlier is not None:
+            self.outlier_rows = merged["outlier"]
+            self.report.insert(0, outlier_line(self.outlier["method"], merged["outlier"]))
         return counts
+
+
+def outlier_line(method, rows):
+    """The one line of the outlier filter: the removed share per side over the pairs of all ranks."""
+    s_in, s_kept, t_in, t_kept = (sum(r[c] for r in rows.values()) for c in range(4))
+    return (f"[roitr_amd] outlier removal ({method}) over {len(rows)} pairs: removed {1 - s_kept / max(s_in, 1):.4f} of the source points "
+            f"({s_in - s_kept} of {s_in}), {1 - t_kept / max(t_in, 1):.4f} of the target points ({t_in - t_kept} of {t_in})")
 
 
 def fpfh_metrics(rows):
