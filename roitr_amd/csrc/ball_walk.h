@@ -1,5 +1,7 @@
 // The float64 fixed-radius walk over the per-cloud grid of knn_grid.h, for the sources that decide in float64 on fp32 inputs
-// (pairgt.hip, icp.hip): the three rounded operations and the cell range of a ball with the proof that it cannot miss a point.
+// (pairgt.hip, icp_common.h, outlier.hip; fpfh.hip takes the rounded operations alone): the three rounded operations and the cell range
+// of a ball with the proof that it cannot miss a point.  The walk itself -- three ball_cells calls, the rows of the box, four candidates
+// in flight -- stands in each of the three kernels: shared forms of it compiled to slower kernels (profiles/cloud_ops_refactor.txt).
 // Include it AFTER `#pragma clang fp contract(off)`: the rule "every product and sum rounded on its own" is written with pg_mul /
 // pg_add / pg_sub, which are plain operators that contraction would fuse again.
 #pragma once

@@ -1,8 +1,8 @@
 // FPFH descriptors: Open3D's compute_fpfh_feature(KDTreeSearchParamHybrid(radius, max_nn)) restated.
 // The operator is defined in include/roitr_pointops.h above roitr_fpfh_batch; this file follows that text.
 //
-// Once per call: the status pass (non-finite coordinates or normals; the cloud of every point; a copy of the points with non-finite
-// coordinates zeroed, which is what the grid is built on, as pairgt.hip and icp.hip do), the grid and the exact kNN(max_nn) of pointops_knn.hip of every cloud
+// Once per call: the status pass of cloud_status.h (non-finite coordinates or normals; the cloud of every point; a copy of the points with
+// non-finite coordinates zeroed, which is what the grid is built on), the grid and the exact kNN(max_nn) of pointops_knn.hip of every cloud
 // against itself, its idx rows (n, max_nn) in the workspace.  Then two launches, one wave per point each:
 //   fpfh_spfh_kernel   lanes own the slots of the point's kNN row (two per lane: max_nn <= 100).  Ballots give every slot its rank
 //                      among the non-self entries and, after the float64 radius test, its place in K(i); the kept indices are
@@ -13,6 +13,7 @@
 //                      b < 33 walks the list in row order on byte b of every staged row; the sum of a group of 11 bins is taken
 //                      over the lanes of the group in bin order after every neighbour, as the definition has it.
 // Counts are integers, every float64 sum runs in row order inside one wave: a point's outputs depend on its own row alone.
+#include "cloud_status.h"
 #include "common.h"
 #include "roitr_pointops.h"
 #include "workspace.h"
@@ -53,26 +54,16 @@ FpfhWs carve(void* ws, int b, int n, int max_nn)
     return w;
 }
 
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
-// One thread per point: its cloud (the binary search over the offsets is done here, 64 points per wave, and not by every wave of the
-// SPFH kernel: there it was ten dependent loads in front of everything else), the cloud's status bit (integer atomicOr on a word the
-// host zeroed) and the copy the kNN runs on.
+// One thread per point (cloud_status.h): its cloud (the binary search over the offsets is done here, 64 points per wave, and not by
+// every wave of the SPFH kernel: there it was ten dependent loads in front of everything else), the cloud's status bit for a non-finite
+// coordinate or normal, and the copy the kNN runs on.
 __global__ __launch_bounds__(FPFH_THREADS) void fpfh_prepare_kernel(int b, int n, const float* __restrict__ xyz,
                                                                     const float* __restrict__ normals, const int* __restrict__ offset,
                                                                     float* __restrict__ clean, int* __restrict__ cloud,
                                                                     int* __restrict__ status)
 {
     const int t = blockIdx.x * FPFH_THREADS + threadIdx.x;
-    if (t >= n) return;
-    const float x = xyz[(size_t)t * 3], y = xyz[(size_t)t * 3 + 1], z = xyz[(size_t)t * 3 + 2];
-    const bool okp = finite3(x, y, z);
-    clean[(size_t)t * 3] = okp ? x : 0.f; clean[(size_t)t * 3 + 1] = okp ? y : 0.f; clean[(size_t)t * 3 + 2] = okp ? z : 0.f;
-    int c = segment_of(t, offset, b);
-    if (t >= offset[c]) c = -1;   // a row behind offset[b - 1] belongs to no cloud
-    cloud[t] = c;
-    if (c >= 0 && (!okp || !finite3(normals[(size_t)t * 3], normals[(size_t)t * 3 + 1], normals[(size_t)t * 3 + 2])))
-        atomicOr(&status[c], FPFH_NONFINITE);
+    if (t < n) cloud_prepare(t, b, xyz, normals, offset, clean, cloud, status, FPFH_NONFINITE);
 }
 
 __device__ __forceinline__ double dot3(const double (&a)[3], const double (&b)[3])
@@ -132,7 +123,8 @@ __global__ __launch_bounds__(FPFH_THREADS) void fpfh_spfh_kernel(int n, int max_
     bool in_cloud = false;
     const int c = valid ? cloud[i] : -1;
     if (c >= 0) {
-        const int start = max(c ? offset[c - 1] : 0, 0), end = min(offset[c], n);   // the clamp: offsets are the caller's
+        const int2 se = cloud_range(offset, c, n);
+        const int start = se.x, end = se.y;
         in_cloud = i < end && !(status[c] & FPFH_NONFINITE);
         const int nv = in_cloud ? min(max_nn, end - start) : 0;     // slots behind the cloud's size are the kNN's padding
         const size_t row = (size_t)i * max_nn;

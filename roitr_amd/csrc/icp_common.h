@@ -8,6 +8,7 @@
 // and include common.h, knn_grid.h and workspace.h BEFORE that pragma, as icp.hip always has, so that their inline fp32 code keeps
 // the contraction it is compiled with everywhere else (the includes below are then no-ops).
 #pragma once
+#include "cloud_status.h"
 #include "common.h"
 #include "knn_grid.h"
 #include "roitr_pointops.h"
@@ -55,8 +56,6 @@ struct IcpOut {   // the caller's arrays; any but T and status may be null
     float* T; double* fitness; double* rmse; int* n_corr; int* steps; int* status; float* trace_T; double* trace_stat;
 };
 
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
 // One thread per pair, per source point and per target point: the status bits (integer atomicOr on a word the host zeroed) and the
 // copy of the target points the grid is built on.  src_normals: null unless the mode reads them (gicp.hip).
 __device__ __forceinline__ void icp_prepare(int b, int n, int m, const float* __restrict__ src, const int* __restrict__ src_offset,
@@ -80,7 +79,7 @@ __device__ __forceinline__ void icp_prepare(int b, int n, int m, const float* __
     if (t < m) {
         const float x = tgt[(size_t)t * 3], y = tgt[(size_t)t * 3 + 1], z = tgt[(size_t)t * 3 + 2];
         bool ok = finite3(x, y, z);
-        clean[(size_t)t * 3] = ok ? x : 0.f; clean[(size_t)t * 3 + 1] = ok ? y : 0.f; clean[(size_t)t * 3 + 2] = ok ? z : 0.f;
+        store_clean(clean, t, x, y, z, ok);
         if (normals) ok = ok && finite3(normals[(size_t)t * 3], normals[(size_t)t * 3 + 1], normals[(size_t)t * 3 + 2]);
         if (!ok) atomicOr(&status[segment_of(t, tgt_offset, b)], ROITR_ICP_NONFINITE);
     }

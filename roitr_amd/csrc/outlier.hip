@@ -1,9 +1,9 @@
 // Outlier removal: Open3D's remove_statistical_outlier and remove_radius_outlier restated.
 // The operators are defined in include/roitr_pointops.h above roitr_remove_statistical_outlier; this file follows that text.
 //
-// Both: the prepare pass of fpfh.hip (the cloud of every point, the status bit, a copy with non-finite coordinates zeroed for the grid),
-// the decision into a flag per point, then the flags to `index` and `new_offset` (tile sums, one-block scan, compaction, one thread per
-// cloud for the offsets: the shape of voxel.hip's cap, written again here on 1024-point tiles -- that file's kernels are untouched).
+// Both: the prepare pass of cloud_status.h (the cloud of every point, the status bit, a copy with non-finite coordinates zeroed for the
+// grid), the decision into a flag per point, then the flags to `index` and `new_offset` (flag_compact.h, which voxel.hip's cap shares:
+// tile sums, one-block scan, compaction with the inclusive counts kept; then one thread per cloud for the offsets).
 // Statistical: the grid and the exact kNN(nb_neighbors) of pointops_knn.hip, its idx rows (n, k) in the workspace, then
 //   outlier_mean_kernel    one LANE per point: the definition is k dependent float64 sqrt + add steps per point, so a wave per point
 //                          (fpfh.hip's shape) idles 44 lanes at k = 20 (measured on the same rows: 0.66 against 0.17 ms for 64 x 30 000
@@ -12,9 +12,12 @@
 //                          over the banks.
 //   outlier_stats_kernel   one workgroup per cloud: thread t sums the cloud's 256-point segments t, t + 256, ... one term after the other,
 //                          thread 0 adds the segment sums in segment order; S1, then S2 on cloud_mean, then the keep flags.
-// Radius: the grid alone (cell size chosen for the radius), one lane per query walking the cells under the ball (ball_walk.h: the walk
-// cannot miss an accepted point) with the float64 test on every candidate; without `count` a lane stops at nb_points + 1.
+// Radius: the grid alone (cell size chosen for the radius), one lane per query walking the cells under the ball (ball_cells of
+// ball_walk.h: the walk cannot miss an accepted point) with the float64 test on every candidate; without `count` a lane stops at
+// nb_points + 1.
+#include "cloud_status.h"
 #include "common.h"
+#include "flag_compact.h"
 #include "knn_grid.h"
 #include "roitr_pointops.h"
 #include "workspace.h"
@@ -22,8 +25,6 @@
 
 #define OL_THREADS 256
 #define OL_SEG 256          // points per segment of a per-cloud sum: part of the definition
-#define OL_ITEMS 4
-#define OL_TILE (OL_THREADS * OL_ITEMS)
 #define OL_MAX_NN 100
 #define OL_MAX_CLOUDS 65535
 
@@ -40,7 +41,7 @@ struct OlWs {
     double* mean;           // (n) mean_i (statistical)
     double* seg;            // (n / 256 + b + 1) segment sums; cloud c owns the slots from start(c) / 256 + c
     int* incl;              // (n) inclusive count of kept rows
-    int* tilesum;           // (ntile + 1) tile sums -> exclusive bases, the total behind them
+    int* tilesum;           // (flag_tiles(n) + 1) tile sums -> exclusive bases, the total behind them
     size_t bytes;
 };
 
@@ -55,34 +56,18 @@ OlWs carve(void* ws, int b, int n, int k)
     w.mean = c.take<double>(k > 0 ? n : 0);
     w.seg = c.take<double>(k > 0 ? (size_t)n / OL_SEG + b + 1 : 0);
     w.incl = c.take<int>(n);
-    w.tilesum = c.take<int>((size_t)div_up(n > 0 ? n : 1, OL_TILE) + 1);
+    w.tilesum = c.take<int>((size_t)flag_tiles(n) + 1);
     w.bytes = c.bytes + 256;   // room to align the caller's pointer
     return w;
 }
 
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
-// One thread per point: its cloud, the cloud's status bit (integer atomicOr on a word the host zeroed) and the copy the grid is built on.
+// One thread per point (cloud_status.h): its cloud, the cloud's status bit and the copy the grid is built on.
 __global__ __launch_bounds__(OL_THREADS) void outlier_prepare_kernel(int b, int n, const float* __restrict__ xyz, const int* __restrict__ offset,
                                                                      float* __restrict__ clean, int* __restrict__ cloud,
                                                                      int* __restrict__ status)
 {
     const int t = blockIdx.x * OL_THREADS + threadIdx.x;
-    if (t >= n) return;
-    const float x = xyz[(size_t)t * 3], y = xyz[(size_t)t * 3 + 1], z = xyz[(size_t)t * 3 + 2];
-    const bool ok = finite3(x, y, z);
-    clean[(size_t)t * 3] = ok ? x : 0.f; clean[(size_t)t * 3 + 1] = ok ? y : 0.f; clean[(size_t)t * 3 + 2] = ok ? z : 0.f;
-    int c = segment_of(t, offset, b);
-    if (t >= offset[c]) c = -1;   // a row behind offset[b - 1] belongs to no cloud
-    cloud[t] = c;
-    if (c >= 0 && !ok) atomicOr(&status[c], ROITR_OUTLIER_NONFINITE);
-}
-
-// [start, end) of cloud c, clamped into [0, n]: the offsets are the caller's
-__device__ __forceinline__ int2 cloud_range(const int* __restrict__ offset, int c, int n)
-{
-    const int s = min(max(c ? offset[c - 1] : 0, 0), n);
-    return make_int2(s, min(max(offset[c], s), n));
+    if (t < n) cloud_prepare(t, b, xyz, nullptr, offset, clean, cloud, status, ROITR_OUTLIER_NONFINITE);
 }
 
 // One lane per point, one wave per workgroup.  rows: 64 rows of k ints at stride k | 1 (dynamic LDS).
@@ -248,57 +233,7 @@ __global__ __launch_bounds__(OL_THREADS) void outlier_radius_kernel(int n, doubl
     if (COUNT) count[i] = have;
 }
 
-// ------------------------------------------------------------------ flags -> index, new_offset
-__device__ __forceinline__ int flags4(const unsigned char* __restrict__ keep, int at, int n)
-{
-    int s = 0;
-#pragma unroll
-    for (int k = 0; k < OL_ITEMS; ++k) s += (at + k < n) ? (int)keep[at + k] : 0;
-    return s;
-}
-
-__global__ __launch_bounds__(OL_THREADS) void outlier_tile_sums_kernel(int n, const unsigned char* __restrict__ keep, int* __restrict__ tilesum)
-{
-    __shared__ int wsum[OL_THREADS / 64];
-    const int s = block_incl_scan<OL_THREADS>(flags4(keep, blockIdx.x * OL_TILE + threadIdx.x * OL_ITEMS, n), wsum);
-    if (threadIdx.x == OL_THREADS - 1) tilesum[blockIdx.x] = s;
-}
-
-// one block: exclusive scan of the tile sums in place, the total behind them
-__global__ __launch_bounds__(OL_THREADS) void outlier_tile_scan_kernel(int ntile, int* __restrict__ tilesum)
-{
-    __shared__ int wsum[OL_THREADS / 64];
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int s = 0; s < ntile; s += OL_THREADS) {
-        const int j = s + threadIdx.x;
-        const int v = j < ntile ? tilesum[j] : 0;
-        const int end = block_running_scan<OL_THREADS>(v, wsum, &carry);
-        if (j < ntile) tilesum[j] = end - v;
-    }
-    if (threadIdx.x == 0) tilesum[ntile] = carry;
-}
-
-// kept rows in ascending input order; incl[i] = kept rows up to and including i
-__global__ __launch_bounds__(OL_THREADS) void outlier_compact_kernel(int n, const unsigned char* __restrict__ keep, const int* __restrict__ tilesum,
-                                                                     int* __restrict__ incl, int* __restrict__ index)
-{
-    __shared__ int wsum[OL_THREADS / 64];
-    const int at = blockIdx.x * OL_TILE + threadIdx.x * OL_ITEMS;
-    const int mine = flags4(keep, at, n);
-    int s = tilesum[blockIdx.x] + block_incl_scan<OL_THREADS>(mine, wsum) - mine;
-#pragma unroll
-    for (int k = 0; k < OL_ITEMS; ++k) {
-        const int i = at + k;
-        if (i >= n) break;
-        const int f = keep[i];
-        s += f;
-        incl[i] = s;
-        if (f) index[s - 1] = i;   // s - 1 < the total <= n
-    }
-}
-
+// ------------------------------------------------------------------ flags -> index, new_offset (flag_compact.h), one thread per cloud
 __global__ __launch_bounds__(OL_THREADS) void outlier_offset_kernel(int b, int n, const int* __restrict__ offset, const int* __restrict__ incl,
                                                                     int* __restrict__ new_offset)
 {
@@ -310,41 +245,29 @@ __global__ __launch_bounds__(OL_THREADS) void outlier_offset_kernel(int b, int n
 
 int compact(const OlWs& w, int b, int n, const int* offset, const unsigned char* keep, int* index, int* new_offset, hipStream_t stream)
 {
-    const int ntile = div_up(n, OL_TILE);
-    outlier_tile_sums_kernel<<<ntile, OL_THREADS, 0, stream>>>(n, keep, w.tilesum);
-    outlier_tile_scan_kernel<<<1, OL_THREADS, 0, stream>>>(ntile, w.tilesum);
-    outlier_compact_kernel<<<ntile, OL_THREADS, 0, stream>>>(n, keep, w.tilesum, w.incl, index);
+    flag_compact(n, keep, w.tilesum, index, w.incl, stream);
     outlier_offset_kernel<<<div_up(b, OL_THREADS), OL_THREADS, 0, stream>>>(b, n, offset, w.incl, new_offset);
     ROITR_LAUNCH_CHECK();
     return ROITR_OK;
 }
 
-// The checks both entry points share.  1: refused;  0: go on;  -1: nothing to do (b == 0, or n == 0 after the outputs were zeroed).
-int common_args(const char* who, int b, int n, const float* xyz, const int* offset, const unsigned char* keep, const int* index,
-                int* new_offset, int* status, const void* workspace, size_t workspace_bytes, int k, double* stats, hipStream_t stream, int& rc)
+// The refusals both entry points share; `who` is the message.
+int check_args(const char* who, int b, int n, const float* xyz, const int* offset, const unsigned char* keep, const int* index,
+               const int* new_offset, const int* status, const void* workspace, size_t workspace_bytes, int k)
 {
-    rc = ROITR_OK;
-    if (b < 0 || n < 0 || b > OL_MAX_CLOUDS || (b == 0 && n > 0) || n > 0x7fffffff - OL_TILE) {
-        rc = refuse(ROITR_ERR_ARG, who);
-        return 1;
-    }
-    if (b == 0) return -1;
-    if (!offset || !new_offset || !status || (n > 0 && (!xyz || !keep || !index || !workspace))) {
-        rc = refuse(ROITR_ERR_ARG, who);
-        return 1;
-    }
-    if (n > 0 && workspace_bytes < carve(nullptr, b, n, k).bytes) {
-        rc = refuse(ROITR_ERR_ARG, who);
-        return 1;
-    }
-    hipError_t e = hipMemsetAsync(status, 0, (size_t)b * 4, stream);
-    if (e == hipSuccess && n == 0) e = hipMemsetAsync(new_offset, 0, (size_t)b * 4, stream);
-    if (e == hipSuccess && n == 0 && stats) e = hipMemsetAsync(stats, 0, (size_t)b * 24, stream);
-    if (e != hipSuccess) {
-        rc = refuse(ROITR_ERR_HIP, hipGetErrorString(e));
-        return 1;
-    }
-    return n == 0 ? -1 : 0;
+    if (b < 0 || n < 0 || b > OL_MAX_CLOUDS || (b == 0 && n > 0) || n > 0x7fffffff - FLAG_TILE) return refuse(ROITR_ERR_ARG, who);
+    if (b > 0 && (!offset || !new_offset || !status || (n > 0 && (!xyz || !keep || !index || !workspace)))) return refuse(ROITR_ERR_ARG, who);
+    if (n > 0 && workspace_bytes < carve(nullptr, b, n, k).bytes) return refuse(ROITR_ERR_ARG, who);
+    return ROITR_OK;
+}
+
+// b > 0: the status words, and what a call without points returns (stats: nullable)
+int zero_outputs(int b, int n, int* new_offset, int* status, double* stats, hipStream_t stream)
+{
+    ROITR_HIP(hipMemsetAsync(status, 0, (size_t)b * 4, stream));
+    if (n == 0) ROITR_HIP(hipMemsetAsync(new_offset, 0, (size_t)b * 4, stream));
+    if (n == 0 && stats) ROITR_HIP(hipMemsetAsync(stats, 0, (size_t)b * 24, stream));
+    return ROITR_OK;
 }
 
 }  // namespace
@@ -362,11 +285,12 @@ extern "C" int roitr_remove_statistical_outlier(int b, int n, const float* xyz, 
     if (nb_neighbors < 2 || nb_neighbors > OL_MAX_NN)
         return refuse(ROITR_ERR_ARG, "remove_statistical_outlier: nb_neighbors must lie in [2, 100]");
     if (!std::isfinite(std_ratio)) return refuse(ROITR_ERR_ARG, "remove_statistical_outlier: std_ratio must be finite");
-    int rc;
-    const int what = common_args("remove_statistical_outlier: 0 <= b <= 65535 clouds, n >= 0, no null pointer, workspace of "
-                                 "roitr_outlier_workspace_bytes(b, n, nb_neighbors)", b, n, xyz, offset, keep, index, new_offset, status,
-                                 workspace, workspace_bytes, nb_neighbors, stats, stream, rc);
-    if (what != 0) return rc;
+    int rc = check_args("remove_statistical_outlier: 0 <= b <= 65535 clouds, n >= 0, no null pointer, workspace of "
+                        "roitr_outlier_workspace_bytes(b, n, nb_neighbors)", b, n, xyz, offset, keep, index, new_offset, status, workspace,
+                        workspace_bytes, nb_neighbors);
+    if (rc != ROITR_OK || b == 0) return rc;
+    rc = zero_outputs(b, n, new_offset, status, stats, stream);
+    if (rc != ROITR_OK || n == 0) return rc;
     const OlWs w = carve(workspace, b, n, nb_neighbors);
     ROITR_HIP(hipMemsetAsync(keep, 0, (size_t)n, stream));   // rows behind offset[b - 1] belong to no cloud's workgroup
     outlier_prepare_kernel<<<div_up(n, OL_THREADS), OL_THREADS, 0, stream>>>(b, n, xyz, offset, w.clean, w.cloud, status);
@@ -389,11 +313,12 @@ extern "C" int roitr_remove_radius_outlier(int b, int n, const float* xyz, const
 {
     if (!(radius > 0.0) || !std::isfinite(radius)) return refuse(ROITR_ERR_ARG, "remove_radius_outlier: radius must be finite and positive");
     if (nb_points < 0) return refuse(ROITR_ERR_ARG, "remove_radius_outlier: nb_points must not be negative");
-    int rc;
-    const int what = common_args("remove_radius_outlier: 0 <= b <= 65535 clouds, n >= 0, no null pointer, workspace of "
-                                 "roitr_outlier_workspace_bytes(b, n, 0)", b, n, xyz, offset, keep, index, new_offset, status, workspace,
-                                 workspace_bytes, 0, nullptr, stream, rc);
-    if (what != 0) return rc;
+    int rc = check_args("remove_radius_outlier: 0 <= b <= 65535 clouds, n >= 0, no null pointer, workspace of "
+                        "roitr_outlier_workspace_bytes(b, n, 0)", b, n, xyz, offset, keep, index, new_offset, status, workspace,
+                        workspace_bytes, 0);
+    if (rc != ROITR_OK || b == 0) return rc;
+    rc = zero_outputs(b, n, new_offset, status, nullptr, stream);
+    if (rc != ROITR_OK || n == 0) return rc;
     const OlWs w = carve(workspace, b, n, 0);
     outlier_prepare_kernel<<<div_up(n, OL_THREADS), OL_THREADS, 0, stream>>>(b, n, xyz, offset, w.clean, w.cloud, status);
     ROITR_LAUNCH_CHECK();

@@ -15,6 +15,7 @@
 // distance filter.  The list: count pass, exclusive scan (tile sums, one-wave scan, positions), fill pass into a candidate buffer in
 // walk order, then one WAVE per run ranks its candidates by (d2, j) and scatters the first K to their final places -- a long run
 // occupies one wave's 64 lanes, never one lane.  No host synchronisation, no float atomics, no workgroup waits for another.
+#include "cloud_status.h"
 #include "common.h"
 #include "knn_grid.h"
 #include "roitr_pointops.h"
@@ -68,11 +69,8 @@ PgWs carve(void* ws, int b, int n, int m, i64 capacity)
     return w;
 }
 
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
 // One thread per pair, per query point and per searched point: the status bits (integer atomicOr on a word the host zeroed), and the
-// copy of the searched points the grid is built on (a non-finite coordinate becomes 0 there: its pair is skipped by every later kernel,
-// the copy only keeps such values away from the grid's cell arithmetic).
+// copy of the searched points the grid is built on (store_clean of cloud_status.h).
 __global__ __launch_bounds__(PG_THREADS) void pairgt_prepare_kernel(int b, int n, int m, const float* __restrict__ src,
                                                                     const int* __restrict__ src_offset, const float* __restrict__ tgt,
                                                                     const int* __restrict__ tgt_offset, const float* __restrict__ rot,
@@ -94,7 +92,7 @@ __global__ __launch_bounds__(PG_THREADS) void pairgt_prepare_kernel(int b, int n
         const float x = tgt[(size_t)t * 3], y = tgt[(size_t)t * 3 + 1], z = tgt[(size_t)t * 3 + 2];
         const bool ok = finite3(x, y, z);
         if (!ok) atomicOr(&status[segment_of(t, tgt_offset, b)], PG_NONFINITE);
-        clean[(size_t)t * 3] = ok ? x : 0.f; clean[(size_t)t * 3 + 1] = ok ? y : 0.f; clean[(size_t)t * 3 + 2] = ok ? z : 0.f;
+        store_clean(clean, t, x, y, z, ok);
     }
 }
 

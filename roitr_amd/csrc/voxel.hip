@@ -20,6 +20,7 @@
 // >> 16 (48 bits), the `limit` points of smallest (u, j) are kept, reported as ascending global row indices.  The same sort on
 // cloud | u (stable: ties fall to the smaller j).  The selection is a function of (seed, key, cloud size, limit) alone.
 #include "common.h"
+#include "flag_compact.h"
 #include "registration_math.h"
 #include "roitr_pointops.h"
 #include "workspace.h"
@@ -30,9 +31,9 @@ namespace {
 
 typedef unsigned long long u64;
 
-constexpr int VX_THREADS = 256;
-constexpr int VX_ITEMS = 16;
-constexpr int VX_TILE = VX_THREADS * VX_ITEMS;   // items per workgroup of every tiled kernel here
+constexpr int VX_THREADS = FLAG_THREADS;
+constexpr int VX_ITEMS = FLAG_ITEMS;
+constexpr int VX_TILE = FLAG_TILE;   // items per workgroup of every tiled kernel here: the sort's tiles are the flag tiles
 constexpr int VX_WAVES = VX_THREADS / 64;
 constexpr int VX_RADIX = 256;
 constexpr int VX_PASSES = 8;
@@ -48,8 +49,8 @@ struct Workspace {
     int* bintotal;      // VX_RADIX
     u64* andor;         // all_and, all_or over the keys of the call
     unsigned* bounds;   // (b, 3) order-preserving images of the per-cloud minima
-    unsigned char* flag;   // nblk * VX_TILE
-    int* blocksum;      // nblk + 1 (the last entry: total)
+    unsigned char* flag;   // n, no padding is read
+    int* blocksum;      // tile sums of the flags -> exclusive bases (flag_compact.h), the last entry: total
     int* start;         // n: first sorted position of every voxel
     size_t bytes;
 };
@@ -67,8 +68,8 @@ static Workspace carve(void* ws, int b, int n)
     w.bintotal = c.take<int>(VX_RADIX);
     w.andor = c.take<u64>(2);
     w.bounds = c.take<unsigned>((size_t)(b > 0 ? b : 1) * 3);
-    w.flag = c.take<unsigned char>(nblk * VX_TILE);
-    w.blocksum = c.take<int>(nblk + 1);
+    w.flag = c.take<unsigned char>(nblk * VX_TILE);   // n of them are used; the size callers are told stays what it has always been
+    w.blocksum = c.take<int>((size_t)flag_tiles(n) + 1);
     w.start = c.take<int>(n);
     w.bytes = c.bytes + 256;   // room to align the caller's pointer
     return w;
@@ -373,20 +374,18 @@ __global__ __launch_bounds__(VX_THREADS) void sort_scatter_kernel(int n, int nbl
     }
 }
 
-// ------------------------------------------------------------------ flags -> ordered positions (tile sums, scan, final pass)
+// ------------------------------------------------------------------ flags -> ordered positions (flag_compact.h: tile sums, scan; the final
+// pass of the cap is that file's compaction, the one of the voxels is voxel_assign_kernel on its tile_inclusive)
 // voxel heads in the sorted order: the first point of every run of equal keys, none in a cloud with a status bit
 __global__ __launch_bounds__(VX_THREADS) void voxel_heads_kernel(int n, const u64* __restrict__ andor, const u64* __restrict__ key0,
                                                                  const u64* __restrict__ key1, const int* __restrict__ status,
                                                                  unsigned char* __restrict__ flag)
 {
     const u64* __restrict__ key = (live_below(andor, VX_PASSES) & 1) ? key1 : key0;
-    const int i = blockIdx.x * VX_THREADS + threadIdx.x;   // the grid covers the padded flag array
-    unsigned char f = 0;
-    if (i < n) {
-        const u64 k = key[i];
-        f = status[(int)(k >> 48)] == 0 && (i == 0 || key[i - 1] != k);
-    }
-    flag[i] = f;
+    const int i = blockIdx.x * VX_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const u64 k = key[i];
+    flag[i] = status[(int)(k >> 48)] == 0 && (i == 0 || key[i - 1] != k);
 }
 
 // the cap: sorted position inside the cloud below the limit -> the point is kept (flag in INPUT order; the array arrives zeroed)
@@ -402,51 +401,6 @@ __global__ __launch_bounds__(VX_THREADS) void subsample_keep_kernel(int n, int l
     if (i - (c ? offset[c - 1] : 0) < limit) flag[(odd ? pay1 : pay0)[i]] = 1;
 }
 
-__device__ __forceinline__ int flags16(const unsigned char* __restrict__ flag, int at)
-{
-    const uint4 v = *reinterpret_cast<const uint4*>(flag + at);
-    return __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);   // flags are 0 / 1
-}
-
-__global__ __launch_bounds__(VX_THREADS) void flag_sums_kernel(const unsigned char* __restrict__ flag, int* __restrict__ blocksum)
-{
-    __shared__ int wsum[VX_WAVES];
-    const int s = block_incl_scan<VX_THREADS>(flags16(flag, blockIdx.x * VX_TILE + threadIdx.x * VX_ITEMS), wsum);
-    if (threadIdx.x == VX_THREADS - 1) blocksum[blockIdx.x] = s;
-}
-
-// one block: exclusive scan of the tile sums in place, the total behind them
-__global__ __launch_bounds__(VX_THREADS) void flag_scan_kernel(int nblk, int* __restrict__ blocksum)
-{
-    __shared__ int wsum[VX_WAVES];
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int s = 0; s < nblk; s += VX_THREADS) {
-        const int j = s + threadIdx.x;
-        const int v = j < nblk ? blocksum[j] : 0;
-        const int end = block_running_scan<VX_THREADS>(v, wsum, &carry);
-        if (j < nblk) blocksum[j] = end - v;
-    }
-    if (threadIdx.x == 0) blocksum[nblk] = carry;
-}
-
-// inclusive count of flags up to every item of the tile, into LDS
-__device__ __forceinline__ void tile_inclusive(const unsigned char* __restrict__ flag, const int* __restrict__ blocksum, int* incl_s, int* wsum)
-{
-    const int at = blockIdx.x * VX_TILE + threadIdx.x * VX_ITEMS;
-    const uint4 v = *reinterpret_cast<const uint4*>(flag + at);
-    const int mine = __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);
-    int s = blocksum[blockIdx.x] + block_incl_scan<VX_THREADS>(mine, wsum) - mine;
-    const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int k = 0; k < VX_ITEMS; ++k) {
-        s += (w[k >> 2] >> (8 * (k & 3))) & 1u;
-        incl_s[threadIdx.x * VX_ITEMS + k] = s;
-    }
-    __syncthreads();
-}
-
 // sorted position -> voxel id: inverse, the first position of every voxel, and new_offset at the cloud boundaries (the cloud id is in
 // the key, clouds without points take the count of the cloud before them)
 __global__ __launch_bounds__(VX_THREADS) void voxel_assign_kernel(int b, int n, const u64* __restrict__ andor, const u64* __restrict__ key0,
@@ -460,7 +414,7 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_assign_kernel(int b, int n, 
     const bool odd = live_below(andor, VX_PASSES) & 1;
     const u64* __restrict__ key = odd ? key1 : key0;
     const unsigned* __restrict__ pay = odd ? pay1 : pay0;
-    tile_inclusive(flag, blocksum, incl_s, wsum);
+    tile_inclusive(n, flag, blocksum, incl_s, wsum);
     for (int r = 0; r < VX_ITEMS; ++r) {
         const int j = r * VX_THREADS + threadIdx.x, i = blockIdx.x * VX_TILE + j;
         if (i >= n) break;
@@ -510,20 +464,6 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_mean_kernel(int n, int c, co
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) if (k < m) out_attr[(size_t)v * c + ch + k] = (float)(s[k] / dn);
-    }
-}
-
-// kept rows in ascending input order
-__global__ __launch_bounds__(VX_THREADS) void subsample_compact_kernel(int n, const unsigned char* __restrict__ flag, const int* __restrict__ blocksum,
-                                                                       int* __restrict__ idx)
-{
-    __shared__ int incl_s[VX_TILE];
-    __shared__ int wsum[VX_WAVES];
-    tile_inclusive(flag, blocksum, incl_s, wsum);
-    for (int r = 0; r < VX_ITEMS; ++r) {
-        const int j = r * VX_THREADS + threadIdx.x, i = blockIdx.x * VX_TILE + j;
-        if (i >= n) break;
-        if (flag[i]) idx[incl_s[j] - 1] = i;
     }
 }
 
@@ -578,19 +518,11 @@ extern "C" int roitr_voxel_downsample(int b, int n, const float* xyz, const int*
                                       float* out_xyz, int* new_offset, int* out_count, int* inverse, float* out_attr, int* status, void* ws,
                                       hipStream_t stream)
 {
-    if (!(voxel_size > 0.0) || !std::isfinite(voxel_size)) {
-        roitr_set_error("voxel_downsample: voxel_size must be finite and positive", __FILE__, __LINE__);
-        return ROITR_ERR_ARG;
-    }
-    if (b <= 0 || b > VX_MAX_CLOUDS) {
-        roitr_set_error("voxel_downsample: the key holds 16 bits of cloud id (1 <= b <= 65536)", __FILE__, __LINE__);
-        return ROITR_ERR_ARG;
-    }
-    if (n < 0 || c < 0 || n > 0x7fffffff - VX_TILE) return ROITR_ERR_ARG;
-    if (!offset || !new_offset || !status || (n > 0 && (!xyz || !out_xyz || !out_count || !inverse || !ws)) || (n > 0 && c > 0 && (!attr || !out_attr))) {
-        roitr_set_error("voxel_downsample: null pointer", __FILE__, __LINE__);
-        return ROITR_ERR_ARG;
-    }
+    if (!(voxel_size > 0.0) || !std::isfinite(voxel_size)) return refuse(ROITR_ERR_ARG, "voxel_downsample: voxel_size must be finite and positive");
+    if (b <= 0 || b > VX_MAX_CLOUDS) return refuse(ROITR_ERR_ARG, "voxel_downsample: the key holds 16 bits of cloud id (1 <= b <= 65536)");
+    if (n < 0 || c < 0 || n > 0x7fffffff - VX_TILE) return refuse(ROITR_ERR_ARG, "voxel_downsample: point or channel count out of range");
+    if (!offset || !new_offset || !status || (n > 0 && (!xyz || !out_xyz || !out_count || !inverse || !ws)) || (n > 0 && c > 0 && (!attr || !out_attr)))
+        return refuse(ROITR_ERR_ARG, "voxel_downsample: null pointer");
     ROITR_HIP(hipMemsetAsync(status, 0, (size_t)b * 4, stream));
     if (n == 0) {
         ROITR_HIP(hipMemsetAsync(new_offset, 0, (size_t)b * 4, stream));
@@ -606,9 +538,8 @@ extern "C" int roitr_voxel_downsample(int b, int n, const float* xyz, const int*
     ROITR_LAUNCH_CHECK();
     rc = radix_sort(w, b, n, stream);
     if (rc != ROITR_OK) return rc;
-    voxel_heads_kernel<<<nblk * VX_ITEMS, VX_THREADS, 0, stream>>>(n, w.andor, w.key[0], w.key[1], status, w.flag);
-    flag_sums_kernel<<<nblk, VX_THREADS, 0, stream>>>(w.flag, w.blocksum);
-    flag_scan_kernel<<<1, VX_THREADS, 0, stream>>>(nblk, w.blocksum);
+    voxel_heads_kernel<<<div_up(n, VX_THREADS), VX_THREADS, 0, stream>>>(n, w.andor, w.key[0], w.key[1], status, w.flag);
+    flag_tile_bases(n, w.flag, w.blocksum, stream);
     voxel_assign_kernel<<<nblk, VX_THREADS, 0, stream>>>(b, n, w.andor, w.key[0], w.key[1], w.pay[0], w.pay[1], status, w.flag, w.blocksum, inverse,
                                                          w.start, new_offset);
     // the voxel count stays on the device: the grid covers the capacity, lanes past the total leave at once
@@ -621,18 +552,9 @@ extern "C" int roitr_voxel_downsample(int b, int n, const float* xyz, const int*
 extern "C" int roitr_random_subsample(int b, int n, const int* offset, int limit, unsigned long long seed, const int* cloud_keys, int* idx,
                                       int* new_offset, void* ws, hipStream_t stream)
 {
-    if (b <= 0 || b > VX_MAX_CLOUDS) {
-        roitr_set_error("random_subsample: the key holds 16 bits of cloud id (1 <= b <= 65536)", __FILE__, __LINE__);
-        return ROITR_ERR_ARG;
-    }
-    if (limit <= 0 || n < 0 || n > 0x7fffffff - VX_TILE) {
-        roitr_set_error("random_subsample: limit must be positive", __FILE__, __LINE__);
-        return ROITR_ERR_ARG;
-    }
-    if (!offset || !new_offset || (n > 0 && (!idx || !ws))) {
-        roitr_set_error("random_subsample: null pointer", __FILE__, __LINE__);
-        return ROITR_ERR_ARG;
-    }
+    if (b <= 0 || b > VX_MAX_CLOUDS) return refuse(ROITR_ERR_ARG, "random_subsample: the key holds 16 bits of cloud id (1 <= b <= 65536)");
+    if (limit <= 0 || n < 0 || n > 0x7fffffff - VX_TILE) return refuse(ROITR_ERR_ARG, "random_subsample: limit must be positive");
+    if (!offset || !new_offset || (n > 0 && (!idx || !ws))) return refuse(ROITR_ERR_ARG, "random_subsample: null pointer");
     if (n == 0) {
         ROITR_HIP(hipMemsetAsync(new_offset, 0, (size_t)b * 4, stream));
         return ROITR_OK;
@@ -641,15 +563,13 @@ extern "C" int roitr_random_subsample(int b, int n, const int* offset, int limit
     const int nblk = div_up(n, VX_TILE);
     int rc = init_andor(w, stream);
     if (rc != ROITR_OK) return rc;
-    ROITR_HIP(hipMemsetAsync(w.flag, 0, (size_t)nblk * VX_TILE, stream));
+    ROITR_HIP(hipMemsetAsync(w.flag, 0, (size_t)n, stream));
     subsample_keys_kernel<<<nblk, VX_THREADS, 0, stream>>>(b, n, offset, seed, cloud_keys, w.key[0], w.pay[0], w.andor);
     ROITR_LAUNCH_CHECK();
     rc = radix_sort(w, b, n, stream);
     if (rc != ROITR_OK) return rc;
     subsample_keep_kernel<<<div_up(n, VX_THREADS), VX_THREADS, 0, stream>>>(n, limit, w.andor, w.key[0], w.key[1], w.pay[0], w.pay[1], offset, w.flag);
-    flag_sums_kernel<<<nblk, VX_THREADS, 0, stream>>>(w.flag, w.blocksum);
-    flag_scan_kernel<<<1, VX_THREADS, 0, stream>>>(nblk, w.blocksum);
-    subsample_compact_kernel<<<nblk, VX_THREADS, 0, stream>>>(n, w.flag, w.blocksum, idx);
+    flag_compact(n, w.flag, w.blocksum, idx, nullptr, stream);
     subsample_offset_kernel<<<1, VX_THREADS, 0, stream>>>(b, limit, offset, new_offset);
     ROITR_LAUNCH_CHECK();
     return ROITR_OK;

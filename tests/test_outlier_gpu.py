@@ -2,7 +2,10 @@
 tests/outlier_util.py on fixtures that test_outlier_cpu.py asserts decided.  Exact: keep, index, new_offset, count, status.  mean_dist
 within 1e-12 relative (at most 100 ordered adds of terms good to one float64 ulp: 100 * 2^-52 = 2.2e-14; measured 0: the device's float64
 sqrt rounds correctly), stats within 1e-10 relative (the squared-deviation sum amplifies the term error by about 2 mean / std).
-Bitwise invariance, the refusals, and nothing written behind the kept rows."""
+Bitwise invariance, the refusals, and nothing written behind the kept rows.  The flags become rows through csrc/flag_compact.h on tiles of
+4096 rows: TILE_CASES puts totals around one and two tiles, with the cloud boundary inside a tile and off a multiple of 16."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -71,6 +74,40 @@ def test_radius_filter_is_exact(name):
     assert got["count"].dtype == np.int32
     for k in RAD:
         assert np.array_equal(got[k], want[k]), (name, k, np.flatnonzero(got[k] != want[k])[:8] if got[k].shape == want[k].shape else got[k].shape)
+
+
+# total rows -> (rows of the first cloud, seed, nb_points): two surfaces of outlier_util.batch at radius 0.05.  nb_points sits near the
+# median count of the restatement (14 - 16 for 1500 + 2600 rows, 28 for 4100 + 4093), so about half of the rows are kept.
+TILE_CASES = {4095: (1500, 21, 14), 4096: (1500, 22, 14), 4097: (1500, 23, 14), 8193: (4100, 24, 28)}
+
+
+@functools.lru_cache(maxsize=None)
+def tile_fixture(total):
+    first, seed, nb_points = TILE_CASES[total]
+    return U.batch(seed, [first, total - first], radius=0.05, nb_points=nb_points)
+
+
+@pytest.mark.parametrize("total", sorted(TILE_CASES))
+def test_radius_filter_is_exact_across_compaction_tiles(total):
+    f = tile_fixture(total)
+    want, got = U.radius_ref(**f), run(f, "radius")
+    share = float(want["keep"].mean())
+    print(total, "kept share", share)
+    assert 0.25 < share < 0.75, (total, share)        # a fixture that keeps all or nothing would test no compaction
+    for k in RAD:
+        assert np.array_equal(got[k], want[k]), (total, k, np.flatnonzero(got[k] != want[k])[:8] if got[k].shape == want[k].shape else got[k].shape)
+
+
+def test_statistical_filter_across_a_compaction_tile():
+    f = U.batch(31, [1500, 2597])
+    assert U.is_decided(f)
+    want, got = U.statistical_ref(**f), run(f, "statistical")
+    for k in ("status", "keep", "index", "new_offset"):
+        assert np.array_equal(got[k], want[k]), (k, np.flatnonzero(got[k] != want[k])[:8] if got[k].shape == want[k].shape else got[k].shape)
+    e_mean, e_stats = rel(got["mean"], want["mean"]), rel(got["stats"], want["stats"])
+    print("max relative error: mean_dist", e_mean, "stats", e_stats)
+    assert e_mean < 1e-12 and e_stats < 1e-10, (e_mean, e_stats)
+    assert 0 < want["index"].shape[0] < 4097
 
 
 @pytest.mark.parametrize("method,keys", [("statistical", STAT), ("radius", RAD)])
@@ -160,6 +197,22 @@ def test_nothing_is_written_behind_the_kept_rows():
         assert bool((t["mean"][n:] == -7).all()) and bool((t["stats"][b:] == -7).all()) and bool((t["count"][n:] == -7).all())
         for key in ("index", "keep"):
             t[key].fill_(7 if key == "keep" else -7)
+    # Rows behind offset[b - 1] (n = 4100, the last offset 4090, past one compaction tile) belong to no cloud: never kept, counted 0, and
+    # index stays untouched behind the total.  The radius filter only: the statistical one hands all n rows to the kNN of
+    # pointops_knn.hip, whose self-sorted query order is defined for the rows of a cloud alone.
+    whole = U.batch(25, [1500, 2600], radius=0.05, nb_points=14)
+    inside = dict(whole, xyz=whole["xyz"][:4090], offset=np.array([1500, 4090], np.int32))
+    f = dict(inside, xyz=whole["xyz"])
+    want = U.radius_ref(**inside)
+    lib, t, _, call = raw_calls(f)
+    assert call("radius") == 0
+    torch.cuda.synchronize()
+    m = int(want["new_offset"][-1])
+    assert 0.25 * 4090 < m < 0.75 * 4090
+    assert np.array_equal(t["index"][:m].cpu().numpy(), want["index"]) and bool((t["index"][m:] == -7).all())
+    assert np.array_equal(t["keep"][:4090].cpu().numpy(), want["keep"].astype(np.uint8)) and not t["keep"][4090:4100].any()
+    assert bool((t["keep"][4100:] == 7).all()) and np.array_equal(t["new_offset"][:2].cpu().numpy(), want["new_offset"])
+    assert np.array_equal(t["count"][:4090].cpu().numpy(), want["count"]) and not t["count"][4090:4100].any()
 
 
 def test_refusals_and_empty_input():
