@@ -259,6 +259,17 @@ typedef struct RoitrLocalFirst {
 } RoitrLocalFirst;
 int roitr_local_first(const RoitrLocalFirst* a, roitr_stream_t stream);
 
+/* The form the engine runs one local transformer in (csrc/engine.cpp; the table in DESIGN.md): decided once, at finalize, from the
+ * layer's shapes (in_dim -> H -> out_dim), its neighbour count K, its role (transition_down != 0: the transformer of a TransitionDown,
+ * rows sampled by node_idx; 0: of a block, with the bn2 residual) and the engine's operand_dtype, through the *_supported predicates
+ * above.  Pure host code: no engine, no device.  fp32 (0) and the three-way split (2) choose alike. */
+#define ROITR_LOCAL_FIRST 0        /* roitr_local_first */
+#define ROITR_LOCAL_FUSED_BLOCK 1  /* k | v GEMM + roitr_local_block */
+#define ROITR_LOCAL_FUSED_TD 2     /* roitr_local_td */
+#define ROITR_LOCAL_TD_FOLD 3      /* roitr_local_attention_fold between its GEMMs */
+#define ROITR_LOCAL_SEQUENCE 4     /* one launch per step around roitr_local_attention */
+int roitr_local_form(int in_dim, int H, int out_dim, int K, int transition_down, int operand_dtype);
+
 /* Fragment-ordered copies of the fp32 weights that the on-chip GEMMs of the three launches above read (csrc/local_block.hip
  * gemm_phase).  Weights stay the same from call to call in real use, so the copy is made once: for every 32-row region and every
  * 32-k slab of W one 4 KB block of four groups of 64 float4 in the order a wave consumes them, (c, n) = (0,0), (0,1), (1,0), (1,1);

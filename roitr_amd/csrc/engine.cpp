@@ -43,23 +43,34 @@ struct Lin {
     const unsigned short* wb = nullptr;   // the weight stored in bf16 (operand_dtype = 1 only)
 };
 
+// How the forward runs one local transformer (roitr_local_form, include/roitr_engine.h; the table in DESIGN.md)
+enum LocalForm { FIRST = ROITR_LOCAL_FIRST, FUSED_BLOCK = ROITR_LOCAL_FUSED_BLOCK, FUSED_TD = ROITR_LOCAL_FUSED_TD, TD_FOLD = ROITR_LOCAL_TD_FOLD,
+                 SEQUENCE = ROITR_LOCAL_SEQUENCE };
+
 struct LocalT {  // LocalPPFTransformer (+ derived weights)
     Lin emb, in_proj, q, k, v, p, vp, lin, out_proj;
     const float* norm_w = nullptr; const float* norm_b = nullptr;
     int in_dim = 0, H = 0, out_dim = 0;
+    int K = 0;          // neighbours per node
+    float scale = 0.f;  // 1 / sqrt(channels per head)
+    bool td = false;    // the transformer of a TransitionDown (rows sampled by node_idx, no bn2 residual); false: of a block
+    // set by fold_local():
+    LocalForm form = SEQUENCE;
+    bool from_x = false;   // in_proj is folded into the q | k | v projections (wqkv_x): they read the layer input, not f = in_proj(x)
     float* wqkv = nullptr;  // rows: [Wq (H) ; Wk (H) ; Wv (H)] x H
     unsigned short* wqkv_b = nullptr;   // the same, stored bf16 (operand_dtype = 1)
     float* bqkv = nullptr;
     // TransitionDown transformers (in_dim != H): [q|k|v] straight from the layer input, W' = Wqkv Win (R x in_dim),
     // b' = Wqkv b_in + bqkv -- in_proj and the q/k/v projections are two linear maps with nothing in between
     float* wqkv_x = nullptr; float* bqkv_x = nullptr; unsigned short* wqkv_x_b = nullptr;
-    float* wkT_x = nullptr;                        // (in_dim, H): transpose of the k rows of wqkv_x (TransitionDown fold, fp32)
-    // TransitionDown fold at in_dim = 64 (round 5): q AND q~ from one GEMM over the gathered input rows --
+    float* wkT_x = nullptr;                        // (in_dim, H): transpose of the k rows of wqkv_x (TD_FOLD, FUSED_TD)
+    // FUSED_TD: q AND q~ from one on-chip GEMM over the gathered input rows --
     // rows 0 .. H-1 = Wq' (q = Wq' x + bq), rows H + h in_dim + i = (Wk'_h^T Wq'_h)[i, :] (q~_h = Wk'_h^T q_h); ((H + 4 in_dim), in_dim)
     float* wqqt_x = nullptr; float* bqqt_x = nullptr;
-    // block transformers in fp32: linear(att) + in_proj(x) as ONE GEMM over the K-concatenated operand [att | x]:
-    // wcat = [Wlin | Win] (H x (H + in_dim)), bcat = b_lin + b_in; f = in_proj(x) is then never materialised
-    float* wcat = nullptr; float* bcat = nullptr; unsigned short* wcat_b = nullptr;   // wcat_b: bf16 copy (bf16 operand mode, fused block)
+    // linear(att) + in_proj(x) as ONE GEMM over the K-concatenated operand [att | x]: cat.w = [Wlin | Win] (H x (H + in_dim)),
+    // cat.b = b_lin + b_in; f = in_proj(x) is then never materialised
+    Lin cat;
+    unsigned short* wcat_b = nullptr;   // cat.w stored bf16 (bf16 operand mode, fused block)
     // the PPF coefficient rows of the query, qp[h] = [Wpe_h^T q_h, q_h . bpe_h], are computed inside the attention kernel from
     // wpe (H,4) / bpe (H): [q|k|v] is 3 H wide = whole 64-column GEMM tiles (as 5 extra GEMM columns per head it was 212 wide: one
     // 64-column tile in four was 31 % full)
@@ -264,35 +275,16 @@ int use_bf16(RoitrGemm& g, const float* W, const unsigned short* Wb, int bf)
     if (bf) { roitr_set_error("engine: bf16-stored activation routed to an fp32 layer", __FILE__, __LINE__); return ROITR_ERR_ARG; }
     return 0;
 }
-int gemm(hipStream_t st, int M, int N, int K, const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc,
-         bool relu = false, const int* a_idx = nullptr, const float* A2 = nullptr, float alpha = 1.0f, const unsigned short* Wb = nullptr,
-         int bf = 0)
-{
-    RoitrGemm g;
-    memset(&g, 0, sizeof(g));
-    g.M = M; g.N = N; g.K = K; g.A = A; g.A2 = A2; g.lda = lda; g.a_idx = a_idx; g.W = W; g.ldw = ldw; g.bias = bias;
-    g.alpha = alpha; g.relu = relu ? 1 : 0; g.C = C; g.ldc = ldc; g.batch = 1;
-    CHK(use_bf16(g, W, Wb, bf));
-    CHK(use_x3(g, st));
-    return roitr_gemm(&g, st);
-}
-int gemm(hipStream_t st, int M, const float* A, const Lin& l, float* C, bool relu = false, const int* a_idx = nullptr, const float* A2 = nullptr,
-         int bf = 0)
-{
-    return gemm(st, M, l.out, l.in, A, l.in, l.w, l.in, l.b, C, l.out, relu, a_idx, A2, 1.0f, l.wb, bf);
-}
 
 // nn.Linear followed by (+ residual) LayerNorm (+ post-add) (ReLU): one launch when the layer is 64 wide (the LayerNorm
 // runs in the GEMM epilogue, the (M, 64) intermediate never reaches HBM), the two-launch sequence otherwise.
-// `tmp` (M x l.out) is only touched by the two-launch form.
+// `tmp` (M x N) is only touched by the two-launch form.
 // The fused form is bitwise the two-launch result, so the choice may depend on the row count without breaking batch invariance.
 // 64 / 128 columns: always fused.  256 columns (fp32 operand mode only; bf16 and the three-way split keep their paths): fused on the
 // 32 x 256 tile of gemm_ln256.hip from LN256_MIN_ROWS rows, see ln256_fuses() for what was measured.
-// TransitionUp's interpolation addend (RoitrGemm::ip_*): rows of `feat` (l.out floats) mixed by the 3-NN of every output row
-struct Interp3 { const float* feat; const int* idx; const float* dist2; };
-bool ln_fuses(int N, int K, int lda, int ldw)
+bool ln_fuses(const RoitrGemm& g)
 {
-    return (N == 64 || N == 128) && K % 32 == 0 && lda % 4 == 0 && ldw % 4 == 0;
+    return (g.N == 64 || g.N == 128) && g.K % 32 == 0 && g.lda % 4 == 0 && g.ldw % 4 == 0;
 }
 // The 256-wide layers (levels 3 - 4, the global transformer, dec4 / dec3).  Measured per shape, events, the forms alternated
 // (scripts/bench_gemm_ln.py, profiles/ln256_shapes.txt), fused 32 x 256 launch against GEMM + add_layernorm, K = 256 / 384 / 512, five
@@ -302,53 +294,76 @@ bool ln_fuses(int N, int K, int lda, int ldw)
 // smallest measured size that won.  The 64 x 256 instantiation of the general kernel loses to both at 39 936 rows and below and to the
 // 32 x 256 tile everywhere (it reaches 0.83 - 0.98 of two launches at 319 488 / 79 872 rows).  Per 512-pair step: 78.63 -> 77.55 ms.
 // K above LN256_MAX_K was not measured (no such layer).
-bool ln256_fuses(int M, int N, int K, int lda, int ldw, const Lin& l, int bf)
+bool ln256_fuses(const RoitrGemm& g, bool bf16_asked)
 {
     const Engine* E = g_engine;
-    if (!E || E->cfg.operand_dtype != 0 || l.wb || bf) return false;
-    return N == 256 && K % 32 == 0 && K <= LN256_MAX_K && lda % 4 == 0 && ldw % 4 == 0 && M >= E->ln256_min_rows;
+    if (!E || E->cfg.operand_dtype != 0 || bf16_asked) return false;
+    return g.N == 256 && g.K % 32 == 0 && g.K <= LN256_MAX_K && g.lda % 4 == 0 && g.ldw % 4 == 0 && g.M >= E->ln256_min_rows;
 }
-// bf: ROITR_BF16_A (A stored bf16; lda in elements) and / or ROITR_BF16_C (out stored bf16: fused form only)
-// A_cat (optional): the second K-half of the operand, [A | A_cat] with A (M, k_cat) dense and A_cat (M, l.in - k_cat) of leading
-// dimension lda_cat (fp32 kernels only)
-int gemm_ln(hipStream_t st, int M, const float* A, const Lin& l, const float* res, const int* res_idx, const float* gamma,
-            const float* beta, const float* post, bool relu, float* tmp, float* out, int bf = 0, const float* A_cat = nullptr,
-            int lda_cat = 0, int k_cat = 0, const float* A2 = nullptr, const Interp3* ip = nullptr, const int* a_cat_idx = nullptr)
-{
-    const float* w = l.w;
-    const float* b = l.b;
-    const int K = l.in, N = l.out;
-    const int lda = A_cat ? k_cat : K, ldw = K;
-    // measured per 128-pair forward: fusing the 64-wide layers -1.55 ms, + the 128-wide ones -0.4 ms
-    // res gathered by res_idx from the buffer the launch writes: another block may have stored the row already (no such call site)
-    const bool gather_in_place = res_idx && res == out;
-    if (ln_fuses(N, K, lda, ldw) || (ln256_fuses(M, N, K, lda, ldw, l, bf) && !gather_in_place)) {
-        RoitrGemm g;
-        memset(&g, 0, sizeof(g));
-        g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.W = w; g.ldw = ldw; g.bias = b; g.alpha = 1.0f; g.C = out; g.ldc = N; g.batch = 1;
-        g.ln_gamma = gamma; g.ln_beta = beta; g.ln_res = res; g.ln_res_idx = res_idx; g.ln_post = post; g.ln_relu = relu ? 1 : 0; g.ln_eps = 1e-5f;
-        g.A_cat = A_cat; g.lda_cat = lda_cat; g.k_cat = k_cat; g.A2 = A2;   // A2 (optional): the operand is A + A2
-        g.a_cat_idx = a_cat_idx;
-        if (ip) { g.ip_feat = ip->feat; g.ip_idx = ip->idx; g.ip_dist2 = ip->dist2; }
-        CHK(use_bf16(g, w, l.wb, bf));
-        return roitr_gemm(&g, st);
+
+// One GEMM of the engine: the launch arguments (RoitrGemm) with every optional part named, the operand-mode choice in run(), and
+// the Linear + LayerNorm rule above in run_ln().  This is the only place a RoitrGemm is zeroed.
+struct Gemm : RoitrGemm {
+    const unsigned short* wb = nullptr;   // the weight stored bf16 (operand_dtype = 1); run() takes the bf16 kernel where it fits
+    int bf = 0;                           // ROITR_BF16_A / ROITR_BF16_C: A is / C shall be stored bf16 (an error on an fp32 kernel)
+    bool w_is_weight = true;              // false: W is an activation -- never a cached three-way split (operand_dtype = 2)
+    struct {                              // LayerNorm epilogue of run_ln(): out = [relu](LN(C + res[res_idx]) * gamma + beta + post) (+ interp)
+        const float *gamma, *beta, *res; const int* res_idx; const float* post; bool relu;
+        const float* ip_feat; const int* ip_idx; const float* ip_dist2;
+    } e = {};
+
+    Gemm(int M_, int N_, int K_, const float* A_, int lda_, const float* W_, int ldw_, const float* bias_, float* C_, int ldc_)
+    {
+        memset(static_cast<RoitrGemm*>(this), 0, sizeof(RoitrGemm));
+        M = M_; N = N_; K = K_; A = A_; lda = lda_; W = W_; ldw = ldw_; bias = bias_; C = C_; ldc = ldc_; alpha = 1.0f; batch = 1;
     }
-    if (bf & ROITR_BF16_C) { roitr_set_error("engine: bf16 LayerNorm output needs the fused epilogue", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-    if (A_cat) {
-        RoitrGemm g;
-        memset(&g, 0, sizeof(g));
-        g.M = M; g.N = N; g.K = K; g.A = A; g.lda = lda; g.W = w; g.ldw = ldw; g.bias = b; g.alpha = 1.0f; g.C = tmp; g.ldc = N; g.batch = 1;
-        g.A_cat = A_cat; g.lda_cat = lda_cat; g.k_cat = k_cat; g.A2 = A2; g.a_cat_idx = a_cat_idx;
-        CHK(use_x3(g, st));
-        CHK(roitr_gemm(&g, st));
-    } else
-    CHK(gemm(st, M, N, K, A, lda, w, ldw, b, tmp, N, false, nullptr, A2, 1.0f, l.wb, bf));
-    if (ip) {
-        if (post) { roitr_set_error("engine: interpolation addend and post-add together", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-        return roitr_add_layernorm_interp(M, N, tmp, res, res_idx, gamma, beta, relu ? 1 : 0, 1e-5f, ip->feat, ip->idx, ip->dist2, out, st);
+    Gemm(int M_, const float* A_, const Lin& l, float* C_) : Gemm(M_, l.out, l.in, A_, l.in, l.w, l.in, l.b, C_, l.out) { wb = l.wb; }
+
+    Gemm& with_relu() { relu = 1; return *this; }
+    Gemm& gather(const int* idx) { a_idx = idx; return *this; }                   // row r of the operand is A[idx[r]]
+    Gemm& plus(const float* A2_) { A2 = A2_; return *this; }                      // the operand is A + A2
+    // the operand is [A | A_cat]: A dense (M, k_cat), A_cat of leading dimension lda_cat, rows optionally gathered by a_cat_idx (fp32 only)
+    Gemm& cat(const float* Ac, int ldac, int kc, const int* idx = nullptr) { A_cat = Ac; lda_cat = ldac; k_cat = kc; a_cat_idx = idx; lda = kc; return *this; }
+    Gemm& heads(int batch_, long sA_, long sW_, long sC_, long sBias_ = 0) { batch = batch_; sA = sA_; sW = sW_; sC = sC_; sBias = sBias_; return *this; }
+    Gemm& bf16_weight(const unsigned short* wb_) { wb = wb_; return *this; }
+    Gemm& stored(int bf_) { bf = bf_; return *this; }
+    Gemm& activations() { w_is_weight = false; return *this; }
+    Gemm& ln(const float* gamma, const float* beta, bool relu_ = false) { e.gamma = gamma; e.beta = beta; e.relu = relu_; return *this; }
+    Gemm& residual(const float* res, const int* res_idx = nullptr) { e.res = res; e.res_idx = res_idx; return *this; }
+    Gemm& post(const float* p) { e.post = p; return *this; }
+    // TransitionUp's interpolation addend (RoitrGemm::ip_*): rows of `feat` (N floats) mixed by the 3-NN of every output row
+    Gemm& interp3(const float* feat, const int* idx, const float* dist2) { e.ip_feat = feat; e.ip_idx = idx; e.ip_dist2 = dist2; return *this; }
+
+    // The kernel choice of every launch: bf16 where a bf16 copy is given and fits (a K-concatenated operand is fp32-only: with A_cat
+    // a copy is never looked at, and a bf16 request stays the error it is on an fp32 kernel), then the three-way split of
+    // operand_dtype = 2 -- which itself refuses a bf16 launch, a batched one and one with a LayerNorm epilogue.
+    int run(hipStream_t st)
+    {
+        CHK(use_bf16(*this, W, A_cat ? nullptr : wb, bf));
+        if (w_is_weight) CHK(use_x3(*this, st));
+        return roitr_gemm(this, st);
     }
-    return roitr_add_layernorm(M, N, tmp, res, res_idx, gamma, beta, post, relu ? 1 : 0, 1e-5f, out, st);
-}
+    // Linear + LayerNorm into C; `tmp` (M x N) holds the GEMM's output where the two run as two launches
+    int run_ln(hipStream_t st, float* tmp)
+    {
+        // measured per 128-pair forward: fusing the 64-wide layers -1.55 ms, + the 128-wide ones -0.4 ms
+        // res gathered by res_idx from the buffer the launch writes: another block may have stored the row already (no such call site)
+        const bool gather_in_place = e.res_idx && e.res == C;
+        if (ln_fuses(*this) || (ln256_fuses(*this, wb || bf) && !gather_in_place)) {
+            ln_gamma = e.gamma; ln_beta = e.beta; ln_res = e.res; ln_res_idx = e.res_idx; ln_post = e.post; ln_relu = e.relu ? 1 : 0; ln_eps = 1e-5f;
+            ip_feat = e.ip_feat; ip_idx = e.ip_idx; ip_dist2 = e.ip_dist2;
+            return run(st);
+        }
+        if (bf & ROITR_BF16_C) { roitr_set_error("engine: bf16 LayerNorm output needs the fused epilogue", __FILE__, __LINE__); return ROITR_ERR_ARG; }
+        if (e.ip_feat && e.post) { roitr_set_error("engine: interpolation addend and post-add together", __FILE__, __LINE__); return ROITR_ERR_ARG; }
+        float* out = C;
+        C = tmp;
+        CHK(run(st));
+        if (e.ip_feat)
+            return roitr_add_layernorm_interp(M, N, tmp, e.res, e.res_idx, e.gamma, e.beta, e.relu ? 1 : 0, 1e-5f, e.ip_feat, e.ip_idx, e.ip_dist2, out, st);
+        return roitr_add_layernorm(M, N, tmp, e.res, e.res_idx, e.gamma, e.beta, e.post, e.relu ? 1 : 0, 1e-5f, out, st);
+    }
+};
 
 int d2d(hipStream_t st, void* dst, const void* src, size_t bytes)
 {
@@ -366,9 +381,10 @@ int tap(Engine& E, hipStream_t st, const std::string& name, void* data, size_t b
 }
 
 // ---------------------------------------------------------------- weight resolution + folding
-int resolve_local(Engine& E, LocalT& L, const std::string& pre, int in_dim, int H, int out_dim)
+int resolve_local(Engine& E, LocalT& L, const std::string& pre, int in_dim, int H, int out_dim, int K, bool td)
 {
-    L.in_dim = in_dim; L.H = H; L.out_dim = out_dim;
+    L.in_dim = in_dim; L.H = H; L.out_dim = out_dim; L.K = K; L.td = td;
+    L.scale = 1.0f / sqrtf((float)(H / HEADS));
     L.emb = lin(E, pre + ".embedding.proj", H, 4);
     L.in_proj = lin(E, pre + ".in_proj", H, in_dim);
     const std::string at = pre + ".transformer.attention";
@@ -392,6 +408,13 @@ void release_fragments(Engine& E)
     E.frag_weights.clear();
 }
 
+// bf16 operand mode: a derived weight, folded in fp32, stored once in bf16
+int bf16_copy(Engine& E, long n, const float* w, unsigned short*& wb, hipStream_t st)
+{
+    wb = E.warena.get<unsigned short>((size_t)n);
+    return E.warena.fail ? ROITR_ERR_ARG : roitr_f32_to_bf16(n, w, wb, st);
+}
+
 int fold_local(Engine& E, LocalT& L, hipStream_t st)
 {
     const int H = L.H;
@@ -409,98 +432,83 @@ int fold_local(Engine& E, LocalT& L, hipStream_t st)
     if (A.fail) return ROITR_ERR_ARG;
     // Wpe^T (4,H) = We^T (4,H) @ Wp^T ; bpe = Wp be + bp        (see csrc/local_attn.hip)
     CHK(roitr_transpose(H, 4, L.emb.w, 4, weT, H, st));
-    CHK(gemm(st, 4, H, H, weT, H, L.p.w, H, nullptr, wpeT, H));
+    CHK(Gemm(4, H, H, weT, H, L.p.w, H, nullptr, wpeT, H).run(st));
     CHK(roitr_transpose(4, H, wpeT, H, wpe, 4, st));
-    CHK(gemm(st, 1, H, H, L.emb.b, H, L.p.w, H, L.p.b, bpe, H));
+    CHK(Gemm(1, H, H, L.emb.b, H, L.p.w, H, L.p.b, bpe, H).run(st));
     L.wpe = wpe; L.bpe = bpe;
-    CHK(gemm(st, 4, H, H, weT, H, L.vp.w, H, nullptr, wvpeT, H));
+    CHK(Gemm(4, H, H, weT, H, L.vp.w, H, nullptr, wvpeT, H).run(st));
     CHK(roitr_transpose(4, H, wvpeT, H, L.wvpe, 4, st));
-    CHK(gemm(st, 1, H, H, L.emb.b, H, L.vp.w, H, L.vp.b, L.bvpe, H));
-    CHK(d2d(st, L.wqkv, L.q.w, sizeof(float) * (size_t)H * H));
-    CHK(d2d(st, L.wqkv + (size_t)H * H, L.k.w, sizeof(float) * (size_t)H * H));
-    CHK(d2d(st, L.wqkv + (size_t)(2 * H) * H, L.v.w, sizeof(float) * (size_t)H * H));
-    CHK(d2d(st, L.bqkv, L.q.b, sizeof(float) * H));
-    CHK(d2d(st, L.bqkv + H, L.k.b, sizeof(float) * H));
-    CHK(d2d(st, L.bqkv + 2 * H, L.v.b, sizeof(float) * H));
-    if (E.cfg.operand_dtype == 1) {   // folded in fp32, stored once in bf16
-        L.wqkv_b = A.get<unsigned short>((size_t)R * H);
-        if (A.fail) return ROITR_ERR_ARG;
-        CHK(roitr_f32_to_bf16((long)R * H, L.wqkv, L.wqkv_b, st));
+    CHK(Gemm(1, H, H, L.emb.b, H, L.vp.w, H, L.vp.b, L.bvpe, H).run(st));
+    const Lin* qkv[3] = {&L.q, &L.k, &L.v};
+    for (int j = 0; j < 3; ++j) {
+        CHK(d2d(st, L.wqkv + (size_t)j * H * H, qkv[j]->w, sizeof(float) * (size_t)H * H));
+        CHK(d2d(st, L.bqkv + j * H, qkv[j]->b, sizeof(float) * H));
     }
-    // bf16 operand mode (round 6): the block transformers of the 64- / 128-wide levels (in_dim == H <= 128, K = 8 / 16: exactly what
-    // roitr_local_block_supported takes) run in the fused kernel of csrc/local_block.hip as well, behind a bf16 k | v GEMM whose rows
-    // the kernel gathers as stored (RoitrLocalBlock::kv_bf16); the q projection, `linear`, the LayerNorms and out_proj inside the
-    // kernel are its fp32 arithmetic.  TransitionDown transformers (in_dim = H / 2) and the wider levels keep the bf16 launch sequence.
-    const bool cat = (E.cfg.operand_dtype != 1 || (L.in_dim == H && H <= 128)) && L.in_dim % 32 == 0;
-    if (cat) {
-        const int I = L.in_dim;
-        L.wcat = A.get<float>((size_t)H * (H + I));
-        L.bcat = A.get<float>(H);
+    const int I = L.in_dim;
+    const bool bf16 = E.cfg.operand_dtype == 1;
+    if (bf16) CHK(bf16_copy(E, (long)R * H, L.wqkv, L.wqkv_b, st));
+    // ---- the form the forward runs this layer in, and exactly the derived weights that form reads
+    L.form = (LocalForm)roitr_local_form(I, H, L.out_dim, L.K, L.td ? 1 : 0, E.cfg.operand_dtype);
+    L.from_x = I % 32 == 0 && (!bf16 || L.form == FUSED_BLOCK || (L.td && I != H));
+    const bool cat = L.form == FUSED_BLOCK || L.form == FUSED_TD || L.form == TD_FOLD || (L.form == SEQUENCE && L.from_x && !L.td);
+    if (cat) {   // [Wlin | Win], b_lin + b_in
+        float* wcat = A.get<float>((size_t)H * (H + I));
+        float* bcat = A.get<float>(H);
         if (A.fail) return ROITR_ERR_ARG;
-        ROITR_HIP(hipMemcpy2DAsync(L.wcat, sizeof(float) * (H + I), L.lin.w, sizeof(float) * H, sizeof(float) * H, H, hipMemcpyDeviceToDevice, st));
-        ROITR_HIP(hipMemcpy2DAsync(L.wcat + H, sizeof(float) * (H + I), L.in_proj.w, sizeof(float) * I, sizeof(float) * I, H, hipMemcpyDeviceToDevice, st));
-        CHK(roitr_add_vectors(H, L.lin.b, L.in_proj.b, L.bcat, st));
-        if (E.cfg.operand_dtype == 1) {
-            L.wcat_b = A.get<unsigned short>((size_t)H * (H + I));
-            if (A.fail) return ROITR_ERR_ARG;
-            CHK(roitr_f32_to_bf16((long)H * (H + I), L.wcat, L.wcat_b, st));
-        }
+        ROITR_HIP(hipMemcpy2DAsync(wcat, sizeof(float) * (H + I), L.lin.w, sizeof(float) * H, sizeof(float) * H, H, hipMemcpyDeviceToDevice, st));
+        ROITR_HIP(hipMemcpy2DAsync(wcat + H, sizeof(float) * (H + I), L.in_proj.w, sizeof(float) * I, sizeof(float) * I, H, hipMemcpyDeviceToDevice, st));
+        CHK(roitr_add_vectors(H, L.lin.b, L.in_proj.b, bcat, st));
+        L.cat.w = wcat; L.cat.b = bcat; L.cat.out = H; L.cat.in = H + I;   // (no Lin::wb: a K-concatenated GEMM is fp32-only)
+        if (bf16) CHK(bf16_copy(E, (long)H * (H + I), wcat, L.wcat_b, st));   // the fused block's on-chip `linear`
     }
-    if ((L.in_dim != H || cat) && L.in_dim % 32 == 0) {
-        const int I = L.in_dim;
+    if (L.from_x) {
         float* winT = A.get<float>((size_t)I * H);
         L.wqkv_x = A.get<float>((size_t)R * I);
         L.bqkv_x = A.get<float>(R);
         if (A.fail) return ROITR_ERR_ARG;
         CHK(roitr_transpose(H, I, L.in_proj.w, I, winT, H, st));                       // (in, H)
-        CHK(gemm(st, R, I, H, L.wqkv, H, winT, H, nullptr, L.wqkv_x, I));               // (R, in) = Wqkv Win
-        CHK(gemm(st, 1, R, H, L.in_proj.b, H, L.wqkv, H, L.bqkv, L.bqkv_x, R));         // Wqkv b_in + bqkv
-        if (E.cfg.operand_dtype != 1) {
-            // q~_h = Wk'_h^T q_h needs the k rows transposed: (I, H), head h = columns h c .. (csrc/local_attn.hip, fold form)
-            L.wkT_x = A.get<float>((size_t)I * H);
-            if (A.fail) return ROITR_ERR_ARG;
-            CHK(roitr_transpose(H, I, L.wqkv_x + (size_t)H * I, I, L.wkT_x, H, st));
-            if (I == 64) {
-                // q~_h = Wk'_h^T (Wq'_h x + bq_h): one (H + 4 I) x I weight instead of the q GEMM followed by the batched q~ GEMM --
-                // at I = 64 those were 1.42 + 1.19 ms per 512-pair step for 2 GB of q / q~ rows (two launches of K = 64 / K = 32);
-                // wider inputs keep the two-step form (the folded weight has (H + 4 I) I entries against H I + H I / 4: more FLOPs
-                // than the launch saves from I = 128 on)
-                const int c = H / HEADS, R2 = H + HEADS * I;
-                float* wqT = A.get<float>((size_t)I * H);
-                L.wqqt_x = A.get<float>((size_t)R2 * I);
-                L.bqqt_x = A.get<float>(R2);
-                if (A.fail) return ROITR_ERR_ARG;
-                CHK(roitr_transpose(H, I, L.wqkv_x, I, wqT, H, st));                                  // (I, H): q rows transposed
-                CHK(d2d(st, L.wqqt_x, L.wqkv_x, sizeof(float) * (size_t)H * I));
-                CHK(d2d(st, L.bqqt_x, L.bqkv_x, sizeof(float) * H));
-                for (int h = 0; h < HEADS; ++h) {
-                    // (Wk'_h^T Wq'_h)[i', i] = sum_c wkT[i', h c + c] wqT[i, h c + c]
-                    CHK(gemm(st, I, I, c, L.wkT_x + (size_t)h * c, H, wqT + (size_t)h * c, H, nullptr, L.wqqt_x + (size_t)(H + h * I) * I, I));
-                    // (Wk'_h^T bq_h)[i'] = sum_c bq[h c + c] wkT[i', h c + c]
-                    CHK(gemm(st, 1, I, c, L.bqkv_x + (size_t)h * c, c, L.wkT_x + (size_t)h * c, H, nullptr, L.bqqt_x + H + (size_t)h * I, I));
-                }
-            }
-        }
-        if (E.cfg.operand_dtype == 1) {
-            L.wqkv_x_b = A.get<unsigned short>((size_t)R * I);
-            if (A.fail) return ROITR_ERR_ARG;
-            CHK(roitr_f32_to_bf16((long)R * I, L.wqkv_x, L.wqkv_x_b, st));
+        CHK(Gemm(R, I, H, L.wqkv, H, winT, H, nullptr, L.wqkv_x, I).run(st));           // (R, in) = Wqkv Win
+        CHK(Gemm(1, R, H, L.in_proj.b, H, L.wqkv, H, L.bqkv, L.bqkv_x, R).run(st));     // Wqkv b_in + bqkv
+        if (bf16) CHK(bf16_copy(E, (long)R * I, L.wqkv_x, L.wqkv_x_b, st));
+    }
+    if (L.form == TD_FOLD || L.form == FUSED_TD) {
+        // q~_h = Wk'_h^T q_h needs the k rows transposed: (I, H), head h = columns h c .. (csrc/local_attn.hip, fold form)
+        L.wkT_x = A.get<float>((size_t)I * H);
+        if (A.fail) return ROITR_ERR_ARG;
+        CHK(roitr_transpose(H, I, L.wqkv_x + (size_t)H * I, I, L.wkT_x, H, st));
+    }
+    if (L.form == FUSED_TD) {
+        // q~_h = Wk'_h^T (Wq'_h x + bq_h): one (H + 4 I) x I weight instead of the q GEMM followed by the batched q~ GEMM --
+        // at I = 64 those were 1.42 + 1.19 ms per 512-pair step for 2 GB of q / q~ rows (two launches of K = 64 / K = 32);
+        // wider inputs keep the two-step form (the folded weight has (H + 4 I) I entries against H I + H I / 4: more FLOPs
+        // than the launch saves from I = 128 on)
+        const int c = H / HEADS, R2 = H + HEADS * I;
+        float* wqT = A.get<float>((size_t)I * H);
+        L.wqqt_x = A.get<float>((size_t)R2 * I);
+        L.bqqt_x = A.get<float>(R2);
+        if (A.fail) return ROITR_ERR_ARG;
+        CHK(roitr_transpose(H, I, L.wqkv_x, I, wqT, H, st));                                  // (I, H): q rows transposed
+        CHK(d2d(st, L.wqqt_x, L.wqkv_x, sizeof(float) * (size_t)H * I));
+        CHK(d2d(st, L.bqqt_x, L.bqkv_x, sizeof(float) * H));
+        for (int h = 0; h < HEADS; ++h) {
+            // (Wk'_h^T Wq'_h)[i', i] = sum_c wkT[i', h c + c] wqT[i, h c + c]
+            CHK(Gemm(I, I, c, L.wkT_x + (size_t)h * c, H, wqT + (size_t)h * c, H, nullptr, L.wqqt_x + (size_t)(H + h * I) * I, I).run(st));
+            // (Wk'_h^T bq_h)[i'] = sum_c bq[h c + c] wkT[i', h c + c]
+            CHK(Gemm(1, I, c, L.bqkv_x + (size_t)h * c, c, L.wkT_x + (size_t)h * c, H, nullptr, L.bqqt_x + H + (size_t)h * I, I).run(st));
         }
     }
-    // fp32 levels that run in the fused kernels of csrc/local_block.hip: their on-chip GEMMs read fragment-ordered weight copies,
-    // under exactly the views local_transformer() hands over
-    if (E.cfg.operand_dtype != 1 && L.wcat && L.wqkv_x && L.out_dim == H) {
-        const int I = L.in_dim;
-        if (I == H && (H == 64 || H == 128)) {                                  // roitr_local_block
-            CHK(prepare_fragments(E, L.wqkv_x, H, H, st));
-            CHK(prepare_fragments(E, L.wcat, H, 2 * H, st));
-            CHK(prepare_fragments(E, L.out_proj.w, H, H, st));
-        } else if (L.wqqt_x && roitr_local_td_supported(I, H, 16)) {           // roitr_local_td
-            CHK(prepare_fragments(E, L.wqqt_x, H + HEADS * I, I, st));
-            CHK(prepare_fragments(E, L.wqkv_x + (size_t)(2 * H) * I, H, I, st));
-            CHK(prepare_fragments(E, L.wcat, H, H + I, st));
-            CHK(prepare_fragments(E, L.out_proj.w, H, H, st));
-        }
+    // the fused fp32 kernels of csrc/local_block.hip read fragment-ordered copies of their weights, under exactly the views
+    // block_args() / td_args() hand over (roitr_local_first's: build_local_first)
+    if (L.form == FUSED_BLOCK && !bf16) {
+        CHK(prepare_fragments(E, L.wqkv_x, H, H, st));
+        CHK(prepare_fragments(E, L.cat.w, H, 2 * H, st));
+        CHK(prepare_fragments(E, L.out_proj.w, H, H, st));
+    }
+    if (L.form == FUSED_TD) {
+        CHK(prepare_fragments(E, L.wqqt_x, H + HEADS * I, I, st));
+        CHK(prepare_fragments(E, L.wqkv_x + (size_t)(2 * H) * I, H, I, st));
+        CHK(prepare_fragments(E, L.cat.w, H, H + I, st));
+        CHK(prepare_fragments(E, L.out_proj.w, H, H, st));
     }
     return 0;
 }
@@ -539,159 +547,164 @@ struct Desc {
     }
 };
 
-// LocalPPFTransformer.forward (ppftransformer.py:227-253) on N_in input rows -> M node rows
-// `bn2_res` != nullptr: the caller is RIPointTransformerBlock and wants out = relu(bn2(out_proj(..)) + bn2_res)
-int local_transformer(Engine& E, hipStream_t st, const LocalT& L, int N_in, const float* x, int M, const int* node_idx, const int* group,
-                      const float* ppf, int K, float* out, const void* order = nullptr, const float* bn2_res = nullptr)
+// ---------------------------------------------------------------- the local transformer: one function per form (LocalT::form)
+// LocalPPFTransformer.forward (ppftransformer.py:227-253) on N_in input rows x -> M node rows.  node_idx (M) = the input row of every
+// node of a TransitionDown that samples (nullptr: node r is row r).  The transformer of a block (!LocalT::td) is followed by the block's
+// tail, out = relu(bn2(out_proj(..)) + x) (RIPointTransformerBlock.forward, model/model.py:131-142).
+struct LocalIn { int N_in; const float* x; int M; const int* node_idx; const int* group; const float* ppf; const void* order; };
+
+int form_error(const char* form)
+{
+    roitr_set_error((std::string("engine: local transformer finalized for another form than ") + form).c_str(), __FILE__, __LINE__);
+    return ROITR_ERR_ARG;
+}
+
+RoitrLocalFirst first_args(const Engine& E, const LocalT& L, const LocalIn& in, float* out)
+{
+    RoitrLocalFirst lf;
+    memset(&lf, 0, sizeof(lf));
+    lf.M = in.M; lf.K = L.K; lf.x = in.x; lf.group_idx = in.group; lf.ppf = in.ppf; lf.node_order = in.order;
+    lf.head_consts = E.first_consts; lf.G = E.first_consts + 64; lf.zero_bias = E.first_consts + 64 + 64 * 32;
+    lf.norm_w = L.norm_w; lf.norm_b = L.norm_b; lf.wout = L.out_proj.w; lf.bout = L.out_proj.b;
+    lf.scale = L.scale; lf.eps = 1e-5f; lf.out = out;
+    return lf;
+}
+RoitrLocalBlock block_args(const LocalT& L, const LocalIn& in, const float* kv, float* out)
+{
+    RoitrLocalBlock b;
+    memset(&b, 0, sizeof(b));
+    b.M = in.M; b.K = L.K; b.H = L.H; b.x = in.x; b.kv = kv; b.group_idx = in.group; b.ppf = in.ppf; b.node_order = in.order;
+    b.wq = L.wqkv_x; b.bq = L.bqkv_x; b.wpe = L.wpe; b.bpe = L.bpe; b.wvpe = L.wvpe; b.bvpe = L.bvpe;
+    b.wcat = L.cat.w; b.bcat = L.cat.b; b.norm_w = L.norm_w; b.norm_b = L.norm_b; b.wout = L.out_proj.w; b.bout = L.out_proj.b;
+    b.bn2_w = L.bn2_w; b.bn2_b = L.bn2_b; b.scale = L.scale; b.eps = 1e-5f; b.out = out;
+    return b;
+}
+RoitrLocalTd td_args(const LocalT& L, const LocalIn& in, float* out)
+{
+    RoitrLocalTd t;
+    memset(&t, 0, sizeof(t));
+    t.M = in.M; t.in_dim = L.in_dim; t.H = L.H; t.x = in.x; t.node_idx = in.node_idx; t.group_idx = in.group; t.ppf = in.ppf; t.node_order = in.order;
+    t.wqqt = L.wqqt_x; t.bqqt = L.bqqt_x; t.wv = L.wqkv_x + (size_t)(2 * L.H) * L.in_dim; t.bv = L.bqkv_x + 2 * L.H;
+    t.wpe = L.wpe; t.wvpe = L.wvpe; t.bvpe = L.bvpe; t.wcat = L.cat.w; t.bcat = L.cat.b; t.norm_w = L.norm_w; t.norm_b = L.norm_b;
+    t.wout = L.out_proj.w; t.bout = L.out_proj.b; t.scale = L.scale; t.eps = 1e-5f; t.out = out;
+    return t;
+}
+
+// FIRST -- the first transformer of the network: scalar input feature -> rank-1 q | k | v, one launch (csrc/local_block.hip)
+int local_first(Engine& E, hipStream_t st, const LocalT& L, const LocalIn& in, float* out)
+{
+    if (!E.first_consts || in.node_idx) return form_error("FIRST");
+    const RoitrLocalFirst lf = first_args(E, L, in, out);
+    return roitr_local_first(&lf, st);
+}
+
+// FUSED_BLOCK -- the 64- / 128-wide block transformers (levels 1-2, where the separate launches are HBM-shaped): one fused launch
+// behind a plain k | v GEMM over all points (csrc/local_block.hip).  f = in_proj(x) is never formed: q|k|v come from x, the residual
+// of the LayerNorm rides in `linear` as the second K-half of [att | x].  bf16 operand mode: the k | v rows are stored bf16 and the
+// kernel's three on-chip GEMMs take bf16 matrix operands.
+int local_fused_block(Engine& E, hipStream_t st, const LocalT& L, const LocalIn& in, float* out)
+{
+    if (!L.wqkv_x || !L.cat.w || in.node_idx || in.M != in.N_in) return form_error("FUSED_BLOCK");
+    Arena& A = E.arena;
+    const size_t mark = A.off;
+    const int H = L.H, I = L.in_dim;
+    float* kv = A.get<float>((size_t)in.N_in * 2 * H);
+    if (A.fail) return ROITR_ERR_ARG;
+    const unsigned short* wkv_b = bf16_layer(L.wqkv_x_b, I) ? L.wqkv_x_b + (size_t)H * I : nullptr;
+    CHK(Gemm(in.N_in, 2 * H, I, in.x, I, L.wqkv_x + (size_t)H * I, I, L.bqkv_x + H, kv, 2 * H)
+            .bf16_weight(wkv_b).stored(wkv_b ? ROITR_BF16_C : 0).run(st));
+    RoitrLocalBlock b = block_args(L, in, kv, out);
+    b.kv_bf16 = wkv_b ? 1 : 0;
+    if (wkv_b && L.wcat_b && L.out_proj.wb) { b.wq_h = L.wqkv_x_b; b.wcat_h = L.wcat_b; b.wout_h = L.out_proj.wb; }
+    CHK(roitr_local_block(&b, st));
+    A.off = mark;
+    return 0;
+}
+
+// FUSED_TD -- the whole TransitionDown transformer of the 64 -> 128 wide level in one launch (csrc/local_block.hip local_td_kernel)
+int local_fused_td(Engine&, hipStream_t st, const LocalT& L, const LocalIn& in, float* out)
+{
+    if (!L.wqqt_x || !L.wqkv_x || !L.cat.w || !in.node_idx) return form_error("FUSED_TD");
+    const RoitrLocalTd t = td_args(L, in, out);
+    return roitr_local_td(&t, st);
+}
+
+// TD_FOLD -- TransitionDown in fp32 with the k | v projections folded into the query side (csrc/local_attn.hip local_attn_fold_kernel):
+// q~ = Wk'^T q per head in front, Wv' applied to the attention-weighted INPUT rows behind; the (N_in, 2H) tensor is never formed.
+// f = in_proj(x[node_idx]) -- only ever the LayerNorm residual -- rides in the K-concatenated `linear` as its second K part.
+int local_td_fold(Engine& E, hipStream_t st, const LocalT& L, const LocalIn& in, float* out)
+{
+    if (!L.wkT_x || !L.wqkv_x || !L.cat.w || !in.node_idx) return form_error("TD_FOLD");
+    Arena& A = E.arena;
+    const size_t mark = A.off;
+    const int M = in.M, H = L.H, I = L.in_dim, c = H / HEADS;
+    float* qe = A.get<float>((size_t)M * H);
+    float* qt = A.get<float>((size_t)M * HEADS * I);
+    float* xbar = A.get<float>((size_t)M * HEADS * I);
+    float* vpart = A.get<float>((size_t)M * H);
+    float* val = A.get<float>((size_t)M * H);
+    float* hid = A.get<float>((size_t)M * H);
+    float* y = A.get<float>((size_t)M * H);
+    if (A.fail) { roitr_set_error("arena exhausted (TransitionDown fold)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
+    CHK(Gemm(M, H, I, in.x, I, L.wqkv_x, I, L.bqkv_x, qe, H).gather(in.node_idx).run(st));
+    // qt[(row, h), :] = Wk'_h^T q_h   (batched over heads; no bias: q_h . bk'_h is constant over the neighbours)
+    CHK(Gemm(M, I, c, qe, H, L.wkT_x, H, nullptr, qt, HEADS * I).heads(HEADS, c, c, I).run(st));
+    RoitrLocalAttnFold a;
+    memset(&a, 0, sizeof(a));
+    a.M = M; a.in_dim = I; a.H = H; a.x = in.x; a.ldx = I; a.q = qe; a.ldq = H; a.qt = qt; a.group_idx = in.group; a.ppf = in.ppf;
+    a.wpe = L.wpe; a.wvpe = L.wvpe; a.bvpe = L.bvpe; a.scale = L.scale; a.xbar = xbar; a.vpart = vpart; a.node_order = in.order;
+    CHK(roitr_local_attention_fold(&a, st));
+    // val[:, h-slice] = Wv'_h xbar_h + bv'_h
+    CHK(Gemm(M, c, I, xbar, HEADS * I, L.wqkv_x + (size_t)(2 * H) * I, I, L.bqkv_x + 2 * H, val, H).heads(HEADS, I, (long)c * I, c, c).run(st));
+    // LN([vpart + val | x[node_idx]] [Wlin | Win]^T + b_lin + b_in): att = vpart + val is formed while the operand is staged
+    CHK(Gemm(M, vpart, L.cat, y).plus(val).cat(in.x, I, H, in.node_idx).ln(L.norm_w, L.norm_b).run_ln(st, hid));
+    CHK(Gemm(M, y, L.out_proj, out).run(st));
+    A.off = mark;
+    return 0;
+}
+
+// SEQUENCE -- one launch per step: (in_proj,) q | k | v, attention, linear + LayerNorm, out_proj (+ the block's tail)
+// (measured and dropped: folding in_proj into the projections of the first transformer of the network, K = 1 -- an outer-product kernel
+//  writing the (T, 212) q|k|v rows is no faster than the K = 64 MFMA GEMM it replaces: 59.9 vs 59.2 ms of GEMM per 512-pair step)
+int local_sequence(Engine& E, hipStream_t st, const LocalT& L, const LocalIn& in, float* out)
 {
     Arena& A = E.arena;
     const size_t mark = A.off;
-    const int H = L.H;
-    // TransitionDown with folded projections: q / k / v come straight from x, and f = in_proj(x) is only needed as the
-    // LayerNorm residual of the M sampled rows
-    // (measured and dropped: the same fold for the first transformer of the network, K = 1 -- an outer-product kernel writing
-    //  the (T, 212) q|k|v rows is no faster than the K = 64 MFMA GEMM it replaces: 59.9 vs 59.2 ms of GEMM per 512-pair step)
-    const bool folded = node_idx != nullptr && L.wqkv_x != nullptr;
-    // block transformer in fp32 with folded projections: f = in_proj(x) is never formed -- q|k|v come from x, and the residual
-    // of the LayerNorm rides in the `linear` GEMM as the second K-half of [att | x]
-    const bool catf = node_idx == nullptr && L.wcat != nullptr && L.wqkv_x != nullptr;
-    // the 64- / 128-wide block transformers (levels 1-2, where the separate launches are HBM-shaped): one fused launch behind
-    // a plain k | v GEMM over all points (csrc/local_block.hip)
-    if (catf && bn2_res == x && M == N_in && roitr_local_block_supported(H, K)) {
-        const int I = L.in_dim;
-        float* kv = A.get<float>((size_t)N_in * 2 * H);
-        if (A.fail) return ROITR_ERR_ARG;
-        const unsigned short* wkv_b = (E.cfg.operand_dtype == 1 && L.wqkv_x_b && I % 64 == 0) ? L.wqkv_x_b + (size_t)H * I : nullptr;
-        CHK(gemm(st, N_in, 2 * H, I, x, I, L.wqkv_x + (size_t)H * I, I, L.bqkv_x + H, kv, 2 * H, false, nullptr, nullptr, 1.0f, wkv_b,
-                 wkv_b ? ROITR_BF16_C : 0));
-        RoitrLocalBlock b;
-        memset(&b, 0, sizeof(b));
-        b.kv_bf16 = wkv_b ? 1 : 0;
-        b.M = M; b.K = K; b.H = H; b.x = x; b.kv = kv; b.group_idx = group; b.ppf = ppf; b.node_order = order;
-        b.wq = L.wqkv_x; b.bq = L.bqkv_x; b.wpe = L.wpe; b.bpe = L.bpe; b.wvpe = L.wvpe; b.bvpe = L.bvpe;
-        b.wcat = L.wcat; b.bcat = L.bcat; b.norm_w = L.norm_w; b.norm_b = L.norm_b; b.wout = L.out_proj.w; b.bout = L.out_proj.b;
-        b.bn2_w = L.bn2_w; b.bn2_b = L.bn2_b; b.scale = 1.0f / sqrtf((float)(H / HEADS)); b.eps = 1e-5f; b.out = out;
-        if (wkv_b && I == H && L.wcat_b && L.out_proj.wb) {   // bf16 operand mode: bf16 matrix operands inside the kernel as well
-            b.wq_h = L.wqkv_x_b; b.wcat_h = L.wcat_b; b.wout_h = L.out_proj.wb;
-        }
-        CHK(roitr_local_block(&b, st));
-        A.off = mark;
-        return 0;
-    }
-    // TransitionDown in the folded-attention form below with the K-concatenated `linear`: f = in_proj(x[node_idx]) -- only ever the
-    // LayerNorm residual -- rides in that GEMM as its second K part (round 4), the gathered (M, H) tensor is never formed
-    const bool td_fold = folded && L.wkT_x && roitr_local_attention_fold_supported(L.in_dim, H, K);
-    const bool td_cat = td_fold && L.wcat != nullptr;
-    float* f = nullptr;
-    if (!catf && !td_cat) {
-        f = A.get<float>((size_t)(folded ? M : N_in) * H);
-        if (folded) CHK(gemm(st, M, x, L.in_proj, f, false, node_idx));
-        else CHK(gemm(st, N_in, x, L.in_proj, f));
-    }
-    // TransitionDown in fp32: the k | v projections folded into the query side (csrc/local_attn.hip local_attn_fold_kernel) --
-    // q~ = Wk'^T q per head in front, Wv' applied to the attention-weighted INPUT rows behind; the (N_in, 2H) tensor is never formed
-    if (td_fold && td_cat && L.wqqt_x && !bn2_res && L.out_dim == H && roitr_local_td_supported(L.in_dim, H, K)) {
-        // the whole TransitionDown transformer of the 64 -> 128 wide level in one launch (csrc/local_block.hip local_td_kernel, round 5)
-        RoitrLocalTd t;
-        memset(&t, 0, sizeof(t));
-        t.M = M; t.in_dim = L.in_dim; t.H = H; t.x = x; t.node_idx = node_idx; t.group_idx = group; t.ppf = ppf; t.node_order = order;
-        t.wqqt = L.wqqt_x; t.bqqt = L.bqqt_x; t.wv = L.wqkv_x + (size_t)(2 * H) * L.in_dim; t.bv = L.bqkv_x + 2 * H;
-        t.wpe = L.wpe; t.wvpe = L.wvpe; t.bvpe = L.bvpe; t.wcat = L.wcat; t.bcat = L.bcat; t.norm_w = L.norm_w; t.norm_b = L.norm_b;
-        t.wout = L.out_proj.w; t.bout = L.out_proj.b; t.scale = 1.0f / sqrtf((float)(H / HEADS)); t.eps = 1e-5f; t.out = out;
-        CHK(roitr_local_td(&t, st));
-        A.off = mark;
-        return 0;
-    }
-    if (td_fold) {
-        const int I = L.in_dim, c = H / HEADS;
-        float* qe = A.get<float>((size_t)M * H);
-        float* qt = A.get<float>((size_t)M * HEADS * I);
-        float* xbar = A.get<float>((size_t)M * HEADS * I);
-        float* vpart = A.get<float>((size_t)M * H);
-        float* val = A.get<float>((size_t)M * H);
-        float* hid = A.get<float>((size_t)M * H);
-        float* y = A.get<float>((size_t)M * H);
-        if (A.fail) { roitr_set_error("arena exhausted (TransitionDown fold)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-        const float* qe_r = qe; const float* qt_r = qt; int ldq_r = H, ldqt_r = 0;
-        float* xg = nullptr;   // x[node_idx] as a dense (M, I) tensor (the single-GEMM form below)
-        if (L.wqqt_x) {   // q | q~ as the two column blocks of one GEMM over the gathered input rows (fold_local)
-            const int R2 = H + HEADS * I;
-            float* qq = A.get<float>((size_t)M * R2);
-            if (A.fail) { roitr_set_error("arena exhausted (TransitionDown fold)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-            // the node rows are gathered ONCE (M x 64 floats) instead of by every column tile of the GEMM: a row gather inside the
-            // GEMM is an index load in front of every tile's first slab, and K = 64 has two slabs to hide it behind -- the gathered
-            // K = 64 launches ran at 0.7 - 1 TB/s (round 4: 0.95 ms for f = in_proj(x[node_idx]); round 5: 2.3 ms for this one)
-            xg = A.get<float>((size_t)M * I);
-            if (A.fail) { roitr_set_error("arena exhausted (TransitionDown fold)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-            CHK(roitr_gather_rows(M, I, x, node_idx, 0, xg, st));
-            CHK(gemm(st, M, R2, I, xg, I, L.wqqt_x, I, L.bqqt_x, qq, R2));
-            qe_r = qq; qt_r = qq + H; ldq_r = R2; ldqt_r = R2;
-        } else {
-        CHK(gemm(st, M, H, I, x, I, L.wqkv_x, I, L.bqkv_x, qe, H, false, node_idx));
-        {   // qt[(row, h), :] = Wk'_h^T q_h   (batched over heads; no bias: q_h . bk'_h is constant over the neighbours)
-            RoitrGemm gq; memset(&gq, 0, sizeof(gq));
-            gq.M = M; gq.N = I; gq.K = c; gq.A = qe; gq.lda = H; gq.W = L.wkT_x; gq.ldw = H; gq.alpha = 1.f;
-            gq.C = qt; gq.ldc = HEADS * I; gq.batch = HEADS; gq.sA = c; gq.sW = c; gq.sC = I;
-            CHK(roitr_gemm(&gq, st));
-        }
-        }
-        RoitrLocalAttnFold a;
-        memset(&a, 0, sizeof(a));
-        a.M = M; a.in_dim = I; a.H = H; a.x = x; a.ldx = I; a.q = qe_r; a.ldq = ldq_r; a.qt = qt_r; a.ldqt = ldqt_r; a.group_idx = group; a.ppf = ppf;
-        a.wpe = L.wpe; a.wvpe = L.wvpe; a.bvpe = L.bvpe; a.scale = 1.0f / sqrtf((float)c); a.xbar = xbar; a.vpart = vpart; a.node_order = order;
-        CHK(roitr_local_attention_fold(&a, st));
-        {   // val[:, h-slice] = Wv'_h xbar_h + bv'_h
-            RoitrGemm gv; memset(&gv, 0, sizeof(gv));
-            gv.M = M; gv.N = c; gv.K = I; gv.A = xbar; gv.lda = HEADS * I; gv.W = L.wqkv_x + (size_t)(2 * H) * I; gv.ldw = I;
-            gv.bias = L.bqkv_x + 2 * H; gv.alpha = 1.f; gv.C = val; gv.ldc = H; gv.batch = HEADS; gv.sA = I; gv.sW = (long)c * I; gv.sC = c; gv.sBias = c;
-            CHK(roitr_gemm(&gv, st));
-        }
-        // linear(att) + f -> LayerNorm, att = vpart + val (the sum is formed while the operand is staged)
-        if (td_cat) {   // LN([vpart + val | x[node_idx]] [Wlin | Win]^T + b_lin + b_in)
-            Lin lc; lc.w = L.wcat; lc.b = L.bcat; lc.out = H; lc.in = H + I;
-            CHK(gemm_ln(st, M, vpart, lc, nullptr, nullptr, L.norm_w, L.norm_b, nullptr, false, hid, y, 0, xg ? xg : x, I, H, val, nullptr,
-                        xg ? nullptr : node_idx));
-        } else
-        CHK(gemm_ln(st, M, vpart, L.lin, f, nullptr, L.norm_w, L.norm_b, nullptr, false, hid, y, 0, nullptr, 0, 0, val));
-        if (bn2_res) {
-            float* t = A.get<float>((size_t)M * L.out_dim);
-            if (A.fail) return ROITR_ERR_ARG;
-            CHK(gemm_ln(st, M, y, L.out_proj, nullptr, nullptr, L.bn2_w, L.bn2_b, bn2_res, true, t, out));
-        } else {
-            CHK(gemm(st, M, y, L.out_proj, out));
-        }
-        A.off = mark;
-        return 0;
-    }
+    const int M = in.M, N_in = in.N_in, H = L.H, R = 3 * H;
+    // the three flavours, fixed at finalize:
+    const bool from_x = L.from_x;            // q | k | v straight from x (in_proj folded into them), else from f = in_proj(x)
+    const bool cat_res = from_x && !L.td;    // the LayerNorm residual f rides in `linear` as the second K-half of [att | x]: f is never formed
     // bf16 operand mode: the q | k | v tensor (operands of the attention products) and the attention output (operand of
     // `linear`) are stored bf16 by their producers -- half the bytes of the gather-bound attention kernel
-    const bool hb = (folded ? bf16_layer(L.wqkv_x_b, L.in_dim) : bf16_layer(L.wqkv_b, H)) && bf16_layer(L.lin.wb, H);
+    const bool hb = (from_x ? bf16_layer(L.wqkv_x_b, L.in_dim) : bf16_layer(L.wqkv_b, H)) && bf16_layer(L.lin.wb, H);
+    if (from_x ? !L.wqkv_x : !L.wqkv) return form_error("SEQUENCE");
+    if (cat_res && !L.cat.w) return form_error("SEQUENCE");
     const int cq = hb ? ROITR_BF16_C : 0;
     const size_t esz = hb ? 2 : 4;
+    // f: the residual and, unless from_x, the operand of the projections -- of the M sampled rows only where only the residual reads it
+    float* f = nullptr;
+    if (!cat_res) {
+        f = A.get<float>((size_t)(from_x ? M : N_in) * H);
+        if (from_x) CHK(Gemm(M, in.x, L.in_proj, f).gather(in.node_idx).run(st));
+        else CHK(Gemm(N_in, in.x, L.in_proj, f).run(st));
+    }
+    const float* src = from_x ? in.x : f;
+    const int Kp = from_x ? L.in_dim : H;
+    const float* w = from_x ? L.wqkv_x : L.wqkv; const float* b = from_x ? L.bqkv_x : L.bqkv;
+    const unsigned short* wb = from_x ? L.wqkv_x_b : L.wqkv_b;
     const float *q, *k, *v; int ldq, ldkv;
-    if (!node_idx) {
-        const int R = 3 * H;
+    if (!in.node_idx) {   // every row is a node: q | k | v in one GEMM
         float* qkv = A.get<float>((size_t)N_in * R);
         if (A.fail) return ROITR_ERR_ARG;
-        if (catf) CHK(gemm(st, N_in, R, L.in_dim, x, L.in_dim, L.wqkv_x, L.in_dim, L.bqkv_x, qkv, R));
-        else
-        CHK(gemm(st, N_in, R, H, f, H, L.wqkv, H, L.bqkv, qkv, R, false, nullptr, nullptr, 1.0f, L.wqkv_b, cq));
+        CHK(Gemm(N_in, R, Kp, src, Kp, w, Kp, b, qkv, R).bf16_weight(wb).stored(cq).run(st));
         const char* b0 = (const char*)qkv;
         q = qkv; k = (const float*)(b0 + (size_t)H * esz); v = (const float*)(b0 + (size_t)(2 * H) * esz); ldq = R; ldkv = R;
-    } else {
+    } else {              // q of the M sampled rows, k | v of all N_in
         float* qe = A.get<float>((size_t)M * H);
         float* kv = A.get<float>((size_t)N_in * 2 * H);
         if (A.fail) return ROITR_ERR_ARG;
-        if (folded) {
-            const int I = L.in_dim;
-            CHK(gemm(st, M, H, I, x, I, L.wqkv_x, I, L.bqkv_x, qe, H, false, node_idx, nullptr, 1.0f, L.wqkv_x_b, cq));
-            CHK(gemm(st, N_in, 2 * H, I, x, I, L.wqkv_x + (size_t)H * I, I, L.bqkv_x + H, kv, 2 * H, false, nullptr, nullptr, 1.0f,
-                     L.wqkv_x_b ? L.wqkv_x_b + (size_t)H * I : nullptr, cq));
-        } else {
-            CHK(gemm(st, M, H, H, f, H, L.wqkv, H, L.bqkv, qe, H, false, node_idx, nullptr, 1.0f, L.wqkv_b, cq));
-            CHK(gemm(st, N_in, 2 * H, H, f, H, L.wqkv + (size_t)H * H, H, L.bqkv + H, kv, 2 * H, false, nullptr, nullptr, 1.0f,
-                     L.wqkv_b ? L.wqkv_b + (size_t)H * H : nullptr, cq));
-        }
+        CHK(Gemm(M, H, Kp, src, Kp, w, Kp, b, qe, H).gather(in.node_idx).bf16_weight(wb).stored(cq).run(st));
+        CHK(Gemm(N_in, 2 * H, Kp, src, Kp, w + (size_t)H * Kp, Kp, b + H, kv, 2 * H).bf16_weight(wb ? wb + (size_t)H * Kp : nullptr).stored(cq).run(st));
         q = qe; k = kv; v = (const float*)((const char*)kv + (size_t)H * esz); ldq = H; ldkv = 2 * H;
     }
     float* att = A.get<float>((size_t)M * H);
@@ -700,39 +713,37 @@ int local_transformer(Engine& E, hipStream_t st, const LocalT& L, int N_in, cons
     if (A.fail) return ROITR_ERR_ARG;
     RoitrLocalAttn a;
     memset(&a, 0, sizeof(a));
-    a.M = M; a.K = K; a.H = H; a.heads = HEADS; a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldkv; a.v = v; a.ldv = ldkv;
-    a.group_idx = group; a.ppf = ppf; a.wvpe = L.wvpe; a.bvpe = L.bvpe; a.scale = 1.0f / sqrtf((float)(H / HEADS));
-    a.out = att; a.ldo = H; a.node_order = order; a.bf16 = hb ? 3 : 0;
+    a.M = M; a.K = L.K; a.H = H; a.heads = HEADS; a.q = q; a.ldq = ldq; a.k = k; a.ldk = ldkv; a.v = v; a.ldv = ldkv;
+    a.group_idx = in.group; a.ppf = in.ppf; a.wvpe = L.wvpe; a.bvpe = L.bvpe; a.scale = L.scale;
+    a.out = att; a.ldo = H; a.node_order = in.order; a.bf16 = hb ? 3 : 0;
     a.wpe = L.wpe; a.bpe = L.bpe;   // qp computed in the kernel
     CHK(roitr_local_attention(&a, st));
     // bf16 operand mode: `y` only feeds out_proj -> the LayerNorm epilogue stores it in bf16 (half the round trip)
-    const bool y_h = ln_fuses(H, H, H, H) && bf16_layer(L.lin.wb, H) && bf16_layer(L.out_proj.wb, H);   // independent of M: batch-invariant storage
-    if (catf) {
-        Lin lc; lc.w = L.wcat; lc.b = L.bcat; lc.out = H; lc.in = H + L.in_dim;
-        CHK(gemm_ln(st, M, att, lc, nullptr, nullptr, L.norm_w, L.norm_b, nullptr, false, hid, y, 0, x, L.in_dim, H));
-    } else
-    CHK(gemm_ln(st, M, att, L.lin, f, folded ? nullptr : node_idx, L.norm_w, L.norm_b, nullptr, false, hid, y,
-                (y_h ? ROITR_BF16_C : 0) | (hb ? ROITR_BF16_A : 0)));
-    if (bn2_res) {
+    Gemm lin_ln(M, att, L.lin, y);
+    const bool y_h = ln_fuses(lin_ln) && bf16_layer(L.lin.wb, H) && bf16_layer(L.out_proj.wb, H);   // independent of M: batch-invariant storage
+    if (cat_res) CHK(Gemm(M, att, L.cat, y).cat(in.x, L.in_dim, H).ln(L.norm_w, L.norm_b).run_ln(st, hid));
+    else
+    CHK(lin_ln.stored((y_h ? ROITR_BF16_C : 0) | (hb ? ROITR_BF16_A : 0)).ln(L.norm_w, L.norm_b).residual(f, from_x ? nullptr : in.node_idx).run_ln(st, hid));
+    if (L.td) CHK(Gemm(M, y, L.out_proj, out).stored(y_h ? ROITR_BF16_A : 0).run(st));
+    else {
         float* t = A.get<float>((size_t)M * L.out_dim);
         if (A.fail) return ROITR_ERR_ARG;
-        CHK(gemm_ln(st, M, y, L.out_proj, nullptr, nullptr, L.bn2_w, L.bn2_b, bn2_res, true, t, out, y_h ? ROITR_BF16_A : 0));
-    } else {
-        CHK(gemm(st, M, y, L.out_proj, out, false, nullptr, nullptr, y_h ? ROITR_BF16_A : 0));
+        CHK(Gemm(M, y, L.out_proj, out).stored(y_h ? ROITR_BF16_A : 0).ln(L.bn2_w, L.bn2_b, true).post(in.x).run_ln(st, t));
     }
     A.off = mark;
     return 0;
 }
 
-// RIPointTransformerBlock.forward (model/model.py:131-142): relu(bn2(transformer(x)) + x)
-int block(Engine& E, hipStream_t st, const LocalT& L, int M, const float* x, const int* group, const float* ppf, int K, float* out,
-          const void* order = nullptr)
+int local_transformer(Engine& E, hipStream_t st, const LocalT& L, const LocalIn& in, float* out)
 {
-    Arena& A = E.arena;
-    const size_t mark = A.off;
-    CHK(local_transformer(E, st, L, M, x, M, nullptr, group, ppf, K, out, order, x));
-    A.off = mark;
-    return 0;
+    switch (L.form) {
+    case FIRST: return local_first(E, st, L, in, out);
+    case FUSED_BLOCK: return local_fused_block(E, st, L, in, out);
+    case FUSED_TD: return local_fused_td(E, st, L, in, out);
+    case TD_FOLD: return local_td_fold(E, st, L, in, out);
+    case SEQUENCE: return local_sequence(E, st, L, in, out);
+    }
+    return form_error("any");
 }
 
 // scratch from `A` (the arena of the stream the launches are queued on), released on return
@@ -744,8 +755,8 @@ int ffn_apply(Arena& A, hipStream_t st, const Ffn& F, int M, int C, const float*
     if (A.fail) { roitr_set_error("arena exhausted (ffn)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
     // bf16 operand mode: the (M, 2C) hidden activation lives in bf16 between the two GEMMs
     const bool e_h = bf16_layer(F.expand.wb, C) && bf16_layer(F.squeeze.wb, 2 * C);
-    CHK(gemm(st, M, x, F.expand, e, true, nullptr, nullptr, e_h ? ROITR_BF16_C : 0));
-    CHK(gemm_ln(st, M, e, F.squeeze, x, nullptr, F.n_w, F.n_b, nullptr, false, s, out, e_h ? ROITR_BF16_A : 0));
+    CHK(Gemm(M, x, F.expand, e).with_relu().stored(e_h ? ROITR_BF16_C : 0).run(st));
+    CHK(Gemm(M, e, F.squeeze, out).stored(e_h ? ROITR_BF16_A : 0).ln(F.n_w, F.n_b).residual(x).run_ln(st, s));
     A.off = mark;
     return 0;
 }
@@ -756,7 +767,7 @@ int ffn_apply(Arena& A, hipStream_t st, const Ffn& F, int M, int C, const float*
 int build_local_first(Engine& E, const LocalT& L, hipStream_t st)
 {
     const int H = L.H, c = H / HEADS;
-    if (L.in_dim != 1 || H != 64 || E.cfg.operand_dtype == 1) return 0;
+    if (L.form != FIRST) return 0;
     ROITR_HIP(hipStreamSynchronize(st));
     auto get = [&](const float* dev, size_t n, std::vector<double>& out) -> int {
         std::vector<float> h(n);
@@ -811,10 +822,23 @@ int build_local_first(Engine& E, const LocalT& L, hipStream_t st)
     ROITR_HIP(hipMemcpy(E.first_consts, hc.data(), sizeof(float) * 64, hipMemcpyHostToDevice));
     ROITR_HIP(hipMemcpy(E.first_consts + 64, G.data(), sizeof(float) * G.size(), hipMemcpyHostToDevice));
     ROITR_HIP(hipMemcpy(E.first_consts + 64 + (size_t)H * 32, zb.data(), sizeof(float) * H, hipMemcpyHostToDevice));
-    if (L.out_dim == H) CHK(prepare_fragments(E, L.out_proj.w, H, H, st));   // roitr_local_first's out_proj
+    CHK(prepare_fragments(E, L.out_proj.w, H, H, st));   // roitr_local_first's out_proj
     return 0;
 }
 }  // namespace
+
+extern "C" int roitr_local_form(int in_dim, int H, int out_dim, int K, int transition_down, int operand_dtype)
+{
+    const bool fp32 = operand_dtype != 1;   // the fused TransitionDown forms are fp32 arithmetic; the three-way split chooses like fp32
+    if (transition_down) {
+        if (fp32 && in_dim == 1 && H == 64 && out_dim == H && (K == 8 || K == 16)) return FIRST;
+        if (fp32 && roitr_local_attention_fold_supported(in_dim, H, K))
+            return out_dim == H && roitr_local_td_supported(in_dim, H, K) ? FUSED_TD : TD_FOLD;
+        return SEQUENCE;
+    }
+    // bf16 too: behind a bf16 k | v GEMM, with bf16 matrix operands inside the kernel
+    return in_dim == H && out_dim == H && roitr_local_block_supported(H, K) ? FUSED_BLOCK : SEQUENCE;
+}
 
 extern "C" void roitr_level_sizes(int n, int* out4)
 {
@@ -919,10 +943,10 @@ extern "C" int roitr_engine_finalize(void* h, hipStream_t st)
         const std::string e = "backbone.enc" + std::to_string(l + 1);
         const int pl = E.planes[l];
         const int hid = pl < 256 * f ? pl : 256 * f;
-        resolve_local(E, E.enc[l][0], e + ".0.transformer", in_planes, hid, pl);
+        resolve_local(E, E.enc[l][0], e + ".0.transformer", in_planes, hid, pl, E.nsample[l], true);
         for (int b = 1; b < E.nblocks[l]; ++b) {
             const std::string bp = e + "." + std::to_string(b);
-            resolve_local(E, E.enc[l][b], bp + ".transformer.transformer", pl, hid, pl);
+            resolve_local(E, E.enc[l][b], bp + ".transformer.transformer", pl, hid, pl, E.nsample[l], false);
             E.enc[l][b].bn2_w = P(E, bp + ".bn2.weight", pl); E.enc[l][b].bn2_b = P(E, bp + ".bn2.bias", pl);
         }
         in_planes = pl;
@@ -942,7 +966,7 @@ extern "C" int roitr_engine_finalize(void* h, hipStream_t st)
             U.l1n_w = P(E, d + ".0.linear1.1.weight", pl); U.l1n_b = P(E, d + ".0.linear1.1.bias", pl);
             U.l2n_w = P(E, d + ".0.linear2.1.weight", pl); U.l2n_b = P(E, d + ".0.linear2.1.bias", pl);
         }
-        resolve_local(E, E.dec[l], d + ".1.transformer.transformer", pl, hid, pl);
+        resolve_local(E, E.dec[l], d + ".1.transformer.transformer", pl, hid, pl, E.nsample[l], false);
         E.dec[l].bn2_w = P(E, d + ".1.bn2.weight", pl); E.dec[l].bn2_b = P(E, d + ".1.bn2.bias", pl);
     }
     const std::string g = "backbone.global_transformer";
@@ -1673,22 +1697,11 @@ int encoder(Engine& E, const RoitrForwardIO* io, const Plan& P, const GeoBufs& S
         float* b = A.get<float>((size_t)V.T[l] * pl);
         if (A.fail) break;
         const int n_in = l == 0 ? T1 : V.T[l - 1];
-        if (l == 0 && E.first_consts && (K == 8 || K == 16)) {
-            // the first transformer of the network: scalar input feature -> rank-1 q | k | v (csrc/local_block.hip)
-            const LocalT& L0 = E.enc[0][0];
-            RoitrLocalFirst lf;
-            memset(&lf, 0, sizeof(lf));
-            lf.M = T1; lf.K = K; lf.x = xin; lf.group_idx = S.g_td[0]; lf.ppf = S.ppf_td[0]; lf.node_order = S.order[0];
-            lf.head_consts = E.first_consts; lf.G = E.first_consts + 64; lf.zero_bias = E.first_consts + 64 + 64 * 32;
-            lf.norm_w = L0.norm_w; lf.norm_b = L0.norm_b; lf.wout = L0.out_proj.w; lf.bout = L0.out_proj.b;
-            lf.scale = 1.0f / sqrtf((float)(L0.H / HEADS)); lf.eps = 1e-5f; lf.out = a;
-            CHK(roitr_local_first(&lf, st));
-        } else
-        CHK(local_transformer(E, st, E.enc[l][0], n_in, xin, V.T[l], l == 0 ? nullptr : S.down[l], S.g_td[l], S.ppf_td[l], K, a, S.order[l]));
+        CHK(local_transformer(E, st, E.enc[l][0], {n_in, xin, V.T[l], l == 0 ? nullptr : S.down[l], S.g_td[l], S.ppf_td[l], S.order[l]}, a));
         CHK(tap(E, st, "enc" + std::to_string(l + 1) + ".0", a, sizeof(float) * (size_t)V.T[l] * pl));
         float* cur = a; float* nxt = b;
         for (int bi = 1; bi < E.nblocks[l]; ++bi) {
-            CHK(block(E, st, E.enc[l][bi], V.T[l], cur, S.g_self[l], S.ppf_self[l], K, nxt, S.order[l]));
+            CHK(local_transformer(E, st, E.enc[l][bi], {V.T[l], cur, V.T[l], nullptr, S.g_self[l], S.ppf_self[l], S.order[l]}, nxt));
             CHK(tap(E, st, "enc" + std::to_string(l + 1) + "." + std::to_string(bi), nxt, sizeof(float) * (size_t)V.T[l] * pl));
             float* t = cur; cur = nxt; nxt = t;
         }
@@ -1712,7 +1725,7 @@ int global_transformer(Engine& E, const Plan& P, const GeoBufs& S, Feats& F, con
     CHK(tap(E, st, "geo.emb", S.Emb, (e_h ? sizeof(unsigned short) : sizeof(float)) * (size_t)etot * C4));   // bf16 mode: the tap holds bf16
 
     float *fcur = R.fcur, *pos = R.pos, *qkv = R.qkv, *qt = R.qt, *ebar = R.ebar, *hid = R.hid, *t1 = R.t1, *t2 = R.t2;
-    CHK(gemm(st, T4, F.xe[3], E.geo_in, fcur));
+    CHK(Gemm(T4, F.xe[3], E.geo_in, fcur).run(st));
     CHK(tap(E, st, "geo.in_proj", fcur, sizeof(float) * (size_t)T4 * C4));
     const int cpe = C4 / HEADS;
     const float scale = 1.0f / sqrtf((float)cpe);
@@ -1720,14 +1733,9 @@ int global_transformer(Engine& E, const Plan& P, const GeoBufs& S, Feats& F, con
     for (size_t li = 0; li < E.geo.size(); ++li) {
         const GeoLayer& L = E.geo[li];
         if (!L.cross) {
-            CHK(gemm(st, T4, 3 * C4, C4, fcur, C4, L.wqkv, C4, L.bqkv, qkv, 3 * C4, false, nullptr, nullptr, 1.0f, L.wqkv_b));
-            {   // qt[(row,h), :] = Wp_h^T q_h   (batched over heads)
-                RoitrGemm gq; memset(&gq, 0, sizeof(gq));
-                gq.M = T4; gq.N = C4; gq.K = cpe; gq.A = qkv; gq.lda = 3 * C4; gq.W = L.wpT; gq.ldw = C4; gq.alpha = 1.f;
-                gq.C = qt; gq.ldc = HEADS * C4; gq.batch = HEADS; gq.sA = cpe; gq.sW = cpe; gq.sC = C4;
-                CHK(use_bf16(gq, L.wpT, L.wpT_b, 0));
-                CHK(roitr_gemm(&gq, st));
-            }
+            CHK(Gemm(T4, 3 * C4, C4, fcur, C4, L.wqkv, C4, L.bqkv, qkv, 3 * C4).bf16_weight(L.wqkv_b).run(st));
+            // qt[(row,h), :] = Wp_h^T q_h   (batched over heads)
+            CHK(Gemm(T4, C4, cpe, qkv, 3 * C4, L.wpT, C4, nullptr, qt, HEADS * C4).heads(HEADS, cpe, cpe, C4).bf16_weight(L.wpT_b).run(st));
             RoitrMha m; memset(&m, 0, sizeof(m));
             m.q_row0 = 0; m.q_rows = T4; m.C = C4; m.heads = HEADS; m.q = qkv; m.ldq = 3 * C4; m.k = qkv + C4; m.ldk = 3 * C4;
             m.v = qkv + 2 * C4; m.ldv = 3 * C4; m.offset = D.off[3]; m.cloud_of_row = D.cloud_of_node; m.partner = nullptr;
@@ -1736,18 +1744,13 @@ int global_transformer(Engine& E, const Plan& P, const GeoBufs& S, Feats& F, con
             // algorithmic bytes of the launch: E read once, q | k | v, the folded queries q~, out and ebar written once
             roitr_prof_next_bytes(ROITR_PROF_MHA, (double)etot * C4 * (e_h ? 2.0 : 4.0) + (double)T4 * C4 * 4.0 * (3 + HEADS + 1 + HEADS));
             CHK(roitr_mha(&m, st));
-            {   // pos_raw[:, h-slice] = Wvp_h ebar_h + bvp_h
-                RoitrGemm gp; memset(&gp, 0, sizeof(gp));
-                gp.M = T4; gp.N = cpe; gp.K = C4; gp.A = ebar; gp.lda = HEADS * C4; gp.W = L.vp.w; gp.ldw = C4; gp.bias = L.vp.b; gp.alpha = 1.f;
-                gp.C = t2; gp.ldc = C4; gp.batch = HEADS; gp.sA = C4; gp.sW = (long)cpe * C4; gp.sC = cpe; gp.sBias = cpe;
-                CHK(use_bf16(gp, L.vp.w, L.vp.wb, 0));
-                CHK(roitr_gemm(&gp, st));
-            }
+            // pos_raw[:, h-slice] = Wvp_h ebar_h + bvp_h
+            CHK(Gemm(T4, cpe, C4, ebar, HEADS * C4, L.vp.w, C4, L.vp.b, t2, C4).heads(HEADS, C4, (long)cpe * C4, cpe, cpe).bf16_weight(L.vp.wb).run(st));
             // RPEAttentionLayer tail (geoattention.py:236-244) + AttentionOutput x2 (l.278-280)
             // (in place is safe for the fused form: a block reads and writes only its own 64 rows)
-            CHK(gemm_ln(st, T4, hid, L.lin, fcur, nullptr, L.n_w, L.n_b, nullptr, false, t1, hid));
+            CHK(Gemm(T4, hid, L.lin, hid).ln(L.n_w, L.n_b).residual(fcur).run_ln(st, t1));
             CHK(ffn_apply(A, st, L.out, T4, C4, hid, fcur));
-            CHK(gemm_ln(st, T4, t2, L.pos_lin, nullptr, nullptr, L.pn_w, L.pn_b, nullptr, false, t1, t2));
+            CHK(Gemm(T4, t2, L.pos_lin, t2).ln(L.pn_w, L.pn_b).run_ln(st, t1));
             CHK(ffn_apply(A, st, L.pos, T4, C4, t2, pos));
             CHK(tap(E, st, "geo.layer" + std::to_string(li) + ".pos", pos, sizeof(float) * (size_t)T4 * C4));
         } else {
@@ -1758,25 +1761,22 @@ int global_transformer(Engine& E, const Plan& P, const GeoBufs& S, Feats& F, con
                 float* qb_ = qkv;                          // (T4, C4) region reused: q rows at their own row index
                 float* kb_ = qkv + (size_t)T4 * C4;
                 float* vb_ = qkv + (size_t)2 * T4 * C4;
-                CHK(gemm(st, qn, C4, C4, fcur + (size_t)q0 * C4, C4, L.q.w, C4, L.q.b, qb_ + (size_t)q0 * C4, C4, false, nullptr, pos + (size_t)q0 * C4,
-                         1.0f, L.q.wb));
-                CHK(gemm(st, kn, C4, C4, fcur + (size_t)k0 * C4, C4, L.k.w, C4, L.k.b, kb_ + (size_t)k0 * C4, C4, false, nullptr, pos + (size_t)k0 * C4,
-                         1.0f, L.k.wb));
-                CHK(gemm(st, kn, C4, C4, fcur + (size_t)k0 * C4, C4, L.v.w, C4, L.v.b, vb_ + (size_t)k0 * C4, C4, false, nullptr, nullptr, 1.0f, L.v.wb));
+                CHK(Gemm(qn, fcur + (size_t)q0 * C4, L.q, qb_ + (size_t)q0 * C4).plus(pos + (size_t)q0 * C4).run(st));
+                CHK(Gemm(kn, fcur + (size_t)k0 * C4, L.k, kb_ + (size_t)k0 * C4).plus(pos + (size_t)k0 * C4).run(st));
+                CHK(Gemm(kn, fcur + (size_t)k0 * C4, L.v, vb_ + (size_t)k0 * C4).run(st));
                 RoitrMha m; memset(&m, 0, sizeof(m));
                 m.q_row0 = q0; m.q_rows = qn; m.C = C4; m.heads = HEADS; m.q = qb_; m.ldq = C4; m.k = kb_; m.ldk = C4; m.v = vb_; m.ldv = C4;
                 m.offset = D.off[3]; m.cloud_of_row = D.cloud_of_node; m.partner = D.partner; m.scale = scale; m.nk_max = V.nmax[3];
                 m.out = hid; m.ldo = C4;
                 roitr_prof_next_bytes(ROITR_PROF_MHA, ((double)qn * 2 + (double)kn * 2) * C4 * 4.0);
                 CHK(roitr_mha(&m, st));
-                CHK(gemm_ln(st, qn, hid + (size_t)q0 * C4, L.lin, fcur + (size_t)q0 * C4, nullptr, L.n_w, L.n_b, nullptr, false,
-                            t1 + (size_t)q0 * C4, t2 + (size_t)q0 * C4));
+                CHK(Gemm(qn, hid + (size_t)q0 * C4, L.lin, t2 + (size_t)q0 * C4).ln(L.n_w, L.n_b).residual(fcur + (size_t)q0 * C4).run_ln(st, t1 + (size_t)q0 * C4));
                 CHK(ffn_apply(A, st, L.out, qn, C4, t2 + (size_t)q0 * C4, fcur + (size_t)q0 * C4));
             }
         }
         CHK(tap(E, st, "geo.layer" + std::to_string(li), fcur, sizeof(float) * (size_t)T4 * C4));
     }
-    CHK(gemm(st, T4, fcur, E.geo_out, gfeat));
+    CHK(Gemm(T4, fcur, E.geo_out, gfeat).run(st));
     CHK(tap(E, st, "geo.out", gfeat, sizeof(float) * (size_t)T4 * C4));
     return 0;
 }
@@ -1798,12 +1798,12 @@ int decoder(Engine& E, const Plan& P, const GeoBufs& S, Feats& F)
         xd[3] = A.get<float>((size_t)T4 * pl);
         if (A.fail) { roitr_set_error("arena exhausted (decoder)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
         CHK(roitr_segment_mean(NC, pl, xe[3], D.off[3], mean, st));
-        CHK(gemm(st, NC, mean, U.l2, tm, true));
-        CHK(gemm(st, NC, pl, pl, tm, pl, U.l1.w + pl, 2 * pl, U.l1.b, um, pl, false, nullptr, nullptr, 1.0f, U.l1.wb ? U.l1.wb + pl : nullptr));
-        CHK(gemm(st, T4, pl, pl, xe[3], pl, U.l1.w, 2 * pl, nullptr, y, pl, false, nullptr, nullptr, 1.0f, U.l1.wb));
+        CHK(Gemm(NC, mean, U.l2, tm).with_relu().run(st));
+        CHK(Gemm(NC, pl, pl, tm, pl, U.l1.w + pl, 2 * pl, U.l1.b, um, pl).bf16_weight(U.l1.wb ? U.l1.wb + pl : nullptr).run(st));
+        CHK(Gemm(T4, pl, pl, xe[3], pl, U.l1.w, 2 * pl, nullptr, y, pl).bf16_weight(U.l1.wb).run(st));
         CHK(roitr_add_layernorm(T4, pl, y, um, D.cloud_of_node, U.l1n_w, U.l1n_b, nullptr, 1, 1e-5f, x0, st));
         CHK(tap(E, st, "dec4.0", x0, sizeof(float) * (size_t)T4 * pl));
-        CHK(block(E, st, E.dec[3], T4, x0, S.g_self[3], S.ppf_self[3], E.nsample[3], xd[3], S.order[3]));
+        CHK(local_transformer(E, st, E.dec[3], {T4, x0, T4, nullptr, S.g_self[3], S.ppf_self[3], S.order[3]}, xd[3]));
         CHK(tap(E, st, "dec4.1", xd[3], sizeof(float) * (size_t)T4 * pl));
     }
     ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_NN3_DONE], 0));   // the 3-NN of the three TransitionUp layers (side stream)
@@ -1819,18 +1819,17 @@ int decoder(Engine& E, const Plan& P, const GeoBufs& S, Feats& F)
         float* x0 = A.get<float>((size_t)Tl * pl);
         xd[l] = A.get<float>((size_t)Tl * pl);
         if (A.fail) { roitr_set_error("arena exhausted (decoder)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-        CHK(gemm_ln(st, Tc, xd[l + 1], U.l2, nullptr, nullptr, U.l2n_w, U.l2n_b, nullptr, true, b0, b1));
+        CHK(Gemm(Tc, xd[l + 1], U.l2, b1).ln(U.l2n_w, U.l2n_b, true).run_ln(st, b0));
         if (E.cfg.operand_dtype != 1) {
             // fp32: `linear1(x1) + interpolation(p2, p1, linear2(x2))` in the launch that computes linear1 -- the interpolation rides in
             // the LayerNorm epilogue (after the ReLU), the (Tl, pl) intermediate a1 is never written
-            const Interp3 ip = {b1, S.i3[l], S.d3[l]};
-            CHK(gemm_ln(st, Tl, xe[l], U.l1, nullptr, nullptr, U.l1n_w, U.l1n_b, nullptr, true, a0, x0, 0, nullptr, 0, 0, nullptr, &ip));
+            CHK(Gemm(Tl, xe[l], U.l1, x0).ln(U.l1n_w, U.l1n_b, true).interp3(b1, S.i3[l], S.d3[l]).run_ln(st, a0));
         } else {
-            CHK(gemm_ln(st, Tl, xe[l], U.l1, nullptr, nullptr, U.l1n_w, U.l1n_b, nullptr, true, a0, a1));
+            CHK(Gemm(Tl, xe[l], U.l1, a1).ln(U.l1n_w, U.l1n_b, true).run_ln(st, a0));
             CHK(roitr_interp3_add(Tl, pl, b1, S.i3[l], S.d3[l], a1, x0, st));
         }
         CHK(tap(E, st, "dec" + std::to_string(l + 1) + ".0", x0, sizeof(float) * (size_t)Tl * pl));
-        CHK(block(E, st, E.dec[l], Tl, x0, S.g_self[l], S.ppf_self[l], E.nsample[l], xd[l], S.order[l]));
+        CHK(local_transformer(E, st, E.dec[l], {Tl, x0, Tl, nullptr, S.g_self[l], S.ppf_self[l], S.order[l]}, xd[l]));
         CHK(tap(E, st, "dec" + std::to_string(l + 1) + ".1", xd[l], sizeof(float) * (size_t)Tl * pl));
     }
     return 0;
@@ -1844,13 +1843,13 @@ int coarse_front(Engine& E, const Plan& P, const GeoBufs& S, const Feats& F, con
     const int B = P.B, T4 = P.T4, C4 = P.C4, LIM = P.LIM, P_ = P.P_; const bool compact = P.compact;
     const size_t NP = P.NPs;
     ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_TAIL_DONE], 0));   // node masks, partition and ground-truth side outputs (side stream)
-    CHK(gemm(st, T4, F.gfeat, E.coarse_proj, R.cp));
+    CHK(Gemm(T4, F.gfeat, E.coarse_proj, R.cp).run(st));
     CHK(roitr_l2_normalize(T4, C4, R.cp, R.node_feats, st));
     {   // all tgt_b x src_b feature dot products in one ragged-batched GEMM (rows: tgt cloud B+b, cols: src cloud b)
-        RoitrGemm g; memset(&g, 0, sizeof(g));
-        g.M = V.nmax[3]; g.N = V.nmax[3]; g.K = C4; g.A = R.node_feats; g.lda = C4; g.W = R.node_feats; g.ldw = C4; g.alpha = 1.f;
-        g.C = R.cxy; g.ldc = V.nmax[3]; g.batch = B; g.sC = R.xystride; g.seg_off = D.off[3]; g.seg_a0 = B; g.seg_w0 = 0;
-        CHK(roitr_gemm(&g, st));
+        Gemm g(V.nmax[3], V.nmax[3], C4, R.node_feats, C4, R.node_feats, C4, nullptr, R.cxy, V.nmax[3]);
+        g.heads(B, 0, 0, R.xystride).activations();
+        g.seg_off = D.off[3]; g.seg_a0 = B; g.seg_w0 = 0;
+        CHK(g.run(st));
     }
     {
         RoitrCoarse c; memset(&c, 0, sizeof(c));
@@ -1881,7 +1880,7 @@ int heads_and_matching(Engine& E, const RoitrForwardIO* io, const Plan& P, const
     const int B = P.B, T1 = P.T1, C4 = P.C4, LIM = P.LIM, P_ = P.P_; const bool compact = P.compact;
     float* point_feats = io->point_feats ? io->point_feats : A.get<float>((size_t)T1 * C4);
     if (A.fail) { roitr_set_error("arena exhausted (heads)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-    CHK(gemm(st, T1, F.xd[0], E.fine_proj, point_feats));
+    CHK(Gemm(T1, F.xd[0], E.fine_proj, point_feats).run(st));
     // the last join: the branch, and the geometry chain's tail (the branch waited for it; the main stream waits for it as well, so
     // that a capture sees every stream joined by the stream it began on)
     if (P.sb != st) {
@@ -1907,24 +1906,23 @@ int heads_and_matching(Engine& E, const RoitrForwardIO* io, const Plan& P, const
     if (A.fail) { roitr_set_error("arena exhausted (matching)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
     const int* live_patches = compact ? pair_off + B : nullptr;
     {   // matching_scores = einsum('bnd,bmd->bnm', tgt, src) / sqrt(C)   (RIGA_v2.py:150-152)
-        RoitrGemm g; memset(&g, 0, sizeof(g));
-        g.M = LIM; g.N = LIM; g.K = C4; g.A = point_feats; g.lda = C4; g.a_idx = trows; g.a_limit = T1; g.W = point_feats; g.ldw = C4;
-        g.w_idx = srows; g.w_limit = T1; g.alpha = 1.0f / sqrtf((float)C4); g.C = mscore; g.ldc = LIM; g.batch = (int)NP;
-        g.sC = (long)LIM * LIM; g.sAidx = LIM; g.sWidx = LIM;
+        Gemm g(LIM, LIM, C4, point_feats, C4, point_feats, C4, nullptr, mscore, LIM);
+        g.gather(trows).heads((int)NP, 0, 0, (long)LIM * LIM).activations();
+        g.a_limit = T1; g.w_idx = srows; g.w_limit = T1; g.alpha = 1.0f / sqrtf((float)C4); g.sAidx = LIM; g.sWidx = LIM;
         g.batch_live = live_patches;   // compacted list: the products of the live patches only
         if (E.cfg.operand_dtype == 1) {
             // bf16 operand mode: both operands of this contraction are the point descriptors -- one bf16 copy of them, products on
             // the bf16 matrix cores, fp32 accumulate; the scores (and the optimal transport behind them) stay fp32
             unsigned short* pf_h = A.get<unsigned short>((size_t)T1 * C4);
             if (A.fail) { roitr_set_error("arena exhausted (matching)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-            RoitrGemm gh = g;
+            Gemm gh = g;
             gh.A = reinterpret_cast<const float*>(pf_h); gh.W = reinterpret_cast<const float*>(pf_h); gh.bf16 = ROITR_BF16_W | ROITR_BF16_A;
             if (roitr_gemm_bf16_supported(&gh)) {
                 CHK(roitr_f32_to_bf16((long)T1 * C4, point_feats, pf_h, st));
                 g = gh;
             }
         }
-        CHK(roitr_gemm(&g, st));
+        CHK(g.run(st));
     }
     {   // optimal transport and fine matching: the transport wave of a patch also sets the patch's flags (roitr_matching_tail)
         RoitrOT o; memset(&o, 0, sizeof(o));
