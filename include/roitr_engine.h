@@ -72,6 +72,23 @@ typedef struct RoitrGemm {
 #define ROITR_BF16_C 4
 #define ROITR_BF16_X3 8
 int roitr_gemm(const RoitrGemm* g, roitr_stream_t stream);
+/* The kernel form roitr_gemm gives this struct (the rule roitr_gemm itself dispatches through; host code, no pointer is followed, no
+ * device is needed), or, for a struct roitr_gemm refuses, MINUS the status it returns (-ROITR_ERR_ARG, -ROITR_ERR_UNSUPPORTED).
+ * "Fast path": K % 32 == 0, K <= 2048, lda / ldw % 4 == 0, 16-byte aligned A, A2 and W with sA / sW % 4 == 0; "tiles": 64 x 64 tiles
+ * of C times batch.  The results of SMALL, TILE and TILE_IL are the same bytes; so are those of the LayerNorm forms of one width. */
+#define ROITR_GEMM_NOTHING 0        /* M, N or batch <= 0: returns ROITR_OK, launches nothing */
+#define ROITR_GEMM_SMALL 1          /* fast path, no LayerNorm, tiles < 512: 32 x 32 tiles of 16x16x4 MFMAs */
+#define ROITR_GEMM_TILE 2           /* fast path, no LayerNorm, 512 <= tiles < 1024: 64 x 64 tiles, staging loads in one burst */
+#define ROITR_GEMM_TILE_IL 3        /* fast path, no LayerNorm, tiles >= 1024: 64 x 64 tiles, staging loads between the MFMAs */
+#define ROITR_GEMM_GENERIC 4        /* off the fast path: 64 x 64 tiles with bounds-checked scalar tails */
+#define ROITR_GEMM_LN_GENERIC 5     /* LayerNorm epilogue off the fast path (N == 64 only) */
+#define ROITR_GEMM_LN_TILE64 6      /* LayerNorm epilogue, fast path, N == 64: 64 x 64 tiles */
+#define ROITR_GEMM_LN_TILE128 7     /* LayerNorm epilogue, fast path, N == 128: 64 x 128 tiles */
+#define ROITR_GEMM_LN_TILE256 8     /* LayerNorm epilogue, fast path, N == 256, what LN256 declines (row gathers): 64 x 256 tiles */
+#define ROITR_GEMM_LN256 9          /* LayerNorm epilogue, fast path, N == 256, dense rows: 32 x 256 tiles (csrc/gemm_ln256.hip) */
+#define ROITR_GEMM_BF16 10          /* RoitrGemm::bf16 with ROITR_BF16_W (csrc/gemm_bf16.hip) */
+#define ROITR_GEMM_X3 11            /* RoitrGemm::bf16 == ROITR_BF16_X3 (csrc/gemm_x3.hip) */
+int roitr_gemm_form(const RoitrGemm* g);
 int roitr_gemm_bf16_supported(const RoitrGemm* g);
 /* Diagnostics: block-tile rows of the fp32 LayerNorm launches with N == 256 -- 32 (csrc/gemm_ln256.hip, the default) or 64 (the
  * 64 x 256 instantiation of the general kernel).  Process-wide; the results are the same bytes. */

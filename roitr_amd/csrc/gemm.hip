@@ -582,8 +582,11 @@ struct ShapeTimer {
 };
 }  // namespace
 
-int roitr_gemm_bf16_launch(const RoitrGemm* g, hipStream_t stream);   // gemm_bf16.hip
-int roitr_gemm_x3_launch(const RoitrGemm* g, hipStream_t stream);     // gemm_x3.hip
+// gemm_bf16.hip, gemm_x3.hip: the tile width and grid of a launch (or the refusal: a status, *why), and the launch of exactly that
+int roitr_gemm_bf16_plan(const RoitrGemm* g, int* tn, int* nx, int* ny, int* T, const char** why);
+int roitr_gemm_bf16_launch(const RoitrGemm* g, int tn, int nx, int ny, int T, hipStream_t stream);
+int roitr_gemm_x3_plan(const RoitrGemm* g, int* tn, int* nx, int* ny, int* T, const char** why);
+int roitr_gemm_x3_launch(const RoitrGemm* g, int tn, int nx, int ny, int T, hipStream_t stream);
 bool roitr_gemm_ln256_takes(const RoitrGemm* g);                      // gemm_ln256.hip: the 32 x 256 LayerNorm tile
 void roitr_gemm_ln256_launch(const RoitrGemm* g, hipStream_t stream);
 
@@ -615,48 +618,100 @@ void roitr_gemm_ln256_launch(const RoitrGemm* g, hipStream_t stream);
 // (M 319488 N 768 K 256: 1.67 vs 1.21 ms; M 1.28 M N 256 K 128: 1.31 vs 0.87 ms; gemm family 48.7 vs 37.6 ms per 512-pair
 // step): a lane's weight float4 comes from its own weight row, so one fragment load touches 16 cache lines at 64 B each --
 // the vector-memory pipe, not LDS, becomes the operand bottleneck once nothing else (attention, LayerNorm) overlaps it.
-extern "C" int roitr_gemm(const RoitrGemm* g, hipStream_t stream)
+namespace {
+// What roitr_gemm does with a struct: the form (ROITR_GEMM_*) and the grid that goes with it.  gemm_plan is the ONE place where that is
+// decided -- roitr_gemm launches what it says, roitr_gemm_form reports it.  Host arithmetic on the fields only: no pointer is followed.
+struct GemmPlan { int form; int tn; bool il; int nx, ny, T; };
+
+// ROITR_OK and *p, or the status roitr_gemm returns for this struct with what is unsupported in *why
+int gemm_plan(const RoitrGemm* g, GemmPlan* p, const char** why)
 {
+    *p = GemmPlan{ROITR_GEMM_NOTHING, 1, false, 0, 0, 0};
     if (g->M <= 0 || g->N <= 0 || g->batch <= 0) return ROITR_OK;
-    if (g->K <= 0 || !g->A || !g->W || !g->C) { roitr_set_error("roitr_gemm: K <= 0 or a null operand", __FILE__, __LINE__); return ROITR_ERR_ARG; }
-    auto al16 = [](const void* p, long stride_floats) { return ((uintptr_t)p & 15) == 0 && (stride_floats % 4) == 0; };
+    if (g->K <= 0 || !g->A || !g->W || !g->C) { *why = "roitr_gemm: K <= 0 or a null operand"; return ROITR_ERR_ARG; }
     if (g->bf16) {
-        ShapeTimer timer(g, true, stream);
-        return (g->bf16 & ROITR_BF16_X3) ? roitr_gemm_x3_launch(g, stream) : roitr_gemm_bf16_launch(g, stream);
+        const bool x3 = (g->bf16 & ROITR_BF16_X3) != 0;
+        p->form = x3 ? ROITR_GEMM_X3 : ROITR_GEMM_BF16;
+        return x3 ? roitr_gemm_x3_plan(g, &p->tn, &p->nx, &p->ny, &p->T, why) : roitr_gemm_bf16_plan(g, &p->tn, &p->nx, &p->ny, &p->T, why);
     }
+    auto al16 = [](const void* q, long stride_floats) { return ((uintptr_t)q & 15) == 0 && (stride_floats % 4) == 0; };
     const bool fast = g->K % BK == 0 && g->K <= ZERO_ROW_LEN && g->lda % 4 == 0 && g->ldw % 4 == 0 && al16(g->A, g->sA) && al16(g->W, g->sW) &&
                       (!g->A2 || al16(g->A2, g->sA));
     if (g->A_cat && (!fast || g->batch != 1 || g->seg_off || g->k_cat % BK || g->k_cat <= 0 || g->k_cat >= g->K || g->lda_cat % 4 ||
                      ((uintptr_t)g->A_cat & 15))) {
-        roitr_set_error("roitr_gemm: K-concatenated A needs the fast path (K % 32, 16-byte rows), k_cat % 32 == 0, no batching", __FILE__, __LINE__);
+        *why = "roitr_gemm: K-concatenated A needs the fast path (K % 32, 16-byte rows), k_cat % 32 == 0, no batching";
         return ROITR_ERR_UNSUPPORTED;
     }
-    if (g->a_cat_idx && !g->A_cat) { roitr_set_error("roitr_gemm: a_cat_idx without A_cat", __FILE__, __LINE__); return ROITR_ERR_ARG; }
+    if (g->a_cat_idx && !g->A_cat) { *why = "roitr_gemm: a_cat_idx without A_cat"; return ROITR_ERR_ARG; }
     const bool ln = g->ln_gamma != nullptr;
     const int tn = ln ? g->N / BN : 1;   // LayerNorm epilogue: one block spans the row
-    if (ln && (!gemm_ln_shape_ok(g) || (!fast && tn != 1))) return ROITR_ERR_UNSUPPORTED;
-    if (g->ip_feat && (!ln || !g->ip_idx || !g->ip_dist2)) { roitr_set_error("roitr_gemm: the interpolation addend rides in the fused LayerNorm epilogue only", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
-    const int nx = div_up(g->N, BN * tn), ny = div_up(g->M, BM);
-    int T;
-    if (!gemm_tile_count(nx, ny, g->batch, &T)) return ROITR_ERR_UNSUPPORTED;
+    if (ln && (!gemm_ln_shape_ok(g) || (!fast && tn != 1))) {
+        *why = "roitr_gemm: LayerNorm epilogue shape not supported (N = 64 / 128 / 256 with gamma and beta, no ReLU before the norm, no batching; "
+               "N = 64 only off the fast path)";
+        return ROITR_ERR_UNSUPPORTED;
+    }
+    if (g->ip_feat && (!ln || !g->ip_idx || !g->ip_dist2)) {
+        *why = "roitr_gemm: the interpolation addend rides in the fused LayerNorm epilogue only";
+        return ROITR_ERR_UNSUPPORTED;
+    }
+    p->tn = tn;
+    p->nx = div_up(g->N, BN * tn); p->ny = div_up(g->M, BM);
+    if (!gemm_tile_count(p->nx, p->ny, g->batch, &p->T)) { *why = GEMM_TOO_MANY_TILES; return ROITR_ERR_UNSUPPORTED; }
+    p->il = p->T >= GEMM_IL_MIN_TILES;   // staging loads spread over the MFMA stream (see the kernel): large grids only
+    if (fast && ln && tn == 4 && roitr_gemm_ln256_takes(g)) p->form = ROITR_GEMM_LN256;   // 256-wide LayerNorm rows: 32 x 256 tiles (what it does not take falls through)
+    else if (fast && !ln && p->T < GEMM_SMALL_MAX_TILES) p->form = ROITR_GEMM_SMALL;       // a fraction of a tile per SIMD: 32 x 32 tiles with 4x shorter accumulator chains
+    else if (!fast) p->form = ln ? ROITR_GEMM_LN_GENERIC : ROITR_GEMM_GENERIC;
+    else if (ln) p->form = tn == 1 ? ROITR_GEMM_LN_TILE64 : tn == 2 ? ROITR_GEMM_LN_TILE128 : ROITR_GEMM_LN_TILE256;
+    else p->form = p->il ? ROITR_GEMM_TILE_IL : ROITR_GEMM_TILE;   // plain launches: 64 x 64 tiles only
+    return ROITR_OK;
+}
+}  // namespace
+
+extern "C" int roitr_gemm_form(const RoitrGemm* g)
+{
+    GemmPlan p;
+    const char* why = nullptr;
+    const int st = gemm_plan(g, &p, &why);
+    return st == ROITR_OK ? p.form : -st;
+}
+
+extern "C" int roitr_gemm(const RoitrGemm* g, hipStream_t stream)
+{
+    GemmPlan p;
+    const char* why = "";
+    const int st = gemm_plan(g, &p, &why);
+    if (st != ROITR_OK) { roitr_set_error(why, __FILE__, __LINE__); return st; }
+    if (p.form == ROITR_GEMM_NOTHING) return ROITR_OK;
+    if (p.form == ROITR_GEMM_BF16 || p.form == ROITR_GEMM_X3) {
+        ShapeTimer timer(g, true, stream);
+        return p.form == ROITR_GEMM_X3 ? roitr_gemm_x3_launch(g, p.tn, p.nx, p.ny, p.T, stream) : roitr_gemm_bf16_launch(g, p.tn, p.nx, p.ny, p.T, stream);
+    }
+    const int nx = p.nx, ny = p.ny, T = p.T;
     const unsigned grid = (unsigned)xcd_grid(T);
     const int prof_cls = gemm_prof_begin(g, stream);
     {
-    ShapeTimer timer(g, fast, stream);
+    ShapeTimer timer(g, p.form != ROITR_GEMM_GENERIC && p.form != ROITR_GEMM_LN_GENERIC, stream);
     const bool a2 = g->A2 != nullptr;
-    const bool il = T >= GEMM_IL_MIN_TILES;   // staging loads spread over the MFMA stream (see the kernel): large grids only
-    if (fast && ln && tn == 4 && roitr_gemm_ln256_takes(g)) {   // 256-wide LayerNorm rows: 32 x 256 tiles (what it does not take falls through)
+    switch (p.form) {
+    case ROITR_GEMM_LN256:
         roitr_gemm_ln256_launch(g, stream);
-    } else if (fast && !ln && T < GEMM_SMALL_MAX_TILES) {   // a fraction of a tile per SIMD: 32 x 32 tiles with 4x shorter accumulator chains
+        break;
+    case ROITR_GEMM_SMALL: {
         const int sx = div_up(g->N, SM), sy = div_up(g->M, SM);
         const int ST = sx * sy * g->batch;
         if (a2) gemm_small_kernel<true><<<xcd_grid(ST), 256, 0, stream>>>(*g, sx, sy, ST);
         else gemm_small_kernel<false><<<xcd_grid(ST), 256, 0, stream>>>(*g, sx, sy, ST);
-    } else if (!fast) {
-        if (ln) gemm_kernel<false, 1, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
-        else gemm_kernel<false, 1, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
-    } else
-        dispatch_tn(tn, [&](auto tn_) {
+        break;
+    }
+    case ROITR_GEMM_GENERIC:
+        gemm_kernel<false, 1, false><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
+        break;
+    case ROITR_GEMM_LN_GENERIC:
+        gemm_kernel<false, 1, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);
+        break;
+    default: {   // the fast 64 x 64 TN tiles: TILE / TILE_IL (TN = 1) and the LayerNorm widths
+        const bool ln = p.form != ROITR_GEMM_TILE && p.form != ROITR_GEMM_TILE_IL, il = p.il;
+        dispatch_tn(p.tn, [&](auto tn_) {
             constexpr int TN = decltype(tn_)::value;
             auto launch = [&](auto ln_) {
                 constexpr bool LN = decltype(ln_)::value;
@@ -668,6 +723,8 @@ extern "C" int roitr_gemm(const RoitrGemm* g, hipStream_t stream)
             if (ln) launch(std::true_type());
             else if constexpr (TN == 1) launch(std::false_type());   // plain launches: 64 x 64 tiles only
         });
+    }
+    }
     }
     roitr_prof_end(prof_cls, stream);
     ROITR_LAUNCH_CHECK();

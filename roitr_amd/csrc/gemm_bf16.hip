@@ -325,11 +325,13 @@ extern "C" int roitr_gemm_bf16_supported(const RoitrGemm* g)
     return 1;
 }
 
-int roitr_gemm_bf16_launch(const RoitrGemm* g, hipStream_t stream)
+// Tile width and grid of the launch roitr_gemm gives a bf16 struct, or the refusal (status, what is unsupported in *why): read by
+// roitr_gemm, which launches exactly this, and by roitr_gemm_form.  Host arithmetic on the fields only.
+int roitr_gemm_bf16_plan(const RoitrGemm* g, int* tn_, int* nx_, int* ny_, int* T, const char** why)
 {
-    if (g->ip_feat) { roitr_set_error("roitr_gemm: the interpolation addend is an fp32-kernel epilogue", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
+    if (g->ip_feat) { *why = "roitr_gemm: the interpolation addend is an fp32-kernel epilogue"; return ROITR_ERR_UNSUPPORTED; }
     if (!roitr_gemm_bf16_supported(g)) {
-        roitr_set_error("roitr_gemm: shape / layout not supported by the bf16 kernel (K % 64, 16-byte rows, bf16 weights)", __FILE__, __LINE__);
+        *why = "roitr_gemm: shape / layout not supported by the bf16 kernel (K % 64, 16-byte rows, bf16 weights)";
         return ROITR_ERR_UNSUPPORTED;
     }
     // tile width: whole rows for the LayerNorm epilogue; plain launches 256 / 128 columns where N allows and the grid still fills the
@@ -342,8 +344,13 @@ int roitr_gemm_bf16_launch(const RoitrGemm* g, hipStream_t stream)
         while (tn > 1 && (long)ny * div_up(g->N, BN * tn) * g->batch < 2048) tn >>= 1;
     }
     const int nx = div_up(g->N, BN * tn);
-    int T;
-    if (!gemm_tile_count(nx, ny, g->batch, &T)) return ROITR_ERR_UNSUPPORTED;
+    if (!gemm_tile_count(nx, ny, g->batch, T)) { *why = GEMM_TOO_MANY_TILES; return ROITR_ERR_UNSUPPORTED; }
+    *tn_ = tn; *nx_ = nx; *ny_ = ny;
+    return ROITR_OK;
+}
+
+int roitr_gemm_bf16_launch(const RoitrGemm* g, int tn, int nx, int ny, int T, hipStream_t stream)
+{
     const unsigned grid = (unsigned)xcd_grid(T);
     const bool a_f32 = (g->bf16 & ROITR_BF16_A) == 0, ln = g->ln_gamma != nullptr;
     const int prof_cls = gemm_prof_begin(g, stream);

@@ -12,7 +12,8 @@ static inline bool gemm_ln_shape_ok(const RoitrGemm* g)
     return g->N % 64 == 0 && (tn == 1 || tn == 2 || tn == 4) && g->batch == 1 && !g->seg_off && !g->relu && g->ln_beta;
 }
 
-// tiles of the launch; false: more than the 1-D grid takes
+// tiles of the launch; false: more than the 1-D grid takes (the refusal's text: GEMM_TOO_MANY_TILES)
+#define GEMM_TOO_MANY_TILES "roitr_gemm: too many tiles for one grid (row tiles x column tiles x batch > 0x7ffffff0)"
 static inline bool gemm_tile_count(int nx, int ny, int batch, int* T)
 {
     const long Tl = (long)nx * ny * batch;

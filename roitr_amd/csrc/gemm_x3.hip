@@ -299,10 +299,12 @@ extern "C" int roitr_gemm_x3_supported(const RoitrGemm* g)
     return 1;
 }
 
-int roitr_gemm_x3_launch(const RoitrGemm* g, hipStream_t stream)
+// Tile width and grid of the launch roitr_gemm gives a split-operand struct, or the refusal (status, what is unsupported in *why):
+// read by roitr_gemm, which launches exactly this, and by roitr_gemm_form.  Host arithmetic on the fields only.
+int roitr_gemm_x3_plan(const RoitrGemm* g, int* tn_, int* nx_, int* ny_, int* T, const char** why)
 {
     if (!roitr_gemm_x3_supported(g)) {
-        roitr_set_error("roitr_gemm: shape / layout not supported by the bf16x3 kernel (K % 32, 16-byte rows, split weights, no batching)", __FILE__, __LINE__);
+        *why = "roitr_gemm: shape / layout not supported by the bf16x3 kernel (K % 32, 16-byte rows, split weights, no batching)";
         return ROITR_ERR_UNSUPPORTED;
     }
     // tile: whole rows for the LayerNorm epilogue (64 x N); otherwise 64 x 256 where N allows and the grid fills the chip (measured at
@@ -314,11 +316,16 @@ int roitr_gemm_x3_launch(const RoitrGemm* g, hipStream_t stream)
     int tn = ln ? g->N / BN : (g->N % 256 == 0 ? 4 : (g->N % 128 == 0 ? 2 : 1));
     while (!ln && tn > 1 && (long)ny * div_up(g->N, BN * tn) < 512) tn >>= 1;
     const int nx = div_up(g->N, BN * tn);
-    int T;
-    if (!gemm_tile_count(nx, ny, 1, &T)) return ROITR_ERR_UNSUPPORTED;
+    if (!gemm_tile_count(nx, ny, 1, T)) { *why = GEMM_TOO_MANY_TILES; return ROITR_ERR_UNSUPPORTED; }
+    *tn_ = tn; *nx_ = nx; *ny_ = ny;
+    return ROITR_OK;
+}
+
+int roitr_gemm_x3_launch(const RoitrGemm* g, int tn, int nx, int ny, int T, hipStream_t stream)
+{
     const unsigned grid = (unsigned)xcd_grid(T);
     const int prof_cls = gemm_prof_begin(g, stream);
-    const bool a2 = g->A2 != nullptr;
+    const bool ln = g->ln_gamma != nullptr, a2 = g->A2 != nullptr;
     dispatch_tn(tn, [&](auto tn_) {
         constexpr int TN = decltype(tn_)::value;
         if (ln && a2) gemm_x3_kernel<1, TN, true, true><<<grid, 256, 0, stream>>>(*g, nx, ny, T);

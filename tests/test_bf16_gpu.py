@@ -25,6 +25,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from gemm_util import _gemm_abi  # noqa: E402
 from gpu_util import build_model, pair_to_device  # noqa: E402
 
 CORES = len(os.sched_getaffinity(0))
@@ -63,18 +64,6 @@ def test_gemm_bf16_matches_bf16_rounded_float64(M, N, K, relu):
     assert got_h.dtype == torch.bfloat16
     gh = got_h.float().cpu().numpy()
     assert (np.abs(gh - ref) <= tol + 2.0 ** -8 * np.abs(ref)).all()      # + one bf16 rounding of the result
-
-
-def _gemm_abi(**fields):
-    """roitr_gemm through the C ABI: RoitrGemm fields by name (tensors as device pointers), everything else zero."""
-    import ctypes
-    from roitr_amd import _lib as L
-    from roitr_amd import ops
-    g = ops._Gemm()
-    for k, v in fields.items():
-        setattr(g, k, L.ptr(v) if torch.is_tensor(v) else v)
-    L.check(L.lib().roitr_gemm(ctypes.byref(g), L.stream_ptr()), "gemm")
-    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("M,N,K,a_h", [(333, 192, 128, False), (70001, 512, 128, False), (517, 256, 64, True)])
