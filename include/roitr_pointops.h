@@ -93,6 +93,34 @@ int roitr_knnquery_ex(int b, int n, int m, int nsample, const float* xyz, const 
                       const float* ref_normals, const float* query_normals, int use_grid, int m_capacity, void* ws,
                       roitr_stream_t stream);
 
+/* Which kernel form roitr_knnquery_ex (capped == 0) or roitr_knn_within (capped != 0, nsample 1, outputs = ROITR_KNN_OUT_DIST2) gives a
+ * call, chosen by shape alone: the launcher dispatches through the same host function, no pointer is followed, no GPU is needed.
+ *   self_query   the queries are the reference points themselves (new_xyz == xyz, new_offset == offset, m == n)
+ *   outputs      ROITR_KNN_OUT_* of the outputs that are not NULL;  normals != 0: both normal arrays are given
+ * Returns ROITR_KNN_FORM | width << 8 | sort << 16 (read with the three macros), or minus the status the call is refused with.
+ *   width   list slots of the kernel's template: L of LANE_BRUTE, LANE and PREFILTER (2, 4, 10, 18, 34), NR of BRUTE (1, 2), else 0
+ *   sort    the queries are counting-sorted by grid cell first: ROITR_KNN_SORT_NONE, _4096 or _MAX (the cell cap of the grid,
+ *           the one roitr_knn_build_grid_ex built it with: 4096 cells per cloud while n <= 6144 b) */
+#define ROITR_KNN_NOTHING 0     /* m <= 0 */
+#define ROITR_KNN_BRUTE 1       /* no grid: a wave per query, index order */
+#define ROITR_KNN_LANE_BRUTE 2  /* no grid, >= 65536 queries, nsample <= 33: a lane per query, clouds staged in LDS */
+#define ROITR_KNN_LANE 3        /* grid, >= 8192 queries, nsample <= 33: a lane per query, ring search */
+#define ROITR_KNN_PREFILTER 4   /* as LANE at nsample 4 .. 9, exact k: radius prefilter, then LANE on its retry list */
+#define ROITR_KNN_WITHIN 5      /* as LANE for roitr_knn_within's call: one pass over the cells of the ball */
+#define ROITR_KNN_CELL 6        /* grid, self query, nsample <= 65: a workgroup per cell, then GRIDSEL on its retry list */
+#define ROITR_KNN_GRIDSEL 7     /* grid, everything else: a wave per query with buffered selection */
+#define ROITR_KNN_OUT_IDX 1
+#define ROITR_KNN_OUT_DIST2 2
+#define ROITR_KNN_OUT_GROUP 4
+#define ROITR_KNN_OUT_PPF 8
+#define ROITR_KNN_SORT_NONE 0
+#define ROITR_KNN_SORT_4096 1
+#define ROITR_KNN_SORT_MAX 2
+#define ROITR_KNN_FORM(v) ((v) & 0xff)
+#define ROITR_KNN_WIDTH(v) (((v) >> 8) & 0xff)
+#define ROITR_KNN_SORT(v) ((v) >> 16)
+int roitr_knn_form(int b, int n, int m, int nsample, int self_query, int outputs, int normals, int use_grid, int capped);
+
 /* ------------------------------------------------------------------ input preparation
  * dataset/tdmatch.py:120-127: open3d estimate_normals(KDTreeSearchParamKNN(knn)) + dataset/common.py:312-320 normal_redirect.
  * normals (n,3) = unit eigenvector of the smallest eigenvalue of the covariance of the knn nearest points (the point

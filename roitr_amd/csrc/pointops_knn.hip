@@ -25,9 +25,11 @@
 #include "common.h"
 #include "knn_grid.h"   // RoitrGrid, GRID_MAX_CELLS, GRID_MAX_DIM
 #include "prof.h"
+#include "roitr_pointops.h"   // ROITR_KNN_*
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #define KNN_FILL 1e10f  // knnquery_cuda_kernel.cu:89
 
@@ -35,7 +37,39 @@ namespace {
 
 __device__ __forceinline__ float rl_f(float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); }
 __device__ __forceinline__ int rl_i(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
+// LDS operations of a wave complete in order, so cross-lane hand-offs inside one wave only need the counter wait
+__device__ __forceinline__ void lds_sync_wave() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// appends query q to a device list (tie list, retry list): one slot from the list's counter
+__device__ __forceinline__ void push_query(int* count, int* list, int q) { list[atomicAdd(count, 1)] = q; }
 
+// ---------------------------------------------------------------- grid geometry shared by the query kernels
+// Home cell of a query.  Clamped in float first: far-away queries must not overflow the int conversion.  (The grid itself is
+// defined by grid_build_kernel's floorf form; for the non-negative values left after the clamp the two agree.)
+__device__ __forceinline__ void home_cell(const RoitrGrid& g, float x, float y, float z, int (&c)[3])
+{
+    c[0] = (int)fminf(fmaxf((x - g.ox) * g.inv_h, 0.f), (float)(g.nx - 1));
+    c[1] = (int)fminf(fmaxf((y - g.oy) * g.inv_h, 0.f), (float)(g.ny - 1));
+    c[2] = (int)fminf(fmaxf((z - g.oz) * g.inv_h, 0.f), (float)(g.nz - 1));
+}
+// cells within Chebyshev distance r of cell c0, cut to the grid
+struct ShellBox { int x0, x1, y0, y1, z0, z1; };
+__device__ __forceinline__ ShellBox shell_box(const int (&c0)[3], int r, const RoitrGrid& g)
+{
+    return ShellBox{max(c0[0] - r, 0), min(c0[0] + r, g.nx - 1), max(c0[1] - r, 0), min(c0[1] + r, g.ny - 1), max(c0[2] - r, 0), min(c0[2] + r, g.nz - 1)};
+}
+// Everything unseen lies outside the searched box: the distance from the query to the nearest face of the box that has cells behind
+// it (+inf: the box is the whole grid).  The callers subtract their rounding margin and apply their own stop rule.
+__device__ __forceinline__ float unseen_bound(const RoitrGrid& g, const ShellBox& B, float qx, float qy, float qz)
+{
+    float dmin = INFINITY;
+    if (B.x0 > 0) dmin = fminf(dmin, qx - __fmaf_rn((float)B.x0, g.h, g.ox));
+    if (B.x1 < g.nx - 1) dmin = fminf(dmin, __fmaf_rn((float)(B.x1 + 1), g.h, g.ox) - qx);
+    if (B.y0 > 0) dmin = fminf(dmin, qy - __fmaf_rn((float)B.y0, g.h, g.oy));
+    if (B.y1 < g.ny - 1) dmin = fminf(dmin, __fmaf_rn((float)(B.y1 + 1), g.h, g.oy) - qy);
+    if (B.z0 > 0) dmin = fminf(dmin, qz - __fmaf_rn((float)B.z0, g.h, g.oz));
+    if (B.z1 < g.nz - 1) dmin = fminf(dmin, __fmaf_rn((float)(B.z1 + 1), g.h, g.oz) - qz);
+    return dmin;
+}
 // ---------------------------------------------------------------- lane-distributed sorted list
 template <int NR>
 struct WaveList {
@@ -166,10 +200,7 @@ template <int NR>
 __device__ __forceinline__ void finish_query(WaveList<NR>& L, const KnnOut& o, int q, int nsample, int lane, const float* xyz, Query Q)
 {
     if (has_tie(L, nsample, lane)) {
-        if (lane == 0) {
-            const int slot = atomicAdd(o.tie_count, 1);
-            o.tie_list[slot] = q;
-        }
+        if (lane == 0) push_query(o.tie_count, o.tie_list, q);
         return;  // the replay kernel owns this query's rows
     }
     write_rows<NR>(o, q, nsample, L.d, L.i, lane, xyz, Q);
@@ -348,112 +379,9 @@ __global__ __launch_bounds__(1024) void grid_build_kernel(const float* __restric
     }
 }
 
-// ---------------------------------------------------------------- grid query
-// Rows (fixed cz, cy; cx in [x0, x1]) of the current shell are gathered into `runs` (one run per
-// lane), prefix-summed across the wave, and the concatenated candidates are consumed 64 at a time.
-template <int NR>
-__global__ __launch_bounds__(256) void knn_grid_kernel(int m, int nsample, const float* __restrict__ xyz,
-                                                       const float* __restrict__ new_xyz, const int* __restrict__ offset,
-                                                       const int* __restrict__ new_offset, const RoitrGrid* __restrict__ grids,
-                                                       const int* __restrict__ cell_start, const float4* __restrict__ sorted, KnnOut o)
-{
-    const int lane = threadIdx.x & 63;
-    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q >= m) return;
-    int start, end, seg;
-    find_segment(q, offset, new_offset, start, end, seg, o.b);
-    const RoitrGrid g = grids[seg];
-    const int* cs = cell_start + (size_t)seg * (GRID_MAX_CELLS + 1);
-    Query Q = {new_xyz[(size_t)q * 3], new_xyz[(size_t)q * 3 + 1], new_xyz[(size_t)q * 3 + 2]};
-    WaveList<NR> L;
-    L.init(start);
-    const int tau_pos = nsample;
-    float tau = KNN_FILL;
-
-    int c0[3];
-    {
-        const float t[3] = {(Q.x - g.ox) * g.inv_h, (Q.y - g.oy) * g.inv_h, (Q.z - g.oz) * g.inv_h};
-        const int dim[3] = {g.nx, g.ny, g.nz};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            // clamp in float first: far-away queries must not overflow the int conversion
-            const float tc = fminf(fmaxf(t[a], 0.f), (float)(dim[a] - 1));
-            c0[a] = (int)tc;
-        }
-    }
-    const float margin = 2e-4f * g.h;
-    const int maxr = max(max(g.nx, g.ny), g.nz);
-    for (int r = 0; r <= maxr; ++r) {
-        const int x0 = max(c0[0] - r, 0), x1 = min(c0[0] + r, g.nx - 1);
-        const int y0 = max(c0[1] - r, 0), y1 = min(c0[1] + r, g.ny - 1);
-        const int z0 = max(c0[2] - r, 0), z1 = min(c0[2] + r, g.nz - 1);
-        const int ny = y1 - y0 + 1, nz = z1 - z0 + 1;
-        // rows of this shell: (z,y) pairs; a row on the shell's z/y faces contributes [x0,x1],
-        // an interior row contributes only the two x end cells (when they are new)
-        const int nrows = ny * nz;
-        for (int rb = 0; rb < nrows; rb += 32) {
-            // lanes 0..31 -> row rb+lane, low piece; lanes 32..63 -> same row, high piece
-            const int row = rb + (lane & 31);
-            int rs = 0, re = 0;
-            if (row < nrows) {
-                const int cy = y0 + row % ny, cz = z0 + row / ny;
-                const bool face = (r == 0) || (cy == c0[1] - r) || (cy == c0[1] + r) || (cz == c0[2] - r) || (cz == c0[2] + r);
-                const int rowbase = (cz * g.ny + cy) * g.nx;
-                if (face) {
-                    if (lane < 32) { rs = cs[rowbase + x0]; re = cs[rowbase + x1 + 1]; }
-                } else {
-                    const int cx = lane < 32 ? c0[0] - r : c0[0] + r;
-                    if (cx >= 0 && cx < g.nx) { rs = cs[rowbase + cx]; re = cs[rowbase + cx + 1]; }
-                }
-            }
-            const int len = re - rs;
-            int incl = len;
-#pragma unroll
-            for (int s = 1; s < 64; s <<= 1) { const int v = __shfl_up(incl, s, 64); if (lane >= s) incl += v; }
-            const int total = rl_i(incl, 63);
-            const int excl = incl - len;
-            for (int b = 0; b < total; b += 64) {
-                const int e = b + lane;
-                // run holding element e = first lane whose inclusive prefix exceeds e (all lanes
-                // run the same 6 probe steps so the cross-lane reads stay convergent)
-                const int es = min(e, total - 1);
-                int lo = 0, hi = 63;
-#pragma unroll
-                for (int it = 0; it < 6; ++it) {
-                    const int mid = (lo + hi) >> 1;
-                    const bool gt = __shfl(incl, mid, 64) > es;
-                    hi = gt ? mid : hi;
-                    lo = gt ? lo : min(mid + 1, 63);
-                }
-                const int src_run = __shfl(rs, lo, 64) + (es - __shfl(excl, lo, 64));
-                const int src = e < total ? src_run : -1;
-                float cd = INFINITY; int ci = 0;
-                if (src >= 0) {
-                    const float4 p = sorted[src];
-                    cd = sqdist3(Q.x, Q.y, Q.z, p.x, p.y, p.z);
-                    ci = __float_as_int(p.w);
-                }
-                consume_batch<NR>(L, cd, ci, tau, tau_pos, lane);
-            }
-        }
-        // everything unseen lies outside the searched box: lower-bound its distance
-        float dmin = INFINITY;
-        if (x0 > 0) dmin = fminf(dmin, Q.x - __fmaf_rn((float)x0, g.h, g.ox));
-        if (x1 < g.nx - 1) dmin = fminf(dmin, __fmaf_rn((float)(x1 + 1), g.h, g.ox) - Q.x);
-        if (y0 > 0) dmin = fminf(dmin, Q.y - __fmaf_rn((float)y0, g.h, g.oy));
-        if (y1 < g.ny - 1) dmin = fminf(dmin, __fmaf_rn((float)(y1 + 1), g.h, g.oy) - Q.y);
-        if (z0 > 0) dmin = fminf(dmin, Q.z - __fmaf_rn((float)z0, g.h, g.oz));
-        if (z1 < g.nz - 1) dmin = fminf(dmin, __fmaf_rn((float)(z1 + 1), g.h, g.oz) - Q.z);
-        if (dmin == INFINITY) break;  // whole grid covered
-        const float dm = dmin - margin;
-        if (dm > 0.f && tau < dm * dm) break;
-    }
-    finish_query<NR>(L, o, q, nsample, lane, xyz, Q);
-}
-
 // ---------------------------------------------------------------- grid query with buffered selection (34 <= nsample + 1 <= 128)
-// For large k the one-at-a-time insertion of knn_grid_kernel (and the 66/101-slot register chains of knn_lane_kernel)
-// cost ~30 instructions per accepted candidate and almost every candidate of the first shells is accepted.  Here the
+// For large k a one-at-a-time insertion into a sorted list (the lane-distributed list of knn_brute_kernel, or a register chain like
+// knn_lane_kernel's) costs ~30 instructions per accepted candidate and almost every candidate of the first shells is accepted.  Here the
 // candidates of a shell that beat the current (nsample+1)-th distance are appended to an LDS buffer by ballot
 // compaction; once the buffer holds nsample+1 entries it is cut down to the <= 128 smallest by ONE histogram pass
 // (64 distance bins in LDS, prefix scan across the lanes, everything up to the bin that contains rank nsample+1 is
@@ -548,15 +476,10 @@ __global__ __launch_bounds__(256) void knn_gridsel_kernel(int m, int nsample, co
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
 
     int c0[3];
-    {
-        const float t[3] = {(Q.x - g.ox) * g.inv_h, (Q.y - g.oy) * g.inv_h, (Q.z - g.oz) * g.inv_h};
-        const int dim[3] = {g.nx, g.ny, g.nz};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) c0[a] = (int)fminf(fmaxf(t[a], 0.f), (float)(dim[a] - 1));
-    }
+    home_cell(g, Q.x, Q.y, Q.z, c0);
     // buffer -> the <= 128 best in L, sorted; buffer front rewritten with them
     auto reduce = [&]() {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        lds_sync_wave();
         int n_in = cnt;
         const float* sd = bd; const int* si = bi;
         if (cnt > 128) {
@@ -566,9 +489,9 @@ __global__ __launch_bounds__(256) void knn_gridsel_kernel(int m, int nsample, co
             if (!(mx > mn)) { overflow = true; return; }
             const float scale = 63.999f / (mx - mn);
             hist[lane] = 0;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds_sync_wave();
             for (int e = lane; e < cnt; e += 64) atomicAdd(&hist[min(63, (int)((bd[e] - mn) * scale))], 1);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds_sync_wave();
             int incl = hist[lane];
 #pragma unroll
             for (int s_ = 1; s_ < 64; s_ <<= 1) { const int v = __shfl_up(incl, s_, 64); if (lane >= s_) incl += v; }
@@ -585,7 +508,7 @@ __global__ __launch_bounds__(256) void knn_gridsel_kernel(int m, int nsample, co
                 if (keep) { const int pos = base + __popcll(mk & lt_mask); ld[pos] = v; li[pos] = bi[e]; }
                 base += __popcll(mk);
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds_sync_wave();
             n_in = nsel; sd = ld; si = li;
         }
 #pragma unroll
@@ -606,9 +529,7 @@ __global__ __launch_bounds__(256) void knn_gridsel_kernel(int m, int nsample, co
     const float margin = 2e-4f * g.h;
     const int maxr = max(max(g.nx, g.ny), g.nz);
     for (int r = 0; r <= maxr && !overflow; ++r) {
-        const int x0 = max(c0[0] - r, 0), x1 = min(c0[0] + r, g.nx - 1);
-        const int y0 = max(c0[1] - r, 0), y1 = min(c0[1] + r, g.ny - 1);
-        const int z0 = max(c0[2] - r, 0), z1 = min(c0[2] + r, g.nz - 1);
+        const ShellBox B = shell_box(c0, r, g);
         // rows of this shell, wave-uniform: a row on a y/z face contributes the run of cells [x0, x1], an interior row only
         // its two (new) x end cells.  Every lane strides a run -- no cross-lane traffic in the enumeration.
         // (Measured and dropped: issuing the first loads of 8 runs together, 7.9 vs 6.7 ms on the k = 64 stress case --
@@ -631,11 +552,11 @@ __global__ __launch_bounds__(256) void knn_gridsel_kernel(int m, int nsample, co
                 sorted_ok = sorted_ok && add == 0;
             }
         };
-        for (int cz = z0; cz <= z1 && !overflow; ++cz) {
-            for (int cy = y0; cy <= y1 && !overflow; ++cy) {
+        for (int cz = B.z0; cz <= B.z1 && !overflow; ++cz) {
+            for (int cy = B.y0; cy <= B.y1 && !overflow; ++cy) {
                 const int rowbase = (cz * g.ny + cy) * g.nx;
                 const bool face = (r == 0) || (cy == c0[1] - r) || (cy == c0[1] + r) || (cz == c0[2] - r) || (cz == c0[2] + r);
-                if (face) scan_run(cs[rowbase + x0], cs[rowbase + x1 + 1]);
+                if (face) scan_run(cs[rowbase + B.x0], cs[rowbase + B.x1 + 1]);
                 else {
                     const int xa = c0[0] - r, xb = c0[0] + r;
                     if (xa >= 0) scan_run(cs[rowbase + xa], cs[rowbase + xa + 1]);
@@ -646,20 +567,14 @@ __global__ __launch_bounds__(256) void knn_gridsel_kernel(int m, int nsample, co
         if (overflow) break;
         if (cnt >= need && !sorted_ok) reduce();
         if (overflow) break;
-        float dmin = INFINITY;
-        if (x0 > 0) dmin = fminf(dmin, Q.x - __fmaf_rn((float)x0, g.h, g.ox));
-        if (x1 < g.nx - 1) dmin = fminf(dmin, __fmaf_rn((float)(x1 + 1), g.h, g.ox) - Q.x);
-        if (y0 > 0) dmin = fminf(dmin, Q.y - __fmaf_rn((float)y0, g.h, g.oy));
-        if (y1 < g.ny - 1) dmin = fminf(dmin, __fmaf_rn((float)(y1 + 1), g.h, g.oy) - Q.y);
-        if (z0 > 0) dmin = fminf(dmin, Q.z - __fmaf_rn((float)z0, g.h, g.oz));
-        if (z1 < g.nz - 1) dmin = fminf(dmin, __fmaf_rn((float)(z1 + 1), g.h, g.oz) - Q.z);
+        const float dmin = unseen_bound(g, B, Q.x, Q.y, Q.z);
         if (dmin == INFINITY) break;  // whole grid covered
         const float dm = dmin - margin;
         if (dm > 0.f && tau < dm * dm) break;
     }
     if (!overflow && !sorted_ok) reduce();   // fewer than nsample+1 candidates in the whole cloud, or a trailing append
     if (overflow) {   // rare: hand the query to the exact replay
-        if (lane == 0) { const int slot = atomicAdd(o.tie_count, 1); o.tie_list[slot] = q; }
+        if (lane == 0) push_query(o.tie_count, o.tie_list, q);
         continue;
     }
     finish_query<2>(L, o, q, nsample, lane, xyz, Q);
@@ -753,8 +668,8 @@ __global__ __launch_bounds__(256) void knn_cell_kernel(int nsample, const float*
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     uint2* nl = nl_[w]; int* hist = hist_[w]; float* sd = sd_[w]; int* sj = sj_[w];
     const float margin = 2e-4f * g.h;
-    auto retry = [&](int q) { if (lane == 0) { const int slot = atomicAdd(retry_count, 1); retry_list[slot] = q; } };
-    auto tie = [&](int q) { if (lane == 0) { const int slot = atomicAdd(o.tie_count, 1); o.tie_list[slot] = q; } };
+    auto retry = [&](int q) { if (lane == 0) push_query(retry_count, retry_list, q); };
+    auto tie = [&](int q) { if (lane == 0) push_query(o.tie_count, o.tie_list, q); };
 
     for (int cell = blockIdx.x; cell < ncell; cell += gridDim.x) {
         const int qs = cs[cell], qe = cs[cell + 1];
@@ -763,6 +678,7 @@ __global__ __launch_bounds__(256) void knn_cell_kernel(int nsample, const float*
         const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.nx - 1);
         const int y0 = max(cy - 1, 0), y1 = min(cy + 1, g.ny - 1);
         const int z0 = max(cz - 1, 0), z1 = min(cz + 1, g.nz - 1);
+        const ShellBox B = {x0, x1, y0, y1, z0, z1};   // shell_box around (cx, cy, cz); its limits are used one by one below
         __syncthreads();                        // the previous cell's queries are done with cand / run tables
         if (tid < 64) {   // lanes 0..8: one (z, y) row of the neighbourhood each; exclusive prefix of the run lengths across them
             int a = 0, b = 0;
@@ -780,7 +696,7 @@ __global__ __launch_bounds__(256) void knn_cell_kernel(int nsample, const float*
         __syncthreads();
         const int C = run_off[9];
         if (C > CELL_CAP) {                     // neighbourhood does not fit: all queries of the cell take the general path
-            for (int p = qs + tid; p < qe; p += 256) { const int slot = atomicAdd(retry_count, 1); retry_list[slot] = __float_as_int(sorted[p].w); }
+            for (int p = qs + tid; p < qe; p += 256) { const int slot = atomicAdd(retry_count, 1); retry_list[slot] = __float_as_int(sorted[p].w); }   // the slot first, then the load: as compiled before
             continue;
         }
         for (int e = tid; e < ((C + 63) & ~63); e += 256) {
@@ -802,13 +718,7 @@ __global__ __launch_bounds__(256) void knn_cell_kernel(int nsample, const float*
             const float4 Qp = cand[qslot];
             const int q = __float_as_int(Qp.w);
             // guarantee radius: distance to the nearest face of the searched box that has unseen cells behind it
-            float dmin = INFINITY;
-            if (x0 > 0) dmin = fminf(dmin, Qp.x - __fmaf_rn((float)x0, g.h, g.ox));
-            if (x1 < g.nx - 1) dmin = fminf(dmin, __fmaf_rn((float)(x1 + 1), g.h, g.ox) - Qp.x);
-            if (y0 > 0) dmin = fminf(dmin, Qp.y - __fmaf_rn((float)y0, g.h, g.oy));
-            if (y1 < g.ny - 1) dmin = fminf(dmin, __fmaf_rn((float)(y1 + 1), g.h, g.oy) - Qp.y);
-            if (z0 > 0) dmin = fminf(dmin, Qp.z - __fmaf_rn((float)z0, g.h, g.oz));
-            if (z1 < g.nz - 1) dmin = fminf(dmin, __fmaf_rn((float)(z1 + 1), g.h, g.oz) - Qp.z);
+            const float dmin = unseen_bound(g, B, Qp.x, Qp.y, Qp.z);
             const bool covered = dmin == INFINITY;          // the box is the whole grid
             const float dm = dmin - margin;
             if (!covered && !(dm > 0.f)) { retry(q); continue; }
@@ -852,13 +762,8 @@ __global__ __launch_bounds__(256) void knn_cell_kernel(int nsample, const float*
                 const int x0b = max(cx - 2, 0), x1b = min(cx + 2, g.nx - 1);
                 const int y0b = max(cy - 2, 0), y1b = min(cy + 2, g.ny - 1);
                 const int z0b = max(cz - 2, 0), z1b = min(cz + 2, g.nz - 1);
-                float dmin2 = INFINITY;
-                if (x0b > 0) dmin2 = fminf(dmin2, Qp.x - __fmaf_rn((float)x0b, g.h, g.ox));
-                if (x1b < g.nx - 1) dmin2 = fminf(dmin2, __fmaf_rn((float)(x1b + 1), g.h, g.ox) - Qp.x);
-                if (y0b > 0) dmin2 = fminf(dmin2, Qp.y - __fmaf_rn((float)y0b, g.h, g.oy));
-                if (y1b < g.ny - 1) dmin2 = fminf(dmin2, __fmaf_rn((float)(y1b + 1), g.h, g.oy) - Qp.y);
-                if (z0b > 0) dmin2 = fminf(dmin2, Qp.z - __fmaf_rn((float)z0b, g.h, g.oz));
-                if (z1b < g.nz - 1) dmin2 = fminf(dmin2, __fmaf_rn((float)(z1b + 1), g.h, g.oz) - Qp.z);
+                const ShellBox B2 = {x0b, x1b, y0b, y1b, z0b, z1b};
+                const float dmin2 = unseen_bound(g, B2, Qp.x, Qp.y, Qp.z);
                 const float dm2 = dmin2 - margin;
                 const float want = lim * powf(1.7f * (float)S / (float)max(cnt - 1, 1), 0.6667f);   // r^2 ~ count^(2/3)
                 const float g1 = covered ? INFINITY : dm * dm;               // what the staged cells alone guarantee
@@ -890,7 +795,7 @@ __global__ __launch_bounds__(256) void knn_cell_kernel(int nsample, const float*
                     }
                 if (cnt > CELL_NEAR || cnt <= S) { retry(q); continue; }
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds_sync_wave();
             float e[4]; int ej[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -905,14 +810,14 @@ __global__ __launch_bounds__(256) void knn_cell_kernel(int nsample, const float*
             const float hi = lim;   // every listed distance is < lim (finite: capped by the density radius)
             const float scale = 64.0f / hi;
             hist[lane] = 0;
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds_sync_wave();
             int bin[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 bin[r] = min(63, (int)(e[r] * scale));       // monotone in the distance; INF (idle slots) -> 63, not counted
                 if (lane + 64 * r < cnt) atomicAdd(&hist[bin[r]], 1);
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds_sync_wave();
             const int h = hist[lane];
             const int incl = wave_incl_scan(h, lane);
             const unsigned long long ge = __ballot(incl >= S1);   // != 0: cnt >= S + 1
@@ -934,7 +839,7 @@ __global__ __launch_bounds__(256) void knn_cell_kernel(int nsample, const float*
                 }
                 too_many = base > 64;
                 if (too_many) { retry(q); continue; }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                lds_sync_wave();
                 const float v = lane < nB ? sd[lane] : INFINITY;
                 int rank = 0;
                 for (int u = 0; u < nB; ++u) rank += (rl_f(v, u) < v) ? 1 : 0;
@@ -957,7 +862,7 @@ __global__ __launch_bounds__(256) void knn_cell_kernel(int nsample, const float*
                 }
                 if (base != S) { retry(q); continue; }            // cannot happen (kept as a guard)
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds_sync_wave();
             float d = lane < S ? sd[lane] : INFINITY;
             int j = lane < S ? sj[lane] : 0;
             wave_sort64(d, j, lane);
@@ -1002,11 +907,9 @@ __global__ __launch_bounds__(1024) void sort_queries_kernel(const float* __restr
     const RoitrGrid g = grids[c];
     const int ncell = g.nx * g.ny * g.nz;
     auto cell_of = [&](int k) {
-        const float x = new_xyz[(size_t)k * 3], y = new_xyz[(size_t)k * 3 + 1], z = new_xyz[(size_t)k * 3 + 2];
-        const int cx = (int)fminf(fmaxf((x - g.ox) * g.inv_h, 0.f), (float)(g.nx - 1));
-        const int cy = (int)fminf(fmaxf((y - g.oy) * g.inv_h, 0.f), (float)(g.ny - 1));
-        const int cz = (int)fminf(fmaxf((z - g.oz) * g.inv_h, 0.f), (float)(g.nz - 1));
-        return (cz * g.ny + cy) * g.nx + cx;
+        int c0[3];
+        home_cell(g, new_xyz[(size_t)k * 3], new_xyz[(size_t)k * 3 + 1], new_xyz[(size_t)k * 3 + 2], c0);
+        return (c0[2] * g.ny + c0[1]) * g.nx + c0[0];
     };
     for (int k = tid; k < ncell; k += 1024) cnt[k] = 0;
     __syncthreads();
@@ -1030,13 +933,16 @@ __global__ __launch_bounds__(1024) void sort_queries_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------- lane-per-query kernels: result rows of one lane
+// Each of the three kernels keeps its sorted best list (d[L], id[L], the median-of-three insertion chain, the tie test) in its own
+// text: hipcc's register allocation follows the spelling of that code (profiles/knn_refactor.txt, part 3: a shared list struct, or
+// free functions on the arrays, cost up to 31 VGPRs and a wave per SIMD in knn_lane_kernel and knn_lane_brute_kernel).
+// a tied query goes to the replay kernel instead
 template <int L>
 __device__ __forceinline__ void lane_emit(const KnnOut& o, int q, int nsample, const float (&d)[L], const int (&id)[L], bool tie,
                                           const float* __restrict__ xyz, float qx, float qy, float qz)
 {
     if (tie) {
-        const int slot = atomicAdd(o.tie_count, 1);
-        o.tie_list[slot] = q;
+        push_query(o.tie_count, o.tie_list, q);
         return;
     }
 #pragma unroll
@@ -1094,24 +1000,11 @@ __global__ __launch_bounds__(256) void knn_prefilter_kernel(int m, int nsample, 
     const int* cs = cell_start + (size_t)seg * (GRID_MAX_CELLS + 1);
     const float qx = new_xyz[(size_t)q * 3], qy = new_xyz[(size_t)q * 3 + 1], qz = new_xyz[(size_t)q * 3 + 2];
     int c0[3];
-    {
-        const float tq[3] = {(qx - g.ox) * g.inv_h, (qy - g.oy) * g.inv_h, (qz - g.oz) * g.inv_h};
-        const int dim[3] = {g.nx, g.ny, g.nz};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) c0[a] = (int)fminf(fmaxf(tq[a], 0.f), (float)(dim[a] - 1));
-    }
-    const int x0 = max(c0[0] - 1, 0), x1 = min(c0[0] + 1, g.nx - 1);
-    const int y0 = max(c0[1] - 1, 0), y1 = min(c0[1] + 1, g.ny - 1);
-    const int z0 = max(c0[2] - 1, 0), z1 = min(c0[2] + 1, g.nz - 1);
+    home_cell(g, qx, qy, qz, c0);
+    const ShellBox B = shell_box(c0, 1, g);
+    const int x0 = B.x0, x1 = B.x1, y0 = B.y0, y1 = B.y1, z0 = B.z0, z1 = B.z1;
     // guarantee radius: distance to the nearest face of the box with unseen cells behind it (the ring kernel's stop rule)
-    float dmin = INFINITY;
-    if (x0 > 0) dmin = fminf(dmin, qx - __fmaf_rn((float)x0, g.h, g.ox));
-    if (x1 < g.nx - 1) dmin = fminf(dmin, __fmaf_rn((float)(x1 + 1), g.h, g.ox) - qx);
-    if (y0 > 0) dmin = fminf(dmin, qy - __fmaf_rn((float)y0, g.h, g.oy));
-    if (y1 < g.ny - 1) dmin = fminf(dmin, __fmaf_rn((float)(y1 + 1), g.h, g.oy) - qy);
-    if (z0 > 0) dmin = fminf(dmin, qz - __fmaf_rn((float)z0, g.h, g.oz));
-    if (z1 < g.nz - 1) dmin = fminf(dmin, __fmaf_rn((float)(z1 + 1), g.h, g.oz) - qz);
-    const float dm = dmin - 2e-4f * g.h;
+    const float dm = unseen_bound(g, B, qx, qy, qz) - 2e-4f * g.h;
     // points in the box (from the cell index alone) -> the radius expected to hold ~2 (nsample + 1) of them
     int nbox = 0;
     for (int cz = z0; cz <= z1; ++cz)
@@ -1163,8 +1056,7 @@ __global__ __launch_bounds__(256) void knn_prefilter_kernel(int m, int nsample, 
         // A box that covers its whole cloud has dm = inf, but tau = min(dm, r_est) = r_est still cuts at the density radius: a
         // query with too few survivors there goes to the ring kernel like any other (a second pass, exact results); that kernel
         // also fills the tail like the reference (KNN_FILL, segment start) when the cloud has fewer than nsample + 1 points.
-        const int slot = atomicAdd(retry_count, 1);
-        retry_list[slot] = q;
+        push_query(retry_count, retry_list, q);
         return;
     }
     float d[L]; int id[L];
@@ -1293,7 +1185,7 @@ __global__ __launch_bounds__(256) void knn_lane_kernel(int m, int nsample, int b
 #pragma unroll
     for (int j = 0; j < L; ++j) { d[j] = KNN_FILL; id[j] = start; }
     int c0[3];
-    {
+    {   // home_cell and segment_of, in this kernel's own text: either call changes the code hipcc makes of L = 18 and 34
         const float tq[3] = {(qx - g.ox) * g.inv_h, (qy - g.oy) * g.inv_h, (qz - g.oz) * g.inv_h};
         const int dim[3] = {g.nx, g.ny, g.nz};
 #pragma unroll
@@ -1329,11 +1221,9 @@ __global__ __launch_bounds__(256) void knn_lane_kernel(int m, int nsample, int b
     const float margin = 2e-4f * g.h;
     const int maxr = max(max(g.nx, g.ny), g.nz);
     for (int r = 0; r <= maxr; ++r) {
-        const int x0 = max(c0[0] - r, 0), x1 = min(c0[0] + r, g.nx - 1);
-        const int y0 = max(c0[1] - r, 0), y1 = min(c0[1] + r, g.ny - 1);
-        const int z0 = max(c0[2] - r, 0), z1 = min(c0[2] + r, g.nz - 1);
-        for (int cz = z0; cz <= z1; ++cz) {
-            for (int cy = y0; cy <= y1; ++cy) {
+        const ShellBox B = shell_box(c0, r, g);
+        for (int cz = B.z0; cz <= B.z1; ++cz) {
+            for (int cy = B.y0; cy <= B.y1; ++cy) {
                 const int rowbase = (cz * g.ny + cy) * g.nx;
                 const bool face = (r == 0) || (cy == c0[1] - r) || (cy == c0[1] + r) || (cz == c0[2] - r) || (cz == c0[2] + r);
                 // a row of cells whose (y, z) slab lies farther from the query than the current worst list entry (or than the cap
@@ -1346,7 +1236,7 @@ __global__ __launch_bounds__(256) void knn_lane_kernel(int m, int nsample, int b
                     const float lb = fmaxf(sqrtf(dy * dy + dz * dz) - margin, 0.f);
                     if (lb * lb > fminf(d[L - 1], cap2)) continue;
                 }
-                if (face) scan(cs[rowbase + x0], cs[rowbase + x1 + 1]);
+                if (face) scan(cs[rowbase + B.x0], cs[rowbase + B.x1 + 1]);
                 else {
                     const int xa = c0[0] - r, xb = c0[0] + r;
                     if (xa >= 0) scan(cs[rowbase + xa], cs[rowbase + xa + 1]);
@@ -1354,13 +1244,7 @@ __global__ __launch_bounds__(256) void knn_lane_kernel(int m, int nsample, int b
                 }
             }
         }
-        float dmin = INFINITY;
-        if (x0 > 0) dmin = fminf(dmin, qx - __fmaf_rn((float)x0, g.h, g.ox));
-        if (x1 < g.nx - 1) dmin = fminf(dmin, __fmaf_rn((float)(x1 + 1), g.h, g.ox) - qx);
-        if (y0 > 0) dmin = fminf(dmin, qy - __fmaf_rn((float)y0, g.h, g.oy));
-        if (y1 < g.ny - 1) dmin = fminf(dmin, __fmaf_rn((float)(y1 + 1), g.h, g.oy) - qy);
-        if (z0 > 0) dmin = fminf(dmin, qz - __fmaf_rn((float)z0, g.h, g.oz));
-        if (z1 < g.nz - 1) dmin = fminf(dmin, __fmaf_rn((float)(z1 + 1), g.h, g.oz) - qz);
+        const float dmin = unseen_bound(g, B, qx, qy, qz);
         if (dmin == INFINITY) break;
         float tau = d[L - 1];  // the (nsample+1)-th best must be final before stopping
 #pragma unroll
@@ -1398,8 +1282,8 @@ __global__ __launch_bounds__(64) void knn_lane_brute_kernel(int m, int nsample, 
     const bool valid = q < m;
     int seg = 0;
     if (valid) {
-        if (b > 0) { int lo = 0, hi = b - 1; while (lo < hi) { const int mid = (lo + hi) >> 1; if (q < new_offset[mid]) hi = mid; else lo = mid + 1; } seg = lo; }
-        else { while (!(q < new_offset[seg])) seg++; }
+        if (b > 0) seg = segment_of(q, new_offset, b);
+        else { while (!(q < new_offset[seg])) seg++; }   // the legacy entry does not know the cloud count
     }
     if (tid == 0) seg_range[0] = seg;
     if (q == min(m, (int)(blockIdx.x + 1) * 64) - 1) seg_range[1] = seg;
@@ -1460,8 +1344,7 @@ __global__ __launch_bounds__(64) void knn_lane_brute_kernel(int m, int nsample, 
 // 2.91 ms for the whole config-5 call, 0.49 vs 0.39 ms of replay per 32-pair 4DMatch forward): with ONE wave per CU nothing
 // hides the SGPR <-> VALU hand-offs of the readlane chain, which cost as much as the LDS round trips they replace; 8 batches of
 // candidate loads in flight (kept) change nothing.  One query per block (up to 1024 blocks) keeps the kernel at one chain.
-// One wave per block: LDS operations of a wave complete in order, so cross-lane hand-offs only need the counter wait.
-__device__ __forceinline__ void lds_sync_wave() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// One wave per block: LDS operations of a wave complete in order, so cross-lane hand-offs only need the counter wait (lds_sync_wave).
 // reheap (knnquery_cuda_kernel.cu:21-36) with the sinking value kept in registers: the entry at `rt` is always the new one; the
 // right child wins only when strictly larger, the walk stops at the first child strictly smaller than the value.
 // Round 6 (temporary s_memtime counters inside the kernel: a replayed query of the config-5 call spent 1.35 M cycles --
@@ -1606,44 +1489,112 @@ __global__ __launch_bounds__(64) void knn_replay_kernel(int nsample, const float
 int* g_legacy_ws = nullptr;
 size_t g_legacy_ws_ints = 0;
 
-}  // namespace
-
-// Workspace layout (ints): [0] tie counter, [1] retry counter (cell kernel -> general kernel), [4 .. 4 + m) tie list, then (grid
-// path) grids (b * 8 words), cell_start (b * (GRID_MAX_CELLS+1)), sorted float4 (n * 4 words, 16-B aligned), then m ints: the
-// query order of non-self lane queries / the retry list of self queries (never both in one call).
-extern "C" size_t roitr_knn_workspace_bytes(int b, int n, int m)
+// Workspace layout, in ints from the 16-byte aligned base (b clouds, n reference points, room for m queries):
+//   [0] tie counter, [1] retry counter, [2 .. 3] unused
+//   tie list      m ints            queries for the replay kernel
+//   grids         b * 8 words       (16-byte aligned)
+//   cell_start    b * (GRID_MAX_CELLS + 1)
+//   sorted        n float4          (16-byte aligned) the counting-sorted reference points
+//   query order   m ints            sort_queries_kernel's order of non-self lane queries; the cell kernel's retry list
+//   retry list    m ints            queries the prefilter kernel hands to the ring-expanding one
+// knn_layout is the one place that computes it: roitr_knn_workspace_bytes returns its end, carve its pointers.
+struct KnnLayout { size_t tie_list, grids, cell_start, sorted, qorder, retry, end; };
+KnnLayout knn_layout(int b, int n, int m)
 {
-    size_t ints = 4 + (size_t)m;
-    ints = (ints + 3) & ~(size_t)3;
-    ints += (size_t)b * 8 + (size_t)b * (GRID_MAX_CELLS + 1);
-    ints = (ints + 3) & ~(size_t)3;
-    ints += (size_t)n * 4;
-    ints += (size_t)m;  // query order (lane kernel, non-self queries)
-    ints += (size_t)m;  // retry list (queries the prefilter kernel hands to the ring-expanding one)
-    return ints * 4 + 64;
+    const auto align4 = [](size_t v) { return (v + 3) & ~(size_t)3; };
+    KnnLayout l;
+    l.tie_list = 4;
+    l.grids = align4(l.tie_list + (size_t)m);
+    l.cell_start = l.grids + (size_t)b * 8;
+    l.sorted = align4(l.cell_start + (size_t)b * (GRID_MAX_CELLS + 1));
+    l.qorder = l.sorted + (size_t)n * 4;
+    l.retry = l.qorder + (size_t)m;
+    l.end = l.retry + (size_t)m;
+    return l;
 }
 
-namespace {
 struct WsView {
     int* tie_count; int* tie_list; RoitrGrid* grids; int* cell_start; float4* sorted; int* qorder; int* retry;
 };
 WsView carve(void* ws, int b, int n, int m)
 {
-    uintptr_t base = ((uintptr_t)ws + 15) & ~(uintptr_t)15;
-    int* p = (int*)base;
-    WsView v;
-    v.tie_count = p; v.tie_list = p + 4;
-    size_t ints = 4 + (size_t)m; ints = (ints + 3) & ~(size_t)3;
-    v.grids = (RoitrGrid*)(p + ints); ints += (size_t)b * 8;
-    v.cell_start = p + ints; ints += (size_t)b * (GRID_MAX_CELLS + 1);
-    ints = (ints + 3) & ~(size_t)3;
-    v.sorted = (float4*)(p + ints);
-    ints += (size_t)n * 4;
-    v.qorder = (b > 0 && n > 0) ? p + ints : nullptr;
-    v.retry = v.qorder ? v.qorder + m : nullptr;
-    return v;
+    int* p = (int*)(((uintptr_t)ws + 15) & ~(uintptr_t)15);
+    const KnnLayout l = knn_layout(b, n, m);
+    const bool grid = b > 0 && n > 0;   // the legacy entry carves counters and tie list only
+    return WsView{p, p + l.tie_list, (RoitrGrid*)(p + l.grids), p + l.cell_start, (float4*)(p + l.sorted), grid ? p + l.qorder : nullptr,
+                  grid ? p + l.retry : nullptr};
+}
+
+// Cells a cloud's grid may have: small clouds are built (grid_build_kernel<CAP>) and their queries sorted (sort_queries_kernel<CAP>)
+// with 4096 LDS counters instead of GRID_MAX_CELLS.
+int knn_grid_cap(int b, int n) { return (long)n <= 6144L * b ? 4096 : GRID_MAX_CELLS; }
+
+// What a query call does: the form (ROITR_KNN_*), the list width of its kernel template and whether the queries are counting-sorted
+// first.  knn_plan is the ONE place where that is decided -- knnquery_impl launches what it says, roitr_knn_form reports it.  By shape
+// only, never by the data; host arithmetic on its arguments, no pointer is followed.
+struct KnnPlan { int form; int width; int sort_cap; };   // sort_cap: 0 = the queries are taken as they come, else knn_grid_cap
+
+// list widths the lane kernels are compiled for: the smallest that holds `need`, and f(integral_constant<width>) for a plan's width
+int lane_width(int need) { return need <= 2 ? 2 : need <= 4 ? 4 : need <= 10 ? 10 : need <= 18 ? 18 : 34; }
+template <class F>
+void with_lane_width(int width, F f)
+{
+    switch (width) {
+    case 2: f(std::integral_constant<int, 2>()); break;
+    case 4: f(std::integral_constant<int, 4>()); break;
+    case 10: f(std::integral_constant<int, 10>()); break;
+    case 18: f(std::integral_constant<int, 18>()); break;
+    default: f(std::integral_constant<int, 34>());
+    }
+}
+
+// ROITR_OK and *p, or the status the call is refused with.  outputs: ROITR_KNN_OUT_* of the non-null ones; cap2 = INFINITY: exact kNN.
+int knn_plan(int b, int n, int m, int nsample, bool self, int outputs, bool normals, bool use_grid, float cap2, KnnPlan* p)
+{
+    *p = KnnPlan{ROITR_KNN_NOTHING, 0, 0};
+    if (m <= 0) return ROITR_OK;
+    if (nsample < 1 || nsample > 100) return ROITR_ERR_ARG;  // best_dist[100], knnquery_cuda_kernel.cu:86
+    const bool ppf = outputs & ROITR_KNN_OUT_PPF, group = outputs & ROITR_KNN_OUT_GROUP;
+    if (ppf && !normals) return ROITR_ERR_ARG;
+    // a lane per query from 8192 queries on a grid; small clouds without a grid: a lane per query once there are enough queries to
+    // fill the chip that way; below that a wave per query (one pair per call: 624 queries at level 3 were 10 waves scanning 1250
+    // references each, 152 us per call).  lane_emit reads the neighbours of the PPF back from group_idx: no lane form without it.
+    constexpr int lane_min = 8192, lane_brute_min = 65536;
+    const int need = nsample + 1;   // the lists keep the best nsample + 1 (tie detection)
+    const bool has_lists = b > 0 && n > 0;   // carve() hands out the query-order and retry regions
+    const bool lane_ok = use_grid && m >= lane_min && (!ppf || group) && b > 0;
+    // non-self queries of a lane-sized call are walked in reference-cell order (whatever form takes them in the end)
+    if (lane_ok && !self && has_lists) p->sort_cap = knn_grid_cap(b, n);
+    if (lane_ok && need <= 34) {   // from nsample + 1 = 35 the selection kernels take over
+        p->width = lane_width(need);
+        // Measured per call at 512 pairs (round 3, rocprofv3 kernel trace): the prefilter form wins where the insertion chain
+        // dominated and the grid is fine enough for the radius rule -- the level-1 self query (need 10, 6 points per cell: 3.56 ->
+        // 2.24 ms) -- and loses on the 3-NN interpolation queries (need 4: the 4-deep chain was never the cost, 0.84 -> 4.0 ms)
+        // and, with grids of 6 points per cell, on need 18 (the sphere of one cell size holds 25 points: most lanes would hand
+        // their query over; with 9 per cell 3 x 1.0 -> 3 x (2.1 + 0.45) ms; re-measured at the end of round 3 with a 48 / 56-slot table and
+        // target counts of 1.4 - 2.0 (nsample + 1): 8 - 15 % of the need-18 queries still go to the ring kernel -- the clouds are
+        // surface-like, the count inside a radius does not follow the box's volume density -- kNN 12.7 -> 17.4 - 19.9 ms per step).
+        // So: need 5..10 only, and only for the exact k: roitr_knn_within (cap2 < inf) stops on the radius, which the ring kernel does.
+        if (cap2 < INFINITY && nsample == 1 && outputs == ROITR_KNN_OUT_DIST2) { p->form = ROITR_KNN_WITHIN; p->width = 0; }
+        else p->form = (need > 4 && need <= 10 && cap2 == INFINITY && has_lists) ? ROITR_KNN_PREFILTER : ROITR_KNN_LANE;
+    } else if (use_grid && self && has_lists && nsample - 1 <= 64) p->form = ROITR_KNN_CELL;
+    else if (use_grid) p->form = ROITR_KNN_GRIDSEL;   // nsample + 1 <= 101 fits its 128-entry sort
+    else if (need <= 34 && (!ppf || group) && m >= lane_brute_min) { p->form = ROITR_KNN_LANE_BRUTE; p->width = lane_width(need); }
+    else { p->form = ROITR_KNN_BRUTE; p->width = need <= 64 ? 1 : 2; }
+    return ROITR_OK;
 }
 }  // namespace
+
+extern "C" int roitr_knn_form(int b, int n, int m, int nsample, int self_query, int outputs, int normals, int use_grid, int capped)
+{
+    KnnPlan p;
+    const int st = knn_plan(b, n, m, nsample, self_query != 0, outputs, normals != 0, use_grid != 0, capped ? 1.0f : INFINITY, &p);
+    if (st != ROITR_OK) return -st;
+    const int sort = p.sort_cap == 0 ? ROITR_KNN_SORT_NONE : p.sort_cap == 4096 ? ROITR_KNN_SORT_4096 : ROITR_KNN_SORT_MAX;
+    return p.form | p.width << 8 | sort << 16;
+}
+
+extern "C" size_t roitr_knn_workspace_bytes(int b, int n, int m) { return knn_layout(b, n, m).end * 4 + 64; }
 
 // Builds the per-cloud uniform grids for `xyz` (b clouds, n points) into `ws`; reusable by any number
 // of roitr_knnquery_grid calls on the same reference cloud set (same b, n, m-capacity carve).
@@ -1663,7 +1614,7 @@ extern "C" int roitr_knn_build_grid_ex(int b, int n, int m_capacity, const float
     WsView v = carve(ws, b, n, m_capacity);
     const float rho = target_occupancy > 0.f ? target_occupancy : 6.0f;
     roitr_prof_begin(ROITR_PROF_GRID, 12.0 * n + 16.0 * n, stream);
-    if ((long)n <= 6144L * b) grid_build_kernel<4096><<<b, 1024, 0, stream>>>(xyz, offset, v.grids, v.cell_start, v.sorted, rho);
+    if (knn_grid_cap(b, n) == 4096) grid_build_kernel<4096><<<b, 1024, 0, stream>>>(xyz, offset, v.grids, v.cell_start, v.sorted, rho);
     else grid_build_kernel<GRID_MAX_CELLS><<<b, 1024, 0, stream>>>(xyz, offset, v.grids, v.cell_start, v.sorted, rho);
     roitr_prof_end(ROITR_PROF_GRID, stream);
     ROITR_LAUNCH_CHECK();
@@ -1691,13 +1642,15 @@ int knnquery_impl(int b, int n, int m, int nsample, const float* xyz, const floa
                   const float* ref_normals, const float* query_normals, int use_grid, int m_capacity, void* ws,
                   float cap2, hipStream_t stream)
 {
-    if (m <= 0) return ROITR_OK;
-    if (nsample < 1 || nsample > 100) return ROITR_ERR_ARG;  // best_dist[100], knnquery_cuda_kernel.cu:86
-    if (ppf && (!ref_normals || !query_normals)) return ROITR_ERR_ARG;
+    const int self_sorted = (new_xyz == xyz && new_offset == offset && m == n) ? 1 : 0;
+    const int outputs = (idx ? ROITR_KNN_OUT_IDX : 0) | (dist2 ? ROITR_KNN_OUT_DIST2 : 0) | (group_idx ? ROITR_KNN_OUT_GROUP : 0) | (ppf ? ROITR_KNN_OUT_PPF : 0);
+    KnnPlan p;
+    const int st = knn_plan(b, n, m, nsample, self_sorted != 0, outputs, ref_normals && query_normals, use_grid != 0, cap2, &p);
+    if (st != ROITR_OK || p.form == ROITR_KNN_NOTHING) return st;
     WsView v = carve(ws, b, n, m_capacity);
     KnnOut o = {idx, dist2, group_idx, ppf, ref_normals, query_normals, v.tie_count, v.tie_list, b > 0 ? b : 0};
     ROITR_HIP(hipMemsetAsync(v.tie_count, 0, 2 * sizeof(int), stream));   // tie counter + retry counter
-    const int blocks = div_up(m, 4);
+    int* const retry_count = v.tie_count + 1;
     // algorithmic bytes: refs xyz(+normals) once, queries when distinct, idx + dist2/ppf rows out
     {
         const int kk = group_idx || ppf ? nsample - 1 : nsample;
@@ -1705,87 +1658,50 @@ int knnquery_impl(int b, int n, int m, int nsample, const float* xyz, const floa
         bytes += ((idx ? 4.0 * nsample : 0.0) + (dist2 ? 4.0 * nsample : 0.0) + (group_idx ? 4.0 * kk : 0.0) + (ppf ? 16.0 * kk : 0.0)) * m;
         roitr_prof_begin(ROITR_PROF_KNN, bytes, stream);
     }
-    // kernel choice by shape only (never by the data): a lane per query from 8192 queries on a grid;
-    // small clouds without a grid: a lane per query once there are enough queries to fill the chip that way; below that a wave
-    // per query (one pair per call: 624 queries at level 3 were 10 waves scanning 1250 references each, 152 us per call)
-    constexpr int lane_min = 8192, lane_brute_min = 65536;
-    const bool lane_ok = use_grid && m >= lane_min && (!ppf || group_idx) && b > 0;
-    const int self_sorted = (new_xyz == xyz && new_offset == offset && m == n) ? 1 : 0;
-    // non-self queries: walk them in reference-cell order; the order array reuses the tie list's tail
-    // (tie slots are handed out from the front; a query is either listed as a tie or not, so m slots suffice for both
-    //  only if disjoint -> the order array lives in its own region carved behind the sorted points)
-    int* qorder = nullptr;
-    if (lane_ok && !self_sorted && v.qorder) {
+    int* qorder = nullptr;   // the order array has a region of its own: a query may be in it AND in the tie list
+    if (p.sort_cap) {
         qorder = v.qorder;
-        if ((long)n <= 6144L * b) sort_queries_kernel<4096><<<b, 1024, 0, stream>>>(new_xyz, new_offset, v.grids, qorder);   // the rule of roitr_knn_build_grid_ex
+        if (p.sort_cap == 4096) sort_queries_kernel<4096><<<b, 1024, 0, stream>>>(new_xyz, new_offset, v.grids, qorder);
         else sort_queries_kernel<GRID_MAX_CELLS><<<b, 1024, 0, stream>>>(new_xyz, new_offset, v.grids, qorder);
     }
-#define LANE_CASE(LC)                                                                                                        \
-    knn_lane_kernel<LC><<<xcd_grid(div_up(m, 256)), 256, 0, stream>>>(m, nsample, b, xyz, new_xyz, offset, new_offset, v.grids, v.cell_start, \
-                                                             v.sorted, o, self_sorted, qorder, cap2, nullptr, nullptr)
-    // prefilter kernel + the ring-expanding kernel in list mode for what it hands over (a fixed grid-stride launch: the count
-    // lives on the device)
-#define PREF_CASE(LC, CAPC)                                                                                                  \
-    do {                                                                                                                     \
-        int* retry_count = v.tie_count + 1;                                                                                  \
-        knn_prefilter_kernel<LC, CAPC><<<xcd_grid(div_up(m, 256)), 256, 0, stream>>>(m, nsample, b, xyz, new_xyz, offset, new_offset, v.grids, \
-                                                                                    v.cell_start, v.sorted, o, self_sorted, qorder, retry_count, v.retry); \
-        knn_lane_kernel<LC><<<min(div_up(m, 256), 1024), 256, 0, stream>>>(m, nsample, b, xyz, new_xyz, offset, new_offset, v.grids, v.cell_start, \
-                                                                           v.sorted, o, self_sorted, qorder, cap2, v.retry, retry_count);   \
-    } while (0)
-    if (lane_ok && nsample + 1 <= 34) {   // from nsample + 1 = 35 the selection kernels take over
-        const int need = nsample + 1;
-        const bool exact_k = cap2 == INFINITY && v.retry != nullptr;   // roitr_knn_within (cap2 < inf) stops on the radius: ring kernel
-        // Measured per call at 512 pairs (round 3, rocprofv3 kernel trace): the prefilter form wins where the insertion chain
-        // dominated and the grid is fine enough for the radius rule -- the level-1 self query (need 10, 6 points per cell: 3.56 ->
-        // 2.24 ms) -- and loses on the 3-NN interpolation queries (need 4: the 4-deep chain was never the cost, 0.84 -> 4.0 ms)
-        // and, with grids of 6 points per cell, on need 18 (the sphere of one cell size holds 25 points: most lanes would hand
-        // their query over; with 9 per cell 3 x 1.0 -> 3 x (2.1 + 0.45) ms; re-measured at the end of round 3 with a 48 / 56-slot table and
-        // target counts of 1.4 - 2.0 (nsample + 1): 8 - 15 % of the need-18 queries still go to the ring kernel -- the clouds are
-        // surface-like, the count inside a radius does not follow the box's volume density -- kNN 12.7 -> 17.4 - 19.9 ms per step).
-        // So: need 5..10 only.
-        if (cap2 < INFINITY && nsample == 1 && dist2 && !idx && !group_idx)   // roitr_knn_within: one pass over the ball's cells
-            knn_within_kernel<<<xcd_grid(div_up(m, 256)), 256, 0, stream>>>(m, b, new_xyz, new_offset, v.grids, v.cell_start, v.sorted,
-                                                                           self_sorted ? nullptr : qorder, cap2, dist2);
-        else if (need <= 2) LANE_CASE(2);
-        else if (need <= 4) LANE_CASE(4);
-        else if (need <= 10) { if (exact_k) PREF_CASE(10, 40); else LANE_CASE(10); }
-        else if (need <= 18) LANE_CASE(18);
-        else LANE_CASE(34);
-    } else if (use_grid && self_sorted && b > 0 && v.qorder && nsample - 1 <= 64) {
-        // large k, self queries: workgroup per cell over the LDS-staged neighbourhood; what it cannot decide goes through the
-        // retry list to the general selection kernel
-        int* retry_count = v.tie_count + 1;
+    const int wave_blocks = div_up(m, 4), lane_blocks = div_up(m, 256);   // a wave / a lane per query, 256 threads
+    switch (p.form) {
+    case ROITR_KNN_WITHIN:
+        knn_within_kernel<<<xcd_grid(lane_blocks), 256, 0, stream>>>(m, b, new_xyz, new_offset, v.grids, v.cell_start, v.sorted, qorder, cap2, dist2);
+        break;
+    case ROITR_KNN_LANE:
+        with_lane_width(p.width, [&](auto L) {
+            knn_lane_kernel<decltype(L)::value><<<xcd_grid(lane_blocks), 256, 0, stream>>>(
+                m, nsample, b, xyz, new_xyz, offset, new_offset, v.grids, v.cell_start, v.sorted, o, self_sorted, qorder, cap2, nullptr, nullptr);
+        });
+        break;
+    case ROITR_KNN_PREFILTER:   // then the ring-expanding kernel in list mode for what it hands over (a fixed grid-stride launch: the count lives on the device)
+        knn_prefilter_kernel<10, 40><<<xcd_grid(lane_blocks), 256, 0, stream>>>(m, nsample, b, xyz, new_xyz, offset, new_offset, v.grids, v.cell_start,
+                                                                               v.sorted, o, self_sorted, qorder, retry_count, v.retry);
+        knn_lane_kernel<10><<<min(lane_blocks, 1024), 256, 0, stream>>>(m, nsample, b, xyz, new_xyz, offset, new_offset, v.grids, v.cell_start, v.sorted, o,
+                                                                        self_sorted, qorder, cap2, v.retry, retry_count);
+        break;
+    case ROITR_KNN_CELL:   // what the cell kernel cannot decide goes through the retry list (the query-order region) to the selection kernel
         knn_cell_kernel<<<dim3(1024, b), 256, 0, stream>>>(nsample, xyz, offset, v.grids, v.cell_start, v.sorted, o, retry_count, v.qorder);
         knn_gridsel_kernel<<<1024, 256, 0, stream>>>(m, nsample, xyz, new_xyz, offset, new_offset, v.grids, v.cell_start, v.sorted, o, v.qorder,
                                                       retry_count);
-    } else if (use_grid && nsample + 1 <= 128) {
-        knn_gridsel_kernel<<<min(blocks, 65536), 256, 0, stream>>>(m, nsample, xyz, new_xyz, offset, new_offset, v.grids, v.cell_start, v.sorted, o,
-                                                                    nullptr, nullptr);
-    } else if (lane_ok && m >= 4 * lane_min) {
-        if (nsample + 1 <= 66) LANE_CASE(66); else LANE_CASE(101);
-    } else
-#undef LANE_CASE
-#undef PREF_CASE
-    if (!use_grid && nsample + 1 <= 34 && (!ppf || group_idx) && m >= lane_brute_min) {
+        break;
+    case ROITR_KNN_GRIDSEL:
+        knn_gridsel_kernel<<<min(wave_blocks, 65536), 256, 0, stream>>>(m, nsample, xyz, new_xyz, offset, new_offset, v.grids, v.cell_start, v.sorted, o,
+                                                                         nullptr, nullptr);
+        break;
+    case ROITR_KNN_LANE_BRUTE: {
         // staging chunk: the mean cloud rounded up to 64 points, 64 .. 1024 (a larger cloud takes several chunks)
         int ch = b > 0 ? (int)(((long)n / b + 63) / 64 * 64) : 1024;
         ch = ch < 64 ? 64 : (ch > 1024 ? 1024 : ch);
-#define LB_CASE(LC) knn_lane_brute_kernel<LC><<<div_up(m, 64), 64, (size_t)ch * 16, stream>>>(m, nsample, b, xyz, new_xyz, offset, new_offset, o, ch)
-        const int need = nsample + 1;
-        if (need <= 2) LB_CASE(2); else if (need <= 4) LB_CASE(4); else if (need <= 10) LB_CASE(10);
-        else if (need <= 18) LB_CASE(18); else LB_CASE(34);
-#undef LB_CASE
-    } else if (use_grid) {
-        if (nsample + 1 <= 64)
-            knn_grid_kernel<1><<<blocks, 256, 0, stream>>>(m, nsample, xyz, new_xyz, offset, new_offset, v.grids, v.cell_start, v.sorted, o);
-        else
-            knn_grid_kernel<2><<<blocks, 256, 0, stream>>>(m, nsample, xyz, new_xyz, offset, new_offset, v.grids, v.cell_start, v.sorted, o);
-    } else {
-        if (nsample + 1 <= 64)
-            knn_brute_kernel<1><<<blocks, 256, 0, stream>>>(m, nsample, xyz, new_xyz, offset, new_offset, o);
-        else
-            knn_brute_kernel<2><<<blocks, 256, 0, stream>>>(m, nsample, xyz, new_xyz, offset, new_offset, o);
+        with_lane_width(p.width, [&](auto L) {
+            knn_lane_brute_kernel<decltype(L)::value><<<div_up(m, 64), 64, (size_t)ch * 16, stream>>>(m, nsample, b, xyz, new_xyz, offset, new_offset, o, ch);
+        });
+        break;
+    }
+    default:   // ROITR_KNN_BRUTE
+        if (p.width == 1) knn_brute_kernel<1><<<wave_blocks, 256, 0, stream>>>(m, nsample, xyz, new_xyz, offset, new_offset, o);
+        else knn_brute_kernel<2><<<wave_blocks, 256, 0, stream>>>(m, nsample, xyz, new_xyz, offset, new_offset, o);
     }
     roitr_prof_end(ROITR_PROF_KNN, stream);
     ROITR_LAUNCH_CHECK();

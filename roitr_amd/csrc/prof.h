@@ -6,7 +6,7 @@
 #define ROITR_PROF_CLASSES 19
 enum {
     ROITR_PROF_FPS = 0,        // fps_kernel, one launch
-    ROITR_PROF_KNN = 1,        // knn_grid_kernel / knn_brute_kernel (the query kernel incl. fused PPF), one launch
+    ROITR_PROF_KNN = 1,        // the query kernels of one kNN call (ROITR_KNN_* form, incl. query sort and fused PPF)
     ROITR_PROF_GRID = 2,       // grid_build_kernel
     ROITR_PROF_REPLAY = 3,     // knn_replay_kernel
     ROITR_PROF_PH_GEOM = 4,    // engine phases

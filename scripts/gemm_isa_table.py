@@ -31,7 +31,7 @@ def assembly(tree, name, tmp):
 
 def demangle(names):
     r = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True)
-    short = [re.sub(r"\(anonymous namespace\)::|\(RoitrGemm, int, int, int\)|^void ", "", s) for s in r.stdout.split("\n")]
+    short = [re.sub(r"\(anonymous namespace\)::|\([^()]*(\([^()]*\)[^()]*)*\)$|^void ", "", s) for s in r.stdout.split("\n")]   # no argument list
     return dict(zip(names, short))
 
 

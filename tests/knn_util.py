@@ -1,30 +1,47 @@
 """Helpers of tests/test_knn_fused_gpu.py: inputs shaped like the engine's kNN calls, a float64 restatement of calc_ppf_gpu, and a
 direct caller of roitr_knn_build_grid_ex / roitr_knnquery_ex that chooses which outputs are NULL.
 
-Everything above `class Grid` is numpy only."""
+Everything above `class Grid` is numpy only, but for knn_form / branch, which ask the built library (no GPU)."""
+import os
+import re
+
 import numpy as np
 
-LANE_MIN, LANE_BRUTE_MIN = 8192, 65536   # knnquery_impl (pointops_knn.hip)
 GUARD = 64                               # elements behind every output buffer that a call must leave alone
 KNN_FILL = np.float32(1e10)
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ERR_ARG = 1
+
+
+def _header(prefix):
+    text = open(os.path.join(ROOT, "include", "roitr_pointops.h")).read()
+    return {name: int(value) for name, value in re.findall(r"#define %s(\w+) (\d+)" % prefix, text)}
+
+
+FORM = _header("ROITR_KNN_(?!OUT_|SORT_)")          # NOTHING .. GRIDSEL
+OUT = _header("ROITR_KNN_OUT_")                     # IDX, DIST2, GROUP, PPF
+SORT = _header("ROITR_KNN_SORT_")                   # NONE, 4096, MAX
+FORM_NAME = {v: k for k, v in FORM.items()}
+_FORMAT = {"BRUTE": "brute<%d>", "LANE_BRUTE": "lane_brute<%d>", "LANE": "lane<%d>", "PREFILTER": "prefilter<%d,40>+lane<%d>", "WITHIN": "within",
+           "CELL": "cell+gridsel", "GRIDSEL": "gridsel", "NOTHING": "nothing"}
+
+
+def knn_form(b, n, m, nsample, use_grid, self_query, want="idgp", normals=True, capped=False):
+    """roitr_knn_form for a call with the outputs `want` (letters of "idgp"): (form name, list width, sort form), or the negative status.
+    Host code that follows no pointer: needs the built library, no GPU."""
+    from roitr_amd import _lib as L
+    outputs = sum(OUT[k] for c, k in zip("idgp", ("IDX", "DIST2", "GROUP", "PPF")) if c in want)
+    v = L.lib().roitr_knn_form(b, n, m, nsample, int(self_query), outputs, int(normals), int(use_grid), int(capped))
+    return v if v < 0 else (FORM_NAME[v & 0xff], (v >> 8) & 0xff, v >> 16)
 
 
 def branch(b, n, m, nsample, use_grid, self_query, ppf=True, group=True):
-    """The kernel knnquery_impl chooses for a roitr_knnquery_ex call (by shape alone), as a name; with a grid and lane kernels on
-    queries that are not the reference points, the query sort's form is appended."""
-    need = nsample + 1
-    lane_ok = use_grid and m >= LANE_MIN and (not ppf or group) and b > 0
-    if lane_ok and need <= 34:
-        k = "lane<2>" if need <= 2 else "lane<4>" if need <= 4 else "prefilter<10,40>+lane<10>" if need <= 10 else \
-            "lane<18>" if need <= 18 else "lane<34>"
-        return k if self_query else k + (" sort<4096>" if n <= 6144 * b else " sort<max>")
-    if use_grid and self_query and b > 0 and nsample - 1 <= 64:
-        return "cell+gridsel"
-    if use_grid:
-        return "gridsel"
-    if need <= 34 and (not ppf or group) and m >= LANE_BRUTE_MIN:
-        return "lane_brute<%d>" % (2 if need <= 2 else 4 if need <= 4 else 10 if need <= 10 else 18 if need <= 18 else 34)
-    return "brute<1>" if need <= 64 else "brute<2>"
+    """The kernel roitr_knnquery_ex gives a call (by shape alone), as the name the GPU tests use: what roitr_knn_form -- the rule the
+    launcher dispatches through -- says; where the queries are counting-sorted first, the sort's form is appended."""
+    form, width, sort = knn_form(b, n, m, nsample, use_grid, self_query, ("g" if group else "") + ("p" if ppf else ""))
+    name = _FORMAT[form]
+    name = name % ((width,) * name.count("%d"))
+    return name + {SORT["NONE"]: "", SORT["4096"]: " sort<4096>", SORT["MAX"]: " sort<max>"}[sort]
 
 
 def ragged(n_clouds, n):

@@ -36,8 +36,10 @@ nearly every query tied, so the rows come from knn_replay_kernel's write_rows<2>
   knn_gridsel_kernel alone        grid, references [5000], 1250 of them as queries, nsample 17; self [2000], nsample 100  write_rows
   ppf without group_idx           lane-sized shapes fall back to the wave kernels (lane_ok: !ppf || group_idx)   write_rows
 
-Not reachable from roitr_knnquery_ex, not tested: LANE_CASE(66) / LANE_CASE(101) and the `else if (use_grid)` arm that launches
-knn_grid_kernel (the `use_grid && nsample + 1 <= 128` arm precedes both and nsample <= 100 always holds).
+  knn_lane_brute_kernel<2>        no grid, 256 x ~260 self, nsample 1: idx and dist2 only (group_idx has no columns)  lane_emit
+
+Every form of roitr_knn_form (the rule the launcher dispatches through; tests/test_knn_form_cpu.py pins the form of every case here
+by its shape) is reached: the kernels that could not be -- a wave-per-query grid kernel and 66- / 101-slot lane lists -- are gone.
 """
 import numpy as np
 import pytest
@@ -264,6 +266,18 @@ def test_knn_fused_one_column():
     g = U.Grid(inp["xyz"], inp["off"], inp["r_nrm"], m_capacity=sum(R8))
     a = check_engine_form(g, g.queries(None, None, inp["q_nrm"]), 2, ridx, rd2, ref, "nsample 2")
     assert a.group.shape == (sum(R8), 1) and a.ppf.shape == (sum(R8), 1, 4)
+
+
+def test_knn_lane_brute_nsample_1():
+    """nsample = 1 without a grid at >= 65536 queries: the width-2 lane list, idx and dist2 against the oracle bit for bit."""
+    n = sum(RLB)
+    assert U.knn_form(256, n, n, 1, False, True, "id") == ("LANE_BRUTE", 2, U.SORT["NONE"])
+    inp = make_inputs(1, RLB, "uniform")
+    ridx, rd2 = O.knnquery_raw(1, inp["xyz"], inp["q_xyz"], inp["off"], inp["q_off"], threads=8)
+    g = U.Grid(inp["xyz"], inp["off"], None, m_capacity=n, use_grid=False)
+    r = g.query(1, g.queries(None, None, None), "id")
+    assert np.array_equal(r.dist2, rd2), f"dist2 rows {np.nonzero(r.dist2 != rd2)[0][:10]}"
+    assert np.array_equal(r.idx, ridx), f"idx rows {np.nonzero(r.idx != ridx)[0][:10]}"
 
 
 def test_knn_ppf_without_normals_is_refused():
