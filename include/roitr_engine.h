@@ -333,7 +333,26 @@ typedef struct RoitrMha {
     float* ebar;
     int e_bf16;   /* E is stored in bf16 (uint16, same element offsets): engine operand_dtype = bf16; needs C = 256 or 512, 4 heads */
 } RoitrMha;
+/* Launches ONE kernel form (below) for the struct, or refuses it with ROITR_ERR_UNSUPPORTED and a message that names the limit:
+ * heads outside 1..8, C % heads, (C / heads) % 4, ldk % 4, bf16 E outside C = 256 / 512 with 4 heads and nk_max <= 512, and for the
+ * generic kernel a heads x nk_max score table over its 150 KB of LDS. */
 int roitr_mha(const RoitrMha* a, roitr_stream_t stream);
+/* The kernel form roitr_mha gives this struct (the rule roitr_mha itself dispatches through; host arithmetic on the fields, E and
+ * partner only tested for NULL, no device is needed), or, for a struct roitr_mha refuses, MINUS the status it returns.
+ * "Quad layout": 4 heads, ldq % 4 == 0 (and ldk % 4 == 0, which every form needs).  "Self with E": E != NULL, partner == NULL.
+ * The forms with a key bound are tried in this order: GEO_WIDE2*, GEO_WIDE_H, (bf16 refusal), PLAIN_WIDE2, GEO*, PLAIN*. */
+#define ROITR_MHA_NOTHING 0         /* q_rows <= 0: returns ROITR_OK, launches nothing */
+#define ROITR_MHA_GEO20 1           /* self with E, quad layout, C = 256, fp32 E, nk_max <= 80: E rows in registers, 20 per wave */
+#define ROITR_MHA_GEO32 2           /* the same, 80 < nk_max <= 128: 32 rows per wave */
+#define ROITR_MHA_GEO_STREAM 3      /* the same, 128 < nk_max <= 1024: E streamed twice */
+#define ROITR_MHA_GEO_WIDE_H 4      /* self with E, quad layout, C = 256, bf16 E, nk_max <= 512: E streamed twice */
+#define ROITR_MHA_GEO_WIDE2 5       /* self with E, quad layout, C = 512, fp32 E, nk_max <= 512: E streamed twice */
+#define ROITR_MHA_GEO_WIDE2_H 6     /* the same with bf16 E */
+#define ROITR_MHA_PLAIN128 7        /* no E, quad layout, C = 256, nk_max <= 128: four query rows per block */
+#define ROITR_MHA_PLAIN1024 8       /* the same, 128 < nk_max <= 1024 */
+#define ROITR_MHA_PLAIN_WIDE2 9     /* no E, quad layout, C = 512, nk_max <= 512: one query row per block */
+#define ROITR_MHA_GENERIC 10        /* everything else (other widths or head counts, ldq % 4 != 0, partner with E, more keys): one key row per lane */
+int roitr_mha_form(const RoitrMha* a);
 
 /* ------------------------------------------------------------------ coarse-to-fine matching tail */
 /* Cloud layout for every batched call below: [src_0 .. src_{B-1}, tgt_0 .. tgt_{B-1}], B = pairs. */

@@ -104,23 +104,109 @@ __global__ __launch_bounds__(256) void geo_indices_kernel(const float* __restric
     }
 }
 
-// ------------------------------------------------------------------ multi-head attention, one block per query row
+// ------------------------------------------------------------------ what the attention kernels below have in common
+__device__ __forceinline__ float dot4(const float4 a, const float4 b) { return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x))); }
+__device__ __forceinline__ void fma4(float4& acc, float w, const float4 v)   // acc += w v
+{
+    acc.x = fmaf(w, v.x, acc.x); acc.y = fmaf(w, v.y, acc.y); acc.z = fmaf(w, v.z, acc.z); acc.w = fmaf(w, v.w, acc.w);
+}
+
+// The first query row (counted from q_row0) of this block in a launch whose blocks take qb consecutive rows each; false for the
+// padding of the rounded-up grid.  XCD-aware row order: every XCD (private L2) gets a contiguous range of query rows, so the key /
+// value rows of a cloud are fetched into ONE L2 instead of all eight (PMC before: 1.27x the algorithmic bytes on the self layers)
+__device__ __forceinline__ bool mha_block_row(const RoitrMha& a, int qb, int& r0)
+{
+    const int nblk = (a.q_rows + qb - 1) / qb, blk = xcd_block_id(nblk);
+    r0 = blk * qb;
+    return blk < nblk;
+}
+// A query row's cloud, the rows of its key cloud (SELF: its own, a.partner is not looked at) and its index inside its own cloud (self
+// attention: the diagonal position)
+struct MhaRow { int cl, ks, nk, qi; };
+template <bool SELF> __device__ __forceinline__ MhaRow mha_row(const RoitrMha& a, int row)
+{
+    MhaRow r;
+    r.cl = a.cloud_of_row[row];
+    const int kc = !SELF && a.partner ? a.partner[r.cl] : r.cl;
+    r.ks = kc == 0 ? 0 : a.offset[kc - 1];
+    r.nk = a.offset[kc] - r.ks;
+    r.qi = row - (SELF ? r.ks : r.cl == 0 ? 0 : a.offset[r.cl - 1]);
+    return r;
+}
+
+// One wave, one head, scores p[0 .. nk) in LDS: the softmax in place and, with `masked`, the diagonal-masked softmax of
+// geoattention.py:117-134 (key qi left out) to p2[j * stride2]
+__device__ __forceinline__ void lds_softmax2(float* p, float* p2, int stride2, bool masked, int nk, int qi, int lane)
+{
+    float mx = -INFINITY, mx2 = -INFINITY;
+    for (int j = lane; j < nk; j += 64) {
+        const float v = p[j];
+        mx = fmaxf(mx, v);
+        if (j != qi) mx2 = fmaxf(mx2, v);
+    }
+    mx = wave_max(mx); mx2 = wave_max(mx2);
+    float sm = 0.f, sm2 = 0.f;
+    for (int j = lane; j < nk; j += 64) {
+        const float v = p[j];
+        const float e1 = expf(v - mx);
+        p[j] = e1; sm += e1;
+        if (masked) {
+            const float e2 = j != qi ? expf(v - mx2) : 0.f;
+            p2[j * stride2] = e2; sm2 += e2;
+        }
+    }
+    sm = wave_sum(sm); sm2 = wave_sum(sm2);
+    for (int j = lane; j < nk; j += 64) {
+        p[j] /= sm;
+        if (masked) p2[j * stride2] /= sm2;
+    }
+}
+
+// hidden by thread = channel, for QB query rows that share their keys: acc[q] = sum_j p[q * qstride + j] vp[j * ldv], 8 value rows
+// requested per trip
+template <int QB> __device__ __forceinline__ void hidden_by_channel(const float* p, int qstride, const float* vp, int ldv, int nk, float (&acc)[QB])
+{
+#pragma unroll
+    for (int q = 0; q < QB; ++q) acc[q] = 0.f;
+    int j = 0;
+    for (; j + 8 <= nk; j += 8) {
+        float vv[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) vv[u] = vp[(size_t)(j + u) * ldv];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+#pragma unroll
+            for (int q = 0; q < QB; ++q) acc[q] = fmaf(p[q * qstride + j + u], vv[u], acc[q]);
+    }
+    for (; j < nk; ++j) {
+        const float vv = vp[(size_t)j * ldv];
+#pragma unroll
+        for (int q = 0; q < QB; ++q) acc[q] = fmaf(p[q * qstride + j], vv, acc[q]);
+    }
+}
+
+// ebar[h][ch] of one query row from the four waves' partial sums red[wave][h * C + ch]: thread = channel tid + 256 u
+template <int C> __device__ __forceinline__ void ebar_sum(const float (&red)[4][4 * C], float* ebar, int tid)
+{
+#pragma unroll
+    for (int h = 0; h < 4; ++h)
+#pragma unroll
+        for (int ch = tid; ch < tid + C; ch += 256)
+            ebar[h * C + ch] = (red[0][h * C + ch] + red[1][h * C + ch]) + (red[2][h * C + ch] + red[3][h * C + ch]);
+}
+
+// ------------------------------------------------------------------ multi-head attention, one block per query row: any width, 1 to 8
+// heads, with or without E
 __global__ __launch_bounds__(256) void mha_kernel(RoitrMha a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    // XCD-aware row order: every XCD (private L2) gets a contiguous range of query rows, so the key / value rows of a cloud
-    // are fetched into ONE L2 instead of all eight (PMC before: 1.27x the algorithmic bytes on the self layers)
-    const int rowi = xcd_block_id(a.q_rows);
-    if (rowi >= a.q_rows) return;
+    int rowi;
+    if (!mha_block_row(a, 1, rowi)) return;
     const int row = a.q_row0 + rowi;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int C = a.C, NH = a.heads, c = C / NH;
-    const int cl = a.cloud_of_row[row];
-    const int kc = a.partner ? a.partner[cl] : cl;
-    const int ks = kc == 0 ? 0 : a.offset[kc - 1], ke = a.offset[kc];
-    const int nk = ke - ks;
-    const int qs_ = cl == 0 ? 0 : a.offset[cl - 1];
-    const int qi = row - qs_;  // index inside its own cloud (self attention: the diagonal position)
+    const MhaRow qr = mha_row<false>(a, row);
+    const int cl = qr.cl, ks = qr.ks, nk = qr.nk, qi = qr.qi;
 
     float* qsh = smem;                      // C        : q row
     float* qt = qsh + C;                    // NH*C     : folded rpe queries (only with E)
@@ -170,29 +256,7 @@ __global__ __launch_bounds__(256) void mha_kernel(RoitrMha a)
                 sc[h * a.nk_max + j] = dot * a.scale;
             }
         }
-        // softmax (and the diagonal-masked softmax of geoattention.py:117-134) over j, inside this wave
-        float mx = -INFINITY, mx2 = -INFINITY;
-        for (int j = lane; j < nk; j += 64) {
-            const float v = sc[h * a.nk_max + j];
-            mx = fmaxf(mx, v);
-            if (j != qi) mx2 = fmaxf(mx2, v);
-        }
-        mx = wave_max(mx); mx2 = wave_max(mx2);
-        float sm = 0.f, sm2 = 0.f;
-        for (int j = lane; j < nk; j += 64) {
-            const float v = sc[h * a.nk_max + j];
-            const float e1 = expf(v - mx);
-            sc[h * a.nk_max + j] = e1; sm += e1;
-            if (a.E) {
-                const float e2 = j != qi ? expf(v - mx2) : 0.f;
-                sc2[h * a.nk_max + j] = e2; sm2 += e2;
-            }
-        }
-        sm = wave_sum(sm); sm2 = wave_sum(sm2);
-        for (int j = lane; j < nk; j += 64) {
-            sc[h * a.nk_max + j] /= sm;
-            if (a.E) sc2[h * a.nk_max + j] /= sm2;
-        }
+        lds_softmax2(sc + h * a.nk_max, sc2 + h * a.nk_max, 1, a.E != nullptr, nk, qi, lane);   // over j, inside this wave
     }
     __syncthreads();
     // ---- hidden[h*c + ch] = sum_j p[h][j] v[j][h*c + ch]
@@ -230,8 +294,6 @@ __global__ __launch_bounds__(256) void mha_kernel(RoitrMha a)
 // waves' partial sums meet in LDS).  Channels 4*lane..4*lane+3 belong to head lane/16 = the lane's DPP row, so q_h . k_j
 // is a row reduction.  mha_kernel streams E twice with one 1 KB row per LANE (uncoalesced, L1-thrashing): 1.9 ms per
 // launch at 128 pairs against 0.3-0.4 ms for one pass over E at HBM speed.
-__device__ __forceinline__ float dot4(const float4 a, const float4 b) { return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x))); }
-
 template <int R>   // R = key rows per wave kept in registers: n <= 4 R
 __global__ __launch_bounds__(256, R <= 20 ? 3 : 2) void mha_geo_kernel(RoitrMha a)
 {
@@ -240,15 +302,12 @@ __global__ __launch_bounds__(256, R <= 20 ? 3 : 2) void mha_geo_kernel(RoitrMha 
     __shared__ __attribute__((aligned(16))) float sc2t[NKP * 4];   // diagonal-masked probabilities [key][head]
     __shared__ __attribute__((aligned(16))) float red[4][NH * C];  // per-wave ebar partials
     __shared__ __attribute__((aligned(16))) float redh[4][C];      // per-wave hidden partials
-    // XCD-aware row order: every XCD (private L2) gets a contiguous range of query rows, so the key / value rows of a cloud
-    // are fetched into ONE L2 instead of all eight (PMC before: 1.27x the algorithmic bytes on the self layers)
-    const int rowi = xcd_block_id(a.q_rows);
-    if (rowi >= a.q_rows) return;
+    int rowi;
+    if (!mha_block_row(a, 1, rowi)) return;
     const int row = a.q_row0 + rowi;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hl = lane >> 4;
-    const int cl = a.cloud_of_row[row];
-    const int ks = cl == 0 ? 0 : a.offset[cl - 1], nk = a.offset[cl] - ks;
-    const int qi = row - ks;
+    const MhaRow qr = mha_row<true>(a, row);
+    const int cl = qr.cl, ks = qr.ks, nk = qr.nk, qi = qr.qi;
     const float* Erow = a.E + a.eoff[cl] * C + (size_t)qi * nk * C;
     float4 e[R];
 #pragma unroll
@@ -375,9 +434,7 @@ __global__ __launch_bounds__(256, R <= 20 ? 3 : 2) void mha_geo_kernel(RoitrMha 
     {
 #pragma unroll
         for (int rr = 0; rr < EB; ++rr) {
-            const int j = wave + 4 * rr;
-            const float p = sc[hl][j];
-            hacc.x = fmaf(p, vfirst[rr].x, hacc.x); hacc.y = fmaf(p, vfirst[rr].y, hacc.y); hacc.z = fmaf(p, vfirst[rr].z, hacc.z); hacc.w = fmaf(p, vfirst[rr].w, hacc.w);
+            fma4(hacc, sc[hl][wave + 4 * rr], vfirst[rr]);
         }
         constexpr int CH = 8;   // rows per later batch (a real loop: unrolled, the compiler hoists every batch's loads and spills)
 #pragma unroll 1
@@ -392,7 +449,7 @@ __global__ __launch_bounds__(256, R <= 20 ? 3 : 2) void mha_geo_kernel(RoitrMha 
             for (int u = 0; u < CH; ++u) {
                 const int j = wave + 4 * (r0 + u);
                 const float p = r0 + u < R ? sc[hl][j < NKP ? j : 0] : 0.f;
-                hacc.x = fmaf(p, vb[u].x, hacc.x); hacc.y = fmaf(p, vb[u].y, hacc.y); hacc.z = fmaf(p, vb[u].z, hacc.z); hacc.w = fmaf(p, vb[u].w, hacc.w);
+                fma4(hacc, p, vb[u]);
             }
         }
         reinterpret_cast<float4*>(redh[wave])[lane] = hacc;
@@ -405,226 +462,18 @@ __global__ __launch_bounds__(256, R <= 20 ? 3 : 2) void mha_geo_kernel(RoitrMha 
     for (int rr = 0; rr < R; ++rr) {
         const int j = wave + 4 * rr;
         const float4 p2 = reinterpret_cast<const float4*>(sc2t)[j];
-        const float w0 = p2.x, w1 = p2.y, w2 = p2.z, w3 = p2.w;
-        acc[0].x = fmaf(w0, e[rr].x, acc[0].x); acc[0].y = fmaf(w0, e[rr].y, acc[0].y); acc[0].z = fmaf(w0, e[rr].z, acc[0].z); acc[0].w = fmaf(w0, e[rr].w, acc[0].w);
-        acc[1].x = fmaf(w1, e[rr].x, acc[1].x); acc[1].y = fmaf(w1, e[rr].y, acc[1].y); acc[1].z = fmaf(w1, e[rr].z, acc[1].z); acc[1].w = fmaf(w1, e[rr].w, acc[1].w);
-        acc[2].x = fmaf(w2, e[rr].x, acc[2].x); acc[2].y = fmaf(w2, e[rr].y, acc[2].y); acc[2].z = fmaf(w2, e[rr].z, acc[2].z); acc[2].w = fmaf(w2, e[rr].w, acc[2].w);
-        acc[3].x = fmaf(w3, e[rr].x, acc[3].x); acc[3].y = fmaf(w3, e[rr].y, acc[3].y); acc[3].z = fmaf(w3, e[rr].z, acc[3].z); acc[3].w = fmaf(w3, e[rr].w, acc[3].w);
+        fma4(acc[0], p2.x, e[rr]); fma4(acc[1], p2.y, e[rr]); fma4(acc[2], p2.z, e[rr]); fma4(acc[3], p2.w, e[rr]);
     }
 #pragma unroll
     for (int h = 0; h < NH; ++h) reinterpret_cast<float4*>(red[wave])[h * 64 + lane] = acc[h];
     __syncthreads();
     a.out[(size_t)row * a.ldo + tid] = (redh[0][tid] + redh[1][tid]) + (redh[2][tid] + redh[3][tid]);
-#pragma unroll
-    for (int h = 0; h < NH; ++h)
-        a.ebar[((size_t)row * NH + h) * C + tid] = (red[0][h * C + tid] + red[1][h * C + tid]) + (red[2][h * C + tid] + red[3][h * C + tid]);
+    ebar_sum<C>(red, a.ebar + (size_t)row * NH * C, tid);
 }
 
 
-// ------------------------------------------------------------------ the same for clouds with more than 128 superpoints
-// (up to the engine's 1024: 30000-point clouds have 468).  The E slab of a query row no longer fits the registers of a
-// block (n x 1 KB), so it is streamed twice -- still one coalesced float4 per lane and row, four rows in flight per
-// wave, the second pass mostly out of L2 / Infinity Cache -- instead of the generic kernel's one-row-per-lane walk.
-__global__ __launch_bounds__(256) void mha_geo_stream_kernel(RoitrMha a)
-{
-    constexpr int C = 256, NH = 4, NKP = 1024;
-    __shared__ __attribute__((aligned(16))) float sc[NH][NKP];
-    __shared__ __attribute__((aligned(16))) float sc2t[NKP * 4];
-    __shared__ __attribute__((aligned(16))) float red[4][NH * C];
-    // XCD-aware row order: every XCD (private L2) gets a contiguous range of query rows, so the key / value rows of a cloud
-    // are fetched into ONE L2 instead of all eight (PMC before: 1.27x the algorithmic bytes on the self layers)
-    const int rowi = xcd_block_id(a.q_rows);
-    if (rowi >= a.q_rows) return;
-    const int row = a.q_row0 + rowi;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hl = lane >> 4;
-    const int cl = a.cloud_of_row[row];
-    const int ks = cl == 0 ? 0 : a.offset[cl - 1], nk = a.offset[cl] - ks;
-    const int qi = row - ks;
-    const float* Erow = a.E + a.eoff[cl] * C + (size_t)qi * nk * C;
-    const float4 qv = reinterpret_cast<const float4*>(a.q + (size_t)row * a.ldq)[lane];
-    float4 qt4[NH];
-#pragma unroll
-    for (int h = 0; h < NH; ++h) qt4[h] = reinterpret_cast<const float4*>(a.qt + ((size_t)row * NH + h) * C)[lane];
-    const float qb = row_allsum(dot4(qv, reinterpret_cast<const float4*>(a.bp)[lane]));
-    // ---- scores: 4 key rows of this wave per trip (E and k rows requested together)
-    for (int j0 = wave; j0 < nk; j0 += 16) {
-        float4 ev[4], kv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int j = min(j0 + 4 * u, nk - 1);
-            ev[u] = reinterpret_cast<const float4*>(Erow + (size_t)j * C)[lane];
-            kv[u] = reinterpret_cast<const float4*>(a.k + (size_t)(ks + j) * a.ldk)[lane];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int j = j0 + 4 * u;
-            const float s1 = row_allsum(dot4(qv, kv[u]));
-            const float se0 = wave_sum(dot4(qt4[0], ev[u])), se1 = wave_sum(dot4(qt4[1], ev[u]));
-            const float se2 = wave_sum(dot4(qt4[2], ev[u])), se3 = wave_sum(dot4(qt4[3], ev[u]));
-            const float se = hl == 0 ? se0 : (hl == 1 ? se1 : (hl == 2 ? se2 : se3));
-            if (j < nk && (lane & 15) == 0) sc[hl][j] = (s1 + (se + qb)) * a.scale;
-        }
-    }
-    __syncthreads();
-    {   // softmax and diagonal-masked softmax: wave = head
-        const int h = wave;
-        float mx = -INFINITY, mx2 = -INFINITY;
-        for (int j = lane; j < nk; j += 64) { const float v = sc[h][j]; mx = fmaxf(mx, v); if (j != qi) mx2 = fmaxf(mx2, v); }
-        mx = wave_max(mx); mx2 = wave_max(mx2);
-        float sm = 0.f, sm2 = 0.f;
-        for (int j = lane; j < nk; j += 64) {
-            const float v = sc[h][j];
-            const float e1 = expf(v - mx), e2 = j != qi ? expf(v - mx2) : 0.f;
-            sc[h][j] = e1; sc2t[j * 4 + h] = e2; sm += e1; sm2 += e2;
-        }
-        sm = wave_sum(sm); sm2 = wave_sum(sm2);
-        for (int j = lane; j < nk; j += 64) { sc[h][j] /= sm; sc2t[j * 4 + h] /= sm2; }
-    }
-    __syncthreads();
-    {   // hidden: thread = channel
-        const int h = tid >> 6;
-        const float* vp = a.v + (size_t)ks * a.ldv + tid;
-        float acc = 0.f;
-        int j = 0;
-        for (; j + 8 <= nk; j += 8) {
-            float vv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) vv[u] = vp[(size_t)(j + u) * a.ldv];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc = fmaf(sc[h][j + u], vv[u], acc);
-        }
-        for (; j < nk; ++j) acc = fmaf(sc[h][j], vp[(size_t)j * a.ldv], acc);
-        a.out[(size_t)row * a.ldo + tid] = acc;
-    }
-    // ---- ebar: second pass over this wave's E rows
-    float4 acc[NH];
-#pragma unroll
-    for (int h = 0; h < NH; ++h) acc[h] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int j0 = wave; j0 < nk; j0 += 16) {
-        float4 ev[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) ev[u] = reinterpret_cast<const float4*>(Erow + (size_t)min(j0 + 4 * u, nk - 1) * C)[lane];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int j = j0 + 4 * u;
-            const float4 p2 = reinterpret_cast<const float4*>(sc2t)[j < nk ? j : 0];
-            const float w[4] = {j < nk ? p2.x : 0.f, j < nk ? p2.y : 0.f, j < nk ? p2.z : 0.f, j < nk ? p2.w : 0.f};
-#pragma unroll
-            for (int h = 0; h < NH; ++h) {
-                acc[h].x = fmaf(w[h], ev[u].x, acc[h].x); acc[h].y = fmaf(w[h], ev[u].y, acc[h].y);
-                acc[h].z = fmaf(w[h], ev[u].z, acc[h].z); acc[h].w = fmaf(w[h], ev[u].w, acc[h].w);
-            }
-        }
-    }
-#pragma unroll
-    for (int h = 0; h < NH; ++h) reinterpret_cast<float4*>(red[wave])[h * 64 + lane] = acc[h];
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < NH; ++h)
-        a.ebar[((size_t)row * NH + h) * C + tid] = (red[0][h * C + tid] + red[1][h * C + tid]) + (red[2][h * C + tid] + red[3][h * C + tid]);
-}
-
-// ------------------------------------------------------------------ plain multi-head attention (cross layers), C = 256, 4 heads
-// geoattention.py:26-66 on the same lane = channel-quad layout as mha_geo_kernel: key rows are read coalesced (one
-// float4 per lane, head = DPP row), the four waves split the keys, values are accumulated by thread = channel.
-// Round 3: a block takes QB = 4 consecutive query rows.  With one row per block every query re-read all key and value rows of the
-// partner cloud from L2 (78 x 2 KB per query: 6.2 GB per launch at 512 pairs = 28 TB/s -- the kernel ran at the L2's bandwidth, not
-// at HBM's); rows of the same cloud now share each loaded row (4 dot products / 4 accumulations per load).  A block whose rows
-// straddle a cloud boundary works through its runs of equal cloud one after the other.  Per query the arithmetic and its order are
-// those of the one-row form: results are bit-identical.
-template <int NKP>   // keys per cloud bound (LDS score rows, softmax registers)
-__global__ __launch_bounds__(256) void mha_plain_kernel(RoitrMha a)
-{
-    constexpr int NH = 4, QB = 4;
-    __shared__ float sc[QB][NH][NKP];
-    // XCD-aware row order: every XCD (private L2) gets a contiguous range of query rows, so the key / value rows of a cloud
-    // are fetched into ONE L2 instead of all eight (PMC before: 1.27x the algorithmic bytes on the self layers)
-    const int nblk = (a.q_rows + QB - 1) / QB;
-    const int blk = xcd_block_id(nblk);
-    if (blk >= nblk) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hl = lane >> 4;
-    const int r_first = blk * QB, r_end = min(r_first + QB, a.q_rows);
-    for (int r0 = r_first; r0 < r_end;) {
-        const int row0 = a.q_row0 + r0;
-        const int cl = a.cloud_of_row[row0];
-        int nq = 1;                                            // rows of this run: same cloud as row0 (block-uniform)
-        while (r0 + nq < r_end && a.cloud_of_row[row0 + nq] == cl) ++nq;
-        const int kc = a.partner ? a.partner[cl] : cl;
-        const int ks = kc == 0 ? 0 : a.offset[kc - 1], nk = a.offset[kc] - ks;
-        float4 qv[QB];
-#pragma unroll
-        for (int q = 0; q < QB; ++q) qv[q] = reinterpret_cast<const float4*>(a.q + (size_t)(row0 + (q < nq ? q : 0)) * a.ldq)[lane];
-        const float* kbase = a.k + (size_t)ks * a.ldk + lane * 4;
-        for (int j0 = wave; j0 < nk; j0 += 16) {   // 4 keys of this wave per trip, loads issued together
-            float4 kv[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int j = j0 + 4 * u;
-                kv[u] = *reinterpret_cast<const float4*>(kbase + (size_t)(j < nk ? j : nk - 1) * a.ldk);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int j = j0 + 4 * u;
-#pragma unroll
-                for (int q = 0; q < QB; ++q) {
-                    const float s = row_allsum(dot4(qv[q], kv[u]));
-                    if (j < nk && (lane & 15) == 0) sc[q][hl][j] = s * a.scale;
-                }
-            }
-        }
-        __syncthreads();
-        {   // softmax over the keys: wave = head, one query after the other
-            const int h = wave;
-            for (int q = 0; q < nq; ++q) {
-                float e1[NKP / 64];
-                float mx = -INFINITY;
-#pragma unroll
-                for (int u = 0; u < NKP / 64; ++u) { const int j = lane + 64 * u; e1[u] = j < nk ? sc[q][h][j] : -INFINITY; mx = fmaxf(mx, e1[u]); }
-                mx = wave_max(mx);
-                float sm = 0.f;
-#pragma unroll
-                for (int u = 0; u < NKP / 64; ++u) { const int j = lane + 64 * u; e1[u] = j < nk ? expf(e1[u] - mx) : 0.f; sm += e1[u]; }
-                sm = wave_sum(sm);
-#pragma unroll
-                for (int u = 0; u < NKP / 64; ++u) { const int j = lane + 64 * u; if (j < nk) sc[q][h][j] = e1[u] / sm; }
-            }
-        }
-        __syncthreads();
-        {
-            const int h = tid >> 6;
-            const float* vp = a.v + (size_t)ks * a.ldv + tid;
-            float acc[QB];
-#pragma unroll
-            for (int q = 0; q < QB; ++q) acc[q] = 0.f;
-            int j = 0;
-            for (; j + 8 <= nk; j += 8) {
-                float vv[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) vv[u] = vp[(size_t)(j + u) * a.ldv];
-#pragma unroll
-                for (int u = 0; u < 8; ++u)
-#pragma unroll
-                    for (int q = 0; q < QB; ++q) acc[q] = fmaf(sc[q][h][j + u], vv[u], acc[q]);
-            }
-            for (; j < nk; ++j) {
-                const float vv = vp[(size_t)j * a.ldv];
-#pragma unroll
-                for (int q = 0; q < QB; ++q) acc[q] = fmaf(sc[q][h][j], vv, acc[q]);
-            }
-#pragma unroll
-            for (int q = 0; q < QB; ++q)
-                if (q < nq) a.out[(size_t)(row0 + q) * a.ldo + tid] = acc[q];
-        }
-        r0 += nq;
-        if (r0 < r_end) __syncthreads();   // the score table is re-used by the next run
-    }
-}
-
-// ------------------------------------------------------------------ the same two kernels for C = 256 CQ (CQ = 2: the factor-2
-// width of the 4DMatch configuration, model/RIGA_v2.py:24-28) and / or an E tensor stored in bf16 (engine operand_dtype =
-// bf16).  Same layout idea: a lane owns 4 CQ consecutive channels (all inside head lane / 16), rows are read coalesced,
-// E is streamed twice (the slab of a query row is n x 2 KB at C = 512: it does not fit the registers of a block).
-// Before these existed the factor-2 configuration ran on the generic mha_kernel (one row per lane, uncoalesced).
+// ------------------------------------------------------------------ rows of 256 CQ channels, 4 CQ consecutive ones per lane (all
+// inside head lane / 16), read coalesced: CQ = 2 is the factor-2 width of the 4DMatch configuration (model/RIGA_v2.py:24-28)
 template <int CQ> __device__ __forceinline__ void ldrow(const float* base, int lane, float4 (&d)[CQ])
 {
 #pragma unroll
@@ -647,20 +496,24 @@ template <int CQ> __device__ __forceinline__ float dotq(const float4 (&x)[CQ], c
     return s;
 }
 
-template <int CQ, bool EH>
+// ------------------------------------------------------------------ the same self attention with E streamed, for what the registers
+// of a block do not hold: clouds with more than 128 superpoints (<1, false, 1024>: up to the engine's 1024; 30000-point clouds have
+// 468), the width C = 256 CQ = 512 (n x 2 KB per query row) and / or an E tensor stored in bf16 (EH: engine operand_dtype = bf16).
+// E is streamed twice -- still one coalesced row per wave and load, four rows in flight per wave, the second pass mostly out of L2 /
+// Infinity Cache -- instead of the generic kernel's one-row-per-lane walk (on which the factor-2 configuration ran before).
+template <int CQ, bool EH, int NKP>   // NKP: keys per cloud bound (the LDS tables)
 __global__ __launch_bounds__(256) void mha_geo_wide_kernel(RoitrMha a)
 {
-    constexpr int C = 256 * CQ, NH = 4, NKP = 512;
+    constexpr int C = 256 * CQ, NH = 4;
     __shared__ __attribute__((aligned(16))) float sc[NH][NKP];
     __shared__ __attribute__((aligned(16))) float sc2t[NKP * 4];
     __shared__ __attribute__((aligned(16))) float red[4][NH * C];
-    const int rowi = xcd_block_id(a.q_rows);
-    if (rowi >= a.q_rows) return;
+    int rowi;
+    if (!mha_block_row(a, 1, rowi)) return;
     const int row = a.q_row0 + rowi;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hl = lane >> 4;
-    const int cl = a.cloud_of_row[row];
-    const int ks = cl == 0 ? 0 : a.offset[cl - 1], nk = a.offset[cl] - ks;
-    const int qi = row - ks;
+    const MhaRow qr = mha_row<true>(a, row);
+    const int cl = qr.cl, ks = qr.ks, nk = qr.nk, qi = qr.qi;
     const size_t e0 = (size_t)a.eoff[cl] * C + (size_t)qi * nk * C;   // element offset of E[i, 0, 0]
     const float* Ef = a.E + e0;
     const unsigned short* Eh = reinterpret_cast<const unsigned short*>(a.E) + e0;
@@ -694,37 +547,14 @@ __global__ __launch_bounds__(256) void mha_geo_wide_kernel(RoitrMha a)
         }
     }
     __syncthreads();
-    {   // softmax and diagonal-masked softmax (geoattention.py:117-134): wave = head
-        const int h = wave;
-        float mx = -INFINITY, mx2 = -INFINITY;
-        for (int j = lane; j < nk; j += 64) { const float v = sc[h][j]; mx = fmaxf(mx, v); if (j != qi) mx2 = fmaxf(mx2, v); }
-        mx = wave_max(mx); mx2 = wave_max(mx2);
-        float sm = 0.f, sm2 = 0.f;
-        for (int j = lane; j < nk; j += 64) {
-            const float v = sc[h][j];
-            const float e1 = expf(v - mx), e2 = j != qi ? expf(v - mx2) : 0.f;
-            sc[h][j] = e1; sc2t[j * 4 + h] = e2; sm += e1; sm2 += e2;
-        }
-        sm = wave_sum(sm); sm2 = wave_sum(sm2);
-        for (int j = lane; j < nk; j += 64) { sc[h][j] /= sm; sc2t[j * 4 + h] /= sm2; }
-    }
+    lds_softmax2(sc[wave], sc2t + wave, 4, true, nk, qi, lane);   // wave = head
     __syncthreads();
 #pragma unroll
     for (int u2 = 0; u2 < CQ; ++u2) {   // hidden: thread = channel tid + 256 u2
         const int ch = tid + 256 * u2;
-        const int h = ch / (64 * CQ);
-        const float* vp = a.v + (size_t)ks * a.ldv + ch;
-        float acc = 0.f;
-        int j = 0;
-        for (; j + 8 <= nk; j += 8) {
-            float vv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) vv[u] = vp[(size_t)(j + u) * a.ldv];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc = fmaf(sc[h][j + u], vv[u], acc);
-        }
-        for (; j < nk; ++j) acc = fmaf(sc[h][j], vp[(size_t)j * a.ldv], acc);
-        a.out[(size_t)row * a.ldo + ch] = acc;
+        float hid[1];
+        hidden_by_channel<1>(sc[ch / (64 * CQ)], 0, a.v + (size_t)ks * a.ldv + ch, a.ldv, nk, hid);
+        a.out[(size_t)row * a.ldo + ch] = hid[0];
     }
     // ---- ebar: second pass over this wave's E rows
     float4 acc[NH][CQ];
@@ -744,10 +574,7 @@ __global__ __launch_bounds__(256) void mha_geo_wide_kernel(RoitrMha a)
 #pragma unroll
             for (int h = 0; h < NH; ++h)
 #pragma unroll
-                for (int c = 0; c < CQ; ++c) {
-                    acc[h][c].x = fmaf(w[h], ev[u][c].x, acc[h][c].x); acc[h][c].y = fmaf(w[h], ev[u][c].y, acc[h][c].y);
-                    acc[h][c].z = fmaf(w[h], ev[u][c].z, acc[h][c].z); acc[h][c].w = fmaf(w[h], ev[u][c].w, acc[h][c].w);
-                }
+                for (int c = 0; c < CQ; ++c) fma4(acc[h][c], w[h], ev[u][c]);
         }
     }
 #pragma unroll
@@ -755,75 +582,82 @@ __global__ __launch_bounds__(256) void mha_geo_wide_kernel(RoitrMha a)
 #pragma unroll
         for (int c = 0; c < CQ; ++c) reinterpret_cast<float4*>(red[wave])[h * (64 * CQ) + lane * CQ + c] = acc[h][c];
     __syncthreads();
-#pragma unroll
-    for (int h = 0; h < NH; ++h)
-#pragma unroll
-        for (int u2 = 0; u2 < CQ; ++u2) {
-            const int ch = tid + 256 * u2;
-            a.ebar[((size_t)row * NH + h) * C + ch] = (red[0][h * C + ch] + red[1][h * C + ch]) + (red[2][h * C + ch] + red[3][h * C + ch]);
-        }
+    ebar_sum<C>(red, a.ebar + (size_t)row * NH * C, tid);
 }
 
-template <int NKP, int CQ>   // plain (cross) attention at C = 256 CQ
-__global__ __launch_bounds__(256) void mha_plain_wide_kernel(RoitrMha a)
+// ------------------------------------------------------------------ plain multi-head attention (cross layers), C = 256 CQ, 4 heads
+// geoattention.py:26-66 on the same lane = channel-quad layout as mha_geo_kernel: key rows are read coalesced (4 CQ channels per
+// lane, head = DPP row), the four waves split the keys, values are accumulated by thread = channel.
+// Round 3: a block takes QB consecutive query rows (4 at C = 256).  With one row per block every query re-read all key and value rows of the
+// partner cloud from L2 (78 x 2 KB per query: 6.2 GB per launch at 512 pairs = 28 TB/s -- the kernel ran at the L2's bandwidth, not
+// at HBM's); rows of the same cloud now share each loaded row (4 dot products / 4 accumulations per load).  A block whose rows
+// straddle a cloud boundary works through its runs of equal cloud one after the other.  Per query the arithmetic and its order are
+// those of the one-row form: results are bit-identical.
+template <int NKP, int CQ, int QB>   // NKP: keys per cloud bound (LDS score rows, softmax registers)
+__global__ __launch_bounds__(256) void mha_plain_kernel(RoitrMha a)
 {
     constexpr int NH = 4;
-    __shared__ float sc[NH][NKP];
-    const int rowi = xcd_block_id(a.q_rows);
-    if (rowi >= a.q_rows) return;
-    const int row = a.q_row0 + rowi;
+    __shared__ float sc[QB][NH][NKP];
+    int r_first;
+    if (!mha_block_row(a, QB, r_first)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, hl = lane >> 4;
-    const int cl = a.cloud_of_row[row];
-    const int kc = a.partner ? a.partner[cl] : cl;
-    const int ks = kc == 0 ? 0 : a.offset[kc - 1], nk = a.offset[kc] - ks;
-    float4 qv[CQ];
-    ldrow<CQ>(a.q + (size_t)row * a.ldq, lane, qv);
-    for (int j0 = wave; j0 < nk; j0 += 16) {   // 4 keys of this wave per trip, loads issued together
-        float4 kv[4][CQ];
+    const int r_end = QB == 1 ? r_first + 1 : min(r_first + QB, a.q_rows);
+    for (int r0 = r_first; r0 < r_end;) {
+        const int row0 = a.q_row0 + r0;
+        const MhaRow qr = mha_row<false>(a, row0);
+        const int ks = qr.ks, nk = qr.nk;
+        int nq = 1;                                            // rows of this run: same cloud as row0 (block-uniform)
+        while (QB > 1 && r0 + nq < r_end && a.cloud_of_row[row0 + nq] == qr.cl) ++nq;
+        float4 qv[QB][CQ];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int j = j0 + 4 * u;
-            ldrow<CQ>(a.k + (size_t)(ks + (j < nk ? j : nk - 1)) * a.ldk, lane, kv[u]);
+        for (int q = 0; q < QB; ++q) ldrow<CQ>(a.q + (size_t)(row0 + (q < nq ? q : 0)) * a.ldq, lane, qv[q]);
+        const float* kbase = a.k + (size_t)ks * a.ldk;
+        for (int j0 = wave; j0 < nk; j0 += 16) {   // 4 keys of this wave per trip, loads issued together
+            float4 kv[4][CQ];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = j0 + 4 * u;
+                ldrow<CQ>(kbase + (size_t)(j < nk ? j : nk - 1) * a.ldk, lane, kv[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = j0 + 4 * u;
+#pragma unroll
+                for (int q = 0; q < QB; ++q) {
+                    const float s = row_allsum(dotq<CQ>(qv[q], kv[u]));
+                    if (j < nk && (lane & 15) == 0) sc[q][hl][j] = s * a.scale;
+                }
+            }
         }
+        __syncthreads();
+        {   // softmax over the keys: wave = head, one query after the other, the row in registers
+            const int h = wave;
+            for (int q = 0; q < nq; ++q) {
+                float e1[NKP / 64];
+                float mx = -INFINITY;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int j = j0 + 4 * u;
-            const float s_ = row_allsum(dotq<CQ>(qv, kv[u]));
-            if (j < nk && (lane & 15) == 0) sc[hl][j] = s_ * a.scale;
+                for (int u = 0; u < NKP / 64; ++u) { const int j = lane + 64 * u; e1[u] = j < nk ? sc[q][h][j] : -INFINITY; mx = fmaxf(mx, e1[u]); }
+                mx = wave_max(mx);
+                float sm = 0.f;
+#pragma unroll
+                for (int u = 0; u < NKP / 64; ++u) { const int j = lane + 64 * u; e1[u] = j < nk ? expf(e1[u] - mx) : 0.f; sm += e1[u]; }
+                sm = wave_sum(sm);
+#pragma unroll
+                for (int u = 0; u < NKP / 64; ++u) { const int j = lane + 64 * u; if (j < nk) sc[q][h][j] = e1[u] / sm; }
+            }
         }
-    }
-    __syncthreads();
-    {   // softmax over the keys: wave = head
-        const int h = wave;
-        float e1[NKP / 64];
-        float mx = -INFINITY;
+        __syncthreads();
 #pragma unroll
-        for (int u = 0; u < NKP / 64; ++u) { const int j = lane + 64 * u; e1[u] = j < nk ? sc[h][j] : -INFINITY; mx = fmaxf(mx, e1[u]); }
-        mx = wave_max(mx);
-        float sm = 0.f;
+        for (int u2 = 0; u2 < CQ; ++u2) {   // hidden: thread = channel tid + 256 u2
+            const int ch = tid + 256 * u2;
+            float hid[QB];
+            hidden_by_channel<QB>(sc[0][ch / (64 * CQ)], NH * NKP, a.v + (size_t)ks * a.ldv + ch, a.ldv, nk, hid);
 #pragma unroll
-        for (int u = 0; u < NKP / 64; ++u) { const int j = lane + 64 * u; e1[u] = j < nk ? expf(e1[u] - mx) : 0.f; sm += e1[u]; }
-        sm = wave_sum(sm);
-#pragma unroll
-        for (int u = 0; u < NKP / 64; ++u) { const int j = lane + 64 * u; if (j < nk) sc[h][j] = e1[u] / sm; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int u2 = 0; u2 < CQ; ++u2) {
-        const int ch = tid + 256 * u2;
-        const int h = ch / (64 * CQ);
-        const float* vp = a.v + (size_t)ks * a.ldv + ch;
-        float acc = 0.f;
-        int j = 0;
-        for (; j + 8 <= nk; j += 8) {
-            float vv[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) vv[u] = vp[(size_t)(j + u) * a.ldv];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc = fmaf(sc[h][j + u], vv[u], acc);
+            for (int q = 0; q < QB; ++q)
+                if (q < nq) a.out[(size_t)(row0 + q) * a.ldo + ch] = hid[q];
         }
-        for (; j < nk; ++j) acc = fmaf(sc[h][j], vp[(size_t)j * a.ldv], acc);
-        a.out[(size_t)row * a.ldo + ch] = acc;
+        r0 += nq;
+        if (r0 < r_end) __syncthreads();   // the score table is re-used by the next run
     }
 }
 
@@ -842,55 +676,73 @@ extern "C" int roitr_geo_indices(int rows, const float* pts, const int* offset, 
     return ROITR_OK;
 }
 
+namespace {
+// What roitr_mha does with a struct: the form (ROITR_MHA_*), the grid, and for the generic kernel its LDS.  mha_plan is the ONE place
+// where that is decided -- roitr_mha launches what it says, roitr_mha_form reports it.  Host arithmetic on the fields only: no pointer
+// is followed, E and partner are tested for null.
+struct MhaPlan { int form; unsigned grid; size_t lds; };
+
+// ROITR_OK and *p, or the status roitr_mha returns for this struct with what is unsupported in *why
+int mha_plan(const RoitrMha* a, MhaPlan* p, const char** why)
+{
+    *p = MhaPlan{ROITR_MHA_NOTHING, 0, 0};
+    if (a->q_rows <= 0) return ROITR_OK;
+    if (a->heads < 1 || a->heads > 8) { *why = "roitr_mha: 1 to 8 heads"; return ROITR_ERR_UNSUPPORTED; }
+    if (a->C % a->heads) { *why = "roitr_mha: C must be a multiple of heads"; return ROITR_ERR_UNSUPPORTED; }
+    if ((a->C / a->heads) % 4) { *why = "roitr_mha: C / heads must be a multiple of 4"; return ROITR_ERR_UNSUPPORTED; }
+    if (a->ldk % 4) { *why = "roitr_mha: ldk must be a multiple of 4"; return ROITR_ERR_UNSUPPORTED; }
+    const int C = a->C, nk = a->nk_max;   // nk_max bounds every cloud
+    const bool lay = a->heads == 4 && a->ldq % 4 == 0;   // head = DPP row, a float4 of a row per lane (ldk % 4: above)
+    const bool geo = a->E && !a->partner && lay, plain = !a->E && lay;
+    p->grid = (unsigned)xcd_grid(a->q_rows);
+    // the factor-2 width and / or E stored in bf16 first: up to 512 keys
+    if (geo && nk <= 512 && C == 512) p->form = a->e_bf16 ? ROITR_MHA_GEO_WIDE2_H : ROITR_MHA_GEO_WIDE2;
+    else if (geo && nk <= 512 && C == 256 && a->e_bf16) p->form = ROITR_MHA_GEO_WIDE_H;
+    else if (a->E && a->e_bf16) { *why = "roitr_mha: bf16 E needs C = 256 or 512, 4 heads, <= 512 keys"; return ROITR_ERR_UNSUPPORTED; }
+    else if (plain && nk <= 512 && C == 512) p->form = ROITR_MHA_PLAIN_WIDE2;
+    // the model's width: E in registers up to 128 keys, streamed up to 1024
+    else if (geo && nk <= 1024 && C == 256) p->form = nk <= 80 ? ROITR_MHA_GEO20 : nk <= 128 ? ROITR_MHA_GEO32 : ROITR_MHA_GEO_STREAM;
+    else if (plain && nk <= 1024 && C == 256) {
+        p->form = nk <= 128 ? ROITR_MHA_PLAIN128 : ROITR_MHA_PLAIN1024;
+        p->grid = (unsigned)xcd_grid(div_up(a->q_rows, 4));   // four query rows per block
+    } else {
+        p->form = ROITR_MHA_GENERIC;
+        p->lds = ((size_t)C + (a->E ? (size_t)a->heads * C : 0) + (size_t)a->heads * nk * (a->E ? 2 : 1) + 8) * sizeof(float);
+        if (p->lds > 150 * 1024) { *why = "roitr_mha: heads x nk_max score table over the 150 KB LDS bound of the generic kernel"; return ROITR_ERR_UNSUPPORTED; }
+    }
+    return ROITR_OK;
+}
+}  // namespace
+
+extern "C" int roitr_mha_form(const RoitrMha* a)
+{
+    MhaPlan p;
+    const char* why = nullptr;
+    const int st = mha_plan(a, &p, &why);
+    return st == ROITR_OK ? p.form : -st;
+}
+
 extern "C" int roitr_mha(const RoitrMha* a, hipStream_t stream)
 {
-    if (a->q_rows <= 0) return ROITR_OK;
-    if (a->heads < 1 || a->heads > 8) { roitr_set_error("roitr_mha: 1 to 8 heads", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
-    if (a->C % a->heads) { roitr_set_error("roitr_mha: C must be a multiple of heads", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
-    const int c = a->C / a->heads;
-    if (c % 4) { roitr_set_error("roitr_mha: C / heads must be a multiple of 4", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
-    if (a->ldk % 4) { roitr_set_error("roitr_mha: ldk must be a multiple of 4", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
-    size_t floats = (size_t)a->C + (a->E ? (size_t)a->heads * a->C : 0) + (size_t)a->heads * a->nk_max * (a->E ? 2 : 1) + 8;
-    if (floats * 4 > 150 * 1024) {
-        roitr_set_error("roitr_mha: heads x nk_max score table over the 150 KB LDS bound of the generic kernel", __FILE__, __LINE__);
-        return ROITR_ERR_UNSUPPORTED;
-    }
-    ROITR_GRANT_LDS(mha_kernel, 150 * 1024);
+    MhaPlan p;
+    const char* why = "";
+    const int st = mha_plan(a, &p, &why);
+    if (st != ROITR_OK) { roitr_set_error(why, __FILE__, __LINE__); return st; }
+    if (p.form == ROITR_MHA_NOTHING) return ROITR_OK;
+    if (p.form == ROITR_MHA_GENERIC) ROITR_GRANT_LDS(mha_kernel, 150 * 1024);
     roitr_prof_begin(ROITR_PROF_MHA, -1.0, stream);   // bytes: roitr_prof_next_bytes of the caller (0 otherwise)
-    {   // factor-2 width (C = 512) and / or E stored in bf16: the wide kernels
-        const bool lay = a->heads == 4 && a->ldq % 4 == 0 && a->ldk % 4 == 0 && a->nk_max <= 512;
-        if (a->E && !a->partner && lay && (a->C == 512 || (a->C == 256 && a->e_bf16))) {
-            const unsigned gr = (unsigned)xcd_grid(a->q_rows);
-            if (a->C == 512) { if (a->e_bf16) mha_geo_wide_kernel<2, true><<<gr, 256, 0, stream>>>(*a); else mha_geo_wide_kernel<2, false><<<gr, 256, 0, stream>>>(*a); }
-            else mha_geo_wide_kernel<1, true><<<gr, 256, 0, stream>>>(*a);
-            roitr_prof_end(ROITR_PROF_MHA, stream);
-            ROITR_LAUNCH_CHECK();
-            return ROITR_OK;
-        }
-        if (a->E && a->e_bf16) { roitr_prof_end(ROITR_PROF_MHA, stream); roitr_set_error("roitr_mha: bf16 E needs C = 256 or 512, 4 heads, <= 512 keys", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
-        if (!a->E && lay && a->C == 512) {
-            mha_plain_wide_kernel<512, 2><<<xcd_grid(a->q_rows), 256, 0, stream>>>(*a);
-            roitr_prof_end(ROITR_PROF_MHA, stream);
-            ROITR_LAUNCH_CHECK();
-            return ROITR_OK;
-        }
+    switch (p.form) {
+    case ROITR_MHA_GEO20: mha_geo_kernel<20><<<p.grid, 256, 0, stream>>>(*a); break;
+    case ROITR_MHA_GEO32: mha_geo_kernel<32><<<p.grid, 256, 0, stream>>>(*a); break;
+    case ROITR_MHA_GEO_STREAM: mha_geo_wide_kernel<1, false, 1024><<<p.grid, 256, 0, stream>>>(*a); break;
+    case ROITR_MHA_GEO_WIDE_H: mha_geo_wide_kernel<1, true, 512><<<p.grid, 256, 0, stream>>>(*a); break;
+    case ROITR_MHA_GEO_WIDE2: mha_geo_wide_kernel<2, false, 512><<<p.grid, 256, 0, stream>>>(*a); break;
+    case ROITR_MHA_GEO_WIDE2_H: mha_geo_wide_kernel<2, true, 512><<<p.grid, 256, 0, stream>>>(*a); break;
+    case ROITR_MHA_PLAIN128: mha_plain_kernel<128, 1, 4><<<p.grid, 256, 0, stream>>>(*a); break;
+    case ROITR_MHA_PLAIN1024: mha_plain_kernel<1024, 1, 4><<<p.grid, 256, 0, stream>>>(*a); break;
+    case ROITR_MHA_PLAIN_WIDE2: mha_plain_kernel<512, 2, 1><<<p.grid, 256, 0, stream>>>(*a); break;
+    default: mha_kernel<<<p.grid, 256, p.lds, stream>>>(*a);
     }
-    // self attention over E at the model's width: the single-pass register-resident kernel (nk_max bounds every cloud)
-    const bool geo_any = a->E && !a->partner && a->C == 256 && a->heads == 4 && a->ldq % 4 == 0 && a->ldk % 4 == 0;
-    const bool geo = geo_any && a->nk_max <= 128;
-    if (geo_any && !geo && a->nk_max <= 1024) {
-        mha_geo_stream_kernel<<<xcd_grid(a->q_rows), 256, 0, stream>>>(*a);
-        roitr_prof_end(ROITR_PROF_MHA, stream);
-        ROITR_LAUNCH_CHECK();
-        return ROITR_OK;
-    }
-    const bool plain = !a->E && a->C == 256 && a->heads == 4 && a->ldq % 4 == 0 && a->ldk % 4 == 0 && a->nk_max <= 1024;
-    if (plain && a->nk_max <= 128) mha_plain_kernel<128><<<xcd_grid(div_up(a->q_rows, 4)), 256, 0, stream>>>(*a);
-    else if (plain) mha_plain_kernel<1024><<<xcd_grid(div_up(a->q_rows, 4)), 256, 0, stream>>>(*a);
-    else if (geo && a->nk_max <= 80) mha_geo_kernel<20><<<xcd_grid(a->q_rows), 256, 0, stream>>>(*a);
-    else if (geo) mha_geo_kernel<32><<<xcd_grid(a->q_rows), 256, 0, stream>>>(*a);
-    else
-    mha_kernel<<<xcd_grid(a->q_rows), 256, floats * sizeof(float), stream>>>(*a);
     roitr_prof_end(ROITR_PROF_MHA, stream);
     ROITR_LAUNCH_CHECK();
     return ROITR_OK;

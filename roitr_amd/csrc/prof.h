@@ -18,7 +18,7 @@ enum {
     ROITR_PROF_OT = 10,        // ot_kernel
     ROITR_PROF_LOCAL_ATTN = 11,// local_attn_kernel
     ROITR_PROF_GEMM = 12,      // gemm_kernel: the "bytes" field carries FLOPs (2*M*N*K*batch)
-    ROITR_PROF_MHA = 13,       // mha_kernel
+    ROITR_PROF_MHA = 13,       // the kernel of one roitr_mha call, whatever its form (ROITR_MHA_*)
     ROITR_PROF_GEO_EMBED = 14, // geo_embed_kernel (GEMM form): "bytes" carries FLOPs
     ROITR_PROF_GEO_TABLE = 15, // geo_table_kernel: HBM bytes
     ROITR_PROF_GEO_ALGO = 16,  // no time: the FLOPs the GEMM form of the embedding would have spent on the rows geo_table_kernel served

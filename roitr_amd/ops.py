@@ -16,7 +16,7 @@ _lib = L.binder("""roitr_calc_ppf roitr_point_to_node_partition roitr_coarse_scr
     roitr_geo_table_build roitr_geo_embed_table roitr_geo_embed_bf16 roitr_split3_bf16 roitr_geo_embed_split roitr_geo_embed
     roitr_local_attention_fold roitr_local_attention roitr_local_td_supported roitr_local_td roitr_local_block
     roitr_local_first roitr_local_weights_prepare roitr_local_weights_release roitr_local_weights_count
-    roitr_local_weights_reorder_host roitr_mha roitr_geo_indices roitr_build_padded_clouds roitr_node_occlusion_score
+    roitr_local_weights_reorder_host roitr_mha roitr_mha_form roitr_geo_indices roitr_build_padded_clouds roitr_node_occlusion_score
     roitr_node_correspondences""".split())
 
 # The argument structs of include/roitr_engine.h: fields in header order, everything not set is 0 / NULL.
@@ -638,6 +638,15 @@ def multi_head_attention(q, k, v, offset, cloud_of_row, nk_max, heads=4, partner
     (n_c, n_c, C) blocks (float32 or bfloat16) at element offsets eoff (b,) int64 / C, qt (T, heads, C) = Wp_h^T q_h,
     bp (C,) = proj_p.bias.  Query rows [q_row0, q_row0 + q_rows) are computed into out (T, C) and ebar (T, heads, C) =
     sum_j a'_hj E_ij (preallocated ones are written in those rows only).  Returns (out, ebar); ebar is None without E."""
+    a, out, ebar = mha_args(q, k, v, offset, cloud_of_row, nk_max, heads, partner, E, eoff, qt, bp, scale, q_row0, q_rows, out, ebar)
+    L.check(_lib().roitr_mha(ctypes.byref(a), L.stream_ptr()), "mha")
+    return out, ebar
+
+
+def mha_args(q, k, v, offset, cloud_of_row, nk_max, heads=4, partner=None, E=None, eoff=None, qt=None, bp=None,
+             scale=None, q_row0=0, q_rows=None, out=None, ebar=None):
+    """The RoitrMha of a multi_head_attention call (below) with its checks, and the output tensors: (struct, out, ebar).  The struct
+    holds addresses only: the caller keeps the tensors alive until the launch is queued."""
     T, C = int(q.shape[0]), int(q.shape[1])
     q_rows = T - q_row0 if q_rows is None else int(q_rows)
     if q_row0 < 0 or q_row0 + q_rows > min(T, int(cloud_of_row.numel())):
@@ -663,8 +672,7 @@ def multi_head_attention(q, k, v, offset, cloud_of_row, nk_max, heads=4, partner
             raise L.RoitrError("multi_head_attention: ebar (T, heads, C) contiguous")
         a.E, a.eoff, a.qt, a.bp, a.ebar = L.ptr(E), L.ptr(eoff), L.ptr(qt), L.ptr(bp), L.ptr(ebar)
         a.e_bf16 = int(E.dtype == torch.bfloat16)
-    L.check(_lib().roitr_mha(ctypes.byref(a), L.stream_ptr()), "mha")
-    return out, ebar
+    return a, out, ebar
 
 
 def geo_indices(points, sizes, sigma_d=0.2, sigma_a=15.0, angle_k=3):

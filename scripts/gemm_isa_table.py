@@ -89,10 +89,11 @@ def main():
             kb = {names[n]: v for n, v in kb.items()}
             names = {n: n for n in list(kp) + list(kb)}
             print("== %s: %d kernels in the parent, %d in this tree" % (f, len(kp), len(kb)))
+            figures = lambda k: "  ".join("%s %s" % (c, k[c]) for c in cols)   # of a kernel without a namesake: a renamed or merged one is read against these
             for n in sorted(set(kp) - set(kb)):
-                print("  only in the parent: " + names[n])
+                print("  only in the parent: %s\n      %s" % (names[n], figures(kp[n])))
             for n in sorted(set(kb) - set(kp)):
-                print("  only in this tree:  " + names[n])
+                print("  only in this tree:  %s\n      %s" % (names[n], figures(kb[n])))
                 verdict = False
             for n in sorted(set(kp) & set(kb), key=lambda x: names[x]):
                 a, b = kp[n], kb[n]

@@ -1,8 +1,10 @@
 """GPU: the global geometric transformer kernels of csrc/geo_attn.hip called directly (ops.multi_head_attention / ops.geo_indices),
 against float64 restatements, at every dispatch threshold of roitr_mha from both sides.
 
-roitr_mha dispatches on C, heads, E, partner, e_bf16 and nk_max to ten kernel instantiations; the forwards reach some of them at
-about N / 64 superpoints per cloud only.  Each case below names the instantiation it is meant to reach.  The data is built to make
+roitr_mha dispatches on C, heads, E, partner, e_bf16 and nk_max to ten kernel forms (ROITR_MHA_*, include/roitr_engine.h: ten
+instantiations of four kernels); the forwards reach some of them at about N / 64 superpoints per cloud only.  Each case below names
+the form it is meant to reach, and every launch first asserts that roitr_mha_form -- the rule roitr_mha dispatches through -- gives
+that form to the very struct it launches (tests/test_mha_form_cpu.py holds the same table without a GPU).  The data is built to make
 index errors visible: scores spread over several units (the softmax is far from uniform), a different gain per head for q and a
 different mean per head for v (a head mix-up shows), ragged clouds under one nk_max bound, launch windows that start at an odd
 row and end short of a multiple of 4 (XCD remap, the four-row blocks of mha_plain_kernel straddling clouds), q | k | v as the
@@ -12,6 +14,8 @@ the softmax a and the diagonal-masked a' differ by O(1) and a wrong diagonal ind
 import numpy as np
 import pytest
 import torch
+
+import mha_util
 
 pytestmark = pytest.mark.gpu
 
@@ -65,15 +69,15 @@ class Setup:
                 E[ii] = 15.0 * u
             self.E = E.to(torch.bfloat16) if e == "bf16" else E
 
-    def launch(self, q_row0=0, q_rows=None, out=None, ebar=None):
-        from roitr_amd import ops
+    def launch(self, form, q_row0=0, q_rows=None, out=None, ebar=None):
+        """The launch, after the assertion that roitr_mha gives its struct the form `form`."""
         if out is None:
             out = torch.full((self.T, self.C), float("nan"), device="cuda")
         if ebar is None and self.E is not None:
             ebar = torch.full((self.T, self.heads, self.C), float("nan"), device="cuda")
         kw = dict(E=self.E, eoff=self.eoff, qt=self.qt, bp=self.bp) if self.E is not None else {}
-        return ops.multi_head_attention(self.q, self.k, self.v, self.offset, self.cloud_of_row, self.nk_max, heads=self.heads,
-                                        partner=self.partner_t, q_row0=q_row0, q_rows=q_rows, out=out, ebar=ebar, **kw)
+        return mha_util.launch(form, self.q, self.k, self.v, self.offset, self.cloud_of_row, self.nk_max, heads=self.heads,
+                               partner=self.partner_t, q_row0=q_row0, q_rows=q_rows, out=out, ebar=ebar, **kw)
 
     def key_range(self, r):
         kc = self.partner[self.cl[r]]
@@ -140,51 +144,51 @@ def window(T):
     return q_row0, q_rows - 1 if q_rows % 4 == 0 else q_rows
 
 
-# (id, kernel the case is meant to reach, C, heads, cloud sizes, cross, E storage, dominant diagonal)
+# (id, form (ROITR_MHA_*) the case is meant to reach, C, heads, cloud sizes, cross, E storage, dominant diagonal)
 CASES = [
-    ("geo20-nk4", "mha_geo_kernel<20>", 256, 4, (4, 3, 4, 2), False, "f32", False),
-    ("geo20-nk79", "mha_geo_kernel<20>", 256, 4, (79, 40, 17, 63), False, "f32", False),
-    ("geo20-nk80", "mha_geo_kernel<20>", 256, 4, (80, 80, 33, 7), False, "f32", True),
-    ("geo32-nk81", "mha_geo_kernel<32>", 256, 4, (81, 5, 60), False, "f32", False),
-    ("geo32-nk127", "mha_geo_kernel<32>", 256, 4, (127, 90, 30), False, "f32", True),
-    ("geo32-nk128", "mha_geo_kernel<32>", 256, 4, (128, 128, 77), False, "f32", False),
-    ("stream-nk129", "mha_geo_stream_kernel", 256, 4, (129, 100, 3), False, "f32", False),
-    ("stream-nk511", "mha_geo_stream_kernel", 256, 4, (511, 200), False, "f32", True),
-    ("stream-nk512", "mha_geo_stream_kernel", 256, 4, (512, 64, 129), False, "f32", False),
-    ("stream-nk513", "mha_geo_stream_kernel", 256, 4, (513, 47), False, "f32", False),
-    ("stream-nk1024", "mha_geo_stream_kernel", 256, 4, (1024, 300, 5), False, "f32", True),
-    ("wide1h-nk4", "mha_geo_wide_kernel<1,true>", 256, 4, (4, 2, 3), False, "bf16", False),
-    ("wide1h-nk80", "mha_geo_wide_kernel<1,true>", 256, 4, (80, 31), False, "bf16", True),
-    ("wide1h-nk129", "mha_geo_wide_kernel<1,true>", 256, 4, (129, 7, 64), False, "bf16", False),
-    ("wide1h-nk511", "mha_geo_wide_kernel<1,true>", 256, 4, (511, 90), False, "bf16", False),
-    ("wide1h-nk512", "mha_geo_wide_kernel<1,true>", 256, 4, (512, 200), False, "bf16", True),
-    ("wide2-nk79", "mha_geo_wide_kernel<2,false>", 512, 4, (79, 50, 2), False, "f32", False),
-    ("wide2-nk128", "mha_geo_wide_kernel<2,false>", 512, 4, (128, 33), False, "f32", True),
-    ("wide2-nk512", "mha_geo_wide_kernel<2,false>", 512, 4, (512, 100), False, "f32", False),
-    ("wide2h-nk81", "mha_geo_wide_kernel<2,true>", 512, 4, (81, 12), False, "bf16", True),
-    ("wide2h-nk511", "mha_geo_wide_kernel<2,true>", 512, 4, (511, 67), False, "bf16", False),
-    ("plain128-nk4", "mha_plain_kernel<128>", 256, 4, (4, 2, 3, 4), True, None, False),
-    ("plain128-nk80", "mha_plain_kernel<128>", 256, 4, (80, 13, 77, 9), True, None, False),
-    ("plain128-nk128", "mha_plain_kernel<128>", 256, 4, (128, 50, 97, 128), True, None, False),
-    ("plain1024-nk129", "mha_plain_kernel<1024>", 256, 4, (129, 40, 100, 66), True, None, False),
-    ("plain1024-nk513", "mha_plain_kernel<1024>", 256, 4, (513, 2, 300, 129), True, None, False),
-    ("plain1024-nk1024", "mha_plain_kernel<1024>", 256, 4, (1024, 77, 600, 5), True, None, False),
-    ("plainwide-nk4", "mha_plain_wide_kernel<512,2>", 512, 4, (4, 3, 2, 4), True, None, False),
-    ("plainwide-nk128", "mha_plain_wide_kernel<512,2>", 512, 4, (128, 21, 61, 127), True, None, False),
-    ("plainwide-nk512", "mha_plain_wide_kernel<512,2>", 512, 4, (300, 512, 511, 17), True, None, False),
-    ("generic-c512-self-nk513", "mha_kernel", 512, 4, (513, 40), False, "f32", True),
-    ("generic-c512-cross-nk513", "mha_kernel", 512, 4, (513, 20, 100, 7), True, None, False),
-    ("generic-h8-self", "mha_kernel", 256, 8, (100, 37, 9), False, "f32", True),
-    ("generic-h8-cross", "mha_kernel", 256, 8, (50, 20, 33, 60), True, None, False),
+    ("geo20-nk4", "GEO20", 256, 4, (4, 3, 4, 2), False, "f32", False),
+    ("geo20-nk79", "GEO20", 256, 4, (79, 40, 17, 63), False, "f32", False),
+    ("geo20-nk80", "GEO20", 256, 4, (80, 80, 33, 7), False, "f32", True),
+    ("geo32-nk81", "GEO32", 256, 4, (81, 5, 60), False, "f32", False),
+    ("geo32-nk127", "GEO32", 256, 4, (127, 90, 30), False, "f32", True),
+    ("geo32-nk128", "GEO32", 256, 4, (128, 128, 77), False, "f32", False),
+    ("stream-nk129", "GEO_STREAM", 256, 4, (129, 100, 3), False, "f32", False),
+    ("stream-nk511", "GEO_STREAM", 256, 4, (511, 200), False, "f32", True),
+    ("stream-nk512", "GEO_STREAM", 256, 4, (512, 64, 129), False, "f32", False),
+    ("stream-nk513", "GEO_STREAM", 256, 4, (513, 47), False, "f32", False),
+    ("stream-nk1024", "GEO_STREAM", 256, 4, (1024, 300, 5), False, "f32", True),
+    ("wide1h-nk4", "GEO_WIDE_H", 256, 4, (4, 2, 3), False, "bf16", False),
+    ("wide1h-nk80", "GEO_WIDE_H", 256, 4, (80, 31), False, "bf16", True),
+    ("wide1h-nk129", "GEO_WIDE_H", 256, 4, (129, 7, 64), False, "bf16", False),
+    ("wide1h-nk511", "GEO_WIDE_H", 256, 4, (511, 90), False, "bf16", False),
+    ("wide1h-nk512", "GEO_WIDE_H", 256, 4, (512, 200), False, "bf16", True),
+    ("wide2-nk79", "GEO_WIDE2", 512, 4, (79, 50, 2), False, "f32", False),
+    ("wide2-nk128", "GEO_WIDE2", 512, 4, (128, 33), False, "f32", True),
+    ("wide2-nk512", "GEO_WIDE2", 512, 4, (512, 100), False, "f32", False),
+    ("wide2h-nk81", "GEO_WIDE2_H", 512, 4, (81, 12), False, "bf16", True),
+    ("wide2h-nk511", "GEO_WIDE2_H", 512, 4, (511, 67), False, "bf16", False),
+    ("plain128-nk4", "PLAIN128", 256, 4, (4, 2, 3, 4), True, None, False),
+    ("plain128-nk80", "PLAIN128", 256, 4, (80, 13, 77, 9), True, None, False),
+    ("plain128-nk128", "PLAIN128", 256, 4, (128, 50, 97, 128), True, None, False),
+    ("plain1024-nk129", "PLAIN1024", 256, 4, (129, 40, 100, 66), True, None, False),
+    ("plain1024-nk513", "PLAIN1024", 256, 4, (513, 2, 300, 129), True, None, False),
+    ("plain1024-nk1024", "PLAIN1024", 256, 4, (1024, 77, 600, 5), True, None, False),
+    ("plainwide-nk4", "PLAIN_WIDE2", 512, 4, (4, 3, 2, 4), True, None, False),
+    ("plainwide-nk128", "PLAIN_WIDE2", 512, 4, (128, 21, 61, 127), True, None, False),
+    ("plainwide-nk512", "PLAIN_WIDE2", 512, 4, (300, 512, 511, 17), True, None, False),
+    ("generic-c512-self-nk513", "GENERIC", 512, 4, (513, 40), False, "f32", True),
+    ("generic-c512-cross-nk513", "GENERIC", 512, 4, (513, 20, 100, 7), True, None, False),
+    ("generic-h8-self", "GENERIC", 256, 8, (100, 37, 9), False, "f32", True),
+    ("generic-h8-cross", "GENERIC", 256, 8, (50, 20, 33, 60), True, None, False),
 ]
 
 
 def measure(case_id, seed=0):
     """Launch the case on its window and return (max |out - ref|, max |ebar - ref| or None, setup, launch results)."""
-    _, _, C, heads, sizes, cross, e, diag = next(c for c in CASES if c[0] == case_id)
+    _, form, C, heads, sizes, cross, e, diag = next(c for c in CASES if c[0] == case_id)
     S = Setup(C, heads, sizes, cross, e, diag, packed=(seed % 2 == 0), seed=seed)
     q_row0, q_rows = window(S.T)
-    out, ebar = S.launch(q_row0, q_rows)
+    out, ebar = S.launch(form, q_row0, q_rows)
     rows = S.check_rows(q_row0, q_rows, np.random.default_rng(seed))
     ro, re_, a, a2 = S.reference(rows)
     err_o = float(np.abs(out[rows].double().cpu().numpy() - ro).max())
@@ -218,13 +222,16 @@ def test_mha_against_float64(case):
         assert err_e < 2e-5, (kernel, err_e)
 
 
+FOLD_FORM = {(256, "f32"): "GEO_STREAM", (256, "bf16"): "GEO_WIDE_H", (512, "f32"): "GEO_WIDE2", (512, "bf16"): "GEO_WIDE2_H"}   # 150 keys
+
+
 @pytest.mark.parametrize("C,e", [(256, "f32"), (256, "bf16"), (512, "f32"), (512, "bf16")])
 def test_rpe_fold_matches_the_unfolded_reference(C, e):
     """geoattention.py:102-136 as written -- p = proj_p(E), vp = proj_vp(E), scores q . k + q . p, pos_states = sum_j a'_j vp_j --
     against the kernel's folded form finished the way the engine finishes it: pos = Wvp_h ebar_h + bvp_h (and out unchanged).
     Pins the fold identity itself (qt = Wp_h^T q_h, bp riding in the scores, ebar on the diagonal-masked softmax)."""
     S = Setup(C, 4, (90, 150, 37), e=e, diag=False, seed=7 + C)
-    out, ebar = S.launch()
+    out, ebar = S.launch(FOLD_FORM[C, e])
     H, c = 4, C // 4
     q, k, v = (t.double().cpu().numpy() for t in (S.q, S.k, S.v))
     Wp, bp, Wvp, bvp = (t.double().cpu().numpy() for t in (S.Wp, S.bp, S.Wvp, S.bvp))
@@ -251,7 +258,7 @@ def test_rpe_fold_matches_the_unfolded_reference(C, e):
     assert err_out < 2e-5 and err_pos < 2e-5, (err_out, err_pos)
 
 
-# one case per instantiation for the bitwise invariants
+# one case per form (GENERIC: with and without E) for the bitwise invariants
 BITWISE = ["geo20-nk79", "geo32-nk127", "stream-nk513", "wide1h-nk129", "wide2-nk79", "wide2h-nk81", "plain128-nk80",
            "plain1024-nk129", "plainwide-nk128", "generic-h8-self", "generic-c512-cross-nk513"]
 
@@ -273,13 +280,13 @@ def test_mha_bits_do_not_depend_on_the_launch(case_id):
     offsets 0) as among the others (same nk_max bound, so the same kernel); (3) two identical launches give identical bits."""
     _, kernel, C, heads, sizes, cross, e, diag = next(c for c in CASES if c[0] == case_id)
     S = Setup(C, heads, sizes, cross, e, diag, seed=50 + BITWISE.index(case_id))
-    full, ebar_full = S.launch()
-    again, ebar_again = S.launch()
+    full, ebar_full = S.launch(kernel)
+    again, ebar_again = S.launch(kernel)
     assert torch.equal(full, again) and (ebar_full is None or torch.equal(ebar_full, ebar_again)), (kernel, "not deterministic")
     out = torch.full_like(full, float("nan"))
     eb = torch.full_like(ebar_full, float("nan")) if ebar_full is not None else None
     for lo, hi in _slices(S):
-        S.launch(lo, hi - lo, out=out, ebar=eb)
+        S.launch(kernel, lo, hi - lo, out=out, ebar=eb)
     assert torch.equal(out, full), (kernel, "sliced launches differ from the full launch")
     assert eb is None or torch.equal(eb, ebar_full), (kernel, "ebar of sliced launches differs")
     # (2) cloud 1 alone: its own rows (and, cross, its partner's) in a layout of its own
@@ -305,7 +312,7 @@ def test_mha_bits_do_not_depend_on_the_launch(case_id):
         A.eoff_h = np.array([0])
         A.eoff = torch.zeros(1, dtype=torch.int64, device="cuda")
         A.qt, A.bp = S.qt[ri].contiguous(), S.bp
-    alone, ebar_alone = A.launch(0, S.sizes[c])
+    alone, ebar_alone = A.launch(kernel, 0, S.sizes[c])
     n = S.sizes[c]
     s = int(S.starts[c])
     assert torch.equal(alone[:n], full[s:s + n]), (kernel, "a cloud's rows depend on the other clouds of the launch")
