@@ -64,11 +64,16 @@ def _fields(body):
     return fields
 
 
+HEADERS = ("roitr_pointops.h", "roitr_engine.h")
+ENCODE_HEADER = "roitr_encode.h"   # part 3 of the ABI (encode once, match many): read by the same reader, listed on its own
+
+
 @functools.lru_cache(maxsize=None)
-def _headers():
-    """(structs, prototypes) of include/roitr_pointops.h and include/roitr_engine.h: the one reader of the headers."""
+def _headers(names=HEADERS):
+    """(structs, prototypes) of the named headers of include/ (default: roitr_pointops.h and roitr_engine.h): the one reader of the
+    headers."""
     structs, protos = {}, {}
-    for h in ("roitr_pointops.h", "roitr_engine.h"):
+    for h in names:
         text = open(os.path.join(os.path.dirname(_HERE), "include", h)).read()
         text = re.sub(r"/\*.*?\*/|//[^\n]*|^\s*#[^\n]*|extern \"C\" \{", "", text, flags=re.S | re.M)
         for name, body in re.findall(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;", text):
@@ -91,10 +96,21 @@ def header_prototypes():
     return _headers()[1]
 
 
+def encode_header():
+    """(structs, prototypes) of include/roitr_encode.h, as header_structs() / header_prototypes() give them for the other two."""
+    return _headers((ENCODE_HEADER,))
+
+
+@functools.lru_cache(maxsize=None)
+def _abi():
+    """(structs, prototypes) of all three headers in one table each: what struct() and the binders look names up in."""
+    return tuple({**a, **b} for a, b in zip(_headers(), encode_header()))
+
+
 @functools.lru_cache(maxsize=None)
 def struct(name):
     """The ctypes.Structure of a struct of the headers (needs the header only, not the library)."""
-    return type(name, (ctypes.Structure,), {"_fields_": header_structs()[name]})
+    return type(name, (ctypes.Structure,), {"_fields_": _abi()[0][name]})
 
 
 def lib():
@@ -120,7 +136,7 @@ def lib():
 
 
 def _assign(handle, names):
-    protos = header_prototypes()
+    protos = _abi()[1]
     for name in names:
         getattr(handle, name).restype, getattr(handle, name).argtypes = protos[name]
 

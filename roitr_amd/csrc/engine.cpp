@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "prof.h"
+#include "roitr_encode.h"
 #include "roitr_engine.h"
 #include "roitr_pointops.h"
 
@@ -531,11 +532,13 @@ struct Levels {
 };
 
 // The descriptor block of one forward, staged on the host and copied to the device in one piece:
-// off[4][NC] | cloud_of_node[T4] | partner[NC] | pad | eoff[NC] (long, 16-byte aligned)
+// off[4][NC] | cloud_of_node[T4] | partner[NC] | pad | eoff[NC] (long, 16-byte aligned) | a match only: slot_cloud[NC]
 struct Desc {
     int* off[4]; int* cloud_of_node; int* partner; long* eoff;
+    int* slot_cloud;   // roitr_engine_match: the cached cloud in every cloud slot of the call (behind the block of a forward)
     static size_t eoff_at(size_t NC, size_t T4) { return ((4 * NC + T4 + NC + 8) * sizeof(int) + 15) & ~(size_t)15; }
     static size_t bytes(size_t NC, size_t T4) { return eoff_at(NC, T4) + NC * sizeof(long); }
+    static size_t bytes_with_slots(size_t NC, size_t T4) { return bytes(NC, T4) + NC * sizeof(int); }
     static Desc at(char* base, size_t NC, size_t T4)   // the fields of a block at `base` (host or device)
     {
         Desc D;
@@ -543,6 +546,7 @@ struct Desc {
         D.cloud_of_node = (int*)base + 4 * NC;
         D.partner = D.cloud_of_node + T4;
         D.eoff = (long*)(base + eoff_at(NC, T4));
+        D.slot_cloud = (int*)(base + bytes(NC, T4));
         return D;
     }
 };
@@ -1140,10 +1144,16 @@ static constexpr int AHEAD_MAX_PAIRS = 128;
 static int forward_body(Engine& E, const RoitrForwardIO* io, hipStream_t st);
 
 // forward_body with the side stream joined on the error path
+static int join_on_error(Engine& E, int rc, hipStream_t st);
 static int forward_joined(Engine& E, const RoitrForwardIO* io, hipStream_t st)
 {
     E.side_forked = false; E.branch_forked = false; E.cur_par = -1; E.garena_short = false;
-    const int rc = forward_body(E, io, st);
+    return join_on_error(E, forward_body(E, io, st), st);
+}
+
+// what a failed call (a forward, an encode) has left on the engine's other streams is joined into `st`
+static int join_on_error(Engine& E, int rc, hipStream_t st)
+{
     // (the branch first: it may itself wait for events of the geometry stream)
     if (rc != ROITR_OK && E.branch_forked && E.branch && E.ev[Engine::EV_BRANCH_ERROR_JOIN]) {
         if (hipEventRecord(E.ev[Engine::EV_BRANCH_ERROR_JOIN], E.branch) == hipSuccess) (void)hipStreamWaitEvent(st, E.ev[Engine::EV_BRANCH_ERROR_JOIN], 0);
@@ -1192,7 +1202,7 @@ namespace {
 // stage only reads it.
 struct Plan {
     Levels V;
-    int B = 0, NC = 0;                        // pairs, clouds
+    int B = 0, NC = 0;                        // pairs, clouds (a forward and a match: 2 B cloud slots; an encode: NC clouds, B = 0)
     int T1 = 0, T4 = 0;                       // rows of the finest / the coarsest level (V.T[0], V.T[3])
     int C4 = 0, LIM = 0, P_ = 0;              // width of the coarsest level, points per patch, patches per pair
     size_t NPs = 0; bool compact = false;     // patch slots of the call; compact: the selected patches of all pairs back to back
@@ -1203,6 +1213,9 @@ struct Plan {
     int Tp = 0, Tsp = 0, Ttp = 0;             // their padded rows: all, source, target
     hipStream_t st = nullptr, sd = nullptr;   // main stream, geometry stream
     hipStream_t sb = nullptr;                 // the stream of the branch: the engine's third stream, or `st` with the phase overlap off
+    // roitr_engine_match: the cloud table the call's slots point into and the cloud of every slot (host).  Such a call has no geometry
+    // stream (sd == nullptr): nothing of it waits for the chain's events
+    const RoitrCloudTable* cache = nullptr; const int* slot_cloud = nullptr;
 };
 
 // Everything the geometry chain reads and writes.  carve_geometry takes every buffer; issue_geometry_chain fills them on the
@@ -1276,15 +1289,16 @@ void carve_branch(const RoitrForwardIO* io, const Plan& P, Arena& A, BranchBufs&
 }
 
 // ---- stage 1: level sizes (host), patch slots, limits
-int plan_sizes(const Engine& E, const RoitrForwardIO* io, Plan& P)
+// the cloud half: level sizes and offsets of NC clouds, where each cloud's block of E starts (back to back)
+int plan_clouds(const Engine& E, const int* n_points, int NC, Plan& P)
 {
-    const int B = io->pairs, NC = 2 * B, f = E.cfg.factor;
-    P.B = B; P.NC = NC; P.C4 = 256 * f; P.LIM = E.cfg.point_limit; P.P_ = E.cfg.num_corr;
+    const int f = E.cfg.factor;
+    P.NC = NC; P.C4 = 256 * f; P.LIM = E.cfg.point_limit; P.P_ = E.cfg.num_corr;
     Levels& V = P.V;
     for (int l = 0; l < 4; ++l) { V.n[l].resize(NC); V.off[l].resize(NC); }
     for (int c = 0; c < NC; ++c) {
         int s[4];
-        roitr_level_sizes(io->n_points[c], s);
+        roitr_level_sizes(n_points[c], s);
         for (int l = 0; l < 4; ++l) V.n[l][c] = s[l];
         if (s[3] < 4) { roitr_set_error("cloud too small: needs >= 256 points (4 nodes)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
     }
@@ -1294,6 +1308,21 @@ int plan_sizes(const Engine& E, const RoitrForwardIO* io, Plan& P)
         V.T[l] = acc;
     }
     P.T1 = V.T[0]; P.T4 = V.T[3];
+    if (V.nmax[3] > 1024) { roitr_set_error("more than 1024 superpoints per cloud", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
+    P.eoff.resize(NC);
+    P.etot = 0;
+    for (int c = 0; c < NC; ++c) { P.eoff[c] = P.etot; P.etot += (long)V.n[3][c] * V.n[3][c]; }
+    // bf16 operand mode: E (an operand of the q~ . E and a' . E contractions of every self layer) is stored bf16 when the
+    // attention kernel for this width reads it (C = 256 / 512, 4 heads, <= 512 superpoints)
+    P.e_h = E.cfg.operand_dtype == 1 && E.proj_d.wb && E.proj_a.wb && (P.C4 == 256 || P.C4 == 512) && V.nmax[3] <= 512;
+    return 0;
+}
+
+// the pair half: ground-truth rows, patch slots and their limits for the B pairs over the 2 B planned clouds
+int plan_pairs(const Engine& E, const RoitrForwardIO* io, Plan& P)
+{
+    const int B = io->pairs, NC = P.NC; const Levels& V = P.V;
+    P.B = B;
     P.gt = io->rot && io->trans && (io->gt_node_occ || io->gt_corr_idx);
     P.gt_corr = P.gt && io->gt_corr_idx && io->gt_corr_overlaps && io->gt_corr_count;
     P.Tp = P.T1 + NC; P.Tsp = V.off[0][B - 1] + B; P.Ttp = P.Tp - P.Tsp;
@@ -1305,14 +1334,13 @@ int plan_sizes(const Engine& E, const RoitrForwardIO* io, Plan& P)
     if (P.compact && io->patch_slots > 0 && (size_t)io->patch_slots < P.NPs) P.NPs = (size_t)io->patch_slots;
     const int LIM = P.LIM;
     if (P.NPs * (size_t)(LIM * LIM) > 0x7fffffffffLL || P.NPs > 0x7ffffff0u / (size_t)LIM) { roitr_set_error("too many patch slots for one call", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
-    if (V.nmax[3] > 1024) { roitr_set_error("more than 1024 superpoints per cloud", __FILE__, __LINE__); return ROITR_ERR_UNSUPPORTED; }
-    P.eoff.resize(NC);
-    P.etot = 0;
-    for (int c = 0; c < NC; ++c) { P.eoff[c] = P.etot; P.etot += (long)V.n[3][c] * V.n[3][c]; }
-    // bf16 operand mode: E (an operand of the q~ . E and a' . E contractions of every self layer) is stored bf16 when the
-    // attention kernel for this width reads it (C = 256 / 512, 4 heads, <= 512 superpoints)
-    P.e_h = E.cfg.operand_dtype == 1 && E.proj_d.wb && E.proj_a.wb && (P.C4 == 256 || P.C4 == 512) && V.nmax[3] <= 512;
     return 0;
+}
+
+int plan_sizes(const Engine& E, const RoitrForwardIO* io, Plan& P)
+{
+    CHK(plan_clouds(E, io->n_points, 2 * io->pairs, P));
+    return plan_pairs(E, io, P);
 }
 
 // ---- stage 4 (and the size of the alternating arena in stage 2): EVERY buffer the geometry chain writes, before the encoder's mark /
@@ -1353,7 +1381,7 @@ void carve_geometry(const Engine& E, const RoitrForwardIO* io, const Plan& P, Ar
     }
     S.d_idx = GF.get<float>(P.etot);
     S.a_idx = GF.get<float>((size_t)P.etot * 3);
-    S.Emb = GF.get<float>((size_t)P.etot * P.C4);
+    if (!S.Emb) S.Emb = GF.get<float>((size_t)P.etot * P.C4);   // (an encode presets it: E is written into the caller's cache)
     S.c3 = GF.get<int>(V.T[2]);
     S.c4 = GF.get<int>(T4);
     S.p2n = GF.get<int>(T1);
@@ -1419,7 +1447,7 @@ int reserve_arenas(Engine& E, const RoitrForwardIO* io, Plan& P)
     }
     hipStream_t sd = P.sd = E.side;
     P.sb = (E.phase_overlap == 2 || (E.phase_overlap == 1 && T4 >= BRANCH_MIN_NODES)) ? E.branch : st;
-    {   // the branch arena: exactly what carve_branch takes (counted the same way as the alternating arenas below)
+    if (P.B > 0) {   // the branch arena: exactly what carve_branch takes (counted the same way as the alternating arenas below); an encode has no branch
         Arena cnt; cnt.cap = ~(size_t)0;
         BranchBufs unused;
         carve_branch(io, P, cnt, unused);
@@ -1495,7 +1523,7 @@ int reserve_arenas(Engine& E, const RoitrForwardIO* io, Plan& P)
 int stage_descriptors(Engine& E, const Plan& P, GeoBufs& S)
 {
     const Levels& V = P.V; const int B = P.B, NC = P.NC; hipStream_t st = P.st, sd = P.sd;
-    const size_t desc_bytes = Desc::bytes(NC, P.T4);
+    const size_t desc_bytes = P.slot_cloud ? Desc::bytes_with_slots(NC, P.T4) : Desc::bytes(NC, P.T4);
     hipStream_t st_desc = P.ahead ? sd : st;   // the stream that stages the descriptors
     const int slot = E.ring_pos;
     char* pin = E.capture_pin;   // a captured forward owns its staging buffer (the graph re-reads it at every launch)
@@ -1515,6 +1543,7 @@ int stage_descriptors(Engine& E, const Plan& P, GeoBufs& S)
     for (int c = 0, r = 0; c < NC; ++c) for (int i = 0; i < V.n[3][c]; ++i) H.cloud_of_node[r++] = c;
     for (int c = 0; c < NC; ++c) H.partner[c] = c < B ? c + B : c - B;
     memcpy(H.eoff, P.eoff.data(), sizeof(long) * NC);
+    if (P.slot_cloud) memcpy(H.slot_cloud, P.slot_cloud, sizeof(int) * NC);
     ROITR_HIP(hipMemcpyAsync(S.desc, pin, desc_bytes, hipMemcpyHostToDevice, st_desc));
     if (!E.capture_pin) ROITR_HIP(hipEventRecord(E.pinned_ev[slot], st_desc));
     if (P.ahead) {   // `st` reads the descriptors (and the inputs) from here on
@@ -1714,19 +1743,34 @@ int encoder(Engine& E, const RoitrForwardIO* io, const Plan& P, const GeoBufs& S
 // ---- stage 7: the global geometric transformer (geotransformer.py:94-133), all pairs batched
 // Queued on the branch's stream (P.sb), in the branch's buffers: it reads the encoder's last level and E, and only the coarse head reads
 // its output, so it runs beside the decoder.
+// the input projection of the global transformer: per cloud (roitr_engine_encode writes these rows into the cache)
+int geo_in_proj(Engine& E, hipStream_t st, int T4, const float* xe4, float* out)
+{
+    CHK(Gemm(T4, xe4, E.geo_in, out).run(st));
+    return tap(E, st, "geo.in_proj", out, sizeof(float) * (size_t)T4 * E.geo_in.out);
+}
+
+int global_layers(Engine& E, const Plan& P, const GeoBufs& S, Feats& F, const BranchBufs& R);
+
 int global_transformer(Engine& E, const Plan& P, const GeoBufs& S, Feats& F, const BranchBufs& R)
 {
-    const Levels& V = P.V; const Desc& D = S.D; hipStream_t st = P.sb; Arena& A = E.barena;
-    const int B = P.B, T4 = P.T4, C4 = P.C4; const long etot = P.etot; const bool e_h = P.e_h;
-    float* gfeat = F.gfeat = R.gfeat;
+    hipStream_t st = P.sb; const int T4 = P.T4, C4 = P.C4; const long etot = P.etot; const bool e_h = P.e_h;
     ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_EMBED_DONE], 0));   // E and its index arrays were written on the side stream
     CHK(tap(E, st, "geo.d_idx", S.d_idx, sizeof(float) * etot));
     CHK(tap(E, st, "geo.a_idx", S.a_idx, sizeof(float) * etot * 3));
     CHK(tap(E, st, "geo.emb", S.Emb, (e_h ? sizeof(unsigned short) : sizeof(float)) * (size_t)etot * C4));   // bf16 mode: the tap holds bf16
+    CHK(geo_in_proj(E, st, T4, F.xe[3], R.fcur));
+    return global_layers(E, P, S, F, R);
+}
 
+// the layers of the global transformer and its output projection over the rows of R.fcur (what roitr_engine_match starts from: its
+// fcur rows are the cached geo_in rows of the call's cloud slots, its E the cache's, addressed per slot through D.eoff)
+int global_layers(Engine& E, const Plan& P, const GeoBufs& S, Feats& F, const BranchBufs& R)
+{
+    const Levels& V = P.V; const Desc& D = S.D; hipStream_t st = P.sb; Arena& A = E.barena;
+    const int B = P.B, T4 = P.T4, C4 = P.C4; const long etot = P.etot; const bool e_h = P.e_h;
+    float* gfeat = F.gfeat = R.gfeat;
     float *fcur = R.fcur, *pos = R.pos, *qkv = R.qkv, *qt = R.qt, *ebar = R.ebar, *hid = R.hid, *t1 = R.t1, *t2 = R.t2;
-    CHK(Gemm(T4, F.xe[3], E.geo_in, fcur).run(st));
-    CHK(tap(E, st, "geo.in_proj", fcur, sizeof(float) * (size_t)T4 * C4));
     const int cpe = C4 / HEADS;
     const float scale = 1.0f / sqrtf((float)cpe);
     const int Ts = V.off[3][B - 1];  // source-cloud rows come first
@@ -1842,7 +1886,7 @@ int coarse_front(Engine& E, const Plan& P, const GeoBufs& S, const Feats& F, con
     const Levels& V = P.V; const Desc& D = S.D; hipStream_t st = P.sb;
     const int B = P.B, T4 = P.T4, C4 = P.C4, LIM = P.LIM, P_ = P.P_; const bool compact = P.compact;
     const size_t NP = P.NPs;
-    ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_TAIL_DONE], 0));   // node masks, partition and ground-truth side outputs (side stream)
+    if (P.sd) ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_TAIL_DONE], 0));   // node masks, partition and ground-truth side outputs (side stream)
     CHK(Gemm(T4, F.gfeat, E.coarse_proj, R.cp).run(st));
     CHK(roitr_l2_normalize(T4, C4, R.cp, R.node_feats, st));
     {   // all tgt_b x src_b feature dot products in one ragged-batched GEMM (rows: tgt cloud B+b, cols: src cloud b)
@@ -1862,7 +1906,14 @@ int coarse_front(Engine& E, const Plan& P, const GeoBufs& S, const Feats& F, con
     }
     // the tail runs on the selected patches only (RIGA_v2.py:126-152): their slots, pair after pair
     if (compact) CHK(roitr_patch_offsets(B, R.n_corr, (int)NP, R.pair_off, st));
-    {
+    if (P.cache) {   // a match: node and point segments of both sides from the cloud table, rows of the cache's point arrays
+        RoitrCachePatch cg; memset(&cg, 0, sizeof(cg));
+        cg.pairs = B; cg.num_corr = P_; cg.limit = LIM; cg.n_corr = R.n_corr; cg.tgt_corr = R.tgt_corr; cg.src_corr = R.src_corr;
+        cg.seg = P.cache->seg_dev; cg.slot_cloud = D.slot_cloud;
+        cg.knn_idx = P.cache->node_knn_idx; cg.knn_mask = P.cache->node_knn_mask; cg.points = P.cache->points;
+        cg.tgt_rows = R.trows; cg.src_rows = R.srows; cg.tgt_masks = R.tmask; cg.src_masks = R.smask; cg.tgt_pts = R.tpts; cg.src_pts = R.spts;
+        CHK(roitr_cache_patch_gather(&cg, st));
+    } else {
         RoitrPatch pg; memset(&pg, 0, sizeof(pg));
         pg.pairs = B; pg.num_corr = P_; pg.limit = LIM; pg.n_corr = R.n_corr; pg.tgt_corr = R.tgt_corr; pg.src_corr = R.src_corr;
         pg.node_offset = D.off[3]; pg.pt_offset = D.off[0]; pg.knn_idx = S.kidx; pg.knn_mask = S.kmask; pg.points = S.pts_out;
@@ -1874,10 +1925,12 @@ int coarse_front(Engine& E, const Plan& P, const GeoBufs& S, const Feats& F, con
 }
 
 // ---- stage 9b: the fine head (RIGA_v2.py:67-68) behind the decoder, then -- behind the branch -- patch scores, optimal transport, fine matching
+int matching_tail(Engine& E, const RoitrForwardIO* io, const Plan& P, const BranchBufs& R, const float* point_feats, int feat_rows);
+
 int heads_and_matching(Engine& E, const RoitrForwardIO* io, const Plan& P, const Feats& F, const BranchBufs& R)
 {
     hipStream_t st = P.st; Arena& A = E.arena;
-    const int B = P.B, T1 = P.T1, C4 = P.C4, LIM = P.LIM, P_ = P.P_; const bool compact = P.compact;
+    const int T1 = P.T1, C4 = P.C4;
     float* point_feats = io->point_feats ? io->point_feats : A.get<float>((size_t)T1 * C4);
     if (A.fail) { roitr_set_error("arena exhausted (heads)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
     CHK(Gemm(T1, F.xd[0], E.fine_proj, point_feats).run(st));
@@ -1890,6 +1943,15 @@ int heads_and_matching(Engine& E, const RoitrForwardIO* io, const Plan& P, const
     // everything the other two streams were given is ordered before `st` from here (on one stream coarse_front, queued just in front of this
     // function, took the EV_TAIL_DONE wait on `st`)
     E.side_forked = false; E.branch_forked = false;
+    return matching_tail(E, io, P, R, point_feats, T1);
+}
+
+// patch scores, optimal transport, fine matching over the patch arrays of coarse_front.  point_feats (feat_rows, C4): the rows the patch
+// rows index -- the call's own fine-head output, or (roitr_engine_match) the cached descriptors of every cloud of the table
+int matching_tail(Engine& E, const RoitrForwardIO* io, const Plan& P, const BranchBufs& R, const float* point_feats, int feat_rows)
+{
+    hipStream_t st = P.st; Arena& A = E.arena;
+    const int B = P.B, T1 = feat_rows, C4 = P.C4, LIM = P.LIM, P_ = P.P_; const bool compact = P.compact;
     const int* n_corr = R.n_corr; const int* pair_off = R.pair_off; const float* cscore = R.cscore;
     const int *trows = R.trows, *srows = R.srows, *tmask = R.tmask, *smask = R.smask; const float *tpts = R.tpts, *spts = R.spts;
     const size_t NP = P.NPs;
@@ -1985,6 +2047,211 @@ static int forward_body(Engine& E, const RoitrForwardIO* io, hipStream_t st)
     roitr_prof_end(ROITR_PROF_PH_MATCH, st);
     roitr_prof_end(ROITR_PROF_PH_FORWARD, st);
     return 0;
+}
+
+// ---------------------------------------------------------------- encode once, match many (include/roitr_encode.h)
+// The forward cut where its per-cloud half ends.  Both halves queue the stage functions above; the forward itself is unchanged.
+static int cache_scope(const Engine& E, const char* who)
+{
+    const std::string w(who);
+    if (!E.finalized) { roitr_set_error((w + ": engine not finalized").c_str(), __FILE__, __LINE__); return ROITR_ERR_ARG; }
+    if (E.cfg.operand_dtype == 1) {
+        roitr_set_error((w + ": operand_dtype 1 (bf16 operand storage) is not supported: the cache holds no bf16 E and no bf16 point descriptors").c_str(), __FILE__, __LINE__);
+        return ROITR_ERR_ARG;
+    }
+    if (E.cfg.adaptive_coarse) {
+        roitr_set_error((w + ": adaptive_coarse (4DMatch, the compacted patch layout) is not supported").c_str(), __FILE__, __LINE__);
+        return ROITR_ERR_ARG;
+    }
+    return ROITR_OK;
+}
+
+// no graph capture: both calls stage descriptors through the pinned ring and may reallocate scratch, which a replay would not repeat
+static int refuse_capture(hipStream_t st, const char* who)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (st && hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return ROITR_OK; }
+    if (cs != hipStreamCaptureStatusNone) {
+        roitr_set_error((std::string(who) + ": the stream is capturing a graph: not supported").c_str(), __FILE__, __LINE__);
+        return ROITR_ERR_ARG;
+    }
+    return ROITR_OK;
+}
+
+// The per-cloud stages exactly as the forward queues them -- the geometry chain (without its ground-truth part) on the geometry stream,
+// encoder, geo_in, decoder, fine_proj on `st` -- for NC unpaired clouds, with the node outputs, E, the geo_in rows and the point
+// descriptors written into the caller's cache arrays.
+static int encode_body(Engine& E, const RoitrEncodeIO* eio, hipStream_t st)
+{
+    RoitrForwardIO io; memset(&io, 0, sizeof(io));
+    io.n_points = eio->n_points; io.points_geom = eio->points_geom; io.normals = eio->normals; io.feats = eio->feats; io.points_out = eio->points_out;
+    io.node_xyz = eio->node_xyz; io.node_masks = eio->node_masks; io.node_knn_idx = eio->node_knn_idx; io.node_knn_mask = eio->node_knn_mask;
+    Plan P; GeoBufs S; Feats F;
+    P.st = st;
+    CHK(plan_clouds(E, eio->n_points, eio->clouds, P));
+    CHK(reserve_arenas(E, &io, P));
+    P.sb = st;   // no branch: the pair half is another call
+    S.Emb = eio->embedding;
+    CHK(carve_geometry_buffers(E, &io, P, S));
+    CHK(stage_descriptors(E, P, S));
+    CHK(issue_geometry_chain(E, &io, P, S));
+    CHK(encoder(E, &io, P, S, F));
+    CHK(geo_in_proj(E, st, P.T4, F.xe[3], eio->node_geo));
+    CHK(decoder(E, P, S, F));
+    CHK(Gemm(P.T1, F.xd[0], E.fine_proj, eio->point_feats).run(st));
+    if (eio->points != S.pts_out) CHK(d2d(st, eio->points, S.pts_out, sizeof(float) * 3 * (size_t)P.T1));
+    // the join: E and the chain's tail (node coordinates, partition) were written on the geometry stream
+    ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_EMBED_DONE], 0));
+    ROITR_HIP(hipStreamWaitEvent(st, E.ev[Engine::EV_TAIL_DONE], 0));
+    E.side_forked = false;
+    return ROITR_OK;
+}
+
+extern "C" int roitr_engine_encode(void* h, const RoitrEncodeIO* eio, hipStream_t st)
+{
+    Engine& E = *(Engine*)h;
+    g_engine = &E;
+    CHK(cache_scope(E, "roitr_engine_encode"));
+    CHK(refuse_capture(st, "roitr_engine_encode"));
+    if (eio->clouds < 1 || !eio->n_points) { roitr_set_error("roitr_engine_encode: needs at least one cloud", __FILE__, __LINE__); return ROITR_ERR_ARG; }
+    if (!eio->points_geom || !eio->normals || !eio->feats || !eio->points || !eio->point_feats || !eio->node_xyz || !eio->node_masks ||
+        !eio->node_knn_idx || !eio->node_knn_mask || !eio->node_geo || !eio->embedding) {
+        roitr_set_error("roitr_engine_encode: an input or a cache array is NULL", __FILE__, __LINE__);
+        return ROITR_ERR_ARG;
+    }
+    for (int c = 0; c < eio->clouds; ++c)   // (before anything is reserved or queued)
+        if (eio->n_points[c] < 256) { roitr_set_error("roitr_engine_encode: cloud too small: needs >= 256 points (4 nodes)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
+    E.side_forked = false; E.branch_forked = false; E.cur_par = -1; E.garena_short = false;
+    const int rc = join_on_error(E, encode_body(E, eio, st), st);
+    E.side_forked = false;
+    return rc;
+}
+
+// The pair half over cached clouds, on `st` alone: the cached geo_in rows and node masks of the call's 2 B cloud slots gathered into the
+// call layout, the global transformer from its first layer on with E read in the cache (per-slot offsets in D.eoff), the coarse front
+// with the cached patch gather, the matching tail on the cached point descriptors.
+static int match_body(Engine& E, const RoitrCloudTable* tab, const RoitrMatchIO* mio, hipStream_t st)
+{
+    const int B = mio->pairs, NC = 2 * B;
+    std::vector<int> slot_cloud(NC), n_pts(NC);
+    for (int b = 0; b < B; ++b) { slot_cloud[b] = mio->src_cloud[b]; slot_cloud[B + b] = mio->tgt_cloud[b]; }
+    for (int c = 0; c < NC; ++c) n_pts[c] = tab->seg[slot_cloud[c]].n_points;
+    long feat_rows = 0;
+    for (int c = 0; c < tab->n_clouds; ++c) {
+        const long end = (long)tab->seg[c].pt_row0 + tab->seg[c].n_points;
+        feat_rows = end > feat_rows ? end : feat_rows;
+    }
+    RoitrForwardIO io; memset(&io, 0, sizeof(io));
+    io.pairs = B; io.n_points = n_pts.data();
+    io.node_xyz = mio->node_xyz; io.node_feats = mio->node_feats;
+    io.tgt_corr = mio->tgt_corr; io.src_corr = mio->src_corr; io.corr_scores = mio->corr_scores; io.n_corr = mio->n_corr;
+    io.tgt_knn_pts = mio->tgt_knn_pts; io.src_knn_pts = mio->src_knn_pts; io.tgt_knn_masks = mio->tgt_knn_masks; io.src_knn_masks = mio->src_knn_masks;
+    io.matching_scores = mio->matching_scores; io.out_tgt_pts = mio->out_tgt_pts; io.out_src_pts = mio->out_src_pts; io.out_scores = mio->out_scores;
+    io.out_patch = mio->out_patch; io.fine_offsets = mio->fine_offsets; io.n_out = mio->n_out; io.pair_starts = mio->pair_starts;
+    Plan P; GeoBufs S; Feats F; BranchBufs R;
+    P.st = st; P.sb = st; P.sd = nullptr; P.cache = tab; P.slot_cloud = slot_cloud.data();
+    CHK(plan_clouds(E, n_pts.data(), NC, P));
+    for (int c = 0; c < NC; ++c) {
+        const RoitrCloudSeg& sg = tab->seg[slot_cloud[c]];
+        if (sg.n_nodes != P.V.n[3][c] || sg.pt_row0 < 0 || sg.node_row0 < 0 || sg.emb0 < 0) {
+            roitr_set_error("roitr_engine_match: a table entry's node count is not the level-4 size of its point count (or a negative row)", __FILE__, __LINE__);
+            return ROITR_ERR_ARG;
+        }
+        P.eoff[c] = sg.emb0;   // E is read in the cache: the slot's block is the cloud's
+    }
+    CHK(plan_pairs(E, &io, P));
+    const size_t T4 = P.T4, C4 = P.C4, LIM = P.LIM;
+    {   // the main arena: what matching_tail takes (the patch term of the forward's bound)
+        const size_t need = P.NPs * (LIM * LIM * 3 + (LIM + 1) * (LIM + 1) + LIM * 6) * 4 + ((size_t)64 << 20);
+        if (need > E.arena.cap) {
+            ROITR_HIP(hipStreamSynchronize(st));
+            if (E.side) ROITR_HIP(hipStreamSynchronize(E.side));
+            if (E.arena.base) ROITR_HIP(hipFree(E.arena.base));
+            E.arena.base = nullptr; E.arena.cap = 0;
+            ROITR_HIP(hipMalloc((void**)&E.arena.base, need));
+            E.arena.cap = need; E.arena.peak = 0;
+            E.arena_epoch++;
+        }
+        E.arena.off = 0; E.arena.fail = false;
+    }
+    // the branch arena: what carve_branch takes, the descriptor block and the gathered node arrays of the call layout -- counted, then carved
+    // (carve_branch last: it ends with the scratch it only reserves, which ffn_apply takes again from the same offset)
+    auto carve = [&](Arena& A, BranchBufs& r, GeoBufs& s) {
+        s.desc = A.get<char>(Desc::bytes_with_slots(NC, T4));
+        s.node_masks = A.get<int>(T4);
+        s.node_xyz = io.node_xyz;   // copied only when the caller asks for it
+        carve_branch(&io, P, A, r);
+    };
+    {
+        Arena cnt; cnt.cap = ~(size_t)0;
+        BranchBufs r0; GeoBufs s0;
+        carve(cnt, r0, s0);
+        if (cnt.peak > E.barena.cap) {
+            ROITR_HIP(hipStreamSynchronize(st));
+            if (E.branch) ROITR_HIP(hipStreamSynchronize(E.branch));
+            if (E.barena.base) ROITR_HIP(hipFree(E.barena.base));
+            E.barena.base = nullptr; E.barena.cap = 0;
+            ROITR_HIP(hipMalloc((void**)&E.barena.base, cnt.peak));
+            E.barena.cap = cnt.peak;
+            E.arena_epoch++;
+        }
+        E.barena.off = 0; E.barena.peak = 0; E.barena.fail = false;
+    }
+    carve(E.barena, R, S);
+    if (E.barena.fail) { roitr_set_error("arena exhausted (match)", __FILE__, __LINE__); return ROITR_ERR_ARG; }
+    S.Emb = const_cast<float*>(tab->embedding);
+    CHK(stage_descriptors(E, P, S));
+    E.on_branch = false;
+    {
+        RoitrCacheGather g; memset(&g, 0, sizeof(g));
+        g.slots = NC; g.C = (int)C4; g.n_max = P.V.nmax[3]; g.seg = tab->seg_dev; g.slot_cloud = S.D.slot_cloud; g.node_offset = S.D.off[3];
+        g.node_geo = tab->node_geo; g.node_masks = tab->node_masks; g.node_xyz = tab->node_xyz;
+        g.out_geo = R.fcur; g.out_masks = S.node_masks; g.out_xyz = S.node_xyz;
+        CHK(roitr_cache_gather_nodes(&g, st));
+    }
+    CHK(global_layers(E, P, S, F, R));
+    CHK(coarse_front(E, P, S, F, R));
+    return matching_tail(E, &io, P, R, tab->point_feats, (int)feat_rows);
+}
+
+extern "C" int roitr_engine_match(void* h, const RoitrCloudTable* tab, const RoitrMatchIO* mio, hipStream_t st)
+{
+    Engine& E = *(Engine*)h;
+    g_engine = &E;
+    CHK(cache_scope(E, "roitr_engine_match"));
+    CHK(refuse_capture(st, "roitr_engine_match"));
+    if (!tab || !tab->seg || !tab->seg_dev || tab->n_clouds < 1 || !tab->points || !tab->point_feats || !tab->node_xyz || !tab->node_masks ||
+        !tab->node_knn_idx || !tab->node_knn_mask || !tab->node_geo || !tab->embedding) {
+        roitr_set_error("roitr_engine_match: the cloud table is empty or an array of it is NULL", __FILE__, __LINE__);
+        return ROITR_ERR_ARG;
+    }
+    if (tab->channels != 256 * E.cfg.factor || tab->limit != E.cfg.point_limit) {
+        roitr_set_error("roitr_engine_match: the cache was encoded with other channels / point_limit than this engine's", __FILE__, __LINE__);
+        return ROITR_ERR_ARG;
+    }
+    if ((uintptr_t)tab->node_geo & 15) {   // the segment gather moves these rows as float4 (channels is a multiple of 256)
+        roitr_set_error("roitr_engine_match: the cache's node_geo array is not 16-byte aligned", __FILE__, __LINE__);
+        return ROITR_ERR_ARG;
+    }
+    for (int c = 0; c < tab->n_clouds; ++c) {   // patch rows are int32 rows of the cache's point arrays
+        const RoitrCloudSeg& sg = tab->seg[c];
+        if (sg.pt_row0 < 0 || sg.n_points < 0 || (long)sg.pt_row0 + sg.n_points > 0x7fffffffL ||
+            sg.node_row0 < 0 || sg.n_nodes < 0 || (long)sg.node_row0 + sg.n_nodes > 0x7fffffffL || sg.emb0 < 0) {
+            roitr_set_error("roitr_engine_match: a table entry has a negative row, or rows past 2^31", __FILE__, __LINE__);
+            return ROITR_ERR_ARG;
+        }
+    }
+    const long max_pairs = (long)(0x7ffffff0u / (size_t)E.cfg.point_limit) / E.cfg.num_corr;   // the forward's bound on patch slots per call
+    if (mio->pairs < 1 || mio->pairs > max_pairs || !mio->src_cloud || !mio->tgt_cloud) {
+        roitr_set_error("roitr_engine_match: pairs outside the range of one call (1 .. what the forward takes)", __FILE__, __LINE__);
+        return ROITR_ERR_ARG;
+    }
+    for (int b = 0; b < mio->pairs; ++b)
+        if (mio->src_cloud[b] < 0 || mio->src_cloud[b] >= tab->n_clouds || mio->tgt_cloud[b] < 0 || mio->tgt_cloud[b] >= tab->n_clouds) {
+            roitr_set_error("roitr_engine_match: cloud index outside the table", __FILE__, __LINE__);
+            return ROITR_ERR_ARG;
+        }
+    return match_body(E, tab, mio, st);
 }
 
 /* The global transformer and the coarse front beside the decoder on the branch stream (2: always; 1, the default: for calls of at least

@@ -127,6 +127,71 @@ def _attach(root, key, tensor, kind):
 
 _CConfig = L.struct("RoitrEngineConfig")
 _CForwardIO = L.struct("RoitrForwardIO")
+# encode once, match many (include/roitr_encode.h)
+_CCloudSeg = L.struct("RoitrCloudSeg")
+_CCloudTable = L.struct("RoitrCloudTable")
+_CEncodeIO = L.struct("RoitrEncodeIO")
+_CMatchIO = L.struct("RoitrMatchIO")
+_cache_lib = L.binder(["roitr_engine_encode_bytes", "roitr_engine_encode", "roitr_engine_match"])
+CACHE_ARRAYS = ("points", "point_feats", "node_xyz", "node_masks", "node_knn_idx", "node_knn_mask", "node_geo", "embedding")
+
+
+def cloud_segments(n_points):
+    """The RoitrCloudSeg entries of clouds of n_points[c] points cached back to back (a ctypes array, host): first point row and
+    count, first node row and count (n4 = n // 64 by the floor rule of level_sizes) and the first entry of the cloud's n4 x n4 block
+    of E -- in entries of C floats, a 64-bit count: 600 clouds of 5000 points are 3.65 million entries, 3.7 GB of fp32 at C = 256."""
+    seg = (_CCloudSeg * len(n_points))()
+    pt = nd = emb = 0
+    for c, n in enumerate(n_points):
+        n4 = RIGA_v2.level_sizes(int(n))[3]
+        seg[c].pt_row0, seg[c].n_points, seg[c].node_row0, seg[c].n_nodes, seg[c].emb0 = pt, int(n), nd, n4, emb
+        pt, nd, emb = pt + int(n), nd + n4, emb + n4 * n4
+    return seg
+
+
+def cache_bytes(n_points, channels, limit):
+    """Bytes of the eight cache arrays (CACHE_ARRAYS order) for these clouds and their sum: the documented per-cloud terms
+    4 * (3 n, C n, 3 n4, n4, L n4, L n4, C n4, C n4^2), in Python (roitr_engine_encode_bytes is the library's own count)."""
+    per = [0] * 8
+    for n in n_points:
+        n4 = RIGA_v2.level_sizes(int(n))[3]
+        for i, t in enumerate((3 * n, channels * n, 3 * n4, n4, limit * n4, limit * n4, channels * n4, channels * n4 * n4)):
+            per[i] += 4 * int(t)
+    return per, sum(per)
+
+
+class EncodedClouds:
+    """The cloud cache of RIGA_v2.encode_clouds: the eight arrays (`arrays`, CACHE_ARRAYS), the cloud table on the host (`seg`) and
+    on the device, the host copies of the counts, and the weight signature of the model at encode time."""
+
+    def __init__(self, arrays, n_points, channels, limit, signature, engine):
+        self.arrays, self.n_points, self.channels, self.limit = arrays, [int(n) for n in n_points], channels, limit
+        self.n4 = [RIGA_v2.level_sizes(n)[3] for n in self.n_points]
+        self.seg = cloud_segments(self.n_points)
+        dev = arrays["points"].device
+        # uploaded from pinned memory on the current stream: nothing here waits for the GPU (the pinned copy lives as long as the cache)
+        self._seg_pin = torch.frombuffer(bytearray(bytes(self.seg)), dtype=torch.uint8).pin_memory()
+        self.seg_dev = self._seg_pin.to(dev, non_blocking=True)
+        self.signature, self.engine = signature, engine
+        t = _CCloudTable()
+        t.n_clouds, t.channels, t.limit = len(self.n_points), channels, limit
+        for k in CACHE_ARRAYS:
+            setattr(t, k, L.ptr(arrays[k]))
+        t.seg = ctypes.cast(self.seg, ctypes.c_void_p)
+        t.seg_dev = L.ptr(self.seg_dev)
+        self.table = t
+        self.nbytes = sum(a.numel() * a.element_size() for a in arrays.values())
+
+    def __len__(self):
+        return len(self.n_points)
+
+    def cloud(self, c):
+        """Views of cloud c's rows in the cache arrays (the embedding as (n4, n4, C))."""
+        s, n4 = self.seg[c], self.n4[c]
+        out = {k: self.arrays[k][s.pt_row0:s.pt_row0 + s.n_points] for k in ("points", "point_feats")}
+        out.update({k: self.arrays[k][s.node_row0:s.node_row0 + n4] for k in ("node_xyz", "node_masks", "node_knn_idx", "node_knn_mask", "node_geo")})
+        out["embedding"] = self.arrays["embedding"][s.emb0:s.emb0 + n4 * n4].view(n4, n4, self.channels)
+        return out
 
 
 def _cfg_get(config, key, default=None):
@@ -238,6 +303,7 @@ class RIGA_v2(nn.Module):
         lib = L.lib()
         if self._engine is None:
             self._engine = self._make_engine()
+            self._engine_token = object()   # what a cloud cache remembers of its engine (an address could be reused by a later one)
         for k, v in self.state_dict(keep_vars=True).items():
             if not v.is_cuda:
                 raise L.RoitrError(f"parameter {k} is not on a ROCm device: call model.cuda() (no CPU fallback)")
@@ -566,7 +632,10 @@ class RIGA_v2(nn.Module):
         return int(L.lib().roitr_engine_graph_count(self._engine)) if self._engine is not None else 0
 
     def finish_batch(self, h):
-        """Wait for the forward of launch_batch() and unpack it per pair (the one host synchronisation of the path)."""
+        """Wait for the forward of launch_batch() -- or the match of launch_match() -- and unpack it per pair (the one host
+        synchronisation of the path)."""
+        if "enc" in h:
+            return self._finish_match(h)
         pairs, out, B, P, n_all, n4, have_gt = h["pairs"], h["out"], h["B"], h["P"], h["n_all"], h["n4"], h["have_gt"]
         h["done"].synchronize()
         t_host = time.perf_counter()
@@ -633,6 +702,159 @@ class RIGA_v2(nn.Module):
         self.host_ms["unpack"] += 1e3 * (time.perf_counter() - t_host)
         return results
 
+    # ---------------------------------------------------------------- encode once, match many (include/roitr_encode.h)
+    def encode_clouds(self, clouds, clouds_per_call=128):
+        """Run the per-cloud half of the forward once per cloud: `clouds` is a list of dicts with `points` (n,3), `normals` (n,3),
+        `feats` (n,1) and optionally `points_out` (n,3: the coordinates the correspondences are reported in; default `points`).
+        Returns the EncodedClouds that launch_match / match_batch take, filled by ceil(len / clouds_per_call) engine calls queued on
+        the current stream (nothing here waits for the GPU).  The cache belongs to this model's weights as they are now."""
+        self._ensure_engine()
+        if not clouds:
+            raise L.RoitrError("encode_clouds needs at least one cloud")
+        lib = _cache_lib()
+        dev = clouds[0]["points"].device
+        f32, i32 = torch.float32, torch.int32
+        C, Lm = 256 * self.factor, self.point_per_patch
+        n_all = [int(c["points"].shape[0]) for c in clouds]
+        arr = (ctypes.c_int * len(n_all))(*n_all)
+        per = (ctypes.c_size_t * 8)()
+        total = lib.roitr_engine_encode_bytes(len(n_all), arr, C, Lm, per)
+        if total == 0:
+            raise L.RoitrError("encode_clouds: a cloud is smaller than the model accepts (256 points = 4 superpoints)")
+        n4 = [self.level_sizes(n)[3] for n in n_all]
+        T, T4, etot = sum(n_all), sum(n4), sum(k * k for k in n4)
+        z = lambda shape, dt=f32: torch.empty(shape, dtype=dt, device=dev)
+        arrays = dict(points=z((T, 3)), point_feats=z((T, C)), node_xyz=z((T4, 3)), node_masks=z((T4,), i32), node_knn_idx=z((T4, Lm), i32),
+                      node_knn_mask=z((T4, Lm), i32), node_geo=z((T4, C)), embedding=z((etot, C)))
+        assert [a.numel() * a.element_size() for a in arrays.values()] == list(per)
+        enc = EncodedClouds(arrays, n_all, C, Lm, self._engine_sig, self._engine_token)   # (_ensure_engine has just brought the signature up to date)
+        for c0 in range(0, len(clouds), max(1, int(clouds_per_call))):
+            part = clouds[c0:c0 + max(1, int(clouds_per_call))]
+            cat = lambda k: torch.cat([c[k].to(f32) for c in part], 0).contiguous()
+            geom, nrm, feats = cat("points"), cat("normals"), cat("feats")
+            pout = torch.cat([c.get("points_out", c["points"]).to(f32) for c in part], 0).contiguous()
+            s0 = enc.seg[c0]
+            io = _CEncodeIO()
+            io.clouds = len(part)
+            io.n_points = ctypes.c_void_p(ctypes.addressof(arr) + 4 * c0)
+            io.points_geom, io.normals, io.feats, io.points_out = L.ptr(geom), L.ptr(nrm), L.ptr(feats), L.ptr(pout)
+            for k in CACHE_ARRAYS:
+                row0 = s0.pt_row0 if k in ("points", "point_feats") else s0.emb0 if k == "embedding" else s0.node_row0
+                setattr(io, k, L.ptr(arrays[k][row0:]))
+            L.check(lib.roitr_engine_encode(self._engine, ctypes.byref(io), L.stream_ptr()), "engine_encode")
+        return enc
+
+    def _check_cache(self, enc):
+        if not isinstance(enc, EncodedClouds):
+            raise L.RoitrError("expected the EncodedClouds of encode_clouds()")
+        if enc.engine is not self._engine_token:
+            raise L.RoitrError("stale cloud cache: it was encoded by another engine")
+        # after _ensure_engine the engine's signature IS the model's (with weights_frozen the caller vouches for it): no second walk
+        if enc.signature != self._engine_sig:
+            raise L.RoitrError("stale cloud cache: the model's weights changed since encode_clouds(): encode again")
+
+    def _match_io(self, enc, src, tgt, out):
+        """The RoitrMatchIO of pairs (src[b], tgt[b]) with the output tensors of `out` (absent = NULL) and what keeps its host arrays alive."""
+        io = _CMatchIO()
+        io.pairs = len(src)
+        a_src, a_tgt = (ctypes.c_int * max(1, len(src)))(*src), (ctypes.c_int * max(1, len(tgt)))(*tgt)
+        io.src_cloud, io.tgt_cloud = ctypes.cast(a_src, ctypes.c_void_p), ctypes.cast(a_tgt, ctypes.c_void_p)
+        for k, v in out.items():
+            setattr(io, k, L.ptr(v))
+        return io, (a_src, a_tgt)
+
+    def launch_match(self, enc, pairs, want_node_xyz=False):
+        """Enqueue the pair half of the forward for `pairs` = [(src_index, tgt_index), ...] over the cached clouds of `enc` on the
+        current stream and return a handle for finish_batch().  Like launch_batch it does not wait for the GPU.  A cloud may appear in
+        any number of pairs, on either side; (a, a) is allowed.  want_node_xyz: also copy the node coordinates into the call layout
+        (handle["out"]["node_xyz"]; the results' *_nodes are views into the cache either way)."""
+        self._ensure_engine()
+        self._check_cache(enc)
+        t_host = time.perf_counter()
+        pairs = [(int(s), int(t)) for s, t in pairs]
+        B = len(pairs)
+        if B == 0:
+            return dict(enc=enc, match_pairs=[], B=0)
+        bad = [p for p in pairs if not (0 <= p[0] < len(enc) and 0 <= p[1] < len(enc))]
+        if bad:
+            raise L.RoitrError(f"launch_match: cloud index outside the table of {len(enc)} clouds: {bad[:4]}")
+        dev = enc.arrays["points"].device
+        f32, i32 = torch.float32, torch.int32
+        src, tgt = [p[0] for p in pairs], [p[1] for p in pairs]
+        slots = src + tgt
+        n4 = [enc.n4[c] for c in slots]
+        T4, C, Lm = sum(n4), enc.channels, enc.limit
+        P, S = self._patch_geometry(B, n4)
+        cap = S * Lm * self.fine_topk * (1 if self.fine_mutual else 2)
+        z = lambda shape, dt=f32: torch.empty(shape, dtype=dt, device=dev)
+        out = dict(node_feats=z((T4, C)), tgt_corr=z((B, P), i32), src_corr=z((B, P), i32), corr_scores=z((B, P)), n_corr=z((B,), i32),
+                   tgt_knn_pts=z((S, Lm, 3)), src_knn_pts=z((S, Lm, 3)), tgt_knn_masks=z((S, Lm), i32), src_knn_masks=z((S, Lm), i32),
+                   matching_scores=z((S, Lm + 1, Lm + 1)), out_tgt_pts=z((cap, 3)), out_src_pts=z((cap, 3)), out_scores=z((cap,)),
+                   out_patch=z((cap,), i32), fine_offsets=z((S,), i32), n_out=z((1,), i32), pair_starts=z((B + 1,), i32))
+        if want_node_xyz:
+            out["node_xyz"] = z((T4, 3))
+        io, keep = self._match_io(enc, src, tgt, out)
+        L.check(_cache_lib().roitr_engine_match(self._engine, ctypes.byref(enc.table), ctypes.byref(io), L.stream_ptr()), "engine_match")
+        meta_dev = torch.cat([out["pair_starts"], out["n_corr"]])
+        meta_host = torch.empty(meta_dev.shape, dtype=meta_dev.dtype, pin_memory=True)
+        meta_host.copy_(meta_dev, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self.host_ms["launch"] += 1e3 * (time.perf_counter() - t_host)
+        self.host_ms["calls"] += 1
+        return dict(enc=enc, match_pairs=pairs, out=out, B=B, P=P, slots=S, compacted=False, n4=n4, have_gt=False, meta_host=meta_host,
+                    done=done, keep=(keep, meta_dev))
+
+    def match_batch(self, enc, pairs, want_node_xyz=False):
+        """launch_match + finish_batch: the results of `pairs` over the cached clouds, one LazyDict per pair with the keys of a forward
+        with want_gt=False."""
+        return self.finish_batch(self.launch_match(enc, pairs, want_node_xyz=want_node_xyz))
+
+    def _finish_match(self, h):
+        if h["B"] == 0:
+            return []
+        enc, pairs, out, B, P, n4 = h["enc"], h["match_pairs"], h["out"], h["B"], h["P"], h["n4"]
+        h["done"].synchronize()
+        t_host = time.perf_counter()
+        meta = h["meta_host"].tolist()
+        starts, n_corr = meta[:B + 1], meta[B + 1:2 * B + 1]
+        h["starts"] = starts
+        o_nod = np.cumsum([0] + n4)
+        A_ = enc.arrays
+        results = []
+        for b, (cs, ct) in enumerate(pairs):
+            ss, st_ = enc.seg[cs], enc.seg[ct]
+            nc, p0 = n_corr[b], b * P
+            rows = lambda k, s, node: A_[k][s.node_row0:s.node_row0 + s.n_nodes] if node else A_[k][s.pt_row0:s.pt_row0 + s.n_points]
+            r = LazyDict()
+            # cloud-level entries: views into the cache
+            r["src_points"], r["tgt_points"] = rows("points", ss, False), rows("points", st_, False)
+            r["src_nodes"], r["tgt_nodes"] = rows("node_xyz", ss, True), rows("node_xyz", st_, True)
+            r["src_point_feats"], r["tgt_point_feats"] = rows("point_feats", ss, False), rows("point_feats", st_, False)
+            r["src_node_feats"] = out["node_feats"][o_nod[b]:o_nod[b + 1]]
+            r["tgt_node_feats"] = out["node_feats"][o_nod[B + b]:o_nod[B + b + 1]]
+            r["gt_node_corr_indices"] = r["gt_node_corr_overlaps"] = r["gt_tgt_node_occ"] = r["gt_src_node_occ"] = None
+            r["src_node_corr_indices"] = lambda b=b, nc=nc: out["src_corr"][b, :nc].long()
+            r["tgt_node_corr_indices"] = lambda b=b, nc=nc: out["tgt_corr"][b, :nc].long()
+            r["src_node_corr_knn_points"] = out["src_knn_pts"][p0:p0 + nc]
+            r["tgt_node_corr_knn_points"] = out["tgt_knn_pts"][p0:p0 + nc]
+            r["src_node_corr_knn_masks"] = lambda p0=p0, nc=nc: out["src_knn_masks"][p0:p0 + nc].bool()
+            r["tgt_node_corr_knn_masks"] = lambda p0=p0, nc=nc: out["tgt_knn_masks"][p0:p0 + nc].bool()
+            r["matching_scores"] = out["matching_scores"][p0:p0 + nc]
+            s, e = starts[b], starts[b + 1]
+            r["tgt_corr_points"] = out["out_tgt_pts"][s:e]
+            r["src_corr_points"] = out["out_src_pts"][s:e]
+            r["corr_scores"] = out["out_scores"][s:e]
+            r["_node_corr_scores"] = out["corr_scores"][b, :nc]
+            r["_src_node_knn_indices"], r["_tgt_node_knn_indices"] = rows("node_knn_idx", ss, True), rows("node_knn_idx", st_, True)
+            r["_src_node_knn_masks"] = lambda ss=ss: rows("node_knn_mask", ss, True).bool()
+            r["_tgt_node_knn_masks"] = lambda st_=st_: rows("node_knn_mask", st_, True).bool()
+            r["_src_node_masks"] = lambda ss=ss: rows("node_masks", ss, True).bool()
+            r["_tgt_node_masks"] = lambda st_=st_: rows("node_masks", st_, True).bool()
+            results.append(r)
+        self.host_ms["unpack"] += 1e3 * (time.perf_counter() - t_host)
+        return results
+
     def forward(self, src_pcd, tgt_pcd, src_feats, tgt_feats, src_normals, tgt_normals, rot, trans, src_raw_pcd):
         """model/RIGA_v2.py:58 -- one pair, same argument order, same output keys."""
         pair = dict(src_pcd=src_pcd, tgt_pcd=tgt_pcd, src_feats=src_feats, tgt_feats=tgt_feats, src_normals=src_normals,
@@ -642,8 +864,17 @@ class RIGA_v2(nn.Module):
 
 # ---- what the evaluation operators read of a launch_batch() handle.  `keep` is read at call time: finish_batch replaces it when it
 # repeats an overfull call, while the sizes (n_all, n4) the cached starts are built from are those of the pairs and stay.
+def _forward_handle(handle, who):
+    """The evaluation operators read clouds laid out src_0 .. src_{B-1}, tgt_0 .. tgt_{B-1}; a match handle's clouds are rows of the
+    cloud cache, anywhere and shared between pairs."""
+    if "enc" in handle:
+        raise L.RoitrError(f"{who}: this is a launch_match() handle: its clouds are rows of the cloud cache, not the contiguous "
+                           "src / tgt layout of a launch_batch() handle (read the per-pair results of finish_batch instead)")
+
+
 def handle_poses(handle, who):
     """rot (B,3,3) / trans (B,3) fp32 device tensors of a handle's pairs, as the engine was given them."""
+    _forward_handle(handle, who)
     if not handle["have_gt"]:
         raise L.RoitrError(f"{who} needs ground-truth transforms (rot / trans) in the pairs")
     return handle["keep"][4], handle["keep"][5]
@@ -653,6 +884,7 @@ def handle_starts(handle, which):
     """(src_starts, tgt_starts) of a handle's "point" rows (point_feats, the clouds the model was fed) or "node" rows (node_feats,
     node_xyz), which hold src_0 .. src_{B-1}, tgt_0 .. tgt_{B-1}: source pair b owns rows [src_starts[b], src_starts[b + 1]), its target
     [tgt_starts[b], tgt_starts[b + 1]); both (B + 1) int32 on the device, uploaded once per handle."""
+    _forward_handle(handle, "handle_starts")
     if which not in ("point", "node"):
         raise L.RoitrError(f"which must be 'point' or 'node', got {which!r}")
     B = handle["B"]
@@ -665,6 +897,7 @@ def handle_starts(handle, which):
 def handle_layout(handle, which):
     """(rows, src_starts, tgt_starts): handle_starts and the coordinates of those rows, the clouds the model was fed (src_pcd then
     tgt_pcd) for "point", node_xyz for "node"."""
+    _forward_handle(handle, "handle_layout")
     src_starts, tgt_starts = handle_starts(handle, which)
     rows = handle["keep"][1] if which == "point" else handle["out"]["node_xyz"]
     return rows[:sum(handle["n_all" if which == "point" else "n4"])], src_starts, tgt_starts
@@ -672,6 +905,7 @@ def handle_layout(handle, which):
 
 def handle_normals(handle):
     """The normals the model was fed for the "point" rows of handle_layout (src_normals then tgt_normals), (rows, 3) fp32."""
+    _forward_handle(handle, "handle_normals")
     return handle["keep"][2][:sum(handle["n_all"])]
 
 
