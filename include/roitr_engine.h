@@ -797,6 +797,91 @@ int roitr_fgr_batch_staged(int pairs, const int* starts, int total_rows, const f
                            double* mu, double* objective, int* status, int* multiplicity, double* trace, roitr_stream_t stream);
 
 
+/* ------------------------------------------------------------------ multiway registration
+ * One pose per fragment of a scene in a common frame from the scene's pairwise poses, with wrong loop closures switched off by a
+ * line process: the pose-graph optimisation of Choi, Zhou and Koltun (CVPR 2015), which Open3D exposes as global_optimization with
+ * GlobalOptimizationLevenbergMarquardt.  PARITY WITH OPEN3D IS NOT CLAIMED: the operator is defined here.  Six-vectors are in the
+ * project's order, rotation first: (a, b, g, tx, ty, tz).  Every product and sum is rounded on its own (no contraction).
+ *
+ * roitr_edge_information: the weight of an edge from the correspondences that produced its pose.  Inputs as roitr_lgr_batch: pair b
+ * owns rows [starts[b], starts[b+1]) (clamped into [0, total_rows]) of src_pts / tgt_pts; transforms (pairs,4,4) fp32, source to
+ * target; radius (finite, > 0).  A row is an inlier when rg_dist2(T p, q) < radius^2, in fp32 and strictly, as roitr_lgr_batch
+ * verifies: n_inlier[b] equals its inliers[b] when its own transform is passed.  info (pairs,6,6) double = the sum over the inliers
+ * of G^T G with G = [ -[p]x | I3 ], p the SOURCE point in its own frame as the double of the fp32 input: the rotation block is
+ * sum (|p|^2 I - p p^T), the off-diagonal blocks hold +- sum p, info[3][3] = info[4][4] = info[5][5] = n_inlier.  Nine sums are
+ * carried (the six of the rotation block and sum x, y, z): the other entries are zero, the count, or an exact negation.  Each is a
+ * strided per-lane sum over the local row index (256 lanes) followed by the fixed butterfly of roitr_fgr_batch, so a pair's result is
+ * bitwise independent of its batch, its slot, its row offset and of repeats.  One launch, one workgroup per pair; a pair without
+ * rows gives zeros.  Refusals (ROITR_ERR_ARG, nothing launched): null pointers, a radius not finite and positive, total_rows < 0,
+ * more than 65535 pairs.
+ *
+ * roitr_pose_graph_batch: `scenes` ragged scenes.  Scene s owns the nodes [node_starts[s], node_starts[s+1]) of init_poses / poses and
+ * the edges [edge_starts[s], edge_starts[s+1]).  Edge e has edge_i, edge_j (int32, node indices LOCAL to the scene), edge_T (4,4 fp32,
+ * mapping points of cloud i into cloud j's frame; only its first three rows are read), edge_info (6,6 double, the matrix Lambda,
+ * rotation first; it must be symmetric, the solver reads the upper triangle of the system) and edge_uncertain (int32; 0: an
+ * odometry edge, anything else: a loop closure under the line process).  init_poses (nodes,4,4) fp32 map a cloud's frame into the
+ * scene's.  Node 0 of every scene is the gauge: it keeps its initial pose and has no unknowns; node k >= 1 owns the unknowns
+ * [6 (k-1), 6 k) of the scene's u = 6 (n - 1).  node_starts_host / edge_starts_host are HOST copies of the two start arrays (scenes + 1
+ * entries): the limits are checked and the workspace is laid out from them, nothing is read back from the device.
+ * Parameters (double): mu (the line-process scale, finite, > 0; see roitr_amd.posegraph.line_process_weight), tau (finite, > 0),
+ * step_tol (finite, >= 0), prune_threshold (0 ... 1); iterations 0 ... 1024.
+ * The state X (one [R | t] per node) is double throughout, X = (double)init_poses at the start.
+ * 1. Residual of edge e = (i, j): D = T_e^-1 X_j^-1 X_i, both inverses in closed form ([R^T | -R^T t]);
+ *    xi = ((D21 - D12) / 2, (D02 - D20) / 2, (D10 - D01) / 2, D03, D13, D23), Drc the entry of row r, column c; e_e = xi^T (Lambda xi).
+ * 2. Line process: l_e = 1 for a certain edge, (mu / (mu + e_e))^2 for an uncertain one.  The objective is
+ *    F = sum_e [ l_e e_e + (uncertain ? mu (sqrt(l_e) - 1)^2 : 0) ], a strided per-lane sum over the scene's local edge index (256 lanes)
+ *    and the fixed butterfly.
+ * 3. Linearisation.  The update is X_k <- dT(delta_k) X_k, dT of compose_step_d (csrc/gauss_newton6.h).  Column k of J_e (6 x 6) is
+ *    the six-vector (as in 1) of T_e^-1 X_j^-1 G_k X_i with the six generators G_k; the j side is exactly -J_e.
+ *    M_e = l_e J^T (Lambda J), g_e = l_e J^T (Lambda xi).  H_ii += M, H_jj += M, H_ij -= M, H_ji -= M, b_i += g, b_j -= g (the gauge's
+ *    rows and columns do not exist).  Every block of H and every segment of b is the sum of its edges' terms in ASCENDING EDGE INDEX,
+ *    gathered through an adjacency list that is built once per scene; no floating-point atomics.
+ * 4. Solve.  lambda_0 = tau * max diag(H) of the first assembly.  Every iteration solves (H + lambda I) delta = -b by a dense
+ *    L D L^T in the workspace: for column j, t_k = V[k][j] / d_k (k < j); V[j][i] = A[i][j] - sum_{k<j} V[k][i] t_k for i >= j, one
+ *    thread's sequential sum in ascending k, with d_j = V[j][j]; the right-hand side is carried as one more row i = u of the same
+ *    recurrence (w_j = -b_j - sum_{k<j} w_k t_k).  Back substitution: delta_i = (w_i - sum_{k>i} V[i][k] delta_k) / d_i, the sum taken
+ *    in DESCENDING k.  No entry depends on the thread mapping.  A pivot d_j that is not positive or not finite sets SINGULAR, keeps the
+ *    state and ends the scene.
+ * 5. Stop and gain.  max |delta| < step_tol, tested before delta is applied, sets CONVERGED and ends the scene.  Otherwise
+ *    X'_k = dT(delta_k) X_k, F' = F(X') with its own line weights, rho = (F - F') / sum_q delta_q (lambda delta_q - b_q).
+ *    rho > 0: X <- X', steps += 1, lambda *= max(1/3, 1 - (2 rho - 1)^3), nu = 2.  Otherwise (a NaN included): X stays,
+ *    lambda *= nu, nu *= 2 (nu starts at 2).  The loop ends after `iterations` solves; iterations = 0 returns the initial poses.
+ * Outputs: poses (nodes,4,4) fp32, rounded once at the end (a node that never moved -- the gauge, every node of a scene without an
+ *   accepted step -- gets the 16 floats of its initial pose); line_weight (edges) double, l_e at the final state; pruned (edges) int32,
+ *   uncertain && l_e < prune_threshold; per scene steps (accepted), solves (run), objective (F at the final state), lambda_out (the
+ *   last lambda) and status (bits below).  Optional (NULL allowed), rows that were not run are zero: trace_scalars (scenes x iterations
+ *   x 8): F, lambda, rho, max |delta|, accepted (0 / 1), F', the denominator of rho, 1.0, per solve; trace_poses (nodes x iterations x
+ *   12): the state [R | t] of every node BEFORE that solve; trace_delta (nodes x iterations x 6): the solve's delta (the gauge's row 0).
+ * Status scenes get their initial poses, l = 1, pruned = 0 and zeros, and touch nothing else in the batch: ONE_NODE (fewer than two
+ *   nodes; set alone, whatever edges the scene lists), else NO_EDGES, else BAD_EDGE (an index outside [0, n) or i == j; found by the
+ *   status pass on the device); and BAD_COUNTS (the device
+ *   start arrays disagree with the host copies: more than ROITR_POSEGRAPH_MAX_NODES nodes or a workspace slice outside the workspace).
+ * Two launches for a whole batch: the status pass and the whole loop, one workgroup per scene; no workgroup waits for another and
+ *   every loop is bounded by `iterations`.  H lives in the workspace, (6 (n - 1))^2 doubles per scene.
+ * Determinism: a scene's results are bitwise independent of its batch, its slot, its node and edge offsets and of repeats.
+ * The workspace (device, caller-owned) holds at least roitr_pose_graph_workspace_bytes() bytes (host-only; 0 for counts the batch
+ *   call refuses).
+ * Refusals (ROITR_ERR_ARG, nothing is launched or written): null pointers, host start arrays that do not begin at 0 or decrease, a
+ *   scene of more than ROITR_POSEGRAPH_MAX_NODES nodes, more than 65535 scenes, parameters out of the ranges above, a short workspace. */
+#define ROITR_POSEGRAPH_MAX_NODES 256
+#define ROITR_POSEGRAPH_ONE_NODE 1
+#define ROITR_POSEGRAPH_NO_EDGES 2
+#define ROITR_POSEGRAPH_BAD_EDGE 4
+#define ROITR_POSEGRAPH_SINGULAR 8
+#define ROITR_POSEGRAPH_CONVERGED 16
+#define ROITR_POSEGRAPH_BAD_COUNTS 32
+int roitr_edge_information(int pairs, const int* starts, int total_rows, const float* src_pts, const float* tgt_pts,
+                           const float* transforms, float radius, double* info, int* n_inlier, roitr_stream_t stream);
+size_t roitr_pose_graph_workspace_bytes(int scenes, const int* node_starts_host, const int* edge_starts_host);
+int roitr_pose_graph_batch(int scenes, const int* node_starts, const int* edge_starts, const int* node_starts_host,
+                           const int* edge_starts_host, const int* edge_i, const int* edge_j, const float* edge_T,
+                           const double* edge_info, const int* edge_uncertain, const float* init_poses, double mu, double tau,
+                           double step_tol, double prune_threshold, int iterations, void* workspace, size_t workspace_bytes,
+                           float* poses, double* line_weight, int* pruned, int* steps, int* solves, double* objective,
+                           double* lambda_out, int* status, double* trace_scalars, double* trace_poses, double* trace_delta,
+                           roitr_stream_t stream);
+
+
 /* ------------------------------------------------------------------ 4DMatch non-rigid evaluation
  * registration/evaluate_fdmatch.py:50-115: NFMR (non-rigid feature matching recall) of every pair of a batch.  Pair b owns points
  * [src_offsets[b], src_offsets[b+1]) of src_raw (the undeformed source) and src_deformed (what the model was fed), both (total_src,

@@ -81,16 +81,6 @@ __global__ __launch_bounds__(FG_THREADS) void fgr_tuple_kernel(const int* __rest
 }
 
 // ------------------------------------------------------------------------------------------------------------------ solve
-__device__ __forceinline__ double block_max_d(double v, double* red)   // red: 4 doubles; a maximum has no order
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
-
 struct FgParams {
     double md2, division_factor;
     int iterations, mu_every, tuples;

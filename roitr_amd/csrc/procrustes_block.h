@@ -59,6 +59,17 @@ __device__ __forceinline__ int block_sum_i(int v, int* red)   // red: 4 ints
     return red[0] + red[1] + red[2] + red[3];
 }
 
+// block maximum of one double per thread, every thread gets it (fgr.hip, posegraph.hip)
+__device__ __forceinline__ double block_max_d(double v, double* red)   // red: 4 doubles; a maximum has no order
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+
 // The two moment passes of one weighted solve over rows j = lane, lane + stride, ... < n (row(j, p, q, w): source, target, weight):
 // a = {sum w, sum w p, sum w q}, then H = sum w (p - cs)(q - ct)^T with cs, ct = sum w p / (sum w + eps).  `sum` reduces an array
 // over the lanes that share the solve.
